@@ -12,12 +12,19 @@ closes the timed region.
 ``--config coffee|spaceship|lamp`` runs BASELINE.json's other configs (procedural
 scenes, their resolutions) through the same path, on 1 or N GPUs.
 
-Prints ONE JSON line (rank 0). Besides the contract fields it carries
+Prints ONE JSON line (rank 0). A plain run does what the headline figure needs
+and no more: set-up, ``--warmup`` images, ``--steps`` timed steps (once), the
+outputs when ``--dump-outputs DIR`` is given (the film the timed steps left, as
+``DIR/film.npy``), the line.
+
+``--full`` adds everything else the benchmark measures: the timed steps are
+repeated (``--repeats``, 5, the value their median), and the line also carries
 ``roofline`` (the merged EXTENSION+SHADOW cast launch: algorithmic bytes per
 launch / HIP-event launch time against the MI355X HBM peak, next to the
 PMC-measured HBM bytes of the same launches when a profile of this workload is
-committed) and ``cpu_baseline`` (the oracle's scalar
-MegakernelPathTracing restatement on this host's cores, bounded sample).
+committed), ``pipeline_roofline`` and ``material``, ``cpu_baseline`` (the
+oracle's scalar MegakernelPathTracing restatement on this host's cores, bounded
+sample) and, on the default Cornell run, the configs[3] ``spaceship`` leg.
 """
 from __future__ import annotations
 
@@ -25,6 +32,7 @@ import argparse
 import json
 import os
 import sys
+import tempfile
 import time
 from pathlib import Path
 
@@ -51,7 +59,9 @@ def parse():
     ap.add_argument("--bounces", type=int, default=8)
     ap.add_argument("--config", default="cornell", choices=["cornell", "coffee", "spaceship", "lamp", "spaceship_close"],
                     help="BASELINE.json configs[1..4]; the headline (and default) is cornell = configs[1]")
-    ap.add_argument("--scene-dir", default="/tmp/dcrt_scenes", help="where the procedural config scenes are written")
+    ap.add_argument("--scene-dir", default=str(Path(tempfile.gettempdir()) / f"dcrt_scenes_{os.getuid()}"),
+                    help="where the procedural config scenes are written (default: this user's own folder under the "
+                         "temporary directory, so that another user's copy is never in the way)")
     ap.add_argument("--no-multiscattering", action="store_true",
                     help="coffee: keep the loaders' Kulla-Conty flag (off) instead of configs[2]'s multiscattering (A/B)")
     ap.add_argument("--snapshot-spp", type=int, default=0,
@@ -89,8 +99,16 @@ def parse():
     ap.add_argument("--traffic-json", default=None,
                     help="PMC summary from tools/pmc_traffic.py (default: the newest profiles/r*_pmc_traffic*.json "
                          "whose recorded workload is this run's)")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed repeats of the K steps; value is the median (SURVEY 8(d): median of 5 after warm-up)")
+    ap.add_argument("--repeats", type=int, default=0,
+                    help="timed repeats of the K steps; value is the median. 0: once for a plain run, 5 with --full "
+                         "(SURVEY 8(d): median of 5 after warm-up)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: 5 timed repeats (median), the cast / MATERIAL / "
+                         "whole-pipeline roofline leg, the CPU baseline and the configs[3] spaceship leg")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the timed steps computed as DIR/<name>.npy: film.npy, the RGBA32F film "
+                         "after the last timed step (height x width x 4, float32); a film above 64 MB is written as a "
+                         "fixed sample of its pixels (n x 4, ascending pixel index, numpy default_rng(0))")
     ap.add_argument("--spaceship-spp", type=int, default=16,
                     help="configs[3] leg of the default Cornell run: spaceship 4K images (0 = skip); 16 = four "
                          "batches per pipeline, the steady state of configs[3]'s 128 spp (4 is one batch: its "
@@ -369,14 +387,14 @@ def main():
             film_buf.copy_(torch.from_numpy(tracer.read_film().reshape(-1)))
         dist.reduce(film_buf, dst=0, op=dist.ReduceOp.SUM)
 
-    # warmup (also builds the graphs)
+    # the timed batches' sample textures and graphs first (not timed work), then the warm-up
+    # through them: the steps are timed once, so their first launch must not be the graphs' first
     for t in tracers:
         t.clear_film()
+    images = args.steps * world            # weak scaling: each step is one image per GPU-equivalent
+    prepare_pipelines(tracers, images)
     if args.warmup:
         render_all(10_000, args.warmup)
-
-    images = args.steps * world            # weak scaling: each step is one image per GPU-equivalent
-    prepare_pipelines(tracers, images)     # sample textures of the timed batches + graph: not timed work
     snapshots = bool(args.snapshot_spp and args.snapshot_spp < images)
 
     calibration = None
@@ -412,9 +430,9 @@ def main():
             tracer = tracers[0]
             for t in tracers:
                 t.clear_film()
+            prepare_pipelines(tracers, images)
             if args.warmup:
                 render_all(10_000, args.warmup)
-            prepare_pipelines(tracers, images)
 
     def timed_run():
         """One timed repeat of exactly K steps: (wall s, this rank's render s, reduce s)."""
@@ -453,7 +471,7 @@ def main():
         barrier_sync()
         return time.perf_counter() - t0, t_render, t_reduce
 
-    runs = [timed_run() for _ in range(max(1, args.repeats))]
+    runs = [timed_run() for _ in range(args.repeats if args.repeats > 0 else (5 if args.full else 1))]
     rays = 0
     for t in tracers:
         c = t.counters()
@@ -478,7 +496,7 @@ def main():
         per_rank = [[float(x) for x in g.cpu()] for g in gathered]
     elapsed = float(np.median(walls))
 
-    if args.save_film and rank == 0:
+    if (args.save_film or args.dump_outputs) and rank == 0:
         # the reduced film (N > 1), the last snapshot (one rank, snapshots taken), else tracer 0's
         # film, which combine_films made the sum of the rank's pipelines
         if dist is not None:
@@ -487,31 +505,17 @@ def main():
             film = snap_dev.cpu().numpy()
         else:
             film = tracer.read_film()
-        np.save(args.save_film, film.reshape(args.height, args.width, 4))
+        film = film.reshape(args.height, args.width, 4)
+        if args.save_film:
+            np.save(args.save_film, film)
+        if args.dump_outputs:
+            dump_outputs(Path(args.dump_outputs), film)
 
-    # ---- roofline leg: same workload (seeds 0..R-1), counters then HIP-event timing, on
-    # ONE pipeline (the rank's whole partition, as with --streams 1): a kernel's duration
-    # is only its own when no other pipeline's kernels share the GPU
-    R = max(1, args.roofline_images or images)
-    if K > 1:
-        for t in tracers:
-            t.destroy()
-        tracer = make_tracer(args.pool, (world, rank, args.stripe) if world > 1 else None,
-                             rank_bands if (rank_bands is not None and world > 1) else None)
-    roof = cast_roofline(tracer, R, filt, {"config": config_name, "resolution": [args.width, args.height], "images": R,
-                                           "path_pool": args.pool, "world": world}, args.traffic_json)
-    st, cr, tm = roof.pop("_stats"), roof.pop("_counters"), roof.pop("_timing")
-    pmc, pmc_src = roof.pop("_pmc")
-    # whole-pipeline figure ("and for the whole pipeline"): the reference's
-    # algorithmic bytes of every stage for the timed images (cast terms, CONTROL + MATERIAL
-    # per path-iteration = per extension ray, NEW_PATH per new path, the film pass per pixel
-    # x image), from the roofline leg's counts of the same images, over the timed region's
-    # wall time, per GPU. These bytes are largely served from LDS / L2 / MALL: the figure is
-    # an algorithmic rate, not an HBM measurement (the HBM statement is roofline.frac).
-    film_bytes = FILM_BYTES_BASE + FILM_BYTES_PER_TAP * (2 * int(filt.radius + 0.5) + 1) ** 2
-    pipe_bytes_R = (roof["bytes_per_launch"] * roof["launches"] + (CONTROL_BYTES + MATERIAL_BYTES) * cr["extension_rays"]
-                    + NEW_PATH_BYTES * cr["new_paths"] + film_bytes * args.width * args.height * R / world)
-    pipe_achieved = pipe_bytes_R * (images / R) / elapsed / 1e9
+    # everything below the timed steps runs with --full only
+    full = {}
+    if args.full:
+        full, tracer = roofline_legs(args, tracers, make_tracer, filt, config_name, world, rank, rank_bands, K, images, elapsed)
+        tracers = [tracer]
 
     result = {
         "metric": ("Mrays/s and ms/spp at 1920x1080, 8-bounce wavefront" if args.config == "cornell"
@@ -542,10 +546,7 @@ def main():
                    "partition": args.partition if rank_bands is not None else ("stripes" if world * K > 1 else "none"),
                    "interleave": interleave, "bands_per_rank": B if rank_bands is not None else None,
                    "rays": int(rays)},
-        "roofline": roof,
-        "pipeline_roofline": pipeline_roofline(pmc, pmc_src, images / world / elapsed, pipe_achieved, pipe_bytes_R / R),
-        "material": material_roofline(tm, pmc, pmc_src),
-        "cpu_baseline": None,
+        **full,
     }
     if per_rank is not None:
         # diagnosable first 8-GPU run: every rank's render time (its stripes + halo rows) and the
@@ -565,16 +566,63 @@ def main():
                                "rank0_rows_owned": owned, "rank0_rows_rendered": rendered,
                                "rank0_halo_overhead": round(rendered / max(1, owned) - 1.0, 4),
                                "calibration": calibration}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         label = "1920x1080 8-bounce Cornell" if args.config == "cornell" else f"{args.config} config"
         result["cpu_baseline"] = cpu_baseline(scene, luts_arrays, args.cpu_seconds, label)
-    tracer.destroy()
-    if rank == 0 and world == 1 and args.config == "cornell" and args.spaceship_spp > 0 and args.mode == "wavefront":
+    for t in tracers:
+        t.destroy()
+    if args.full and rank == 0 and world == 1 and args.config == "cornell" and args.spaceship_spp > 0 and args.mode == "wavefront":
         result["spaceship"] = spaceship_leg(args, luts_arrays)
     if rank == 0:
         print(json.dumps(result), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+def roofline_legs(args, tracers, make_tracer, filt, config_name, world, rank, rank_bands, K, images, elapsed):
+    """--full: the roofline leg of the timed workload (seeds 0..R-1), counters then HIP-event
+    timing, on ONE pipeline (the rank's whole partition, as with --streams 1): a kernel's
+    duration is only its own when no other pipeline's kernels share the GPU. Returns the line's
+    roofline / pipeline_roofline / material / cpu_baseline entries and the tracer it ran on."""
+    tracer = tracers[0]
+    R = max(1, args.roofline_images or images)
+    if K > 1:
+        for t in tracers:
+            t.destroy()
+        tracer = make_tracer(args.pool, (world, rank, args.stripe) if world > 1 else None,
+                             rank_bands if (rank_bands is not None and world > 1) else None)
+    roof = cast_roofline(tracer, R, filt, {"config": config_name, "resolution": [args.width, args.height], "images": R,
+                                           "path_pool": args.pool, "world": world}, args.traffic_json)
+    st, cr, tm = roof.pop("_stats"), roof.pop("_counters"), roof.pop("_timing")
+    pmc, pmc_src = roof.pop("_pmc")
+    # whole-pipeline figure (SURVEY 8(d): "and for the whole pipeline"): the reference's
+    # algorithmic bytes of every stage for the timed images (cast terms, CONTROL + MATERIAL
+    # per path-iteration = per extension ray, NEW_PATH per new path, the film pass per pixel
+    # x image), from the roofline leg's counts of the same images, over the timed region's
+    # wall time, per GPU. These bytes are largely served from LDS / L2 / MALL: the figure is
+    # an algorithmic rate, not an HBM measurement (the HBM statement is roofline.frac).
+    film_bytes = FILM_BYTES_BASE + FILM_BYTES_PER_TAP * (2 * int(filt.radius + 0.5) + 1) ** 2
+    pipe_bytes_R = (roof["bytes_per_launch"] * roof["launches"] + (CONTROL_BYTES + MATERIAL_BYTES) * cr["extension_rays"]
+                    + NEW_PATH_BYTES * cr["new_paths"] + film_bytes * args.width * args.height * R / world)
+    pipe_achieved = pipe_bytes_R * (images / R) / elapsed / 1e9
+    return {"roofline": roof,
+            "pipeline_roofline": pipeline_roofline(pmc, pmc_src, images / world / elapsed, pipe_achieved, pipe_bytes_R / R),
+            "material": material_roofline(tm, pmc, pmc_src),
+            "cpu_baseline": None}, tracer
+
+
+def dump_outputs(directory: Path, film: np.ndarray, limit_bytes: int = 64 << 20) -> None:
+    """--dump-outputs: what a caller of the timed path receives, the RGBA32F film, as
+    directory/film.npy. A film above `limit_bytes` (the 4K configs) is written as a fixed
+    sample of its pixels (the same pixels every run, half the limit: 2^21), in ascending pixel
+    index."""
+    directory.mkdir(parents=True, exist_ok=True)
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    if film.nbytes > limit_bytes:
+        flat = film.reshape(-1, 4)
+        pick = np.sort(np.random.default_rng(0).choice(flat.shape[0], size=limit_bytes // 32, replace=False))
+        film = flat[pick]
+    np.save(directory / "film.npy", film)
 
 
 def cast_roofline(tracer, R, filt, workload_key, traffic_json=None) -> dict:

@@ -222,18 +222,26 @@ def build_oracle(force: bool = False) -> Path:
 REFERENCE = Path(os.environ.get("DCRT_REFERENCE", "/root/reference"))
 
 
+def _readable(path: Path) -> bool:
+    """path exists and this user may reach it (a folder closed to this user counts as absent)."""
+    try:
+        return path.exists()
+    except OSError:
+        return False
+
+
 def build_reference_checkers() -> Path | None:
     """TEST INFRASTRUCTURE: when the reference sources are present (the build container,
     never the GPU box), compile its own OBJ dependencies -- tinyobjloader + MikkTSpace,
     unmodified, from where they lie -- with our load-flow harness into
     oracle/_ref/librefobj.so (oracle/ref_obj/Makefile). tests/test_obj_pin.py uses it."""
-    if not (REFERENCE / "tinyobjloader" / "tiny_obj_loader.h").exists():
+    if not _readable(REFERENCE / "tinyobjloader" / "tiny_obj_loader.h"):
         return None
     with _build_lock("reference"):
         subprocess.run(["make", "-s", "-C", str(ORACLE_DIR / "ref_obj"), f"REF={REFERENCE}"], check=True,
                        stdout=subprocess.DEVNULL)
         # ... and its vendored RapidXml for tests/test_xml_pin.py (oracle/ref_xml/Makefile)
-        if (REFERENCE / "RapidXml" / "rapidxml.hpp").exists():
+        if _readable(REFERENCE / "RapidXml" / "rapidxml.hpp"):
             subprocess.run(["make", "-s", "-C", str(ORACLE_DIR / "ref_xml"), f"REF={REFERENCE}"], check=True,
                            stdout=subprocess.DEVNULL)
     return ORACLE_DIR / "_ref" / "librefobj.so"

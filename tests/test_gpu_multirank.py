@@ -23,7 +23,7 @@ def _port():
 
 def test_two_rank_bench_film_equals_single_rank(tmp_path):
     common = ["--steps", "1", "--warmup", "0", "--width", "256", "--height", "144", "--bounces", "4",
-              "--pool", str(1 << 16), "--no-cpu-baseline", "--roofline-images", "1", "--stripe", "16",
+              "--pool", str(1 << 16), "--full", "--no-cpu-baseline", "--roofline-images", "1", "--stripe", "16",
               "--spaceship-spp", "0"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     single = tmp_path / "single.npy"
@@ -116,7 +116,7 @@ def test_bench_default_line_fields(tmp_path):
     configs[3] spaceship leg (ms/spp, traversal counts, its own roofline)."""
     import json
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "1", "--width", "320",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--width", "320",
                         "--height", "180", "--pool", str(1 << 18), "--cpu-seconds", "1", "--spaceship-spp", "1",
                         "--scene-dir", str(tmp_path)], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -138,6 +138,36 @@ def test_bench_default_line_fields(tmp_path):
     sp = d["spaceship"]
     assert sp["ms_per_spp"] > 0 and sp["roofline"]["per_shadow_ray"]["nodes"] > 0
     assert sp["roofline"]["bound"].startswith("memory latency") and not sp["roofline"]["scene_in_lds"]
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain run times its --steps once and stops there: the contract fields, none of the
+    --full legs. --dump-outputs writes the film of the timed steps as float32 film.npy, the
+    same bits from run to run and the same as --save-film's."""
+    import json
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    common = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--width", "200", "--height", "120", "--bounces", "4",
+              "--pool", str(1 << 16)]
+    films = []
+    for k in range(2):
+        out = tmp_path / f"out{k}"
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), *common, "--dump-outputs", str(out),
+                            "--save-film", str(tmp_path / f"saved{k}.npy")], capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["repeats"] == 1 and len(d["repeat_ms_per_spp"]) == 1
+        assert d["unit"] == "Mrays/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["value"] > 0
+        assert d["ms_per_step"] > 0 and abs(d["ms_per_step"] - d["repeat_ms_per_spp"][0]) < 1e-3   # (1 spp per step)
+        assert not {"roofline", "pipeline_roofline", "material", "cpu_baseline", "spaceship"} & set(d)
+        assert sorted(p.name for p in out.iterdir()) == ["film.npy"]
+        film = np.load(out / "film.npy")
+        assert film.dtype == np.float32 and film.shape == (120, 200, 4)
+        assert np.isfinite(film).all() and film[..., 3].min() > 0
+        assert np.array_equal(film.view(np.uint32), np.load(tmp_path / f"saved{k}.npy").view(np.uint32))
+        films.append(film)
+    assert np.array_equal(films[0].view(np.uint32), films[1].view(np.uint32))
 
 
 def test_torch_rccl_buffer_interop():

@@ -221,3 +221,23 @@ def test_bench_world_check_and_launcher_command():
     assert cmd[i - 1] == "-m" and cmd[cmd.index("--nproc-per-node") + 1] == "8"
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and cmd[cmd.index("--master-port") + 1] == "29555"
     assert cmd[-4:] == ["--gpus", "8", "--steps", "5"] and cmd[-5].endswith("bench.py")
+
+
+def test_bench_dump_outputs_writes_the_film_or_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: a film within the size limit is written whole as float32; a larger
+    one as half the limit's worth of its pixels, the same ascending pixel indices every time."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    film = np.random.default_rng(5).random((30, 50, 4), dtype=np.float32)
+    bench.dump_outputs(tmp_path / "whole", film)
+    got = np.load(tmp_path / "whole" / "film.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, film)
+    for name in ("a", "b"):
+        bench.dump_outputs(tmp_path / name, film, limit_bytes=3200)    # 24000 B film: 100 of its 1500 pixels
+    a, b = np.load(tmp_path / "a" / "film.npy"), np.load(tmp_path / "b" / "film.npy")
+    assert a.dtype == np.float32 and a.shape == (100, 4) and a.nbytes <= 3200 and np.array_equal(a, b)
+    flat = film.reshape(-1, 4)
+    rows = [int(np.flatnonzero((flat == px).all(1))[0]) for px in a]
+    assert rows == sorted(set(rows))

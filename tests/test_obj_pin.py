@@ -6,8 +6,8 @@ The reference loads OBJ files with tinyobjloader and generates tangents with Mik
 with ``oracle/ref_obj/refobj_harness.cpp``, our restatement of the load flow around
 them. Here the product's ``dcrt_obj_load`` must equal that pipeline bit for bit:
 vertices (position, normal, MikkTSpace tangent, uv), vertex order, triangle order and
-material ids, plus the translated materials. Skipped where /root/reference is absent
-(the GPU box); the CPU suite runs it in the build container.
+material ids, plus the translated materials. Skipped where neither the reference sources
+nor the checker build() compiled from them (oracle/_ref) can be read.
 """
 from __future__ import annotations
 
@@ -24,15 +24,26 @@ GOLDEN = ROOT / "tests" / "golden"
 REF = Path(os.environ.get("DCRT_REFERENCE", "/root/reference"))
 REF_LIB = ROOT / "oracle" / "_ref" / "librefobj.so"
 
-pytestmark = pytest.mark.skipif(not (REF / "tinyobjloader" / "tiny_obj_loader.h").exists(),
-                                reason="reference sources not present (parity pin runs in the build container)")
+
+
+def _have_reference() -> bool:
+    try:
+        return (REF / "tinyobjloader" / "tiny_obj_loader.h").exists()
+    except OSError:     # (a folder this user may not enter counts as absent)
+        return False
+
+
+# runs against the checker build() compiled (oracle/_ref), refreshed where the sources can be read
+pytestmark = pytest.mark.skipif(not (_have_reference() or REF_LIB.exists()),
+                                reason="reference sources not present and oracle/_ref/librefobj.so not built")
 
 FIXTURES = sorted(p for p in GOLDEN.rglob("*.obj"))
 
 
 @pytest.fixture(scope="module")
 def ref():
-    subprocess.run(["make", "-s", "-C", str(ROOT / "oracle" / "ref_obj"), f"REF={REF}"], check=True)
+    if _have_reference():
+        subprocess.run(["make", "-s", "-C", str(ROOT / "oracle" / "ref_obj"), f"REF={REF}"], check=True)
     lib = C.CDLL(str(REF_LIB))
     lib.refobj_load.argtypes = [C.c_char_p, C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]
     lib.refobj_mesh_count.argtypes = [C.c_void_p]

@@ -7,7 +7,7 @@ for pass in $(seq 1 ${PASSES:-2}); do
 for cfg in ${AB_CONFIGS:-spaceship}; do
 while read -r name args; do
   [ -z "$name" ] && continue
-  timeout -k 10 200 python bench.py --config $cfg --steps ${AB_STEPS:-16} --warmup 1 --no-cpu-baseline \
+  timeout -k 10 200 python bench.py --full --config $cfg --steps ${AB_STEPS:-16} --warmup 1 --no-cpu-baseline \
       --spaceship-spp 0 --roofline-images 1 $args > gpurun_out/abb_${name}_$cfg.log 2>&1 || exit $?
   echo "$name $cfg $(python -c "import json;d=json.load(open('gpurun_out/abb_${name}_$cfg.log'));print(d['ms_per_spp'], d['repeat_ms_per_spp'])")"
 done <<< "${AB_VARIANTS}"

@@ -12,7 +12,7 @@ for lib in "$ROOTDIR"/gpu_ab/*.so; do
   OUT="$ROOTDIR/gpurun_out/abk_${n}_$pass"
   mkdir -p "$OUT"
   DCRT_LIB=$lib timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$OUT" -o trace -- \
-      python3 "$ROOTDIR/bench.py" --steps ${AB_IMAGES:-64} --warmup 0 --no-cpu-baseline --streams 1 \
+      python3 "$ROOTDIR/bench.py" --full --steps ${AB_IMAGES:-64} --warmup 0 --no-cpu-baseline --streams 1 \
       ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1 || exit $?
   python3 - "$OUT/trace_kernel_stats.csv" "$n" <<'PY'
 import csv, sys

@@ -3,10 +3,11 @@
 # BASELINE config at 16 spp (one JSON line each), each under its own time limit.
 set -e
 TAG=${TAG:-r06}
-mkdir -p gpurun_out
-timeout -k 10 300 python bench.py --steps 20 > gpurun_out/${TAG}_bench_s20.json
-timeout -k 10 400 python bench.py > gpurun_out/${TAG}_bench_default.json
-: > gpurun_out/${TAG}_configs.jsonl
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
+timeout -k 10 300 python bench.py --full --steps 20 > $OUT/${TAG}_bench_s20.json
+timeout -k 10 400 python bench.py --full > $OUT/${TAG}_bench_default.json
+: > $OUT/${TAG}_configs.jsonl
 for c in cornell coffee "coffee --no-multiscattering" spaceship spaceship_close lamp; do
-  timeout -k 10 300 python bench.py --config $c --steps 16 --no-cpu-baseline --spaceship-spp 0 >> gpurun_out/${TAG}_configs.jsonl
+  timeout -k 10 300 python bench.py --full --config $c --steps 16 --no-cpu-baseline --spaceship-spp 0 >> $OUT/${TAG}_configs.jsonl
 done

@@ -10,7 +10,7 @@ cd /tmp
 for spec in "cornell 8" "spaceship 4" "spaceship_close 2" "coffee 4"; do
   set -- $spec
   timeout -s KILL 300 rocprofv3 --pmc SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_VALU GRBM_GUI_ACTIVE --kernel-trace -f csv -d "$OUT" -o "$1" -- \
-      python3 "$ROOTDIR/bench.py" --config "$1" --steps "$2" --warmup 0 --no-cpu-baseline --streams 1 --repeats 1 --spaceship-spp 0 --roofline-images 1 > "$OUT/$1.log" 2>&1
+      python3 "$ROOTDIR/bench.py" --full --config "$1" --steps "$2" --warmup 0 --no-cpu-baseline --streams 1 --repeats 1 --spaceship-spp 0 --roofline-images 1 > "$OUT/$1.log" 2>&1
   rc=$?; echo "$1 rc=$rc"; [ $rc -eq 0 ] || exit $rc
 done
 python3 - "$OUT" <<'PY'

@@ -14,7 +14,7 @@ IFS=';' read -ra groups <<< "${PMC_GROUPS:-SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLE
 for grp in "${groups[@]}"; do
   i=$((i+1))
   timeout -k 10 120 rocprofv3 --pmc $grp --kernel-trace -f csv -d "$OUT" -o pass$i -- \
-      python3 "$ROOTDIR/bench.py" --steps ${PMC_IMAGES:-8} --warmup 0 --streams 1 --roofline-images 1 --no-cpu-baseline \
+      python3 "$ROOTDIR/bench.py" --full --steps ${PMC_IMAGES:-8} --warmup 0 --streams 1 --roofline-images 1 --no-cpu-baseline \
       ${BENCH_ARGS:-} > "$OUT/pass$i.log" 2>&1
   rc=$?; echo "pass $i ($grp) rc=$rc"; [ $rc -eq 0 ] || exit $rc
 done

@@ -12,7 +12,7 @@ for lib in "$ROOTDIR"/gpu_ab/*.so; do
   OUT="$ROOTDIR/gpurun_out/pmcl_$n"
   mkdir -p "$OUT"
   DCRT_LIB=$lib timeout -k 10 120 rocprofv3 --pmc ${PMC_COUNTERS:-SQ_INSTS_VALU SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY GRBM_GUI_ACTIVE} \
-      --kernel-trace -f csv -d "$OUT" -o p -- python3 "$ROOTDIR/bench.py" --steps 8 --warmup 0 --streams 1 \
+      --kernel-trace -f csv -d "$OUT" -o p -- python3 "$ROOTDIR/bench.py" --full --steps 8 --warmup 0 --streams 1 \
       --roofline-images 1 --no-cpu-baseline > "$OUT/bench.log" 2>&1 || exit $?
   python3 - "$OUT/p_counter_collection.csv" "$n" "${KERNEL:-material_kernel}" "${DISPATCH:-1}" <<'PY'
 import collections, csv, sys

@@ -15,7 +15,7 @@ for S in ${PROF_STEPS:-20 64}; do
   # ONE pipeline (--streams 1), no warmup: every cast launch of the run is then one of the
   # S-image workload the bench's roofline leg times (always one pipeline), so the
   # kernel-stats average is comparable with roofline.avg_launch_us
-  ARGS="--steps $S --warmup 0 --no-cpu-baseline --streams 1 ${PROF_ARGS:-}"
+  ARGS="--full --steps $S --warmup 0 --no-cpu-baseline --streams 1 ${PROF_ARGS:-}"
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d "$OUT" -o trace -- \
       python3 "$ROOTDIR/bench.py" $ARGS > "$OUT/trace_bench.log" 2>&1
   rc=$?; echo "trace S=$S rc=$rc"; [ $rc -eq 0 ] || exit $rc
@@ -31,6 +31,6 @@ if [ -z "${NO_DEFAULT_TRACE:-}" ]; then
   OUT="$ROOTDIR/gpurun_out/prof"
   mkdir -p "$OUT"
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d "$OUT" -o trace_default -- \
-      python3 "$ROOTDIR/bench.py" --no-cpu-baseline ${PROF_ARGS:-} > "$OUT/trace_default_bench.log" 2>&1
+      python3 "$ROOTDIR/bench.py" --full --no-cpu-baseline ${PROF_ARGS:-} > "$OUT/trace_default_bench.log" 2>&1
   rc=$?; echo "trace (default command) rc=$rc"; [ $rc -eq 0 ] || exit $rc
 fi
