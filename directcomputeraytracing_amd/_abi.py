@@ -27,6 +27,13 @@ FEATURE_ALLOW_ANYHIT = 0x10
 FEATURE_DEFAULT = FEATURE_GGX_SAMPLE_VNDF | FEATURE_LIGHT_VISIBLE | FEATURE_WATERTIGHT
 FILTER_BOX, FILTER_TRIANGLE, FILTER_GAUSSIAN, FILTER_MITCHELL, FILTER_LANCZOS = range(5)
 MATERIAL_DIFFUSE, MATERIAL_PLASTIC, MATERIAL_CONDUCTOR, MATERIAL_DIELECTRIC, MATERIAL_THIN_DIELECTRIC = range(5)
+MAX_LIGHT_COUNT = 5000
+# DCRT_DIRTY_*: what dcrt_scene_acquire_dirty reports
+DIRTY_LIGHTS = 0x01
+DIRTY_MATERIALS = 0x02
+DIRTY_INSTANCE_FLAGS = 0x04
+DIRTY_CAMERA = 0x08
+DIRTY_SCENE = 0x10
 
 
 class Vertex(C.Structure):
@@ -143,6 +150,12 @@ class TracerInfo(C.Structure):
                 ("cast_waves_per_cu", C.c_uint32)]
 
 
+class UploadStats(C.Structure):
+    _fields_ = [("scene_uploads", C.c_uint64), ("material_updates", C.c_uint64), ("light_updates", C.c_uint64),
+                ("instance_flag_updates", C.c_uint64), ("geometry_bytes", C.c_uint64), ("shading_bytes", C.c_uint64),
+                ("graph_invalidations", C.c_uint64)]
+
+
 class MaterialSetting(C.Structure):
     _fields_ = [("albedo", C.c_float * 3), ("roughness", C.c_float), ("ior", C.c_float * 3), ("opacity", C.c_float),
                 ("k", C.c_float * 3), ("tiling", C.c_float * 2), ("material_type", C.c_uint32),
@@ -189,6 +202,11 @@ SIGNATURES = [
     ("dcrt_scene_reset", _I, [_P, _U, _U]),
     ("dcrt_scene_load_from_file", _I, [_P, C.c_char_p]),
     ("dcrt_scene_add_punctual_light", _I, [_P, _FP, _FP, _FP, _I]),
+    ("dcrt_scene_set_punctual_light", _I, [_P, _U, _FP, _FP, _FP, _I]),
+    ("dcrt_scene_remove_punctual_light", _I, [_P, _U]),
+    ("dcrt_scene_remove_environment_light", _I, [_P]),
+    ("dcrt_scene_acquire_dirty", _I, [_P, C.POINTER(C.c_uint32)]),
+    ("dcrt_scene_flatten", _I, [_P]),
     ("dcrt_scene_set_environment_light", _I, [_P, _FP, _FP, _U]),
     ("dcrt_scene_set_camera", _I, [_P, _FP, _FP]),
     ("dcrt_scene_set_lens", _I, [_P, _I, C.c_float, C.c_float, C.c_float, C.c_float, _U, C.c_float, _FP]),
@@ -226,6 +244,10 @@ SIGNATURES = [
     ("dcrt_tracer_create", _I, [C.POINTER(TracerConfig), C.POINTER(_P)]),
     ("dcrt_tracer_destroy", None, [_P]),
     ("dcrt_tracer_upload_scene", _I, [_P, C.POINTER(FlatScene)]),
+    ("dcrt_tracer_update_materials", _I, [_P, C.POINTER(Material), _U]),
+    ("dcrt_tracer_update_lights", _I, [_P, C.POINTER(Light), _U]),
+    ("dcrt_tracer_update_instance_flags", _I, [_P, C.POINTER(C.c_uint32), _U]),
+    ("dcrt_tracer_upload_stats", _I, [_P, C.POINTER(UploadStats)]),
     ("dcrt_tracer_set_frame_params", _I, [_P, C.POINTER(FrameParams)]),
     ("dcrt_tracer_set_film_partition", _I, [_P, C.POINTER(FilmPartition)]),
     ("dcrt_tracer_set_film_bands", _I, [_P, C.POINTER(C.c_uint32), _U, _U]),

@@ -470,6 +470,16 @@ struct dcrt_tracer {
     bool virtualStart = true;          // virtual batch starts where the cast kernel has them (DCRT_VIRTUAL_START=0: off)
     uint32_t sceneCaps = kCapAll;      // what the uploaded scene uses (kCap* of dscene.h)
     uint32_t materialCaps = kCapAll;   // the MATERIAL variant launched for it
+    // The arrays the partial updates replace (UpdateMaterials / UpdateLights / UpdateInstanceFlags):
+    // their device buffers, and host copies of the two that DeriveShading reads. The lights
+    // buffer holds DCRT_MAX_LIGHT_COUNT entries, so a changed count never moves it.
+    dcrt_material* dMaterials = nullptr;
+    dcrt_light* dLights = nullptr;
+    uint32_t* dInstanceFlags = nullptr;
+    std::vector<dcrt_material> hostMaterials;
+    std::vector<dcrt_light> hostLights;
+    uint32_t cuCount = 1;              // compute units (the persistent grids' factor)
+    dcrt_upload_stats uploadStats{};
 
     dcrt_bxdf_luts* dLuts = nullptr;
     Film film{};
@@ -554,6 +564,13 @@ struct dcrt_tracer {
     int Create(const dcrt_tracer_config& cfg);
     int BuildLuts();
     int UploadScene(const dcrt_flat_scene& s);
+    void DeriveShading();
+    int DeriveDrainGrid();
+    int RederiveShading();
+    int UpdateMaterials(const dcrt_material* materials, uint32_t count);
+    int UpdateLights(const dcrt_light* lights, uint32_t count);
+    int UpdateInstanceFlags(const uint32_t* flags, uint32_t count);
+    int CheckFrameLights() const;
     int SetFrame(const dcrt_frame_params& p);
     int SetPartition(const dcrt_film_partition& p);
     int SetBands(const uint32_t* b, uint32_t count, uint32_t halo);
@@ -578,6 +595,8 @@ struct dcrt_tracer {
     int Accumulate(const dcrt_filter_params& filter);
     void InvalidateGraph()
     {
+        for (const GraphCache& g : graphs)
+            if (g.exec) { ++uploadStats.graph_invalidations; break; }   // (a drop of captured graphs, not of none)
         for (GraphCache& g : graphs) {
             if (g.exec) (void)hipGraphExecDestroy(g.exec);
             g.exec = nullptr;
@@ -784,26 +803,175 @@ int dcrt_tracer::BuildLuts()
     return DCRT_OK;
 }
 
+// What UploadScene and the partial updates ask of the three arrays an edit replaces.
+static int ValidateMaterials(const dcrt_material* materials, uint32_t count)
+{
+    if (!materials || count == 0) { SetLastError("no materials"); return DCRT_E_INVALID_ARG; }
+    return DCRT_OK;
+}
+static int ValidateLights(const dcrt_light* lights, uint32_t count)
+{
+    if (count > DCRT_MAX_LIGHT_COUNT) { SetLastError("more than 5000 lights"); return DCRT_E_LIMIT; }
+    if (!lights && count) { SetLastError("no light array"); return DCRT_E_INVALID_ARG; }
+    return DCRT_OK;
+}
+static int ValidateInstanceFlags(const uint32_t* flags, uint32_t count)
+{
+    if (!flags || count == 0) { SetLastError("no instance flags"); return DCRT_E_INVALID_ARG; }
+    return DCRT_OK;
+}
+
+// Everything the tracer derives from the materials and the lights (hostMaterials, hostLights;
+// the triangle / instance counts and the cube of `scene`): the MATERIAL / drain variant and
+// MATERIAL's LDS scene copy, written to all the DeviceScene copies in use. UploadScene and the
+// partial updates both come here.
+void dcrt_tracer::DeriveShading()
+{
+    const uint32_t materialCount = (uint32_t)hostMaterials.size(), lightCount = (uint32_t)hostLights.size();
+    // MATERIAL variant: the smallest compiled one whose capabilities cover the scene
+    sceneCaps = scene.envCube ? kCapEnvCube : 0u;
+    for (const dcrt_material& m : hostMaterials) {
+        const uint32_t type = m.flags & DCRT_MATERIAL_FLAG_TYPE_MASK;
+        sceneCaps |= type <= DCRT_MATERIAL_TYPE_THIN_DIELECTRIC ? (1u << type) : kCapAll;
+        if (m.flags & DCRT_MATERIAL_FLAG_MULTISCATTERING) sceneCaps |= kCapMultiscatter;
+        if (m.albedo_texture_index != -1 || (m.flags & DCRT_MATERIAL_FLAG_ROUGHNESS_TEXTURE)) sceneCaps |= kCapTextures;
+    }
+    for (const dcrt_light& l : hostLights) sceneCaps |= (l.flags & 0xFu) << kCapLightShift;
+    materialCaps = (sceneCaps & ~kCapOpaqueDelta) == 0u ? kCapOpaqueDelta : kCapAll;
+    if (const char* g = std::getenv("DCRT_MATERIAL_GENERIC")) {   // A/B: always the generic variant
+        if (std::atoi(g)) materialCaps = kCapAll;
+    }
+    // MATERIAL's LDS scene copy (material_kernel<CAPS, mode>): the whole shading data of a small
+    // scene (mode 1), else everything but the triangles (mode 2) -- DCRT_MATERIAL_LDS = bytes
+    // budget, 0: off; DCRT_MATERIAL_LDS_PARTIAL=0: no mode 2
+    uint32_t budget = 16384;
+    if (const char* e = std::getenv("DCRT_MATERIAL_LDS")) budget = (uint32_t)std::max(0, std::atoi(e));
+    bool partial = true;
+    if (const char* e = std::getenv("DCRT_MATERIAL_LDS_PARTIAL")) partial = std::atoi(e) != 0;
+    const bool counts = scene.triangleCount > 0 && scene.triangleCount < (1u << 20) && scene.instanceCount < (1u << 20) &&
+                        materialCount < (1u << 20) && lightCount < (1u << 20);
+    const uint64_t whole = material_lds_bytes(scene.triangleCount, scene.instanceCount, materialCount, lightCount);
+    const uint64_t rest = material_lds_bytes(0u, scene.instanceCount, materialCount, lightCount);
+    materialLdsMode = !counts ? 0u : whole <= budget ? 1u : (partial && rest <= budget ? 2u : 0u);
+    materialLds = materialLdsMode == 1 ? (uint32_t)whole : materialLdsMode == 2 ? (uint32_t)rest : 0u;
+    for (DeviceScene* d : { &scene, &sceneFlat, &sceneRing }) {   // (the two variants' copies: unused ones are rewritten with the next upload)
+        d->ldsMaterials = materialLdsMode ? materialCount : 0u;
+        d->ldsLights = materialLdsMode ? lightCount : 0u;
+    }
+}
+
+// drain_kernel's grid: resident workgroups of the variant materialCaps selects
+int dcrt_tracer::DeriveDrainGrid()
+{
+    const void* fn = materialCaps == kCapOpaqueDelta ? (const void*)drain_kernel<kCapOpaqueDelta> : (const void*)drain_kernel<kCapAll>;
+    int drainPerCU = 0;
+    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&drainPerCU, materialCaps == kCapOpaqueDelta ? drain_kernel<kCapOpaqueDelta> : drain_kernel<kCapAll>,
+                                                          (int)castBlock, castLdsFull));
+    drainResident = (uint32_t)std::max(1, std::min(drainPerCU, LdsResident(castLdsFull, fn))) * cuCount;
+    return DCRT_OK;
+}
+
+// After an update replaced the materials or the lights: the derived state again, and the
+// captured graphs dropped exactly when something they bake in changed -- the MATERIAL / drain
+// variant, MATERIAL's LDS bytes, the drain grid or a DeviceScene field (kernels take it by value).
+int dcrt_tracer::RederiveShading()
+{
+    const uint32_t caps = materialCaps, mode = materialLdsMode, lds = materialLds, grid = drainResident;
+    const uint32_t ldsM = scene.ldsMaterials, ldsL = scene.ldsLights;
+    DeriveShading();
+    if (materialCaps != caps) CHECKED(DeriveDrainGrid());
+    if (materialCaps != caps || materialLdsMode != mode || materialLds != lds || drainResident != grid ||
+        scene.ldsMaterials != ldsM || scene.ldsLights != ldsL) {
+        HIPCHECK(hipStreamSynchronize(stream));
+        InvalidateGraph();
+    }
+    return DCRT_OK;
+}
+
+int dcrt_tracer::UpdateMaterials(const dcrt_material* materials, uint32_t count)
+{
+    Annotation an("UpdateMaterials");
+    if (!hasScene) { SetLastError("no scene uploaded"); return DCRT_E_NO_SCENE; }
+    CHECKED(ValidateMaterials(materials, count));
+    if (count != hostMaterials.size()) { SetLastError("material count differs from the uploaded scene's"); return DCRT_E_INVALID_ARG; }
+    // (the host copy is the copy's source: the caller's array is free on return)
+    HIPCHECK(hipStreamSynchronize(stream));
+    hostMaterials.assign(materials, materials + count);
+    HIPCHECK(hipMemcpyAsync(dMaterials, hostMaterials.data(), (size_t)count * sizeof(dcrt_material), hipMemcpyHostToDevice, stream));
+    uploadStats.shading_bytes += (uint64_t)count * sizeof(dcrt_material);
+    ++uploadStats.material_updates;
+    CHECKED(RederiveShading());
+    HIPCHECK(hipStreamSynchronize(stream));
+    return DCRT_OK;
+}
+
+int dcrt_tracer::UpdateLights(const dcrt_light* lights, uint32_t count)
+{
+    Annotation an("UpdateLights");
+    if (!hasScene) { SetLastError("no scene uploaded"); return DCRT_E_NO_SCENE; }
+    CHECKED(ValidateLights(lights, count));
+    HIPCHECK(hipStreamSynchronize(stream));
+    if (count) hostLights.assign(lights, lights + count);
+    else hostLights.clear();
+    if (count) HIPCHECK(hipMemcpyAsync(dLights, hostLights.data(), (size_t)count * sizeof(dcrt_light), hipMemcpyHostToDevice, stream));
+    uploadStats.shading_bytes += (uint64_t)count * sizeof(dcrt_light);
+    ++uploadStats.light_updates;
+    CHECKED(RederiveShading());
+    HIPCHECK(hipStreamSynchronize(stream));
+    return DCRT_OK;
+}
+
+int dcrt_tracer::UpdateInstanceFlags(const uint32_t* flags, uint32_t count)
+{
+    Annotation an("UpdateInstanceFlags");
+    if (!hasScene) { SetLastError("no scene uploaded"); return DCRT_E_NO_SCENE; }
+    CHECKED(ValidateInstanceFlags(flags, count));
+    if (count != scene.instanceCount) { SetLastError("instance count differs from the uploaded scene's"); return DCRT_E_INVALID_ARG; }
+    // nothing is derived from the flags; the copy is done on return (the caller's array is free)
+    HIPCHECK(hipMemcpyAsync(dInstanceFlags, flags, (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+    uploadStats.shading_bytes += (uint64_t)count * sizeof(uint32_t);
+    ++uploadStats.instance_flag_updates;
+    return DCRT_OK;
+}
+
+// The frame's lights index the lights buffer (BeginImage: fc.lightCount): refuse more than it holds
+int dcrt_tracer::CheckFrameLights() const
+{
+    if (hasScene && frame.light_count > hostLights.size()) {
+        SetLastError("frame light_count " + std::to_string(frame.light_count) + " exceeds the " + std::to_string(hostLights.size()) +
+                     " lights uploaded");
+        return DCRT_E_INVALID_ARG;
+    }
+    return DCRT_OK;
+}
+
 int dcrt_tracer::UploadScene(const dcrt_flat_scene& s)
 {
     Annotation an("UploadScene");
-    if (!s.vertices || !s.triangles || !s.bvh_nodes || !s.material_ids || !s.instance_transforms || !s.materials ||
-        !s.instance_light_indices || !s.instance_flags || !s.instance_material_overrides || s.triangle_count == 0 ||
-        s.bvh_node_count == 0 || s.instance_count == 0 || s.material_count == 0) {
+    if (!s.vertices || !s.triangles || !s.bvh_nodes || !s.material_ids || !s.instance_transforms ||
+        !s.instance_light_indices || !s.instance_material_overrides || s.triangle_count == 0 ||
+        s.bvh_node_count == 0 || s.instance_count == 0 || ValidateMaterials(s.materials, s.material_count) != DCRT_OK ||
+        ValidateInstanceFlags(s.instance_flags, s.instance_count) != DCRT_OK) {
         SetLastError("incomplete flat scene");
         return DCRT_E_INVALID_ARG;
     }
-    if (s.light_count > DCRT_MAX_LIGHT_COUNT) { SetLastError("more than 5000 lights"); return DCRT_E_LIMIT; }
+    CHECKED(ValidateLights(s.lights, s.light_count));
     HIPCHECK(hipStreamSynchronize(stream));
     InvalidateGraph();
     FreeAll(&sceneAllocs);
     hasScene = false;
+    ++uploadStats.scene_uploads;
     DeviceScene d{};
-    auto upload = [&](auto** dst, const auto* src, size_t count) -> int {
+    uint64_t* uploaded = &uploadStats.geometry_bytes;   // (shading_bytes around the three arrays an edit replaces)
+    auto upload = [&](auto** dst, const auto* src, size_t count, size_t capacity = 0) -> int {
         using T = std::remove_const_t<std::remove_pointer_t<decltype(src)>>;
         T* p = nullptr;
-        CHECKED(DeviceAlloc(&p, count, &sceneAllocs));
-        if (count && src) HIPCHECK(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, stream));
+        CHECKED(DeviceAlloc(&p, std::max(count, capacity), &sceneAllocs));
+        if (count && src) {
+            HIPCHECK(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, stream));
+            *uploaded += count * sizeof(T);
+        }
         *dst = p;
         return DCRT_OK;
     };
@@ -828,7 +996,9 @@ int dcrt_tracer::UploadScene(const dcrt_flat_scene& s)
     CHECKED(upload(&mids, s.material_ids, s.triangle_count));
     CHECKED(upload(&xf, s.instance_transforms, (size_t)s.instance_count * 2));
     CHECKED(upload(&lidx, s.instance_light_indices, s.instance_count));
+    uploaded = &uploadStats.shading_bytes;
     CHECKED(upload(&iflags, s.instance_flags, s.instance_count));
+    uploaded = &uploadStats.geometry_bytes;
     CHECKED(upload(&ovr, s.instance_material_overrides, s.instance_count));
     // instances whose world->instance matrix is exactly the identity (every OBJ shape):
     // traversal then reuses the world ray instead of transforming it (bit-identical
@@ -843,8 +1013,18 @@ int dcrt_tracer::UploadScene(const dcrt_flat_scene& s)
     }
     uint32_t* ident = nullptr;
     CHECKED(upload(&ident, identity.data(), s.instance_count));
+    uploaded = &uploadStats.shading_bytes;
     CHECKED(upload(&mats, s.materials, s.material_count));
-    CHECKED(upload(&lights, s.lights, std::max<uint32_t>(s.light_count, 1)));
+    // (room for DCRT_MAX_LIGHT_COUNT lights, 5000 x 28 B as the reference allocates: UpdateLights
+    // changes the count in place)
+    CHECKED(upload(&lights, s.lights, s.light_count, DCRT_MAX_LIGHT_COUNT));
+    uploaded = &uploadStats.geometry_bytes;
+    dMaterials = mats;
+    dLights = lights;
+    dInstanceFlags = iflags;
+    hostMaterials.assign(s.materials, s.materials + s.material_count);
+    if (s.light_count) hostLights.assign(s.lights, s.lights + s.light_count);
+    else hostLights.clear();
     float4* triVerts = nullptr;
     float4* triShade = nullptr;
     CHECKED(DeviceAlloc(&triVerts, (size_t)s.triangle_count * 3, &sceneAllocs));
@@ -910,38 +1090,10 @@ int dcrt_tracer::UploadScene(const dcrt_flat_scene& s)
         if (!(misc & 0x4u) && ((misc >> 3) & DCRT_BVHNODE_MISC_MASK_PRIMITIVE_COUNT) > 1u) { d.singlePrimLeaves = 0u; break; }
     }
     scene = d;
-    // MATERIAL variant: the smallest compiled one whose capabilities cover the scene
-    sceneCaps = dEnv ? kCapEnvCube : 0u;
-    for (uint32_t i = 0; i < s.material_count; ++i) {
-        const dcrt_material& m = s.materials[i];
-        const uint32_t type = m.flags & DCRT_MATERIAL_FLAG_TYPE_MASK;
-        sceneCaps |= type <= DCRT_MATERIAL_TYPE_THIN_DIELECTRIC ? (1u << type) : kCapAll;
-        if (m.flags & DCRT_MATERIAL_FLAG_MULTISCATTERING) sceneCaps |= kCapMultiscatter;
-        if (m.albedo_texture_index != -1 || (m.flags & DCRT_MATERIAL_FLAG_ROUGHNESS_TEXTURE)) sceneCaps |= kCapTextures;
-    }
-    for (uint32_t i = 0; i < s.light_count; ++i) sceneCaps |= (s.lights[i].flags & 0xFu) << kCapLightShift;
-    materialCaps = (sceneCaps & ~kCapOpaqueDelta) == 0u ? kCapOpaqueDelta : kCapAll;
-    // MATERIAL's LDS scene copy (material_kernel<CAPS, mode>): the whole shading data of a small
-    // scene (mode 1), else everything but the triangles (mode 2) -- DCRT_MATERIAL_LDS = bytes
-    // budget, 0: off; DCRT_MATERIAL_LDS_PARTIAL=0: no mode 2
-    {
-        uint32_t budget = 16384;
-        if (const char* e = std::getenv("DCRT_MATERIAL_LDS")) budget = (uint32_t)std::max(0, std::atoi(e));
-        bool partial = true;
-        if (const char* e = std::getenv("DCRT_MATERIAL_LDS_PARTIAL")) partial = std::atoi(e) != 0;
-        const bool counts = s.triangle_count > 0 && s.triangle_count < (1u << 20) && s.instance_count < (1u << 20) &&
-                            s.material_count < (1u << 20) && s.light_count < (1u << 20);
-        const uint64_t whole = material_lds_bytes(s.triangle_count, s.instance_count, s.material_count, s.light_count);
-        const uint64_t rest = material_lds_bytes(0u, s.instance_count, s.material_count, s.light_count);
-        materialLdsMode = !counts ? 0u : whole <= budget ? 1u : (partial && rest <= budget ? 2u : 0u);
-        materialLds = materialLdsMode == 1 ? (uint32_t)whole : materialLdsMode == 2 ? (uint32_t)rest : 0u;
-        d.ldsMaterials = materialLdsMode ? s.material_count : 0u;
-        d.ldsLights = materialLdsMode ? s.light_count : 0u;
-        scene = d;
-    }
-    if (const char* g = std::getenv("DCRT_MATERIAL_GENERIC")) {   // A/B: always the generic variant
-        if (std::atoi(g)) materialCaps = kCapAll;
-    }
+    // the MATERIAL variant and its LDS scene copy (the later copies of d carry the two counts on)
+    DeriveShading();
+    d.ldsMaterials = scene.ldsMaterials;
+    d.ldsLights = scene.ldsLights;
     // LDS stack: [stackSize + 2][block] u32 (two spare rows per lane, see stack_at in
     // dscene.h); keep a workgroup's stack <= 32 KiB
     castBlock = 256;
@@ -1167,13 +1319,8 @@ int dcrt_tracer::UploadScene(const dcrt_flat_scene& s)
         HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&megaPerCU, megakernel<false>, (int)castBlock, castLdsFull));
         megaResident = (uint32_t)std::max(1, std::min(megaPerCU, LdsResident(castLdsFull, (const void*)megakernel<false>))) *
                        (uint32_t)std::max(1, prop.multiProcessorCount);
-        int drainPerCU = 0;
-        HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&drainPerCU, materialCaps == kCapOpaqueDelta ? drain_kernel<kCapOpaqueDelta> : drain_kernel<kCapAll>,
-                                                              (int)castBlock, castLdsFull));
-        drainResident = (uint32_t)std::max(1, std::min(drainPerCU, LdsResident(castLdsFull, materialCaps == kCapOpaqueDelta
-                                                                                                 ? (const void*)drain_kernel<kCapOpaqueDelta>
-                                                                                                 : (const void*)drain_kernel<kCapAll>))) *
-                        (uint32_t)std::max(1, prop.multiProcessorCount);
+        cuCount = (uint32_t)std::max(1, prop.multiProcessorCount);
+        CHECKED(DeriveDrainGrid());
         if (ringRows) {
             // the spill columns: stackSize entries per lane of the persistent ring grid
             uint32_t* spill = nullptr;
@@ -1615,6 +1762,7 @@ int dcrt_tracer::Render(uint32_t maxIterations)
 {
     if (!hasScene) { SetLastError("no scene uploaded"); return DCRT_E_NO_SCENE; }
     if (!hasFrame) { SetLastError("no frame parameters"); return DCRT_E_INVALID_ARG; }
+    CHECKED(CheckFrameLights());
     if (newImage) CHECKED(BeginImage());
     lastSlot = 0;
     CHECKED(RunIterations(maxIterations ? maxIterations : iterationsPerRender));
@@ -1655,6 +1803,7 @@ int dcrt_tracer::RenderImages(uint32_t firstSeed, uint32_t count, const dcrt_fil
     Annotation an("RenderImages");
     if (!hasScene) { SetLastError("no scene uploaded"); return DCRT_E_NO_SCENE; }
     if (!hasFrame) { SetLastError("no frame parameters"); return DCRT_E_INVALID_ARG; }
+    CHECKED(CheckFrameLights());
     if (count == 0) return DCRT_OK;
     if (partition.world_size > 1 || !bands.empty()) {
         // a partitioned film's convolution reads the filter's window rows beyond its stripes
@@ -1830,6 +1979,34 @@ DCRT_API int dcrt_tracer_upload_scene(dcrt_tracer* t, const dcrt_flat_scene* s)
     TRACER_GUARD(t);
     if (!s) return DCRT_E_INVALID_ARG;
     return t->UploadScene(*s);
+}
+
+DCRT_API int dcrt_tracer_update_materials(dcrt_tracer* t, const dcrt_material* materials, uint32_t material_count)
+{
+    if (!t || !materials) return DCRT_E_INVALID_ARG;   // (before any device call)
+    TRACER_GUARD(t);
+    return t->UpdateMaterials(materials, material_count);
+}
+
+DCRT_API int dcrt_tracer_update_lights(dcrt_tracer* t, const dcrt_light* lights, uint32_t light_count)
+{
+    if (!t || (!lights && light_count)) return DCRT_E_INVALID_ARG;   // (no lights: a null array is fine)
+    TRACER_GUARD(t);
+    return t->UpdateLights(lights, light_count);
+}
+
+DCRT_API int dcrt_tracer_update_instance_flags(dcrt_tracer* t, const uint32_t* flags, uint32_t instance_count)
+{
+    if (!t || !flags) return DCRT_E_INVALID_ARG;
+    TRACER_GUARD(t);
+    return t->UpdateInstanceFlags(flags, instance_count);
+}
+
+DCRT_API int dcrt_tracer_upload_stats(dcrt_tracer* t, dcrt_upload_stats* out)
+{
+    if (!t || !out) return DCRT_E_INVALID_ARG;
+    *out = t->uploadStats;
+    return DCRT_OK;
 }
 
 DCRT_API int dcrt_tracer_set_frame_params(dcrt_tracer* t, const dcrt_frame_params* p)

@@ -22,6 +22,10 @@ struct dcrt_scene {
     // reset or loads more content (the pointers handed out stay valid until then)
     std::vector<std::vector<uint32_t>> loadedIndices, loadedMaterialIds;
     void DropLoadedBuffers() { loadedIndices.clear(); loadedMaterialIds.clear(); }
+    // DCRT_DIRTY_*: what the edits since the last dcrt_scene_acquire_dirty left for the tracer
+    // to pick up (Scene.h:211-215 m_Is*GPUBufferDirty, Camera.h:14 m_IsDirty)
+    uint32_t dirty = 0;
+    bool HasCube() const { return scene.hasEnvironmentLight && scene.environmentLight.cubeSize != 0; }
 };
 
 using dcrt::SetLastError;
@@ -63,6 +67,7 @@ DCRT_API int dcrt_scene_reset(dcrt_scene* s, uint32_t w, uint32_t h)
     if (!s || !w || !h) return DCRT_E_INVALID_ARG;
     s->DropLoadedBuffers();
     s->scene.Reset(w, h);
+    s->dirty |= DCRT_DIRTY_SCENE;
     return DCRT_OK;
 }
 
@@ -72,6 +77,7 @@ DCRT_API int dcrt_scene_load_from_file(dcrt_scene* s, const char* path)
     DCRT_GUARD_BEGIN
     SetLastError("");
     s->DropLoadedBuffers();
+    s->dirty |= DCRT_DIRTY_SCENE;
     if (!s->scene.LoadFromFile(path)) {
         const std::string detail = dcrt_last_error();
         SetLastError(std::string("failed to load scene ") + path + (detail.empty() ? "" : ": " + detail));
@@ -91,13 +97,73 @@ DCRT_API int dcrt_scene_add_punctual_light(dcrt_scene* s, const float position[3
     l.color = dcrt::Float3(color[0], color[1], color[2]);
     l.isDirectional = is_directional != 0;
     s->scene.punctualLights.push_back(l);
+    s->scene.FlattenLights();
+    s->dirty |= DCRT_DIRTY_LIGHTS;
+    return DCRT_OK;
+}
+
+// The UI's punctual-light fields (ImGui.cpp:468-497)
+DCRT_API int dcrt_scene_set_punctual_light(dcrt_scene* s, uint32_t index, const float position[3], const float euler[3],
+                                           const float color[3], int is_directional)
+{
+    if (!s || !position || !euler || !color || index >= s->scene.punctualLights.size()) return DCRT_E_INVALID_ARG;
+    dcrt::SPunctualLight& l = s->scene.punctualLights[index];
+    l.position = dcrt::Float3(position[0], position[1], position[2]);
+    l.eulerAngles = dcrt::Float3(euler[0], euler[1], euler[2]);
+    l.color = dcrt::Float3(color[0], color[1], color[2]);
+    l.isDirectional = is_directional != 0;
+    s->scene.FlattenLights();
+    s->dirty |= DCRT_DIRTY_LIGHTS;
+    return DCRT_OK;
+}
+
+// The UI's Delete on a selected punctual light (ImGui.cpp:351-372)
+DCRT_API int dcrt_scene_remove_punctual_light(dcrt_scene* s, uint32_t index)
+{
+    if (!s || index >= s->scene.punctualLights.size()) return DCRT_E_INVALID_ARG;
+    s->scene.punctualLights.erase(s->scene.punctualLights.begin() + index);
+    s->scene.FlattenLights();
+    s->dirty |= DCRT_DIRTY_LIGHTS;
+    return DCRT_OK;
+}
+
+// ... and on the environment light: a removed cube is a scene reload (ImGui.cpp:360-366)
+DCRT_API int dcrt_scene_remove_environment_light(dcrt_scene* s)
+{
+    if (!s) return DCRT_E_INVALID_ARG;
+    if (!s->scene.hasEnvironmentLight) { SetLastError("the scene has no environment light"); return DCRT_E_INVALID_ARG; }
+    s->dirty |= s->HasCube() ? DCRT_DIRTY_SCENE : DCRT_DIRTY_LIGHTS;
+    s->scene.hasEnvironmentLight = false;
+    s->scene.environmentLight = dcrt::SEnvironmentLight();
+    s->scene.FlattenLights();
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_scene_acquire_dirty(dcrt_scene* s, uint32_t* out_bits)
+{
+    if (!s || !out_bits) return DCRT_E_INVALID_ARG;
+    *out_bits = s->dirty;
+    s->dirty = 0;
+    return DCRT_OK;
+}
+
+// Every flat array again: what each edit did before it re-flattened only its own part.
+DCRT_API int dcrt_scene_flatten(dcrt_scene* s)
+{
+    if (!s) return DCRT_E_INVALID_ARG;
+    if (!s->scene.hasValidScene) { SetLastError("scene has no content"); return DCRT_E_NO_SCENE; }
+    DCRT_GUARD_BEGIN
     s->scene.Flatten();
     return DCRT_OK;
+    DCRT_GUARD_END
 }
 
 DCRT_API int dcrt_scene_set_environment_light(dcrt_scene* s, const float color[3], const float* cube, uint32_t cube_size)
 {
     if (!s || !color) return DCRT_E_INVALID_ARG;
+    // a cube that appears, disappears or changes is a scene reload (ImGui.cpp:520-538); the
+    // colour alone is the lights buffer
+    s->dirty |= (s->HasCube() || (cube && cube_size)) ? DCRT_DIRTY_SCENE : DCRT_DIRTY_LIGHTS;
     s->scene.hasEnvironmentLight = true;
     s->scene.environmentLight.color = dcrt::Float3(color[0], color[1], color[2]);
     if (cube && cube_size) {
@@ -107,7 +173,7 @@ DCRT_API int dcrt_scene_set_environment_light(dcrt_scene* s, const float color[3
         s->scene.environmentLight.cubeSize = 0;
         s->scene.environmentLight.cubeRGB.clear();
     }
-    s->scene.Flatten();
+    s->scene.FlattenLights();
     return DCRT_OK;
 }
 
@@ -116,6 +182,7 @@ DCRT_API int dcrt_scene_set_camera(dcrt_scene* s, const float position[3], const
     if (!s || !position || !euler) return DCRT_E_INVALID_ARG;
     s->scene.camera.position = dcrt::Float3(position[0], position[1], position[2]);
     s->scene.camera.eulerAngles = dcrt::Float3(euler[0], euler[1], euler[2]);
+    s->dirty |= DCRT_DIRTY_CAMERA;
     return DCRT_OK;
 }
 
@@ -131,6 +198,7 @@ DCRT_API int dcrt_scene_set_lens(dcrt_scene* s, int camera_type, float fov_x, fl
     s->scene.apertureBladeCount = blade_count;
     s->scene.apertureRotation = aperture_rotation;
     if (film_size) s->scene.filmSize = { film_size[0], film_size[1] };
+    s->dirty |= DCRT_DIRTY_CAMERA;
     return DCRT_OK;
 }
 
@@ -175,17 +243,18 @@ DCRT_API int dcrt_scene_get_material_count(const dcrt_scene* s, uint32_t* out)
     return DCRT_OK;
 }
 
-// Material edits: mesh OPAQUE flags (Scene.cpp:57-80) and the flattened buffers
-// (instance flags, Scene.cpp:785-800) follow the materials.
-static void RefreshMaterials(dcrt_scene* s)
+// Material edits re-flatten the materials (UpdateMaterialGPUData, Scene.cpp:742-774); an opacity
+// edit also the mesh OPAQUE flags and the instance flags that follow them (SetMeshFlagsDirty,
+// ImGui.cpp:639-650; Scene.cpp:62-90, 662-670, 776-807). No geometry array is touched.
+static void RefreshMaterials(dcrt_scene* s, bool opacityChanged)
 {
+    s->dirty |= DCRT_DIRTY_MATERIALS | (opacityChanged ? DCRT_DIRTY_INSTANCE_FLAGS : 0u);
     if (!s->scene.hasValidScene) return;
-    for (size_t i = 0; i < s->scene.meshes.size(); ++i) {
-        bool opaque = true;
-        for (uint32_t id : s->scene.meshes[i].materialIds) opaque = opaque && s->scene.materials[id].IsOpaque();
-        s->scene.meshOpaque[i] = opaque;
+    s->scene.FlattenMaterials();
+    if (opacityChanged) {
+        s->scene.RebuildMeshFlags();
+        s->scene.FlattenInstanceFlags();
     }
-    s->scene.Flatten();
 }
 
 DCRT_API int dcrt_scene_set_material(dcrt_scene* s, uint32_t index, int type, const float albedo[3], float roughness,
@@ -200,7 +269,7 @@ DCRT_API int dcrt_scene_set_material(dcrt_scene* s, uint32_t index, int type, co
     if (k) m.k = dcrt::Float3(k[0], k[1], k[2]);
     m.multiscattering = multiscattering != 0;
     m.isTwoSided = two_sided != 0;
-    RefreshMaterials(s);
+    RefreshMaterials(s, false);
     return DCRT_OK;
 }
 
@@ -234,7 +303,7 @@ DCRT_API int dcrt_scene_set_material_multiscattering(dcrt_scene* s, uint32_t ind
         return DCRT_E_INVALID_ARG;
     }
     m.multiscattering = enable != 0;
-    RefreshMaterials(s);
+    RefreshMaterials(s, false);
     return DCRT_OK;
 }
 
@@ -246,7 +315,7 @@ DCRT_API int dcrt_scene_set_material_opacity(dcrt_scene* s, uint32_t index, floa
     dcrt::SMaterial& m = s->scene.materials[index];
     m.opacity = opacity;
     m.opacityTextureIndex = opacity_texture_index;
-    RefreshMaterials(s);
+    RefreshMaterials(s, true);
     return DCRT_OK;
 }
 

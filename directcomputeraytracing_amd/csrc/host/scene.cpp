@@ -231,13 +231,7 @@ bool CScene::LoadFromFile(const std::string& path)
         reorderedInstanceIndices.assign(instanceCount, 0);
         for (uint32_t r = 0; r < instanceCount; ++r) reorderedInstanceIndices[originalInstanceIndices[r]] = r;
     }
-    // Mesh flags (Scene.cpp:62-90)
-    meshOpaque.resize(meshes.size());
-    for (size_t i = 0; i < meshes.size(); ++i) {
-        bool opaque = true;
-        for (uint32_t id : meshes[i].materialIds) opaque = opaque && materials[id].IsOpaque();
-        meshOpaque[i] = opaque;
-    }
+    RebuildMeshFlags();
     uint64_t totalNodes = tlas.size();
     for (const Mesh& m : meshes) totalNodes += m.bvhNodes.size();
     if (totalNodes > 2147483647ull) return false;   // Scene.cpp:266-271
@@ -267,7 +261,26 @@ void CScene::FillMaterial(dcrt_material* out, const SMaterial& s) const
 
 static inline float AsFloat(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 
+// Mesh flags (Scene.cpp:62-90)
+void CScene::RebuildMeshFlags()
+{
+    meshOpaque.resize(meshes.size());
+    for (size_t i = 0; i < meshes.size(); ++i) {
+        bool opaque = true;
+        for (uint32_t id : meshes[i].materialIds) opaque = opaque && materials[id].IsOpaque();
+        meshOpaque[i] = opaque;
+    }
+}
+
 void CScene::Flatten()
+{
+    FlattenGeometry();
+    FlattenInstanceFlags();
+    FlattenMaterials();
+    FlattenLights();
+}
+
+void CScene::FlattenGeometry()
 {
     const uint32_t instanceCount = (uint32_t)meshInstances.size();
     // vertices (Scene.cpp:273-300)
@@ -327,7 +340,24 @@ void CScene::Flatten()
     flatLightIndices_.assign(instanceCount, DCRT_LIGHT_INDEX_INVALID);
     for (uint32_t li = 0; li < meshLights.size(); ++li)
         flatLightIndices_[reorderedInstanceIndices[meshLights[li].instanceIndex]] = li;
-    // instance flags (Scene.cpp:776-807)
+    // material overrides (Scene.cpp:522-552)
+    flatOverrides_.assign(instanceCount, 0u);
+    for (uint32_t i = 0; i < instanceCount; ++i) flatOverrides_[i] = meshInstances[originalInstanceIndices[i]].materialIdOverride;
+    flatTextures_.clear();
+    for (const CTexture& t : textures) {
+        dcrt_texture d{};
+        d.width = t.IsValid() ? t.width : 0;
+        d.height = t.IsValid() ? t.height : 0;
+        d.format = t.format;
+        d.pixels = t.IsValid() ? t.pixels.data() : nullptr;
+        flatTextures_.push_back(d);
+    }
+}
+
+// instance flags (Scene.cpp:776-807)
+void CScene::FlattenInstanceFlags()
+{
+    const uint32_t instanceCount = (uint32_t)meshInstances.size();
     flatInstanceFlags_.assign(instanceCount, 0u);
     for (uint32_t i = 0; i < instanceCount; ++i) {
         const SMeshInstance& inst = meshInstances[originalInstanceIndices[i]];
@@ -335,13 +365,18 @@ void CScene::Flatten()
                                                                           : (bool)meshOpaque[inst.meshIndex];
         flatInstanceFlags_[i] = opaque ? DCRT_INSTANCE_FLAG_OPAQUE : 0u;
     }
-    // material overrides (Scene.cpp:522-552)
-    flatOverrides_.assign(instanceCount, 0u);
-    for (uint32_t i = 0; i < instanceCount; ++i) flatOverrides_[i] = meshInstances[originalInstanceIndices[i]].materialIdOverride;
-    // materials (Scene.cpp:742-774)
+}
+
+// materials (Scene.cpp:742-774)
+void CScene::FlattenMaterials()
+{
     flatMaterials_.assign(materials.size(), dcrt_material{});
     for (size_t i = 0; i < materials.size(); ++i) FillMaterial(&flatMaterials_[i], materials[i]);
-    // lights: mesh, environment, punctual (Scene.cpp:672-735)
+}
+
+// lights: mesh, environment, punctual (Scene.cpp:672-735)
+void CScene::FlattenLights()
+{
     flatLights_.clear();
     {
         std::vector<uint32_t> triOffsets;
@@ -371,15 +406,6 @@ void CScene::Flatten()
             l.flags = pl.isDirectional ? DCRT_LIGHT_FLAGS_DIRECTIONAL_LIGHT : DCRT_LIGHT_FLAGS_POINT_LIGHT;
             flatLights_.push_back(l);
         }
-    }
-    flatTextures_.clear();
-    for (const CTexture& t : textures) {
-        dcrt_texture d{};
-        d.width = t.IsValid() ? t.width : 0;
-        d.height = t.IsValid() ? t.height : 0;
-        d.format = t.format;
-        d.pixels = t.IsValid() ? t.pixels.data() : nullptr;
-        flatTextures_.push_back(d);
     }
 }
 

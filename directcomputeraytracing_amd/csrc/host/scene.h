@@ -91,8 +91,15 @@ public:
     float CalculateFilmDistance() const;           // Scene.cpp:837-842
     float CalculateApertureDiameter() const;       // Scene.cpp:844-847
 
-    // Rebuilds the flat arrays (GPU buffer contents) and returns views of them.
+    // Rebuilds the flat arrays (GPU buffer contents) and returns views of them. Flatten() is
+    // the four parts in turn; an edit re-flattens only the part it changed (the reference's
+    // UpdateMaterial / Light / InstanceFlagsGPUData, Scene.cpp:672-807).
     void Flatten();
+    void FlattenGeometry();        // vertices, triangles, nodes, ids, transforms, light indices, overrides, textures
+    void FlattenMaterials();       // Scene.cpp:742-774
+    void FlattenLights();          // Scene.cpp:672-735
+    void FlattenInstanceFlags();   // Scene.cpp:776-807
+    void RebuildMeshFlags();       // Scene.cpp:62-90
     dcrt_flat_scene GetFlat() const;
     dcrt_frame_params GetFrameParams(uint32_t frameSeed) const;   // WavefrontPathTracer.cpp:372-428
     dcrt_filter_params GetFilterParams() const;

@@ -18,6 +18,13 @@ from ._abi import check, f3
 class Scene:
     """CScene: LoadFromFile / Reset / lights / camera / film settings."""
 
+    # what acquire_dirty() reports (DCRT_DIRTY_*)
+    DIRTY_LIGHTS = _abi.DIRTY_LIGHTS
+    DIRTY_MATERIALS = _abi.DIRTY_MATERIALS
+    DIRTY_INSTANCE_FLAGS = _abi.DIRTY_INSTANCE_FLAGS
+    DIRTY_CAMERA = _abi.DIRTY_CAMERA
+    DIRTY_SCENE = _abi.DIRTY_SCENE
+
     def __init__(self, resolution=(1920, 1080)):
         self._lib = _abi.load_library()
         h = C.c_void_p()
@@ -53,6 +60,28 @@ class Scene:
     def add_directional_light(self, euler_angles, color) -> None:
         check(self._lib.dcrt_scene_add_punctual_light(self._h, f3((0, 0, 0)), f3(euler_angles), f3(color), 1),
               "AddDirectionalLight")
+
+    def set_punctual_light(self, index, position=(0, 0, 0), euler_angles=(0, 0, 0), color=(1, 1, 1),
+                           is_directional: bool = False) -> None:   # ImGui.cpp:468-497
+        check(self._lib.dcrt_scene_set_punctual_light(self._h, int(index), f3(position), f3(euler_angles), f3(color),
+                                                      int(bool(is_directional))), "SetPunctualLight")
+
+    def remove_punctual_light(self, index) -> None:              # ImGui.cpp:351-372
+        check(self._lib.dcrt_scene_remove_punctual_light(self._h, int(index)), "RemovePunctualLight")
+
+    def remove_environment_light(self) -> None:                  # ImGui.cpp:360-366
+        check(self._lib.dcrt_scene_remove_environment_light(self._h), "RemoveEnvironmentLight")
+
+    def acquire_dirty(self) -> int:
+        """The DIRTY_* bits of the edits since the last call (cleared by it): what
+        WavefrontPathTracer.apply_edits takes."""
+        bits = C.c_uint32()
+        check(self._lib.dcrt_scene_acquire_dirty(self._h, C.byref(bits)), "AcquireDirty")
+        return bits.value
+
+    def flatten(self) -> None:
+        """Rebuild every flat array (each edit re-flattens only its own)."""
+        check(self._lib.dcrt_scene_flatten(self._h), "Flatten")
 
     def set_environment_light(self, color, cube: np.ndarray | None = None) -> None:
         if cube is None:

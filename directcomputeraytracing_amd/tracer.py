@@ -68,6 +68,41 @@ class WavefrontPathTracer:
         self.set_frame_params(scene.frame_params(frame_seed))
         self.filter = scene.filter_params()
 
+    # ---- partial scene updates (UpdateMaterial / Light / InstanceFlagsGPUData, Scene.cpp:672-807)
+    def update_materials(self, scene: Scene) -> None:
+        f = scene.flat()
+        check(self._lib.dcrt_tracer_update_materials(self._h, f.materials, f.material_count), "UpdateMaterials")
+
+    def update_lights(self, scene: Scene) -> None:
+        f = scene.flat()
+        check(self._lib.dcrt_tracer_update_lights(self._h, f.lights, f.light_count), "UpdateLights")
+
+    def update_instance_flags(self, scene: Scene) -> None:
+        f = scene.flat()
+        check(self._lib.dcrt_tracer_update_instance_flags(self._h, f.instance_flags, f.instance_count), "UpdateInstanceFlags")
+
+    def upload_stats(self) -> dict:
+        s = _abi.UploadStats()
+        check(self._lib.dcrt_tracer_upload_stats(self._h, C.byref(s)), "UploadStats")
+        return {k: getattr(s, k) for k, _ in _abi.UploadStats._fields_}
+
+    def apply_edits(self, scene: Scene, bits: int, frame_seed: int = 0) -> None:
+        """Bring the tracer up to the scene's edits: `bits` from scene.acquire_dirty() (an
+        argument, so every pipeline of make_pipelines applies the same acquired bits). DIRTY_SCENE
+        is the full on_scene_loaded; otherwise only the arrays the bits name are sent. The frame
+        parameters (camera, light count) are always re-sent. The image is the caller's to restart
+        (reset_image), as in the reference's frame loop."""
+        if bits & _abi.DIRTY_SCENE:
+            self.on_scene_loaded(scene, frame_seed)
+            return
+        if bits & _abi.DIRTY_MATERIALS:
+            self.update_materials(scene)
+        if bits & _abi.DIRTY_LIGHTS:
+            self.update_lights(scene)
+        if bits & _abi.DIRTY_INSTANCE_FLAGS:
+            self.update_instance_flags(scene)
+        self.set_frame_params(scene.frame_params(frame_seed))
+
     def set_frame_params(self, params: _abi.FrameParams) -> None:
         check(self._lib.dcrt_tracer_set_frame_params(self._h, C.byref(params)), "SetFrameParams")
         self.width, self.height = params.resolution[0], params.resolution[1]

@@ -7,6 +7,14 @@
 //   dcrt_render <scene.obj|scene.xml> <width> <height> <spp> <max_bounce> <out.bmp>
 //               [--batch] [--point x y z r g b] [--seed-type sample-count|frame-index|fixed]
 //               [--fixed-seed N] [--iterations N] [--pool N] [--film out.f32] [--samples out.f32]
+//               [--edit N:KIND:ARGS]...
+//
+// --edit (repeatable, frame loop only) edits the scene after N full-resolution images have
+// completed since the start or the previous edit: material:INDEX:TYPE:R,G,B:ROUGHNESS,
+// opacity:INDEX:VALUE, point:X,Y,Z:R,G,B (adds a point light), movepoint:INDEX:X,Y,Z,
+// camera:X,Y,Z. The frame loop takes the edit as the reference's does (a preview frame, the
+// film restarted, only the edited array sent); the run ends once `spp` images have completed
+// after the last edit, and the JSON line gains "edits_applied" and "upload_stats".
 //
 // Frame-loop mode (default) runs frames until `spp` full-resolution images are in the film;
 // --batch instead hands all images to dcrt_tracer_render_images (device-side image
@@ -46,9 +54,100 @@ int Usage(const char* exe)
     std::fprintf(stderr,
                  "usage: %s scene.{obj,xml} width height spp max_bounce out.bmp [--batch] [--point x y z r g b]\n"
                  "       [--seed-type sample-count|frame-index|fixed] [--fixed-seed N] [--iterations N] [--pool N]\n"
-                 "       [--film out.f32] [--samples out.f32]\n",
+                 "       [--film out.f32] [--samples out.f32] [--edit N:KIND:ARGS]...\n",
                  exe);
     return 2;
+}
+
+// --edit N:KIND:ARGS -- a scene edit the frame loop applies after N full-resolution images have
+// completed since the start or the previous edit, as the reference's UI would between two frames
+struct SEdit {
+    uint32_t m_AfterImages = 0;
+    std::string m_Kind;
+    std::vector<std::string> m_Args;   // the ':'-separated fields after KIND
+};
+
+std::vector<std::string> Split(const std::string& s, char sep)
+{
+    std::vector<std::string> out;
+    size_t start = 0;
+    for (;;) {
+        const size_t end = s.find(sep, start);
+        out.push_back(s.substr(start, end == std::string::npos ? std::string::npos : end - start));
+        if (end == std::string::npos) return out;
+        start = end + 1;
+    }
+}
+
+bool ParseFloats(const std::string& s, float* out, size_t count)
+{
+    const std::vector<std::string> parts = Split(s, ',');
+    if (parts.size() != count) return false;
+    for (size_t i = 0; i < count; ++i) {
+        char* end = nullptr;
+        out[i] = std::strtof(parts[i].c_str(), &end);
+        if (end == parts[i].c_str() || *end) return false;
+    }
+    return true;
+}
+
+bool ParseEdit(const char* text, SEdit* edit)
+{
+    const std::vector<std::string> f = Split(text, ':');
+    if (f.size() < 3) return false;
+    char* end = nullptr;
+    edit->m_AfterImages = (uint32_t)std::strtoul(f[0].c_str(), &end, 10);
+    if (end == f[0].c_str() || *end) return false;
+    edit->m_Kind = f[1];
+    edit->m_Args.assign(f.begin() + 2, f.end());
+    const size_t n = edit->m_Args.size();
+    return (edit->m_Kind == "material" && n == 4) || (edit->m_Kind == "opacity" && n == 2) || (edit->m_Kind == "point" && n == 2) ||
+           (edit->m_Kind == "movepoint" && n == 2) || (edit->m_Kind == "camera" && n == 1);
+}
+
+// The edit through the kept host API: the setters re-flatten their own arrays and leave the
+// dirty bits CScene::AcquireEdits moves into the frame loop's flags.
+bool ApplyEdit(dcrt_scene* scene, const SEdit& e)
+{
+    const std::vector<std::string>& a = e.m_Args;
+    if (e.m_Kind == "material") {   // material:INDEX:TYPE:R,G,B:ROUGHNESS
+        const uint32_t index = (uint32_t)std::atoi(a[0].c_str());
+        float albedo[3];
+        dcrt_material_setting m;
+        if (!ParseFloats(a[2], albedo, 3) || !Check(dcrt_scene_get_material_setting(scene, index, &m), "GetMaterialSetting")) return false;
+        return Check(dcrt_scene_set_material(scene, index, std::atoi(a[1].c_str()), albedo, (float)std::atof(a[3].c_str()), nullptr,
+                                             nullptr, (int)m.multiscattering, (int)m.is_two_sided),
+                     "SetMaterial");
+    }
+    if (e.m_Kind == "opacity") {    // opacity:INDEX:VALUE
+        const uint32_t index = (uint32_t)std::atoi(a[0].c_str());
+        dcrt_material_setting m;
+        if (!Check(dcrt_scene_get_material_setting(scene, index, &m), "GetMaterialSetting")) return false;
+        return Check(dcrt_scene_set_material_opacity(scene, index, (float)std::atof(a[1].c_str()), m.opacity_texture_index),
+                     "SetMaterialOpacity");
+    }
+    if (e.m_Kind == "point") {      // point:X,Y,Z:R,G,B
+        float position[3], color[3];
+        const float euler[3] = {0, 0, 0};
+        if (!ParseFloats(a[0], position, 3) || !ParseFloats(a[1], color, 3)) return false;
+        return Check(dcrt_scene_add_punctual_light(scene, position, euler, color, 0), "AddPointLight");
+    }
+    if (e.m_Kind == "movepoint") {  // movepoint:INDEX:X,Y,Z
+        const uint32_t index = (uint32_t)std::atoi(a[0].c_str());
+        float old[3], euler[3], color[3], position[3];
+        int directional = 0;
+        if (!ParseFloats(a[1], position, 3) ||
+            !Check(dcrt_scene_get_punctual_light(scene, index, old, euler, color, &directional), "GetPunctualLight"))
+            return false;
+        return Check(dcrt_scene_set_punctual_light(scene, index, position, euler, color, directional), "SetPunctualLight");
+    }
+    if (e.m_Kind == "camera") {     // camera:X,Y,Z
+        float position[3];
+        dcrt_scene_settings settings;
+        if (!ParseFloats(a[0], position, 3) || !Check(dcrt_scene_get_settings(scene, &settings), "GetSettings")) return false;
+        return Check(dcrt_scene_set_camera(scene, position, settings.camera_euler_angles), "SetCamera");
+    }
+    return false;
 }
 
 }  // namespace
@@ -66,6 +165,7 @@ int main(int argc, char** argv)
     uint32_t fixedSeed = 0, iterations = 16, pool = 0;
     const char* filmPath = nullptr;
     const char* samplesPath = nullptr;
+    std::vector<SEdit> edits;
     for (int i = 7; i < argc; ++i) {
         const bool more = i + 1 < argc;
         if (!std::strcmp(argv[i], "--batch")) {
@@ -91,11 +191,16 @@ int main(int argc, char** argv)
             filmPath = argv[++i];
         } else if (!std::strcmp(argv[i], "--samples") && more) {
             samplesPath = argv[++i];
+        } else if (!std::strcmp(argv[i], "--edit") && more) {
+            SEdit e;
+            if (!ParseEdit(argv[++i], &e)) return Usage(argv[0]);
+            edits.push_back(e);
         } else {
             return Usage(argv[0]);
         }
     }
     if (width == 0 || height == 0 || spp == 0 || iterations == 0) return Usage(argv[0]);
+    if (batch && !edits.empty()) return Usage(argv[0]);   // (edits belong to the frame loop)
 
     // CDirectComputeRayTracing::Init: new + Create (LaunchRendererLoop.cpp:58-64)
     CScene scene;
@@ -123,7 +228,8 @@ int main(int argc, char** argv)
     const auto t0 = std::chrono::steady_clock::now();
     uint32_t firstSeed = 0;
     uint64_t previewFrames = 0;
-    std::vector<uint32_t> seeds;   // frame seed of each full-resolution image, in film order
+    size_t editsApplied = 0;
+    std::vector<uint32_t> seeds;  // frame seed of each full-resolution image, in film order
     if (batch) {
         const dcrt_filter_params filter = MakeFilter(scene);
         if (!Check(dcrt_tracer_clear_film(tracer.GetTracer()), "ClearFilm") ||
@@ -132,8 +238,15 @@ int main(int argc, char** argv)
         for (uint32_t s = 0; s < spp; ++s) seeds.push_back(s);
     } else {
         // RenderOneFrame until spp full-resolution images are in the film
-        const uint64_t maxFrames = (uint64_t)spp * 100000ull + 1000ull;
-        while (seeds.size() < spp) {
+        // (with edits: until spp images have completed after the last one)
+        uint64_t imagesWanted = spp;
+        for (const SEdit& e : edits) imagesWanted += e.m_AfterImages;
+        const uint64_t maxFrames = imagesWanted * 100000ull + 1000ull;
+        uint32_t imagesSinceEdit = 0;
+        // the load's own dirty bits are spent: AfterSceneEdited uploaded everything
+        uint32_t spentBits = 0;
+        if (!edits.empty() && !Check(dcrt_scene_acquire_dirty(scene.m_Handle, &spentBits), "AcquireDirty")) return 1;
+        while (seeds.size() < spp || editsApplied < edits.size()) {
             SRenderContext rc;
             if (!loop.RenderOneFrame(&rc)) return 1;
             if (rc.m_IsSmallResolutionEnabled) {
@@ -141,8 +254,18 @@ int main(int argc, char** argv)
                 continue;
             }
             // (the seed advances right after the image completes, except under Fixed)
-            if (loop.m_LastFrameCompletedImage)
+            if (loop.m_LastFrameCompletedImage) {
                 seeds.push_back(seedType == CRendererLoop::EFrameSeedType::Fixed ? scene.m_FrameSeed : scene.m_FrameSeed - 1u);
+                ++imagesSinceEdit;
+            }
+            if (editsApplied < edits.size() && imagesSinceEdit >= edits[editsApplied].m_AfterImages) {
+                // between two frames, as the UI edits: the next frame finds the dirty flags, restarts
+                // the film with a preview and sends only the edited arrays
+                if (!ApplyEdit(scene.m_Handle, edits[editsApplied]) || !scene.AcquireEdits()) return 1;
+                ++editsApplied;
+                imagesSinceEdit = 0;
+                seeds.clear();   // (the film restarts: its images are the ones after the edit)
+            }
             if (loop.m_FrameIndex > maxFrames) {
                 std::fprintf(stderr, "the frame loop did not complete %u images\n", spp);
                 return 1;
@@ -177,11 +300,26 @@ int main(int argc, char** argv)
     const double rays = (double)(stats.extension_rays + stats.shadow_rays);
     std::string seedList;
     for (size_t i = 0; i < seeds.size(); ++i) seedList += (i ? "," : "") + std::to_string(seeds[i]);
+    std::string editReport;   // (only with --edit: the line is otherwise what it always was)
+    if (!edits.empty()) {
+        dcrt_upload_stats up;
+        if (!tracer.GetUploadStats(&up)) return 1;
+        char buf[512];
+        std::snprintf(buf, sizeof(buf),
+                      ", \"edits_applied\": %zu, \"upload_stats\": {\"scene_uploads\": %llu, \"material_updates\": %llu, "
+                      "\"light_updates\": %llu, \"instance_flag_updates\": %llu, \"geometry_bytes\": %llu, \"shading_bytes\": %llu, "
+                      "\"graph_invalidations\": %llu}",
+                      editsApplied, (unsigned long long)up.scene_uploads, (unsigned long long)up.material_updates,
+                      (unsigned long long)up.light_updates, (unsigned long long)up.instance_flag_updates,
+                      (unsigned long long)up.geometry_bytes, (unsigned long long)up.shading_bytes,
+                      (unsigned long long)up.graph_invalidations);
+        editReport = buf;
+    }
     std::printf("{\"images\": %u, \"seconds\": %.4f, \"ms_per_spp\": %.3f, \"mrays_per_s\": %.1f, \"extension_rays\": %llu, "
                 "\"shadow_rays\": %llu, \"mode\": \"%s\", \"frames\": %llu, \"preview_frames\": %llu, \"first_seed\": %u, "
-                "\"seeds\": [%s]}\n",
+                "\"seeds\": [%s]%s}\n",
                 spp, seconds, seconds * 1e3 / spp, rays / seconds / 1e6, (unsigned long long)stats.extension_rays,
                 (unsigned long long)stats.shadow_rays, batch ? "render_images" : "frame_loop", (unsigned long long)loop.m_FrameIndex,
-                (unsigned long long)previewFrames, firstSeed, seedList.c_str());
+                (unsigned long long)previewFrames, firstSeed, seedList.c_str(), editReport.c_str());
     return 0;
 }

@@ -28,6 +28,33 @@ bool CScene::LoadFromFile(const char* path)
     return dcrt_scene_get_resolution(m_Handle, &m_ResolutionWidth, &m_ResolutionHeight) == DCRT_OK;
 }
 
+void CScene::UpdateLightGPUData()
+{
+    if (m_GPUScene) (void)m_GPUScene->UpdateLights(*this);
+}
+
+void CScene::UpdateMaterialGPUData()
+{
+    if (m_GPUScene) (void)m_GPUScene->UpdateMaterials(*this);
+}
+
+void CScene::UpdateInstanceFlagsGPUData()
+{
+    if (m_GPUScene) (void)m_GPUScene->UpdateInstanceFlags(*this);
+}
+
+bool CScene::AcquireEdits()
+{
+    uint32_t bits = 0;
+    if (!m_Handle || dcrt_scene_acquire_dirty(m_Handle, &bits) != DCRT_OK) return false;
+    m_IsLightGPUBufferDirty = m_IsLightGPUBufferDirty || (bits & DCRT_DIRTY_LIGHTS) != 0;
+    m_IsMaterialGPUBufferDirty = m_IsMaterialGPUBufferDirty || (bits & DCRT_DIRTY_MATERIALS) != 0;
+    m_IsInstanceFlagsBufferDirty = m_IsInstanceFlagsBufferDirty || (bits & DCRT_DIRTY_INSTANCE_FLAGS) != 0;
+    m_IsSceneGPUBufferDirty = m_IsSceneGPUBufferDirty || (bits & DCRT_DIRTY_SCENE) != 0;
+    if (bits & DCRT_DIRTY_CAMERA) m_Camera.SetDirty();
+    return true;
+}
+
 // ---- the constant / buffer / filter helpers -------------------------------------------------
 dcrt_frame_params MakeFrameParams(const CScene& scene, const SRenderContext& renderContext)
 {
@@ -139,6 +166,32 @@ bool CMI355XPathTracer::ClearFilm() { return m_Tracer && Ok(dcrt_tracer_clear_fi
 bool CMI355XPathTracer::ExecuteSampleConvolution(const dcrt_filter_params& filter)
 {
     return m_Tracer && Ok(dcrt_tracer_accumulate_film(m_Tracer, &filter), "SampleConvolution");
+}
+
+bool CMI355XPathTracer::UpdateLights(const CScene& scene)
+{
+    if (!m_Tracer || !m_HasScene) return false;
+    const dcrt_flat_scene flat = MakeFlatScene(scene);
+    return Ok(dcrt_tracer_update_lights(m_Tracer, flat.lights, flat.light_count), "UpdateLights");
+}
+
+bool CMI355XPathTracer::UpdateMaterials(const CScene& scene)
+{
+    if (!m_Tracer || !m_HasScene) return false;
+    const dcrt_flat_scene flat = MakeFlatScene(scene);
+    return Ok(dcrt_tracer_update_materials(m_Tracer, flat.materials, flat.material_count), "UpdateMaterials");
+}
+
+bool CMI355XPathTracer::UpdateInstanceFlags(const CScene& scene)
+{
+    if (!m_Tracer || !m_HasScene) return false;
+    const dcrt_flat_scene flat = MakeFlatScene(scene);
+    return Ok(dcrt_tracer_update_instance_flags(m_Tracer, flat.instance_flags, flat.instance_count), "UpdateInstanceFlags");
+}
+
+bool CMI355XPathTracer::GetUploadStats(dcrt_upload_stats* stats)
+{
+    return m_Tracer && stats && Ok(dcrt_tracer_upload_stats(m_Tracer, stats), "UploadStats");
 }
 
 bool CMI355XPathTracer::GetSampleTextures(void** devicePosition, void** deviceValue)

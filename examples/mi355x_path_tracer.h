@@ -4,7 +4,8 @@
 // Source/PathTracer.h:6-26 (eight virtuals, restated here because the reference header cannot be
 // compiled on Linux), `SRenderContext` (Source/RenderContext.h:1-8), the members of `CScene` the
 // frame loop and the plugin read (Source/Scene.h: m_ResolutionWidth/Height, m_FrameSeed,
-// m_IsFilmDirty, m_IsLastFrameFilmDirty, m_PathTracer[]), and `CMI355XPathTracer`, a CPathTracer
+// m_IsFilmDirty, m_IsLastFrameFilmDirty, the three GPU-buffer dirty flags and their Update*GPUData,
+// m_Camera's dirty flag, m_PathTracer[]), and `CMI355XPathTracer`, a CPathTracer
 // that forwards to libdcrt.so through the C ABI of include/dcrt.h alone.
 //
 // On the reference side a maintainer drops CMI355XPathTracer next to CWavefrontPathTracer and
@@ -26,6 +27,18 @@ struct SRenderContext {
 };
 
 class CScene;
+class CMI355XPathTracer;
+
+// Source/Camera.h:14, 41-42: the frame loop restarts the image when the camera moved
+class CCamera {
+public:
+    bool IsDirty() const { return m_IsDirty; }
+    void ClearDirty() { m_IsDirty = false; }
+    void SetDirty() { m_IsDirty = true; }
+
+private:
+    bool m_IsDirty = false;
+};
 
 // Source/PathTracer.h:6-26 -- the plugin slot (CScene::m_PathTracer[], Scene.h:209)
 class CPathTracer {
@@ -54,14 +67,29 @@ public:
     bool Reset(uint32_t width, uint32_t height);
     bool LoadFromFile(const char* path);
 
+    // UpdateLight / Material / InstanceFlagsGPUData (Scene.cpp:672-807): only the edited array
+    // goes to the device. The tracer owns the scene buffers here, so these forward to the
+    // plugin (dcrt_tracer_update_lights / _materials / _instance_flags).
+    void UpdateLightGPUData();
+    void UpdateMaterialGPUData();
+    void UpdateInstanceFlagsGPUData();
+    // dcrt_scene_acquire_dirty's bits (the host scene's record of its edits) moved into the
+    // flags below, as the reference's UI sets them; DCRT_DIRTY_SCENE -> m_IsSceneGPUBufferDirty
+    bool AcquireEdits();
+
     dcrt_scene* m_Handle = nullptr;
+    CMI355XPathTracer* m_GPUScene = nullptr;   // the plugin that holds this scene's GPU buffers
+    CCamera m_Camera;                     // (its dirty flag; the camera itself lives in m_Handle)
     uint32_t m_ResolutionWidth = 0;
     uint32_t m_ResolutionHeight = 0;
     uint32_t m_FrameSeed = 0;             // Scene.h:138, advanced by the frame loop's seed policy
     bool m_IsFilmDirty = false;
     bool m_IsLastFrameFilmDirty = false;
-    // UpdateLight/Material/InstanceFlagsGPUData (Scene.cpp:672-807): the frame loop re-uploads
-    // the scene buffers when the host scene was edited
+    bool m_IsLightGPUBufferDirty = false;        // Scene.h:211-215
+    bool m_IsMaterialGPUBufferDirty = false;
+    bool m_IsInstanceFlagsBufferDirty = false;
+    // the full reload (OnSceneLoaded): content the partial updates do not cover, e.g. an
+    // environment cube that appeared, disappeared or changed (ImGui.cpp:360-366, 520-538)
     bool m_IsSceneGPUBufferDirty = false;
     CPathTracer* m_PathTracer[2] = {nullptr, nullptr};
 };
@@ -95,6 +123,11 @@ public:
     bool ClearFilm();                                         // ClearFilmTexture (LaunchRendererLoop.cpp:192-199)
     bool ExecuteSampleConvolution(const dcrt_filter_params& filter);   // SampleConvolution.cpp:89-170
     bool GetSampleTextures(void** devicePosition, void** deviceValue); // m_SamplePosition/ValueTexture
+    // The scene's GPU buffers live in the tracer: CScene::Update*GPUData come here.
+    bool UpdateLights(const CScene& scene);
+    bool UpdateMaterials(const CScene& scene);
+    bool UpdateInstanceFlags(const CScene& scene);
+    bool GetUploadStats(dcrt_upload_stats* stats);
     dcrt_tracer* GetTracer() const { return m_Tracer; }
     int LastStatus() const { return m_LastStatus; }
 

@@ -19,6 +19,7 @@ public:
     CRendererLoop(CScene* scene, CMI355XPathTracer* pathTracer) : m_Scene(scene), m_PathTracer(pathTracer)
     {
         m_Scene->m_PathTracer[0] = pathTracer;
+        m_Scene->m_GPUScene = pathTracer;
     }
 
     // LaunchRendererLoop.cpp:159-190: the film is dirty from here on, so the next frame is the
@@ -49,7 +50,10 @@ public:
     {
         CScene* scene = m_Scene;
         CPathTracer* pt = scene->m_PathTracer[m_ActivePathTracerIndex];
-        scene->m_IsFilmDirty = scene->m_IsFilmDirty || scene->m_IsSceneGPUBufferDirty || pt->AcquireFilmClearTrigger();
+        // :203-204 (and the full reload, which the reference's UI runs on the spot)
+        scene->m_IsFilmDirty = scene->m_IsFilmDirty || scene->m_IsSceneGPUBufferDirty || scene->m_IsLightGPUBufferDirty ||
+                               scene->m_IsMaterialGPUBufferDirty || scene->m_IsInstanceFlagsBufferDirty || scene->m_Camera.IsDirty() ||
+                               pt->AcquireFilmClearTrigger();
 
         const bool isResolutionChanged = scene->m_IsFilmDirty != scene->m_IsLastFrameFilmDirty;
         renderContext->m_IsSmallResolutionEnabled = scene->m_IsFilmDirty;
@@ -66,9 +70,14 @@ public:
             m_SPP = 0;
             pt->ResetImage();
         }
-        // UpdateLight/Material/InstanceFlagsGPUData (:239-252): the edited host scene re-flattened
-        // and uploaded
-        if (scene->m_IsSceneGPUBufferDirty) pt->OnSceneLoaded(scene);
+        if (scene->m_IsSceneGPUBufferDirty) {
+            pt->OnSceneLoaded(scene);   // (every buffer: the three below included)
+        } else {
+            // :239-252: only the edited array goes to the device
+            if (scene->m_IsLightGPUBufferDirty) scene->UpdateLightGPUData();
+            if (scene->m_IsMaterialGPUBufferDirty) scene->UpdateMaterialGPUData();
+            if (scene->m_IsInstanceFlagsBufferDirty) scene->UpdateInstanceFlagsGPUData();
+        }
 
         pt->Render(scene, *renderContext);
 
@@ -76,6 +85,11 @@ public:
             if (m_FrameSeedType != EFrameSeedType::Fixed) scene->m_FrameSeed++;
             ++m_SPP;
         }
+        // :266-270
+        scene->m_Camera.ClearDirty();
+        scene->m_IsLightGPUBufferDirty = false;
+        scene->m_IsMaterialGPUBufferDirty = false;
+        scene->m_IsInstanceFlagsBufferDirty = false;
         scene->m_IsSceneGPUBufferDirty = false;
         scene->m_IsFilmDirty = false;
     }

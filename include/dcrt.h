@@ -320,6 +320,32 @@ DCRT_API int dcrt_scene_load_from_file(dcrt_scene* scene, const char* path);
 /* Equivalent of UI "Create -> Point/Directional Light" (ImGui.cpp:322-331). */
 DCRT_API int dcrt_scene_add_punctual_light(dcrt_scene* scene, const float position[3], const float euler_angles[3],
                                            const float color[3], int is_directional);
+/* Edit / delete punctual light `index` (ImGui.cpp:351-372, 468-497); the lights after a
+ * removed one keep their order. DCRT_E_INVALID_ARG for an index out of range. */
+DCRT_API int dcrt_scene_set_punctual_light(dcrt_scene* scene, uint32_t index, const float position[3],
+                                           const float euler_angles[3], const float color[3], int is_directional);
+DCRT_API int dcrt_scene_remove_punctual_light(dcrt_scene* scene, uint32_t index);
+/* Delete the environment light (ImGui.cpp:360-366); DCRT_E_INVALID_ARG without one. */
+DCRT_API int dcrt_scene_remove_environment_light(dcrt_scene* scene);
+/* What the edits since the last dcrt_scene_acquire_dirty changed (Scene.h:211-215, Camera.h:14).
+ * An edit re-flattens only its own arrays (dcrt_scene_get_flat's materials / lights /
+ * instance_flags; no vertex, triangle, node or transform is copied), and the tracer takes them
+ * through dcrt_tracer_update_materials / _lights / _instance_flags. DCRT_DIRTY_SCENE asks for a
+ * full dcrt_tracer_upload_scene: set by load and reset, and whenever an environment cube
+ * appears, disappears or changes (the reference calls OnSceneLoaded then, ImGui.cpp:360-366,
+ * 520-538). DCRT_DIRTY_CAMERA: new frame parameters (camera / lens). Every bit also means the
+ * image restarts (LaunchRendererLoop.cpp:203-204). */
+#define DCRT_DIRTY_LIGHTS          0x01u   /* punctual-light edits, environment colour        */
+#define DCRT_DIRTY_MATERIALS       0x02u   /* material fields, multiscattering, opacity       */
+#define DCRT_DIRTY_INSTANCE_FLAGS  0x04u   /* opacity / opacity texture (with MATERIALS)      */
+#define DCRT_DIRTY_CAMERA          0x08u   /* dcrt_scene_set_camera / _set_lens               */
+#define DCRT_DIRTY_SCENE           0x10u
+/* Returns the bits and clears them. */
+DCRT_API int dcrt_scene_acquire_dirty(dcrt_scene* scene, uint32_t* out_bits);
+/* Rebuild every flat array (what each edit did before the partial paths; the full-reload
+ * side of tools/bench_scene_update.py and of the tests' byte comparison); DCRT_E_NO_SCENE
+ * before any content is loaded. */
+DCRT_API int dcrt_scene_flatten(dcrt_scene* scene);
 /* Constant environment light (SceneXMLLoading.cpp:1454-1467); cube may be NULL. */
 DCRT_API int dcrt_scene_set_environment_light(dcrt_scene* scene, const float color[3],
                                               const float* cube_rgb, uint32_t cube_size);
@@ -465,6 +491,30 @@ DCRT_API int dcrt_tracer_create(const dcrt_tracer_config* config, dcrt_tracer** 
 DCRT_API void dcrt_tracer_destroy(dcrt_tracer* tracer);                                        /* Destroy() */
 /* OnSceneLoaded + the uploads of Scene.cpp:273-608. Copies everything to HBM. */
 DCRT_API int dcrt_tracer_upload_scene(dcrt_tracer* tracer, const dcrt_flat_scene* scene);
+/* Partial updates of the uploaded scene (CScene::UpdateMaterial / Light / InstanceFlagsGPUData,
+ * Scene.cpp:672-807): only the named array goes to the device -- no geometry, no node
+ * re-layout. DCRT_E_NO_SCENE before a scene is uploaded; material_count / instance_count must
+ * equal the uploaded scene's (DCRT_E_INVALID_ARG); light_count may differ, 0 ..
+ * DCRT_MAX_LIGHT_COUNT (DCRT_E_LIMIT above). Each call is ordered after the work already
+ * enqueued on the tracer's stream and has copied the array on return. What the tracer derives
+ * from materials and lights (the MATERIAL / drain variant, MATERIAL's LDS scene copy) follows;
+ * captured graphs are dropped only when something baked into them changed, so a content-only
+ * edit (a colour, a roughness, a moved light) keeps them. The film, the path state and the
+ * environment cube are untouched: the caller restarts the image (dcrt_tracer_reset_image) and
+ * sends frame parameters with the new light count, as the reference's frame loop does. */
+DCRT_API int dcrt_tracer_update_materials(dcrt_tracer* tracer, const dcrt_material* materials, uint32_t material_count);
+DCRT_API int dcrt_tracer_update_lights(dcrt_tracer* tracer, const dcrt_light* lights, uint32_t light_count);
+DCRT_API int dcrt_tracer_update_instance_flags(dcrt_tracer* tracer, const uint32_t* flags, uint32_t instance_count);
+/* Upload counters since dcrt_tracer_create. */
+typedef struct dcrt_upload_stats {
+    uint64_t scene_uploads, material_updates, light_updates, instance_flag_updates;
+    uint64_t geometry_bytes;       /* H2D bytes of vertices, triangles, nodes, transforms, textures, cube */
+    uint64_t shading_bytes;        /* H2D bytes of materials, lights, instance flags */
+    uint64_t graph_invalidations;  /* times captured graphs were dropped */
+} dcrt_upload_stats;
+DCRT_API int dcrt_tracer_upload_stats(dcrt_tracer* tracer, dcrt_upload_stats* out_stats);
+/* While a scene is uploaded, the render entry points refuse (DCRT_E_INVALID_ARG) frame
+ * parameters whose light_count exceeds the lights the tracer holds. */
 DCRT_API int dcrt_tracer_set_frame_params(dcrt_tracer* tracer, const dcrt_frame_params* params);
 DCRT_API int dcrt_tracer_set_film_partition(dcrt_tracer* tracer, const dcrt_film_partition* partition);
 /* Explicit film bands (cost-balanced film tiling): the tracer owns the rows of the
