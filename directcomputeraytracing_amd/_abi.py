@@ -34,6 +34,9 @@ DIRTY_MATERIALS = 0x02
 DIRTY_INSTANCE_FLAGS = 0x04
 DIRTY_CAMERA = 0x08
 DIRTY_SCENE = 0x10
+# DCRT_OUTPUT_*: the megakernel tracer's "Output" views, in s_OutputNames order
+(OUTPUT_PATH_TRACING, OUTPUT_SHADING_NORMAL, OUTPUT_SHADING_TANGENT, OUTPUT_ALBEDO, OUTPUT_NEGATIVE_NDOTV,
+ OUTPUT_BACKFACE, OUTPUT_ITERATION_COUNT) = range(7)
 
 
 class Vertex(C.Structure):
@@ -120,6 +123,10 @@ class PostFxParams(C.Structure):
 class TracerConfig(C.Structure):
     _fields_ = [("path_pool_size", C.c_uint32), ("iterations_per_render", C.c_uint32), ("device", C.c_int32),
                 ("stream", C.c_void_p), ("debug_rng", C.c_uint32)]
+
+
+class OutputParams(C.Structure):
+    _fields_ = [("output_type", C.c_uint32), ("iteration_threshold", C.c_uint32)]
 
 
 class RayStats(C.Structure):
@@ -259,6 +266,8 @@ SIGNATURES = [
     ("dcrt_tracer_image_sample_ptrs", _I, [_P, _U, C.POINTER(_P), C.POINTER(_P)]),
     ("dcrt_tracer_accumulate_images", _I, [_P, C.POINTER(_P), C.POINTER(_P), _U, C.POINTER(FilterParams)]),
     ("dcrt_tracer_set_mode", _I, [_P, _I]),
+    ("dcrt_tracer_set_output", _I, [_P, C.POINTER(OutputParams)]),
+    ("dcrt_tracer_get_output", _I, [_P, C.POINTER(OutputParams)]),
     ("dcrt_tracer_set_image_batch", _I, [_P, C.c_uint32]),
     ("dcrt_tracer_reset_image", _I, [_P]),
     ("dcrt_tracer_is_image_complete", _I, [_P, C.POINTER(C.c_int)]),

@@ -1315,6 +1315,87 @@ __global__ __launch_bounds__(256) void megakernel(DeviceScene sc, const FrameCon
     if (lane == 0) { atomicAdd(&g->extRays, e); atomicAdd(&g->shadowRays, sh); }
 }
 
+// ---- first-hit debug views (MegakernelPathTracing.hlsl:212-291, the OUTPUT_* variants) ------
+// The megakernel's launch shape (persistent grid, one claimed 8x8 block per wave, the LDS scene
+// cache and stack columns), but a pixel's work ends at its camera ray's closest hit: the view's
+// colour is a function of that hit (hit_to_intersection, as MATERIAL and the megakernel call
+// it) or, for the iteration-count heat map, of the ray's node visits. The traversal is the
+// counting one (trav_visit<INSTR>: one call per visited node in the reference's order, in
+// either device node order), so `nodes` is BVHAccel.inc.hlsl:121's iterationCounter. The view
+// and the threshold are kernel arguments: the traversal dominates a pixel's time.
+template <bool OPACITY>
+__global__ __launch_bounds__(256) void view_kernel(DeviceScene sc, const FrameConstants* __restrict__ fcp, Film film, Globals* g, uint32_t debugRng,
+                                                   uint32_t outputType, uint32_t iterationThreshold)
+{
+    extern __shared__ uint32_t stackMem[];
+    scene_cache_load(sc, stackMem, block_shift());
+    __shared__ uint32_t sm[64];
+    const FrameConstants& fc = *fcp;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t shard = blockIdx.x % kShards;
+    uint32_t* cursor = &g->nextBlock[shard * kShardStride];
+    const uint32_t shardBlocks = g->totalBlocks > shard ? (g->totalBlocks - shard + kShards - 1) / kShards : 0u;
+    const bool watertight = (fc.features & DCRT_FEATURE_WATERTIGHT) != 0;
+    const bool f2b = (fc.features & DCRT_FEATURE_NO_FRONT_TO_BACK) == 0;
+    uint32_t* lds = stackMem + threadIdx.x;
+    const uint32_t shift = block_shift();
+    uint32_t extRays = 0;
+    for (;;) {
+        // every wave of the block claims one block per round (one atomic per workgroup)
+        bool want = false;
+        if (lane == 0) want = __hip_atomic_load(cursor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < shardBlocks;
+        const uint32_t bslot = block_append(want, cursor, sm);
+        const uint32_t claimed = (uint32_t)__shfl((int)bslot, 0, 64);
+        const bool got = __shfl((int)want, 0, 64) != 0 && claimed < shardBlocks;
+        if (__syncthreads_or(got ? 1 : 0) == 0) break;
+        if (!got) continue;
+        const uint32_t block = shard + claimed * kShards;
+        uint32_t px = 0, py = 0, image = 0;
+        if (!block_pixel(fc, film, block, lane, &px, &py, &image)) continue;
+        Rng rng = rng_init(px, py, image_seed(fc, image));
+        const float psx = next1(rng), psy = next1(rng);
+        const float fsx = (psx + (float)px) / (float)fc.resolution[0];
+        const float fsy = (psy + (float)py) / (float)fc.resolution[1];
+        const float a0 = next1(rng), a1 = next1(rng), a2 = next1(rng);
+        V3 ro, rd;
+        generate_ray(fc, fsx, fsy, a0, a1, a2, &ro, &rd);
+        ++extRays;
+        TravState s;
+        trav_init(s, ro, rd, 0.0f, inf(), f2b);
+        // IntersectScene draws the ray's opacity sample (MegakernelPathTracing.hlsl:27-28)
+        s.opacitySample = OPACITY ? next1(rng) : 0.0f;
+        TraversalStats st = {};
+        for (;;) {
+            if (trav_visit<true>(sc, s, lds, shift, st)) break;
+            if (s.parked && trav_leaf<false, true, OPACITY>(sc, s, watertight, lds, shift, st)) break;
+        }
+        V3 l = mk(0.0f, 0.0f, 0.0f);
+        if (outputType == DCRT_OUTPUT_ITERATION_COUNT) {
+            // (hits and misses alike, :286-288; an IEEE division as the HLSL's)
+            const float f = (float)st.nodes / (float)iterationThreshold;
+            l = st.nodes <= iterationThreshold ? mk(f, f, f) : mk(1.0f, 0.0f, 0.0f);
+        } else if (s.found) {
+            Intersection it;
+            hit_to_intersection(sc, s.hit, it);
+            const V3 green = mk(0.0f, 1.0f, 0.0f), red = mk(1.0f, 0.0f, 0.0f);
+            switch (outputType) {
+            case DCRT_OUTPUT_SHADING_NORMAL: l = it.normal * 0.5f + mk(0.5f, 0.5f, 0.5f); break;
+            case DCRT_OUTPUT_SHADING_TANGENT: l = it.tangent * 0.5f + mk(0.5f, 0.5f, 0.5f); break;
+            case DCRT_OUTPUT_ALBEDO: l = it.albedo; break;
+            case DCRT_OUTPUT_NEGATIVE_NDOTV: l = dot(-rd, it.normal) < 0.0f ? green : red; break;
+            case DCRT_OUTPUT_BACKFACE: l = it.backface ? green : red; break;
+            default: break;
+            }
+        }
+        const size_t p = (size_t)image * film.width * film.height + (size_t)py * film.width + px;
+        film.samplePosition[p] = make_float2(psx, psy);
+        film.sampleValue[p] = make_float4(l.x, l.y, l.z, 0.0f);
+        if (debugRng) film.debugRng[p] = make_uint4(rng.s0, rng.s1, rng.s2, rng.s3);
+    }
+    const unsigned long long e = wave_sum(extRays);
+    if (lane == 0) atomicAdd(&g->extRays, e);
+}
+
 // ---- drain completion ----------------------------------------------------------------------
 // Launched after every iteration's cast. Once a batch has no pixel block left to claim and
 // at most fc.drainPaths paths are live, it runs each of them to its end in one lane, as the
@@ -1947,6 +2028,8 @@ template __global__ void cast_kernel<false, false, false, false, true>(PathPool,
 template __global__ void cast_kernel<true, false, false, false, true>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
 template __global__ void megakernel<false>(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t);
 template __global__ void megakernel<true>(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t);
+template __global__ void view_kernel<false>(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t, uint32_t, uint32_t);
+template __global__ void view_kernel<true>(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t, uint32_t, uint32_t);
 template __global__ void batch_trace_kernel<false, false>(DeviceScene, const dcrt_ray*, uint32_t, uint32_t, dcrt_ray_hit*, uint32_t*, unsigned long long*);
 template __global__ void batch_trace_kernel<true, false>(DeviceScene, const dcrt_ray*, uint32_t, uint32_t, dcrt_ray_hit*, uint32_t*, unsigned long long*);
 template __global__ void batch_trace_kernel<false, true>(DeviceScene, const dcrt_ray*, uint32_t, uint32_t, dcrt_ray_hit*, uint32_t*, unsigned long long*);

@@ -589,6 +589,7 @@ struct dcrt_tracer {
     int UploadFilter(const dcrt_filter_params& f);
     int ReadCompletion(bool* complete);
     int Render(uint32_t maxIterations);
+    int LaunchView();
     int RenderImages(uint32_t firstSeed, uint32_t count, const dcrt_filter_params& filter, uint32_t stride = 1,
                      bool convolve = true);
     int AccumulateImages(const void* const* pos, const void* const* val, uint32_t count, const dcrt_filter_params& filter);
@@ -612,6 +613,10 @@ struct dcrt_tracer {
     uint32_t castResident = 0;         // persistent cast grid: resident workgroups on the whole chip
     uint32_t castResidentOpacity = 0;  // the same for the ALLOW_ANYHIT_SHADER variant
     uint32_t megaResident = 0;         // persistent megakernel grid
+    uint32_t viewResident = 0;         // persistent view_kernel grid
+    uint32_t viewResidentOpacity = 0;  // the same for the ALLOW_ANYHIT_SHADER variant
+    // the "Output" view (dcrt_tracer_set_output): anything but PATH_TRACING renders first hits
+    dcrt_output_params output{ DCRT_OUTPUT_PATH_TRACING, 20u };
     uint32_t drainResident = 0;        // drain_kernel grid (resident workgroups)
     uint32_t drainPaths = 0;           // drain_kernel threshold (DCRT_DRAIN_PATHS; 0: no drain launches -- the default: profiles/r04_ab_virtual_drain.txt)
     int mode = 0;                      // 0 wavefront (WavefrontPathTracer), 1 megakernel (MegakernelPathTracer)
@@ -1319,6 +1324,14 @@ int dcrt_tracer::UploadScene(const dcrt_flat_scene& s)
         HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&megaPerCU, megakernel<false>, (int)castBlock, castLdsFull));
         megaResident = (uint32_t)std::max(1, std::min(megaPerCU, LdsResident(castLdsFull, (const void*)megakernel<false>))) *
                        (uint32_t)std::max(1, prop.multiProcessorCount);
+        // the first-hit view kernel: the megakernel's launch shape, its own register budget
+        int viewPerCU = 0, viewOpacityPerCU = 0;
+        HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&viewPerCU, view_kernel<false>, (int)castBlock, castLdsFull));
+        HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&viewOpacityPerCU, view_kernel<true>, (int)castBlock, castLdsFull));
+        viewResident = (uint32_t)std::max(1, std::min(viewPerCU, LdsResident(castLdsFull, (const void*)view_kernel<false>))) *
+                       (uint32_t)std::max(1, prop.multiProcessorCount);
+        viewResidentOpacity = (uint32_t)std::max(1, std::min(viewOpacityPerCU, LdsResident(castLdsFull, (const void*)view_kernel<true>))) *
+                              (uint32_t)std::max(1, prop.multiProcessorCount);
         cuCount = (uint32_t)std::max(1, prop.multiProcessorCount);
         CHECKED(DeriveDrainGrid());
         if (ringRows) {
@@ -1758,11 +1771,39 @@ int dcrt_tracer::ReadCompletion(bool* complete)
     return DCRT_OK;
 }
 
+// One first-hit view image (dcrt_tracer_set_output) of the frame constants BeginImage uploaded,
+// into sample slot 0: one persistent launch, as the megakernel's
+int dcrt_tracer::LaunchView()
+{
+    Annotation an("Output view", !capturing);
+    const bool opacity = (frame.features & DCRT_FEATURE_ALLOW_ANYHIT) != 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (extTiming) CHECKED(TimedPair(kTimedCast, &e0, &e1));
+    auto vk = opacity ? view_kernel<true> : view_kernel<false>;
+    hipExtLaunchKernelGGL(vk, dim3(opacity ? viewResidentOpacity : viewResident), dim3(castBlock), castLdsFull, stream, e0, e1, 0, scene,
+                          (const FrameConstants*)dFrame, film, dGlobals, (uint32_t)(film.debugRng != nullptr), output.output_type,
+                          output.iteration_threshold);
+    HIPCHECK(hipGetLastError());
+    return DCRT_OK;
+}
+
 int dcrt_tracer::Render(uint32_t maxIterations)
 {
     if (!hasScene) { SetLastError("no scene uploaded"); return DCRT_E_NO_SCENE; }
     if (!hasFrame) { SetLastError("no frame parameters"); return DCRT_E_INVALID_ARG; }
     CHECKED(CheckFrameLights());
+    if (output.output_type != DCRT_OUTPUT_PATH_TRACING) {
+        // a view image is one launch: the whole image of the current frame seed, complete on return
+        keptSlots = false;   // (slot 0 is this image's now)
+        lastSlot = 0;
+        CHECKED(BeginImage());
+        CHECKED(LaunchView());
+        HIPCHECK(hipStreamSynchronize(stream));
+        ++imagesCompleted;
+        imageComplete = true;
+        newImage = true;
+        return DCRT_OK;
+    }
     if (newImage) CHECKED(BeginImage());
     lastSlot = 0;
     CHECKED(RunIterations(maxIterations ? maxIterations : iterationsPerRender));
@@ -1814,17 +1855,27 @@ int dcrt_tracer::RenderImages(uint32_t firstSeed, uint32_t count, const dcrt_fil
         }
     }
     lastSlot = 0;
-    if (mode == 1) {   // MegakernelPathTracer::Render: one persistent launch + SampleConvolution per image
-        if (!convolve) { SetLastError("the megakernel mode convolves every image"); return DCRT_E_INVALID_ARG; }
+    // MegakernelPathTracer::Render: one persistent launch + SampleConvolution per image -- the
+    // path-tracing megakernel, or the first-hit kernel of the selected output view
+    const bool view = output.output_type != DCRT_OUTPUT_PATH_TRACING;
+    if (view || mode == 1) {
+        if (!convolve) {
+            SetLastError(view ? "an output view convolves every image" : "the megakernel mode convolves every image");
+            return DCRT_E_INVALID_ARG;
+        }
         CHECKED(UploadFilter(filter));
         for (uint32_t img = 0; img < count; ++img) {
             frame.frame_seed = firstSeed + img * seedStride;
             CHECKED(BeginImage());
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (extTiming) CHECKED(TimedPair(kTimedCast, &e0, &e1));
-            auto mk = (frame.features & DCRT_FEATURE_ALLOW_ANYHIT) ? megakernel<true> : megakernel<false>;
-            hipExtLaunchKernelGGL(mk, dim3(megaResident), dim3(castBlock), castLdsFull, stream, e0, e1, 0, scene,
-                                  (const FrameConstants*)dFrame, film, dGlobals, (uint32_t)(film.debugRng != nullptr));
+            if (view) {
+                CHECKED(LaunchView());
+            } else {
+                hipEvent_t e0 = nullptr, e1 = nullptr;
+                if (extTiming) CHECKED(TimedPair(kTimedCast, &e0, &e1));
+                auto mk = (frame.features & DCRT_FEATURE_ALLOW_ANYHIT) ? megakernel<true> : megakernel<false>;
+                hipExtLaunchKernelGGL(mk, dim3(megaResident), dim3(castBlock), castLdsFull, stream, e0, e1, 0, scene,
+                                      (const FrameConstants*)dFrame, film, dGlobals, (uint32_t)(film.debugRng != nullptr));
+            }
             hipLaunchKernelGGL(film_kernel, dim3(FilmGrid()), dim3(kFilmThreads), 0, stream, film, (const FilterConsts*)dFilter, 1u,
                                (const Globals*)nullptr, (const float2* const*)nullptr, (const float4* const*)nullptr);
             HIPCHECK(hipGetLastError());
@@ -2400,6 +2451,32 @@ DCRT_API int dcrt_tracer_set_mode(dcrt_tracer* t, int mode)
     TRACER_GUARD(t);
     if (mode != 0 && mode != 1) return DCRT_E_INVALID_ARG;
     t->mode = mode;
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_set_output(dcrt_tracer* t, const dcrt_output_params* p)
+{
+    TRACER_GUARD(t);
+    if (!p) return DCRT_E_INVALID_ARG;
+    if (p->output_type > DCRT_OUTPUT_ITERATION_COUNT) { SetLastError("unknown output type"); return DCRT_E_INVALID_ARG; }
+    if (p->output_type == DCRT_OUTPUT_ITERATION_COUNT && (p->iteration_threshold < 1u || p->iteration_threshold > 10000u)) {
+        SetLastError("iteration threshold: 1..10000");
+        return DCRT_E_INVALID_ARG;
+    }
+    if (p->output_type != t->output.output_type || p->iteration_threshold != t->output.iteration_threshold) {
+        t->filmClearTrigger = true;
+        t->newImage = true;
+        t->imageComplete = false;
+    }
+    t->output = *p;
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_get_output(dcrt_tracer* t, dcrt_output_params* out)
+{
+    TRACER_GUARD(t);
+    if (!out) return DCRT_E_INVALID_ARG;
+    *out = t->output;
     return DCRT_OK;
 }
 

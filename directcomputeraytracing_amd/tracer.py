@@ -21,6 +21,12 @@ assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 20
 
 MATH_SIN, MATH_COS, MATH_EXP, MATH_ATAN = range(4)
 
+# set_output's names for the DCRT_OUTPUT_* views (s_OutputNames, MegakernelPathTracer.cpp:360)
+OUTPUT_NAMES = {"path_tracing": _abi.OUTPUT_PATH_TRACING, "normal": _abi.OUTPUT_SHADING_NORMAL,
+                "tangent": _abi.OUTPUT_SHADING_TANGENT, "albedo": _abi.OUTPUT_ALBEDO,
+                "negative_ndotv": _abi.OUTPUT_NEGATIVE_NDOTV, "backface": _abi.OUTPUT_BACKFACE,
+                "iteration_count": _abi.OUTPUT_ITERATION_COUNT}
+
 
 def make_rays(origins, directions, t_min=0.0, t_max=np.inf) -> np.ndarray:
     o = np.asarray(origins, np.float32).reshape(-1, 3)
@@ -165,6 +171,20 @@ class WavefrontPathTracer:
     def set_mode(self, mode: str) -> None:
         """"wavefront" (CWavefrontPathTracer) or "megakernel" (CMegakernelPathTracer) for render_images."""
         check(self._lib.dcrt_tracer_set_mode(self._h, {"wavefront": 0, "megakernel": 1}[mode]), "SetMode")
+
+    def set_output(self, output, iteration_threshold: int = 20) -> None:
+        """The "Output" view: an OUTPUT_NAMES key or a DCRT_OUTPUT_* int. Anything but
+        "path_tracing" makes render / render_images draw the camera rays' first hits (normal,
+        tangent, albedo, facing flags) or their BVH node visits over iteration_threshold."""
+        kind = OUTPUT_NAMES[output] if isinstance(output, str) else int(output)
+        p = _abi.OutputParams(kind, int(iteration_threshold))
+        check(self._lib.dcrt_tracer_set_output(self._h, C.byref(p)), "SetOutput")
+
+    def output(self) -> tuple[str, int]:
+        """(view name, iteration threshold) as set_output takes them."""
+        p = _abi.OutputParams()
+        check(self._lib.dcrt_tracer_get_output(self._h, C.byref(p)), "GetOutput")
+        return {v: k for k, v in OUTPUT_NAMES.items()}[p.output_type], int(p.iteration_threshold)
 
     def reset_image(self) -> None:
         check(self._lib.dcrt_tracer_reset_image(self._h), "ResetImage")

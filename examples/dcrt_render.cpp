@@ -7,7 +7,12 @@
 //   dcrt_render <scene.obj|scene.xml> <width> <height> <spp> <max_bounce> <out.bmp>
 //               [--batch] [--point x y z r g b] [--seed-type sample-count|frame-index|fixed]
 //               [--fixed-seed N] [--iterations N] [--pool N] [--film out.f32] [--samples out.f32]
-//               [--edit N:KIND:ARGS]...
+//               [--edit N:KIND:ARGS]... [--output NAME [--iteration-threshold N]]
+//
+// --output selects the tracer's "Output" view, in either mode: path_tracing (default), normal,
+// tangent, albedo, negative_ndotv, backface or iteration_count (BVH node visits of the camera
+// ray over --iteration-threshold, default 20, as a grey level; red above it). The film,
+// post-processing and the BMP are as for a path-traced image.
 //
 // --edit (repeatable, frame loop only) edits the scene after N full-resolution images have
 // completed since the start or the previous edit: material:INDEX:TYPE:R,G,B:ROUGHNESS,
@@ -54,7 +59,9 @@ int Usage(const char* exe)
     std::fprintf(stderr,
                  "usage: %s scene.{obj,xml} width height spp max_bounce out.bmp [--batch] [--point x y z r g b]\n"
                  "       [--seed-type sample-count|frame-index|fixed] [--fixed-seed N] [--iterations N] [--pool N]\n"
-                 "       [--film out.f32] [--samples out.f32] [--edit N:KIND:ARGS]...\n",
+                 "       [--film out.f32] [--samples out.f32] [--edit N:KIND:ARGS]...\n"
+                 "       [--output path_tracing|normal|tangent|albedo|negative_ndotv|backface|iteration_count]\n"
+                 "       [--iteration-threshold N]\n",
                  exe);
     return 2;
 }
@@ -166,6 +173,7 @@ int main(int argc, char** argv)
     const char* filmPath = nullptr;
     const char* samplesPath = nullptr;
     std::vector<SEdit> edits;
+    uint32_t outputType = DCRT_OUTPUT_PATH_TRACING, iterationThreshold = 20;
     for (int i = 7; i < argc; ++i) {
         const bool more = i + 1 < argc;
         if (!std::strcmp(argv[i], "--batch")) {
@@ -191,6 +199,16 @@ int main(int argc, char** argv)
             filmPath = argv[++i];
         } else if (!std::strcmp(argv[i], "--samples") && more) {
             samplesPath = argv[++i];
+        } else if (!std::strcmp(argv[i], "--output") && more) {
+            static const char* const kOutputNames[] = {"path_tracing", "normal", "tangent", "albedo", "negative_ndotv", "backface",
+                                                       "iteration_count"};   // DCRT_OUTPUT_* order
+            const char* name = argv[++i];
+            outputType = ~0u;
+            for (uint32_t k = 0; k < 7; ++k)
+                if (!std::strcmp(name, kOutputNames[k])) outputType = k;
+            if (outputType == ~0u) return Usage(argv[0]);
+        } else if (!std::strcmp(argv[i], "--iteration-threshold") && more) {
+            iterationThreshold = (uint32_t)std::atoi(argv[++i]);
         } else if (!std::strcmp(argv[i], "--edit") && more) {
             SEdit e;
             if (!ParseEdit(argv[++i], &e)) return Usage(argv[0]);
@@ -209,6 +227,7 @@ int main(int argc, char** argv)
     loop.m_FrameSeedType = seedType;
     if (!scene.m_Handle) return 1;
     if (!tracer.Create()) return 1;
+    if (outputType != DCRT_OUTPUT_PATH_TRACING && !tracer.SetOutputType(outputType, iterationThreshold)) return 1;
 
     // LoadScene: Reset + LoadFromFile (+ UI "Create -> Point Light", max bounce), then
     // OnSceneLoaded and the small-resolution size

@@ -194,6 +194,14 @@ bool CMI355XPathTracer::GetUploadStats(dcrt_upload_stats* stats)
     return m_Tracer && stats && Ok(dcrt_tracer_upload_stats(m_Tracer, stats), "UploadStats");
 }
 
+bool CMI355XPathTracer::SetOutputType(uint32_t type, uint32_t iterationThreshold)
+{
+    dcrt_output_params p;
+    p.output_type = type;
+    p.iteration_threshold = iterationThreshold;
+    return m_Tracer && Ok(dcrt_tracer_set_output(m_Tracer, &p), "SetOutputType");
+}
+
 bool CMI355XPathTracer::GetSampleTextures(void** devicePosition, void** deviceValue)
 {
     return m_Tracer && Ok(dcrt_tracer_sample_device_ptrs(m_Tracer, devicePosition, deviceValue), "SampleTextures");

@@ -128,6 +128,10 @@ public:
     bool UpdateMaterials(const CScene& scene);
     bool UpdateInstanceFlags(const CScene& scene);
     bool GetUploadStats(dcrt_upload_stats* stats);
+    // CMegakernelPathTracer's "Output" combo and "Iteration Threshold" field (MegakernelPathTracer.cpp:
+    // 360-372): a DCRT_OUTPUT_* view. A change raises the film-clear trigger, which the frame
+    // loop takes through AcquireFilmClearTrigger() as it takes the reference's.
+    bool SetOutputType(uint32_t type, uint32_t iterationThreshold);
     dcrt_tracer* GetTracer() const { return m_Tracer; }
     int LastStatus() const { return m_LastStatus; }
 

@@ -563,6 +563,30 @@ DCRT_API int dcrt_tracer_set_image_batch(dcrt_tracer* tracer, uint32_t images);
 /* 0 = wavefront (CWavefrontPathTracer, default), 1 = megakernel (CMegakernelPathTracer,
  * MegakernelPathTracing.hlsl) for dcrt_tracer_render_images. */
 DCRT_API int dcrt_tracer_set_mode(dcrt_tracer* tracer, int mode);
+/* The megakernel tracer's "Output" views (MegakernelPathTracer.cpp:208-212 s_OutputNames, in
+ * that order; MegakernelPathTracing.hlsl:212-291): anything but PATH_TRACING renders the
+ * camera ray's first hit only -- the shading normal or tangent as n * 0.5 + 0.5, the albedo,
+ * green / red for a shading normal facing away from / towards the ray (Negative NdotV) or a
+ * back- / front-face hit, black for a miss; ITERATION_COUNT is the ray's BVH node visits over
+ * iteration_threshold as a grey level, red above the threshold, hit or miss. */
+#define DCRT_OUTPUT_PATH_TRACING 0
+#define DCRT_OUTPUT_SHADING_NORMAL 1
+#define DCRT_OUTPUT_SHADING_TANGENT 2
+#define DCRT_OUTPUT_ALBEDO 3
+#define DCRT_OUTPUT_NEGATIVE_NDOTV 4
+#define DCRT_OUTPUT_BACKFACE 5
+#define DCRT_OUTPUT_ITERATION_COUNT 6
+typedef struct dcrt_output_params {
+    uint32_t output_type;          /* DCRT_OUTPUT_* (m_OutputType, default PATH_TRACING)            */
+    uint32_t iteration_threshold;  /* m_IterationThreshold (default 20); 1..10000 for ITERATION_COUNT */
+} dcrt_output_params;
+/* Select the view. With a view selected, whatever dcrt_tracer_set_mode says,
+ * dcrt_tracer_render_images renders one view image per seed (first-hit kernel + SampleConvolution,
+ * every image convolved) and dcrt_tracer_render renders the whole view image of the current frame
+ * seed into the sample textures in one call and reports it complete. A change of the type or
+ * the threshold raises the film-clear trigger (MegakernelPathTracer.cpp:361-372). */
+DCRT_API int dcrt_tracer_set_output(dcrt_tracer* tracer, const dcrt_output_params* params);
+DCRT_API int dcrt_tracer_get_output(dcrt_tracer* tracer, dcrt_output_params* out_params);
 DCRT_API int dcrt_tracer_reset_image(dcrt_tracer* tracer);                                     /* ResetImage() */
 DCRT_API int dcrt_tracer_is_image_complete(dcrt_tracer* tracer, int* out_complete);           /* IsImageComplete() */
 DCRT_API int dcrt_tracer_acquire_film_clear_trigger(dcrt_tracer* tracer, int* out_trigger);    /* AcquireFilmClearTrigger() */
