@@ -129,6 +129,12 @@ class OutputParams(C.Structure):
     _fields_ = [("output_type", C.c_uint32), ("iteration_threshold", C.c_uint32)]
 
 
+class DenoiseParams(C.Structure):
+    """dcrt_denoise_params; dcrt_denoise_default_params fills in 5, 4.0, 0.2, 0.1, 1."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_albedo", C.c_float), ("demodulate", C.c_uint32)]
+
+
 class RayStats(C.Structure):
     _fields_ = [("extension_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("new_paths", C.c_uint64),
                 ("iterations", C.c_uint64), ("images_completed", C.c_uint64)]
@@ -297,6 +303,17 @@ SIGNATURES = [
     ("dcrt_scene_get_postfx_params", _I, [_P, C.POINTER(PostFxParams)]),
     ("dcrt_srgb_encode_thresholds", _I, [_FP]),
     ("dcrt_tracer_resolve_image", _I, [_P, C.POINTER(PostFxParams), C.POINTER(C.c_uint8), _FP]),
+    ("dcrt_denoise_default_params", _I, [C.POINTER(DenoiseParams)]),
+    ("dcrt_tracer_render_guides", _I, [_P, _U, _U]),
+    ("dcrt_tracer_guide_device_ptrs", _I, [_P, C.POINTER(_P), C.POINTER(_P)]),
+    ("dcrt_tracer_read_guides", _I, [_P, _FP, _FP]),
+    ("dcrt_tracer_denoise", _I, [_P, C.POINTER(DenoiseParams)]),
+    ("dcrt_tracer_denoise_device", _I, [_P, C.POINTER(DenoiseParams), _U, _U, _P, _P, _P, _P]),
+    ("dcrt_tracer_denoise_images", _I, [_P, C.POINTER(DenoiseParams), _U, _U, _FP, _FP, _FP, _FP]),
+    ("dcrt_tracer_read_denoised", _I, [_P, _FP]),
+    ("dcrt_tracer_denoised_device_ptr", _I, [_P, C.POINTER(_P)]),
+    ("dcrt_tracer_resolve_denoised", _I, [_P, C.POINTER(PostFxParams), C.POINTER(C.c_uint8), _FP]),
+    ("dcrt_tracer_denoise_timings", _I, [_P, _FP, _U, C.POINTER(C.c_uint32)]),
     ("dcrt_write_bmp", _I, [C.c_char_p, _U, _U, C.POINTER(C.c_uint8)]),
     ("dcrt_device_math_eval", _I, [_P, _I, _FP, _U, _FP]),
 ]

@@ -2002,6 +2002,236 @@ __global__ void lut_finalize_kernel(const float* brdf, const float* brdfd, const
     }
 }
 
+// ---- film denoiser: variance-guided, edge-avoiding a-trous wavelet filter ------------------
+// (Dammertz et al. 2010 with the spatial variance guidance of SVGF, Schied et al. 2017; no
+// temporal part.) dcrt.h states the arithmetic; tests/denoise_ref.py restates it in numpy
+// float32, and every kernel below computes a pixel with the same operations in the same order
+// -- each thread sums its own pixel's taps sequentially (rows outer, columns inner, ascending),
+// whatever the staging, so all variants give the same bits. Taps outside the image are skipped.
+// Working image: (c.rgb, var) per pixel plus the decoded guides (n.xyz, 0), (a.xyz, 0).
+struct DenoiseConsts { float sigmaL, kn, ka; uint32_t demodulate; };
+
+constexpr int kDnTile = 16;                       // a workgroup: 16 x 16 pixels (or lattice points), one per thread
+constexpr int kDnThreads = kDnTile * kDnTile;
+constexpr int kDnVarHalo = 3;                     // the variance estimate's 7 x 7 window
+
+DEV float dn_lum(float4 c) { return c.x * 0.299f + c.y * 0.587f + c.z * 0.114f; }
+DEV float dn_dist2(float4 q, float4 p)
+{
+    const float x = q.x - p.x, y = q.y - p.y, z = q.z - p.z;
+    return x * x + y * y + z * z;
+}
+DEV V3 dn_resolve(float4 f) { return f.w > 0.0f ? mk(f.x / f.w, f.y / f.w, f.z / f.w) : mk(0.0f, 0.0f, 0.0f); }
+DEV V3 dn_demodulation(float4 a, uint32_t demodulate)
+{
+    return demodulate ? mk(fmaxf(a.x, 1e-3f), fmaxf(a.y, 1e-3f), fmaxf(a.z, 1e-3f)) : mk(1.0f, 1.0f, 1.0f);
+}
+
+// Resolve the three films and pack the working image: c0 = c / d, var = 0 (the variance kernel fills it in)
+__global__ __launch_bounds__(256) void denoise_prologue_kernel(const float4* __restrict__ color, const float4* __restrict__ normal,
+                                                               const float4* __restrict__ albedo, uint32_t n, uint32_t demodulate,
+                                                               float4* __restrict__ cv, float4* __restrict__ gn, float4* __restrict__ ga)
+{
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const V3 c = dn_resolve(color[i]), nr = dn_resolve(normal[i]), a = dn_resolve(albedo[i]);
+        const float4 a4 = make_float4(a.x, a.y, a.z, 0.0f);
+        const V3 d = dn_demodulation(a4, demodulate);
+        cv[i] = make_float4(c.x / d.x, c.y / d.y, c.z / d.z, 0.0f);
+        gn[i] = make_float4(2.0f * nr.x - 1.0f, 2.0f * nr.y - 1.0f, 2.0f * nr.z - 1.0f, 0.0f);
+        ga[i] = a4;
+    }
+}
+
+// Where a pixel's taps come from. tap(): the tap at pixel (qx, qy) = p + step * (dx, dy), inside
+// the image; var(): var of the pixel at p + (dx, dy), inside the image (the 3 x 3 prefilter).
+struct DnGlobalSrc {
+    const float4 *cv, *gn, *ga;
+    int W;
+    DEV void tap(int qx, int qy, int, int, float4* c, float4* n, float4* a) const
+    {
+        const size_t q = (size_t)qy * W + qx;
+        *c = cv[q]; *n = gn[q]; *a = ga[q];
+    }
+    DEV float var(int qx, int qy, int, int) const { return cv[(size_t)qy * W + qx].w; }
+};
+// The staged span of a workgroup: span x span lattice points around its 16 x 16, `base` this
+// thread's own, a tap `t` points apart. With varStaged the lattice is the pixel grid itself
+// (stride 1) and the prefilter's neighbours are staged too; otherwise they come from memory.
+struct DnLdsSrc {
+    const float4 *sC, *sN, *sA, *cv;
+    int base, span, t, W;
+    bool varStaged;
+    DEV void tap(int, int, int dx, int dy, float4* c, float4* n, float4* a) const
+    {
+        const int i = base + dy * t * span + dx * t;
+        *c = sC[i]; *n = sN[i]; *a = sA[i];
+    }
+    DEV float var(int qx, int qy, int dx, int dy) const
+    {
+        return varStaged ? sC[base + dy * span + dx].w : cv[(size_t)qy * W + qx].w;
+    }
+};
+
+// Stage the lattice points {(ox, oy) + L * (i - halo, j - halo)}, 0 <= i, j < span, that lie in the image
+DEV void dn_stage(float4* sC, float4* sN, float4* sA, const float4* __restrict__ cv, const float4* __restrict__ gn,
+                  const float4* __restrict__ ga, int ox, int oy, int L, int halo, int span, int W, int H)
+{
+    for (int e = (int)threadIdx.x; e < span * span; e += kDnThreads) {
+        const int j = e / span, i = e - j * span;
+        const int qx = ox + (i - halo) * L, qy = oy + (j - halo) * L;
+        if (qx >= 0 && qx < W && qy >= 0 && qy < H) {
+            const size_t q = (size_t)qy * W + qx;
+            sC[e] = cv[q]; sN[e] = gn[q]; sA[e] = ga[q];
+        }
+    }
+    __syncthreads();
+}
+
+// var0 of pixel (px, py): the guide-weighted second moment of the luminance over 7 x 7
+template <class Src>
+DEV float dn_variance_pixel(const DenoiseConsts& k, int px, int py, int W, int H, const Src& src)
+{
+    float4 cp, np, ap;
+    src.tap(px, py, 0, 0, &cp, &np, &ap);
+    float m1 = 0.0f, m2 = 0.0f, ws = 0.0f;
+    for (int dy = -kDnVarHalo; dy <= kDnVarHalo; ++dy) {
+        const int qy = py + dy;
+        if (qy < 0 || qy >= H) continue;
+        for (int dx = -kDnVarHalo; dx <= kDnVarHalo; ++dx) {
+            const int qx = px + dx;
+            if (qx < 0 || qx >= W) continue;
+            float4 cq, nq, aq;
+            src.tap(qx, qy, dx, dy, &cq, &nq, &aq);
+            const float wg = det_exp(-(dn_dist2(nq, np) * k.kn + dn_dist2(aq, ap) * k.ka));
+            const float l = dn_lum(cq);
+            m1 = m1 + l * wg;
+            m2 = m2 + l * l * wg;
+            ws = ws + wg;
+        }
+    }
+    const float mean = m1 / ws;
+    return fmaxf(m2 / ws - mean * mean, 0.0f);
+}
+
+// One a-trous pass at pixel (px, py), taps `step` pixels apart: (c_{i+1}.rgb, var_{i+1})
+template <class Src>
+DEV float4 dn_pass_pixel(const DenoiseConsts& k, int px, int py, int W, int H, int step, const Src& src)
+{
+    constexpr float h[5] = { 1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f };
+    constexpr float g[3] = { 1.0f / 4.0f, 1.0f / 2.0f, 1.0f / 4.0f };
+    float gs = 0.0f, gw = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy) {
+        const int qy = py + dy;
+        if (qy < 0 || qy >= H) continue;
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int qx = px + dx;
+            if (qx < 0 || qx >= W) continue;
+            const float w = g[dy + 1] * g[dx + 1];
+            gs = gs + src.var(qx, qy, dx, dy) * w;
+            gw = gw + w;
+        }
+    }
+    const float gv = gs / gw;
+    const float kl = k.sigmaL > 0.0f ? 1.0f / (k.sigmaL * sqrtf(gv) + 1e-6f) : 0.0f;
+    float4 cp, np, ap;
+    src.tap(px, py, 0, 0, &cp, &np, &ap);
+    const float lp = dn_lum(cp);
+    float sx = 0.0f, sy = 0.0f, sz = 0.0f, sv = 0.0f, ws = 0.0f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int qy = py + dy * step;
+        if (qy < 0 || qy >= H) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int qx = px + dx * step;
+            if (qx < 0 || qx >= W) continue;
+            float4 cq, nq, aq;
+            src.tap(qx, qy, dx, dy, &cq, &nq, &aq);
+            const float e = fabsf(dn_lum(cq) - lp) * kl + dn_dist2(nq, np) * k.kn + dn_dist2(aq, ap) * k.ka;
+            const float w = (h[dy + 2] * h[dx + 2]) * det_exp(-e);
+            sx = sx + cq.x * w; sy = sy + cq.y * w; sz = sz + cq.z * w;
+            sv = sv + cq.w * (w * w);
+            ws = ws + w;
+        }
+    }
+    return make_float4(sx / ws, sy / ws, sz / ws, sv / (ws * ws));
+}
+
+// The last pass remodulates: (c_N * d, 1) into the caller's image instead of the working one
+DEV void dn_store(float4 r, float4 a, const DenoiseConsts& k, size_t p, float4* __restrict__ dst, float4* __restrict__ finalOut)
+{
+    if (finalOut) {
+        const V3 d = dn_demodulation(a, k.demodulate);
+        finalOut[p] = make_float4(r.x * d.x, r.y * d.y, r.z * d.z, 1.0f);
+    } else {
+        dst[p] = r;
+    }
+}
+
+// Variance estimate, a 16 x 16 tile plus its 3-pixel halo staged in LDS (22 x 22 x 48 B): dst = (c0, var0)
+__global__ __launch_bounds__(kDnThreads) void denoise_variance_kernel(DenoiseConsts k, const float4* __restrict__ cv,
+                                                                      const float4* __restrict__ gn, const float4* __restrict__ ga,
+                                                                      int W, int H, float4* __restrict__ dst)
+{
+    constexpr int span = kDnTile + 2 * kDnVarHalo;
+    __shared__ float4 sC[span * span], sN[span * span], sA[span * span];
+    const int tilesX = (W + kDnTile - 1) / kDnTile;
+    const int x0 = (int)(blockIdx.x % (uint32_t)tilesX) * kDnTile, y0 = (int)(blockIdx.x / (uint32_t)tilesX) * kDnTile;
+    dn_stage(sC, sN, sA, cv, gn, ga, x0, y0, 1, kDnVarHalo, span, W, H);
+    const int li = (int)threadIdx.x % kDnTile, lj = (int)threadIdx.x / kDnTile;
+    const int px = x0 + li, py = y0 + lj;
+    if (px >= W || py >= H) return;
+    const DnLdsSrc src{ sC, sN, sA, cv, (lj + kDnVarHalo) * span + li + kDnVarHalo, span, 1, W, true };
+    const float4 c = sC[src.base];
+    dst[(size_t)py * W + px] = make_float4(c.x, c.y, c.z, dn_variance_pixel(k, px, py, W, H, src));
+}
+
+// A-trous pass, every tap from memory: one thread per pixel of a 16 x 16 tile
+__global__ __launch_bounds__(kDnThreads) void denoise_pass_global_kernel(DenoiseConsts k, const float4* __restrict__ cv,
+                                                                         const float4* __restrict__ gn, const float4* __restrict__ ga,
+                                                                         int W, int H, int step, float4* __restrict__ dst,
+                                                                         float4* __restrict__ finalOut)
+{
+    const int tilesX = (W + kDnTile - 1) / kDnTile;
+    const int px = (int)(blockIdx.x % (uint32_t)tilesX) * kDnTile + (int)threadIdx.x % kDnTile;
+    const int py = (int)(blockIdx.x / (uint32_t)tilesX) * kDnTile + (int)threadIdx.x / kDnTile;
+    if (px >= W || py >= H) return;
+    const DnGlobalSrc src{ cv, gn, ga, W };
+    const size_t p = (size_t)py * W + px;
+    dn_store(dn_pass_pixel(k, px, py, W, H, step, src), ga[p], k, p, dst, finalOut);
+}
+
+// A-trous pass from an LDS-staged span (dynamic LDS: 3 x span^2 float4). The workgroup owns
+// 16 x 16 points of the lattice {r + L * (i, j)} of residue class r = (rx, ry), 0 <= rx, ry < L:
+//   L = 1:    a pixel tile; the taps are step pixels apart, the halo 2 * step (small steps);
+//   L = step: the decimated lattice, whose taps are neighbours again: halo 2 at any step.
+// blockIdx.x = class * tiles + tile, tiles = tilesX * tilesY over the largest class's lattice.
+__global__ __launch_bounds__(kDnThreads) void denoise_pass_staged_kernel(DenoiseConsts k, const float4* __restrict__ cv,
+                                                                         const float4* __restrict__ gn, const float4* __restrict__ ga,
+                                                                         int W, int H, int step, int L, float4* __restrict__ dst,
+                                                                         float4* __restrict__ finalOut)
+{
+    extern __shared__ float4 dnSpan[];
+    const int t = step / L, halo = 2 * t, span = kDnTile + 2 * halo;
+    float4 *sC = dnSpan, *sN = sC + span * span, *sA = sN + span * span;
+    const int tilesX = ((W + L - 1) / L + kDnTile - 1) / kDnTile, tilesY = ((H + L - 1) / L + kDnTile - 1) / kDnTile;
+    const uint32_t tiles = (uint32_t)(tilesX * tilesY);
+    const int cls = (int)(blockIdx.x / tiles), tile = (int)(blockIdx.x % tiles);
+    const int rx = cls % L, ry = cls / L;
+    const int i0 = (tile % tilesX) * kDnTile, j0 = (tile / tilesX) * kDnTile;   // lattice coordinates of the tile
+    const int x0 = rx + i0 * L, y0 = ry + j0 * L;
+    if (x0 >= W || y0 >= H) return;   // (the whole workgroup: a class or tile without a pixel)
+    dn_stage(sC, sN, sA, cv, gn, ga, x0, y0, L, halo, span, W, H);
+    const int li = (int)threadIdx.x % kDnTile, lj = (int)threadIdx.x / kDnTile;
+    const int px = x0 + li * L, py = y0 + lj * L;
+    if (px >= W || py >= H) return;
+    const DnLdsSrc src{ sC, sN, sA, cv, (lj + halo) * span + li + halo, span, t, W, L == 1 };
+    const size_t p = (size_t)py * W + px;
+    dn_store(dn_pass_pixel(k, px, py, W, H, step, src), sA[src.base], k, p, dst, finalOut);
+}
+
 // ---- explicit instantiations used by tracer.hip ---------------------------------------
 template __global__ void extension_kernel<false, false>(PathPool, DeviceScene, const FrameConstants*, const Counters*, Globals*, unsigned long long*);
 template __global__ void extension_kernel<false, true>(PathPool, DeviceScene, const FrameConstants*, const Counters*, Globals*, unsigned long long*);

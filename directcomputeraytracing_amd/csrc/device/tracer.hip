@@ -590,6 +590,7 @@ struct dcrt_tracer {
     int ReadCompletion(bool* complete);
     int Render(uint32_t maxIterations);
     int LaunchView();
+    int LaunchView(uint32_t type, const Film& target);
     int RenderImages(uint32_t firstSeed, uint32_t count, const dcrt_filter_params& filter, uint32_t stride = 1,
                      bool convolve = true);
     int AccumulateImages(const void* const* pos, const void* const* val, uint32_t count, const dcrt_filter_params& filter);
@@ -617,7 +618,27 @@ struct dcrt_tracer {
     uint32_t viewResidentOpacity = 0;  // the same for the ALLOW_ANYHIT_SHADER variant
     // the "Output" view (dcrt_tracer_set_output): anything but PATH_TRACING renders first hits
     dcrt_output_params output{ DCRT_OUTPUT_PATH_TRACING, 20u };
-    uint32_t drainResident = 0;        // drain_kernel grid (resident workgroups)
+    // the film denoiser (dcrt_tracer_render_guides / dcrt_tracer_denoise*): two guide films and the
+    // denoised image follow the film (filmAllocs); the working images follow the denoised size
+    float4* guideNormal = nullptr;
+    float4* guideAlbedo = nullptr;
+    float4* denoised = nullptr;
+    bool guidesRendered = false, hasDenoised = false;
+    dcrt_filter_params lastFilter{};   // the reconstruction filter on the device (UploadFilter)
+    bool hasFilter = false;
+    std::vector<void*> denoiseAllocs;
+    float4* dnWork[2] = { nullptr, nullptr };   // (c.rgb, var), ping-pong
+    float4* dnNormal = nullptr;        // decoded guides (n.xyz, 0), (a.xyz, 0)
+    float4* dnAlbedo = nullptr;
+    uint32_t dnW = 0, dnH = 0;
+    std::vector<hipEvent_t> dnEvents;  // ext_timing: one event per kernel boundary of the last denoise
+    uint32_t dnEventsUsed = 0;
+    int EnsureGuides();
+    int RenderGuides(uint32_t firstSeed, uint32_t count);
+    int EnsureDenoiseWork(uint32_t w, uint32_t h);
+    int Denoise(const dcrt_denoise_params& p, uint32_t w, uint32_t h, const float4* color, const float4* normal,
+                const float4* albedo, float4* out);
+    uint32_t drainResident = 0;       // drain_kernel grid (resident workgroups)
     uint32_t drainPaths = 0;           // drain_kernel threshold (DCRT_DRAIN_PATHS; 0: no drain launches -- the default: profiles/r04_ab_virtual_drain.txt)
     int mode = 0;                      // 0 wavefront (WavefrontPathTracer), 1 megakernel (MegakernelPathTracer)
     uint32_t castResidentInstr = 0;    // the same for the counting kernels (whole stack: castLdsFull)
@@ -637,6 +658,8 @@ dcrt_tracer::~dcrt_tracer()
     InvalidateGraph();
     for (hipEvent_t e : events) (void)hipEventDestroy(e);
     for (hipEvent_t e : stopEvents) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : dnEvents) (void)hipEventDestroy(e);
+    FreeAll(&denoiseAllocs);
     if (hFilter) (void)hipHostFree(hFilter);
     if (dSourceLists) (void)hipFree(dSourceLists);
     if (hStop) (void)hipHostFree(hStop);
@@ -1360,6 +1383,8 @@ int dcrt_tracer::EnsureFilm(uint32_t w, uint32_t h)
     FreeAll(&filmAllocs);
     FreeAll(&sampleAllocs);
     sampleImages = 0;
+    guideNormal = guideAlbedo = denoised = nullptr;   // (they follow the film: EnsureGuides)
+    guidesRendered = hasDenoised = false;
     const size_t n = (size_t)w * h;
     CHECKED(DeviceAlloc(&film.accum, n, &filmAllocs));
     HIPCHECK(hipMemsetAsync(film.accum, 0, n * sizeof(float4), stream));
@@ -1773,7 +1798,10 @@ int dcrt_tracer::ReadCompletion(bool* complete)
 
 // One first-hit view image (dcrt_tracer_set_output) of the frame constants BeginImage uploaded,
 // into sample slot 0: one persistent launch, as the megakernel's
-int dcrt_tracer::LaunchView()
+int dcrt_tracer::LaunchView() { return LaunchView(output.output_type, film); }
+
+// ... of output `type` into the sample textures of `target` (RenderGuides: the tracer's own, by value)
+int dcrt_tracer::LaunchView(uint32_t type, const Film& target)
 {
     Annotation an("Output view", !capturing);
     const bool opacity = (frame.features & DCRT_FEATURE_ALLOW_ANYHIT) != 0;
@@ -1781,7 +1809,7 @@ int dcrt_tracer::LaunchView()
     if (extTiming) CHECKED(TimedPair(kTimedCast, &e0, &e1));
     auto vk = opacity ? view_kernel<true> : view_kernel<false>;
     hipExtLaunchKernelGGL(vk, dim3(opacity ? viewResidentOpacity : viewResident), dim3(castBlock), castLdsFull, stream, e0, e1, 0, scene,
-                          (const FrameConstants*)dFrame, film, dGlobals, (uint32_t)(film.debugRng != nullptr), output.output_type,
+                          (const FrameConstants*)dFrame, target, dGlobals, (uint32_t)(target.debugRng != nullptr), type,
                           output.iteration_threshold);
     HIPCHECK(hipGetLastError());
     return DCRT_OK;
@@ -1819,6 +1847,8 @@ int dcrt_tracer::UploadFilter(const dcrt_filter_params& f)
 {
     HIPCHECK(hipStreamSynchronize(stream));     // the pinned staging buffer is reused
     *hFilter = MakeFilter(f);
+    lastFilter = f;
+    hasFilter = true;
     HIPCHECK(hipMemcpyAsync(dFilter, hFilter, sizeof(FilterConsts), hipMemcpyHostToDevice, stream));
     return DCRT_OK;
 }
@@ -1831,6 +1861,180 @@ int dcrt_tracer::Accumulate(const dcrt_filter_params& f)
     hipLaunchKernelGGL(film_kernel, dim3(FilmGrid()), dim3(kFilmThreads), 0, stream, film, (const FilterConsts*)dFilter, 1u,
                        (const Globals*)nullptr, (const float2* const*)nullptr, (const float4* const*)nullptr);
     HIPCHECK(hipGetLastError());
+    return DCRT_OK;
+}
+
+// The guide films and the denoised image, W x H of the film; EnsureFilm drops them with it.
+int dcrt_tracer::EnsureGuides()
+{
+    if (guideNormal) return DCRT_OK;
+    if (!film.accum) { SetLastError("no film"); return DCRT_E_INVALID_ARG; }
+    const size_t n = (size_t)filmW * filmH;
+    CHECKED(DeviceAlloc(&guideNormal, n, &filmAllocs));
+    CHECKED(DeviceAlloc(&guideAlbedo, n, &filmAllocs));
+    CHECKED(DeviceAlloc(&denoised, n, &filmAllocs));
+    return DCRT_OK;
+}
+
+// The denoiser's guides: for each seed the first-hit shading-normal and albedo views (view_kernel,
+// the sub-pixel positions of the path-traced image of that seed), convolved with the film's
+// reconstruction filter into the two guide films. The film, the selected output, the frame seed
+// and the counters stay; the sample textures (slot 0) and the path pool are overwritten.
+int dcrt_tracer::RenderGuides(uint32_t firstSeed, uint32_t count)
+{
+    Annotation an("RenderGuides");
+    if (!hasScene) { SetLastError("no scene uploaded"); return DCRT_E_NO_SCENE; }
+    if (!hasFrame) { SetLastError("no frame parameters"); return DCRT_E_INVALID_ARG; }
+    if (!hasFilter) { SetLastError("render_guides convolves with the film's filter: render or accumulate the film first"); return DCRT_E_INVALID_ARG; }
+    CHECKED(CheckFrameLights());
+    if (partition.world_size > 1 || !bands.empty()) {
+        const uint32_t halo = partition.halo_rows ? partition.halo_rows : 2u;
+        if (!(lastFilter.radius >= 0.0f) || FilterSupportRows(lastFilter.radius, filmH) > halo) {
+            SetLastError("filter radius needs more halo rows than the film partition renders");
+            return DCRT_E_INVALID_ARG;
+        }
+    }
+    CHECKED(EnsureGuides());
+    const size_t n = (size_t)filmW * filmH;
+    HIPCHECK(hipMemsetAsync(guideNormal, 0, n * sizeof(float4), stream));
+    HIPCHECK(hipMemsetAsync(guideAlbedo, 0, n * sizeof(float4), stream));
+    guidesRendered = false;
+    keptSlots = false;   // (slot 0 holds the last guide image now)
+    lastSlot = 0;
+    const uint32_t seed = frame.frame_seed;
+    int rc = DCRT_OK;
+    for (uint32_t img = 0; img < count && rc == DCRT_OK; ++img) {
+        for (int which = 0; which < 2 && rc == DCRT_OK; ++which) {
+            Film target = film;
+            target.accum = which == 0 ? guideNormal : guideAlbedo;
+            frame.frame_seed = firstSeed + img;
+            rc = BeginImage();
+            if (rc == DCRT_OK) rc = LaunchView(which == 0 ? DCRT_OUTPUT_SHADING_NORMAL : DCRT_OUTPUT_ALBEDO, target);
+            if (rc != DCRT_OK) break;
+            hipLaunchKernelGGL(film_kernel, dim3(FilmGrid()), dim3(kFilmThreads), 0, stream, target, (const FilterConsts*)dFilter, 1u,
+                               (const Globals*)nullptr, (const float2* const*)nullptr, (const float4* const*)nullptr);
+            if (hipGetLastError() != hipSuccess) { SetLastError("guide film pass failed to launch"); rc = DCRT_E_HIP; }
+        }
+    }
+    frame.frame_seed = seed;
+    newImage = true;   // (BeginImage reset the pool: a progressive image in flight starts over)
+    if (rc != DCRT_OK) return rc;
+    HIPCHECK(hipStreamSynchronize(stream));
+    guidesRendered = true;
+    return DCRT_OK;
+}
+
+int dcrt_tracer::EnsureDenoiseWork(uint32_t w, uint32_t h)
+{
+    if (w == dnW && h == dnH && dnWork[0]) return DCRT_OK;
+    HIPCHECK(hipStreamSynchronize(stream));
+    FreeAll(&denoiseAllocs);
+    dnW = dnH = 0;
+    dnWork[0] = dnWork[1] = dnNormal = dnAlbedo = nullptr;
+    const size_t n = (size_t)w * h;
+    CHECKED(DeviceAlloc(&dnWork[0], n, &denoiseAllocs));
+    CHECKED(DeviceAlloc(&dnWork[1], n, &denoiseAllocs));
+    CHECKED(DeviceAlloc(&dnNormal, n, &denoiseAllocs));
+    CHECKED(DeviceAlloc(&dnAlbedo, n, &denoiseAllocs));
+    dnW = w; dnH = h;
+    return DCRT_OK;
+}
+
+static int CheckDenoiseParams(const dcrt_denoise_params& p)
+{
+    if (p.iterations < 1u || p.iterations > 8u) { SetLastError("denoise: iterations 1..8"); return DCRT_E_INVALID_ARG; }
+    for (const float s : { p.sigma_luminance, p.sigma_normal, p.sigma_albedo }) {
+        if (!(s >= 0.0f) || !std::isfinite(s)) { SetLastError("denoise: sigmas are finite and >= 0 (0 switches a term off)"); return DCRT_E_INVALID_ARG; }
+    }
+    return DCRT_OK;
+}
+
+// The lattice stride L of the pass at `step` (DESIGN "Film denoiser", profiles/denoise_ab_pass.txt):
+// 0 every tap from memory; 1 the LDS-staged pixel tile (halo 2 * step); L > 1 the LDS-staged
+// lattice of every L-th pixel, its taps step / L points apart. DCRT_DENOISE_PASS=global | tile |
+// lattice (L = step) | latticeN (L = min(N, step)) forces one for an A/B, where its span fits.
+// All compute the same bits. The default is what measured fastest per step at 1920x1080
+// (profiles/denoise_ab_pass.txt): the tile up to step 4; from memory at step 8 (the lattice's
+// staging loads lie 128 B apart there and take twice as long); the lattice at 16 and 32; from
+// memory again at 64 and 128, where most taps fall outside the image and most lattice
+// workgroups hold a handful of points.
+static uint32_t DenoisePassLattice(uint32_t step)
+{
+    uint32_t L = step <= 4u ? 1u : (step == 16u || step == 32u) ? step : 0u;
+    if (const char* e = std::getenv("DCRT_DENOISE_PASS")) {
+        uint32_t want = L;
+        if (!std::strcmp(e, "global")) want = 0u;
+        else if (!std::strcmp(e, "tile")) want = 1u;
+        else if (!std::strcmp(e, "lattice")) want = step;
+        else if (!std::strncmp(e, "lattice", 7)) want = std::min<uint32_t>(step, std::max(1, std::atoi(e + 7)));
+        // (a stride that divides the step and leaves taps at most 4 lattice points apart: 48 KiB of LDS)
+        if (want == 0u || (step % want == 0u && step / want <= 4u)) L = want;
+    }
+    return L;
+}
+
+// The filter of dcrt.h "film denoiser" over W x H device images in film convention, into `out`
+// (c_N * d, 1): prologue (resolve + pack), variance estimate, `iterations` a-trous passes that
+// ping-pong between the two working images, the last one remodulating into `out`. Synchronous.
+int dcrt_tracer::Denoise(const dcrt_denoise_params& p, uint32_t w, uint32_t h, const float4* color, const float4* normal,
+                         const float4* albedo, float4* out)
+{
+    Annotation an("Denoise");
+    CHECKED(CheckDenoiseParams(p));
+    if (w == 0 || h == 0 || w > 65535u || h > 65535u) { SetLastError("denoise: invalid image size"); return DCRT_E_INVALID_ARG; }
+    if (!color || !normal || !albedo || !out) { SetLastError("denoise: null image"); return DCRT_E_INVALID_ARG; }
+    const size_t n = (size_t)w * h, bytes = n * sizeof(float4);
+    for (const float4* in : { color, normal, albedo }) {
+        const char *a = (const char*)in, *b = (const char*)out;
+        if (a < b + bytes && b < a + bytes) { SetLastError("denoise: the output image overlaps an input"); return DCRT_E_INVALID_ARG; }
+    }
+    CHECKED(EnsureDenoiseWork(w, h));
+    DenoiseConsts k;
+    k.sigmaL = p.sigma_luminance;
+    k.kn = p.sigma_normal > 0.0f ? 1.0f / (p.sigma_normal * p.sigma_normal) : 0.0f;
+    k.ka = p.sigma_albedo > 0.0f ? 1.0f / (p.sigma_albedo * p.sigma_albedo) : 0.0f;
+    k.demodulate = p.demodulate ? 1u : 0u;
+    dnEventsUsed = 0;
+    auto mark = [&]() -> int {
+        if (!extTiming) return DCRT_OK;
+        if (dnEvents.size() <= dnEventsUsed) {
+            hipEvent_t e;
+            HIPCHECK(hipEventCreate(&e));
+            dnEvents.push_back(e);
+        }
+        HIPCHECK(hipEventRecord(dnEvents[dnEventsUsed++], stream));
+        return DCRT_OK;
+    };
+    const int W = (int)w, H = (int)h;
+    const uint32_t tiles = ((w + kDnTile - 1) / kDnTile) * ((h + kDnTile - 1) / kDnTile);
+    CHECKED(mark());
+    hipLaunchKernelGGL(denoise_prologue_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)((n + 255) / 256), kMaxPersistentBlocks * 4u))),
+                       dim3(256), 0, stream, color, normal, albedo, (uint32_t)n, k.demodulate, dnWork[0], dnNormal, dnAlbedo);
+    CHECKED(mark());
+    hipLaunchKernelGGL(denoise_variance_kernel, dim3(tiles), dim3(kDnThreads), 0, stream, k, (const float4*)dnWork[0],
+                       (const float4*)dnNormal, (const float4*)dnAlbedo, W, H, dnWork[1]);
+    CHECKED(mark());
+    uint32_t src = 1;
+    for (uint32_t i = 0; i < p.iterations; ++i) {
+        const uint32_t step = 1u << i;
+        float4* finalOut = i + 1 == p.iterations ? out : nullptr;
+        uint32_t L = DenoisePassLattice(step);
+        const uint32_t Ls = std::max(1u, L), t = step / Ls, span = (uint32_t)kDnTile + 4u * t;
+        const uint64_t blocks = (uint64_t)Ls * Ls * (((w + Ls - 1) / Ls + kDnTile - 1) / kDnTile) * (((h + Ls - 1) / Ls + kDnTile - 1) / kDnTile);
+        if (blocks > 0x7FFFFFFFull) L = 0u;   // (a lattice of a huge image at a large step: more classes than a grid holds)
+        if (L == 0u) {
+            hipLaunchKernelGGL(denoise_pass_global_kernel, dim3(tiles), dim3(kDnThreads), 0, stream, k, (const float4*)dnWork[src],
+                               (const float4*)dnNormal, (const float4*)dnAlbedo, W, H, (int)step, dnWork[src ^ 1u], finalOut);
+        } else {
+            hipLaunchKernelGGL(denoise_pass_staged_kernel, dim3((uint32_t)blocks), dim3(kDnThreads), (size_t)3 * span * span * sizeof(float4),
+                               stream, k, (const float4*)dnWork[src], (const float4*)dnNormal, (const float4*)dnAlbedo, W, H, (int)step,
+                               (int)L, dnWork[src ^ 1u], finalOut);
+        }
+        CHECKED(mark());
+        src ^= 1u;
+    }
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(stream));
     return DCRT_OK;
 }
 
@@ -2480,10 +2684,9 @@ DCRT_API int dcrt_tracer_get_output(dcrt_tracer* t, dcrt_output_params* out)
     return DCRT_OK;
 }
 
-DCRT_API int dcrt_tracer_resolve_image(dcrt_tracer* t, const dcrt_postfx_params* prm, uint8_t* out, float* outSumLogLum)
+// SumLuminance + post-processing of `image` (the film, or the denoised image: W x H of the film)
+static int ResolveFrom(dcrt_tracer* t, const float4* image, const dcrt_postfx_params* prm, uint8_t* out, float* outSumLogLum)
 {
-    TRACER_GUARD(t);
-    if (!prm || !out || !t->film.accum) return DCRT_E_INVALID_ARG;
     const uint32_t W = t->filmW, H = t->filmH;
     float hth[255];
     dcrt_srgb_encode_thresholds(hth);
@@ -2497,7 +2700,7 @@ DCRT_API int dcrt_tracer_resolve_image(dcrt_tracer* t, const dcrt_postfx_params*
     float *la = nullptr, *lb = nullptr;
     CHECKED(DeviceAlloc(&la, (size_t)bx * by + 1, &tmp));
     CHECKED(DeviceAlloc(&lb, (size_t)bx * by + 1, &tmp));
-    hipLaunchKernelGGL(luminance_1d_kernel, dim3(bx, by), dim3(64), 0, t->stream, (const float4*)t->film.accum, W, H, bx, by, la);
+    hipLaunchKernelGGL(luminance_1d_kernel, dim3(bx, by), dim3(64), 0, t->stream, image, W, H, bx, by, la);
     uint32_t count = bx * by;
     while (count != 1) {
         const uint32_t groups = (count + 127) / 128;
@@ -2508,13 +2711,144 @@ DCRT_API int dcrt_tracer_resolve_image(dcrt_tracer* t, const dcrt_postfx_params*
     uchar4* dout = nullptr;
     CHECKED(DeviceAlloc(&dout, (size_t)W * H, &tmp));
     const uint32_t grid = std::max<uint32_t>(1u, std::min<uint32_t>((W * H + 255) / 256, kMaxPersistentBlocks));
-    hipLaunchKernelGGL(postfx_kernel, dim3(grid), dim3(256), 0, t->stream, (const float4*)t->film.accum, W, H, prm->enabled,
+    hipLaunchKernelGGL(postfx_kernel, dim3(grid), dim3(256), 0, t->stream, image, W, H, prm->enabled,
                        prm->auto_exposure, prm->ev100, prm->luminance_white * prm->luminance_white, (const float*)la,
                        (const float*)dth, dout);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpyAsync(out, dout, (size_t)W * H * 4, hipMemcpyDeviceToHost, t->stream));
     if (outSumLogLum) HIPCHECK(hipMemcpyAsync(outSumLogLum, la, sizeof(float), hipMemcpyDeviceToHost, t->stream));
     HIPCHECK(hipStreamSynchronize(t->stream));
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_resolve_image(dcrt_tracer* t, const dcrt_postfx_params* prm, uint8_t* out, float* outSumLogLum)
+{
+    TRACER_GUARD(t);
+    if (!prm || !out || !t->film.accum) return DCRT_E_INVALID_ARG;
+    return ResolveFrom(t, (const float4*)t->film.accum, prm, out, outSumLogLum);
+}
+
+// ---- film denoiser ------------------------------------------------------------------------
+DCRT_API int dcrt_denoise_default_params(dcrt_denoise_params* out)
+{
+    if (!out) return DCRT_E_INVALID_ARG;
+    out->iterations = 5u;
+    out->sigma_luminance = 4.0f;
+    out->sigma_normal = 0.2f;
+    out->sigma_albedo = 0.1f;
+    out->demodulate = 1u;
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_render_guides(dcrt_tracer* t, uint32_t first_seed, uint32_t image_count)
+{
+    TRACER_GUARD(t);
+    return t->RenderGuides(first_seed, image_count);
+}
+
+DCRT_API int dcrt_tracer_guide_device_ptrs(dcrt_tracer* t, void** out_normal, void** out_albedo)
+{
+    TRACER_GUARD(t);
+    if (!out_normal || !out_albedo) return DCRT_E_INVALID_ARG;
+    if (!t->guidesRendered) { SetLastError("no guides rendered at this resolution"); return DCRT_E_INVALID_ARG; }
+    *out_normal = t->guideNormal;
+    *out_albedo = t->guideAlbedo;
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_read_guides(dcrt_tracer* t, float* out_normal, float* out_albedo)
+{
+    TRACER_GUARD(t);
+    if (!out_normal || !out_albedo) return DCRT_E_INVALID_ARG;
+    if (!t->guidesRendered) { SetLastError("no guides rendered at this resolution"); return DCRT_E_INVALID_ARG; }
+    const size_t bytes = (size_t)t->filmW * t->filmH * sizeof(float4);
+    HIPCHECK(hipMemcpyAsync(out_normal, t->guideNormal, bytes, hipMemcpyDeviceToHost, t->stream));
+    HIPCHECK(hipMemcpyAsync(out_albedo, t->guideAlbedo, bytes, hipMemcpyDeviceToHost, t->stream));
+    HIPCHECK(hipStreamSynchronize(t->stream));
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_denoise(dcrt_tracer* t, const dcrt_denoise_params* p)
+{
+    TRACER_GUARD(t);
+    if (!p) return DCRT_E_INVALID_ARG;
+    if (t->partition.world_size > 1 || !t->bands.empty()) {
+        SetLastError("denoise: a banded or partitioned film lacks its neighbours' rows; reduce the films and guides and "
+                     "use dcrt_tracer_denoise_device on the sums");
+        return DCRT_E_INVALID_ARG;
+    }
+    if (!t->guidesRendered || !t->film.accum) {
+        SetLastError("denoise: no guides rendered at this resolution (dcrt_tracer_render_guides)");
+        return DCRT_E_INVALID_ARG;
+    }
+    CHECKED(t->Denoise(*p, t->filmW, t->filmH, t->film.accum, t->guideNormal, t->guideAlbedo, t->denoised));
+    t->hasDenoised = true;
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_denoise_device(dcrt_tracer* t, const dcrt_denoise_params* p, uint32_t width, uint32_t height,
+                                        const void* d_color, const void* d_normal, const void* d_albedo, void* d_out)
+{
+    TRACER_GUARD(t);
+    if (!p) return DCRT_E_INVALID_ARG;
+    return t->Denoise(*p, width, height, (const float4*)d_color, (const float4*)d_normal, (const float4*)d_albedo, (float4*)d_out);
+}
+
+DCRT_API int dcrt_tracer_denoise_images(dcrt_tracer* t, const dcrt_denoise_params* p, uint32_t width, uint32_t height,
+                                        const float* color, const float* normal, const float* albedo, float* out)
+{
+    TRACER_GUARD(t);
+    if (!p || !color || !normal || !albedo || !out || width == 0 || height == 0 || width > 65535u || height > 65535u)
+        return DCRT_E_INVALID_ARG;
+    CHECKED(CheckDenoiseParams(*p));
+    const size_t n = (size_t)width * height, bytes = n * sizeof(float4);
+    std::vector<void*> tmp;
+    struct Free { std::vector<void*>* v; ~Free() { FreeAll(v); } } guard{ &tmp };
+    float4* d[4] = {};
+    for (float4*& q : d) CHECKED(DeviceAlloc(&q, n, &tmp));
+    const float* src[3] = { color, normal, albedo };
+    for (int i = 0; i < 3; ++i) HIPCHECK(hipMemcpyAsync(d[i], src[i], bytes, hipMemcpyHostToDevice, t->stream));
+    CHECKED(t->Denoise(*p, width, height, d[0], d[1], d[2], d[3]));
+    HIPCHECK(hipMemcpyAsync(out, d[3], bytes, hipMemcpyDeviceToHost, t->stream));
+    HIPCHECK(hipStreamSynchronize(t->stream));
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_read_denoised(dcrt_tracer* t, float* out)
+{
+    TRACER_GUARD(t);
+    if (!out) return DCRT_E_INVALID_ARG;
+    if (!t->hasDenoised) { SetLastError("no denoised image (dcrt_tracer_denoise)"); return DCRT_E_INVALID_ARG; }
+    HIPCHECK(hipMemcpyAsync(out, t->denoised, (size_t)t->filmW * t->filmH * sizeof(float4), hipMemcpyDeviceToHost, t->stream));
+    HIPCHECK(hipStreamSynchronize(t->stream));
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_denoised_device_ptr(dcrt_tracer* t, void** out)
+{
+    TRACER_GUARD(t);
+    if (!out) return DCRT_E_INVALID_ARG;
+    if (!t->hasDenoised) { SetLastError("no denoised image (dcrt_tracer_denoise)"); return DCRT_E_INVALID_ARG; }
+    *out = t->denoised;
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_resolve_denoised(dcrt_tracer* t, const dcrt_postfx_params* prm, uint8_t* out, float* outSumLogLum)
+{
+    TRACER_GUARD(t);
+    if (!prm || !out) return DCRT_E_INVALID_ARG;
+    if (!t->hasDenoised) { SetLastError("no denoised image (dcrt_tracer_denoise)"); return DCRT_E_INVALID_ARG; }
+    return ResolveFrom(t, (const float4*)t->denoised, prm, out, outSumLogLum);
+}
+
+DCRT_API int dcrt_tracer_denoise_timings(dcrt_tracer* t, float* out_ms, uint32_t capacity, uint32_t* out_count)
+{
+    TRACER_GUARD(t);
+    if (!out_count || (capacity && !out_ms)) return DCRT_E_INVALID_ARG;
+    const uint32_t kernels = t->dnEventsUsed ? t->dnEventsUsed - 1u : 0u;
+    *out_count = kernels;
+    for (uint32_t i = 0; i < kernels && i < capacity; ++i)
+        HIPCHECK(hipEventElapsedTime(&out_ms[i], t->dnEvents[i], t->dnEvents[i + 1]));
     return DCRT_OK;
 }
 

@@ -243,14 +243,75 @@ class WavefrontPathTracer:
         """film += the RGBA32F film at device address d_src (another partition's film)."""
         check(self._lib.dcrt_tracer_add_film_device(self._h, C.c_void_p(d_src)), "AddFilmDevice")
 
-    def resolve_image(self, params: _abi.PostFxParams | None = None, with_luminance: bool = False):
-        """Post-processing (exposure + Reinhard) into sRGB8 RGBA, H x W x 4 uint8."""
+    def resolve_image(self, params: _abi.PostFxParams | None = None, with_luminance: bool = False, denoised: bool = False):
+        """Post-processing (exposure + Reinhard) into sRGB8 RGBA, H x W x 4 uint8: of the film, or
+        with denoised=True of the last denoise()'s image."""
         p = params or _abi.PostFxParams(1, 1, 15.0, 1.0)
         out = np.empty((self.height, self.width, 4), np.uint8)
         lum = C.c_float()
-        check(self._lib.dcrt_tracer_resolve_image(self._h, C.byref(p), out.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                  C.byref(lum)), "ResolveImage")
+        fn = self._lib.dcrt_tracer_resolve_denoised if denoised else self._lib.dcrt_tracer_resolve_image
+        check(fn(self._h, C.byref(p), out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(lum)),
+              "ResolveDenoised" if denoised else "ResolveImage")
         return (out, lum.value) if with_luminance else out
+
+    # ---- film denoiser ---------------------------------------------------------
+    def render_guides(self, first_seed: int, count: int) -> None:
+        """The denoiser's guide films of images first_seed .. first_seed + count - 1 (the seeds the
+        film was rendered with): first-hit shading normal and albedo, convolved with the film's
+        filter. Overwrites the sample textures; the film and the selected output stay."""
+        check(self._lib.dcrt_tracer_render_guides(self._h, int(first_seed), int(count)), "RenderGuides")
+
+    def read_guides(self):
+        """(normal film, albedo film), H x W x 4 float32 each, in film convention."""
+        nrm = np.empty((self.height, self.width, 4), np.float32)
+        alb = np.empty((self.height, self.width, 4), np.float32)
+        check(self._lib.dcrt_tracer_read_guides(self._h, nrm.ctypes.data_as(_abi._FP), alb.ctypes.data_as(_abi._FP)), "ReadGuides")
+        return nrm, alb
+
+    def guide_device_ptrs(self) -> tuple[int, int]:
+        nrm, alb = C.c_void_p(), C.c_void_p()
+        check(self._lib.dcrt_tracer_guide_device_ptrs(self._h, C.byref(nrm), C.byref(alb)), "GuideDevicePtrs")
+        return nrm.value or 0, alb.value or 0
+
+    def denoise(self, params: _abi.DenoiseParams | None = None) -> np.ndarray:
+        """Filter the film with the rendered guides; returns the denoised image (H x W x 4 float32,
+        film convention with w = 1), which resolve_image(denoised=True) tone-maps."""
+        p = params or denoise_default_params()
+        check(self._lib.dcrt_tracer_denoise(self._h, C.byref(p)), "Denoise")
+        out = np.empty((self.height, self.width, 4), np.float32)
+        check(self._lib.dcrt_tracer_read_denoised(self._h, out.ctypes.data_as(_abi._FP)), "ReadDenoised")
+        return out
+
+    def denoised_device_ptr(self) -> int:
+        p = C.c_void_p()
+        check(self._lib.dcrt_tracer_denoised_device_ptr(self._h, C.byref(p)), "DenoisedDevicePtr")
+        return p.value or 0
+
+    def denoise_images(self, color, normal, albedo, params: _abi.DenoiseParams | None = None) -> np.ndarray:
+        """The same filter over host images (H x W x 4 float32, film convention)."""
+        p = params or denoise_default_params()
+        c, n, a = (np.ascontiguousarray(x, np.float32) for x in (color, normal, albedo))
+        if c.ndim != 3 or c.shape[2] != 4 or n.shape != c.shape or a.shape != c.shape:
+            raise ValueError("denoise_images: three H x W x 4 images of one shape")
+        out = np.empty_like(c)
+        check(self._lib.dcrt_tracer_denoise_images(self._h, C.byref(p), c.shape[1], c.shape[0], c.ctypes.data_as(_abi._FP),
+                                                   n.ctypes.data_as(_abi._FP), a.ctypes.data_as(_abi._FP),
+                                                   out.ctypes.data_as(_abi._FP)), "DenoiseImages")
+        return out
+
+    def denoise_device(self, width: int, height: int, d_color: int, d_normal: int, d_albedo: int, d_out: int,
+                       params: _abi.DenoiseParams | None = None) -> None:
+        """... over device images, e.g. the reduced films of a multi-GPU render; d_out may not overlap an input."""
+        p = params or denoise_default_params()
+        check(self._lib.dcrt_tracer_denoise_device(self._h, C.byref(p), int(width), int(height), C.c_void_p(d_color),
+                                                   C.c_void_p(d_normal), C.c_void_p(d_albedo), C.c_void_p(d_out)), "DenoiseDevice")
+
+    def denoise_timings(self) -> list:
+        """ms per kernel of the last denoise (prologue, variance, passes) with ext_timing on."""
+        ms = (C.c_float * 16)()
+        n = C.c_uint32()
+        check(self._lib.dcrt_tracer_denoise_timings(self._h, ms, 16, C.byref(n)), "DenoiseTimings")
+        return [float(ms[i]) for i in range(min(16, n.value))]
 
     # ---- statistics ----------------------------------------------------------
     def counters(self) -> dict:
@@ -317,6 +378,13 @@ class WavefrontPathTracer:
         check(self._lib.dcrt_device_math_eval(self._h, int(function), x.ctypes.data_as(_abi._FP), x.size,
                                               y.ctypes.data_as(_abi._FP)), "MathEval")
         return y
+
+
+def denoise_default_params() -> _abi.DenoiseParams:
+    """dcrt_denoise_default_params: 5 iterations, sigmas 4 / 0.2 / 0.1, demodulation on (no device needed)."""
+    p = _abi.DenoiseParams()
+    check(_abi.load_library().dcrt_denoise_default_params(C.byref(p)), "DenoiseDefaultParams")
+    return p
 
 
 def srgb_thresholds() -> np.ndarray:

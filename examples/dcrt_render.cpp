@@ -7,7 +7,11 @@
 //   dcrt_render <scene.obj|scene.xml> <width> <height> <spp> <max_bounce> <out.bmp>
 //               [--batch] [--point x y z r g b] [--seed-type sample-count|frame-index|fixed]
 //               [--fixed-seed N] [--iterations N] [--pool N] [--film out.f32] [--samples out.f32]
-//               [--edit N:KIND:ARGS]... [--output NAME [--iteration-threshold N]]
+//               [--edit N:KIND:ARGS]... [--output NAME [--iteration-threshold N]] [--denoise]
+//
+// --denoise renders the denoiser's guide films (first-hit normal and albedo) with the seeds of the
+// film's images, filters the film with the default parameters (dcrt_tracer_denoise) and writes the
+// BMP from the denoised image; --film still writes the unfiltered film. Path tracing only.
 //
 // --output selects the tracer's "Output" view, in either mode: path_tracing (default), normal,
 // tangent, albedo, negative_ndotv, backface or iteration_count (BVH node visits of the camera
@@ -61,7 +65,7 @@ int Usage(const char* exe)
                  "       [--seed-type sample-count|frame-index|fixed] [--fixed-seed N] [--iterations N] [--pool N]\n"
                  "       [--film out.f32] [--samples out.f32] [--edit N:KIND:ARGS]...\n"
                  "       [--output path_tracing|normal|tangent|albedo|negative_ndotv|backface|iteration_count]\n"
-                 "       [--iteration-threshold N]\n",
+                 "       [--iteration-threshold N] [--denoise]\n",
                  exe);
     return 2;
 }
@@ -166,7 +170,7 @@ int main(int argc, char** argv)
     const uint32_t width = (uint32_t)std::atoi(argv[2]), height = (uint32_t)std::atoi(argv[3]);
     const uint32_t spp = (uint32_t)std::atoi(argv[4]), maxBounce = (uint32_t)std::atoi(argv[5]);
     const char* outPath = argv[6];
-    bool batch = false, pointLight = false;
+    bool batch = false, pointLight = false, denoise = false;
     float lightPos[3] = {0, 0, 0}, lightColor[3] = {0, 0, 0};
     CRendererLoop::EFrameSeedType seedType = CRendererLoop::EFrameSeedType::SampleCount;
     uint32_t fixedSeed = 0, iterations = 16, pool = 0;
@@ -178,6 +182,8 @@ int main(int argc, char** argv)
         const bool more = i + 1 < argc;
         if (!std::strcmp(argv[i], "--batch")) {
             batch = true;
+        } else if (!std::strcmp(argv[i], "--denoise")) {
+            denoise = true;
         } else if (!std::strcmp(argv[i], "--point") && i + 6 < argc) {
             pointLight = true;
             for (int k = 0; k < 3; ++k) lightPos[k] = (float)std::atof(argv[i + 1 + k]);
@@ -219,6 +225,7 @@ int main(int argc, char** argv)
     }
     if (width == 0 || height == 0 || spp == 0 || iterations == 0) return Usage(argv[0]);
     if (batch && !edits.empty()) return Usage(argv[0]);   // (edits belong to the frame loop)
+    if (denoise && outputType != DCRT_OUTPUT_PATH_TRACING) return Usage(argv[0]);   // (a view is noise-free)
 
     // CDirectComputeRayTracing::Init: new + Create (LaunchRendererLoop.cpp:58-64)
     CScene scene;
@@ -312,7 +319,27 @@ int main(int argc, char** argv)
     if (!Check(dcrt_scene_get_postfx_params(scene.m_Handle, &post), "GetPostFxParams")) return 1;
     std::vector<uint8_t> rgba(n * 4);
     float sumLogLuminance = 0.0f;
-    if (!Check(dcrt_tracer_resolve_image(tracer.GetTracer(), &post, rgba.data(), &sumLogLuminance), "ResolveImage")) return 1;
+    if (denoise) {
+        // the guides of the film's own images: the same seeds, so the same sub-pixel positions
+        // (a fixed seed repeats one image: its guides are every image's)
+        bool consecutive = !seeds.empty(), equal = !seeds.empty();
+        for (size_t i = 0; i < seeds.size(); ++i) {
+            consecutive = consecutive && seeds[i] == seeds[0] + (uint32_t)i;
+            equal = equal && seeds[i] == seeds[0];
+        }
+        if (!consecutive && !equal) {
+            std::fprintf(stderr, "--denoise: the film's frame seeds are not consecutive (use sample-count seeds or --batch)\n");
+            return 1;
+        }
+        dcrt_denoise_params dn;
+        if (!Check(dcrt_denoise_default_params(&dn), "DenoiseDefaultParams") ||
+            !Check(dcrt_tracer_render_guides(tracer.GetTracer(), seeds[0], consecutive ? (uint32_t)seeds.size() : 1u), "RenderGuides") ||
+            !Check(dcrt_tracer_denoise(tracer.GetTracer(), &dn), "Denoise") ||
+            !Check(dcrt_tracer_resolve_denoised(tracer.GetTracer(), &post, rgba.data(), &sumLogLuminance), "ResolveDenoised"))
+            return 1;
+    } else if (!Check(dcrt_tracer_resolve_image(tracer.GetTracer(), &post, rgba.data(), &sumLogLuminance), "ResolveImage")) {
+        return 1;
+    }
     if (!Check(dcrt_write_bmp(outPath, W, H, rgba.data()), "WriteBmp")) return 1;
     dcrt_ray_stats stats;
     if (!Check(dcrt_tracer_counters(tracer.GetTracer(), &stats), "Counters")) return 1;

@@ -303,7 +303,9 @@ typedef struct dcrt_scene dcrt_scene;
 /* ABI version of this header: bumped whenever a struct changes size or an entry point its
  * meaning (2: dcrt_tracer_info grew cast_waves_per_cu / ring_rows / stack_lds_rows). A caller
  * compiled against another header checks dcrt_abi_version() == DCRT_ABI_VERSION before it
- * passes any struct (a smaller dcrt_tracer_info would be written past its end). */
+ * passes any struct (a smaller dcrt_tracer_info would be written past its end). Added entry
+ * points with structs of their own (the scene updates, the output views, the film denoiser)
+ * leave it as it is: nothing an older caller passes has changed. */
 #define DCRT_ABI_VERSION 2
 DCRT_API int dcrt_abi_version(void);
 DCRT_API const char* dcrt_version(void);
@@ -653,6 +655,84 @@ DCRT_API int dcrt_srgb_encode_thresholds(float out_thresholds[255]);
 /* Tone-map the film into sRGB8 RGBA (W*H*4 bytes); optional sum of log luminance (auto exposure). */
 DCRT_API int dcrt_tracer_resolve_image(dcrt_tracer* tracer, const dcrt_postfx_params* params, uint8_t* out_rgba8,
                                        float* out_sum_log_luminance);
+/* ===== film denoiser ========================================================
+ * A variance-guided, edge-avoiding a-trous wavelet filter (Dammertz et al. 2010 with the spatial
+ * variance guidance of SVGF, Schied et al. 2017; no temporal part, no depth guide) for the 1-16 spp
+ * films of an interactive loop. No reference counterpart. Inputs are three W x H RGBA32F images in
+ * film convention (sum w*L, sum w): the colour film and two guide films holding the first hit's
+ * shading normal (stored as n * 0.5 + 0.5, the view's encoding) and albedo.
+ *
+ * All arithmetic is fp32 in exactly this order (no contraction, correctly rounded / and sqrt,
+ * exp = the det_exp of dcrt_device_math_eval function 2), so a float32 restatement matches bit
+ * for bit (tests/denoise_ref.py):
+ *   resolve(f) = f.w > 0 ? f.rgb / f.w : 0;  c = resolve(colour), a = resolve(albedo),
+ *   n = 2 * resolve(normal) - 1;  kn = 1 / (sigma_normal * sigma_normal), ka likewise (0 for a
+ *   sigma of 0: the term is off);  d = demodulate ? max(a, 1e-3) per channel : 1;
+ *   lum(x) = x.r * 0.299 + x.g * 0.587 + x.b * 0.114;  h = [1/16, 1/4, 3/8, 1/4, 1/16],
+ *   g = [1/4, 1/2, 1/4];  |v|^2 = v.x * v.x + v.y * v.y + v.z * v.z;  every sum runs dy outer,
+ *   dx inner, ascending, by sequential adds from 0, and skips the taps outside the image.
+ *   1. c_0 = c / d.
+ *   2. Over the 7 x 7 window q = p + (dx, dy): wg = exp(-(|n_q - n_p|^2 * kn + |a_q - a_p|^2 * ka)),
+ *      l = lum(c_0(q)); m1 += l * wg, m2 += (l * l) * wg, ws += wg; mean = m1 / ws,
+ *      var_0 = max(m2 / ws - mean * mean, 0).
+ *   3. Pass i = 0 .. iterations - 1, step s = 2^i: over the 3 x 3 window at step 1,
+ *      gs += var_i(q) * (g[dy+1] * g[dx+1]), gw += g[dy+1] * g[dx+1]; gv = gs / gw;
+ *      kl = sigma_luminance > 0 ? 1 / (sigma_luminance * sqrt(gv) + 1e-6) : 0. Over the 5 x 5 taps
+ *      q = p + s * (dx, dy): e = |lum(c_i(q)) - lum(c_i(p))| * kl + |n_q - n_p|^2 * kn + |a_q - a_p|^2 * ka,
+ *      w = (h[dy+2] * h[dx+2]) * exp(-e); sum += c_i(q) * w, sv += var_i(q) * (w * w), ws += w;
+ *      c_{i+1} = sum / ws, var_{i+1} = sv / (ws * ws).
+ *   4. Output (c_N * d, 1): an RGBA32F image in film convention, so the resolve / post-processing
+ *      path takes it as it takes the film.
+ * Non-finite input pixels are out of scope: they spread through the windows that contain them. */
+typedef struct dcrt_denoise_params {
+    uint32_t iterations;       /* a-trous passes, 1..8 (default 5: steps 1, 2, 4, 8, 16)            */
+    float sigma_luminance;     /* in standard deviations of the local luminance (default 4)        */
+    float sigma_normal;        /* default 0.2                                                       */
+    float sigma_albedo;        /* default 0.1                                                       */
+    uint32_t demodulate;       /* nonzero (default): filter c / albedo, multiply the albedo back    */
+} dcrt_denoise_params;
+/* A sigma of 0 switches its term off; a negative or non-finite sigma, or iterations outside 1..8,
+ * is DCRT_E_INVALID_ARG in every denoise call. */
+DCRT_API int dcrt_denoise_default_params(dcrt_denoise_params* out_params);   /* needs no device */
+/* The guides of images first_seed .. first_seed + image_count - 1: per seed the first-hit
+ * Shading Normal and Albedo views (the kernel of dcrt_tracer_set_output, at the sub-pixel
+ * positions of that seed's path-traced image), each convolved into a tracer-owned guide film
+ * with the reconstruction filter of the tracer's last render_images / accumulate call
+ * (DCRT_E_INVALID_ARG before any), after both guide films were cleared. The film, the selected
+ * output, the film-clear trigger, the counters and the frame seed stay as they are; the sample
+ * textures are overwritten, and a progressive dcrt_tracer_render image in flight starts over. On
+ * a banded or partitioned tracer it renders the tracer's own rows, as a view render does, and the
+ * guide films of the ranks sum as their films do. */
+DCRT_API int dcrt_tracer_render_guides(dcrt_tracer* tracer, uint32_t first_seed, uint32_t image_count);
+/* The guide films (W*H RGBA32F each) in device memory / copied out; DCRT_E_INVALID_ARG before
+ * dcrt_tracer_render_guides at the current resolution. */
+DCRT_API int dcrt_tracer_guide_device_ptrs(dcrt_tracer* tracer, void** out_normal, void** out_albedo);
+DCRT_API int dcrt_tracer_read_guides(dcrt_tracer* tracer, float* out_normal_rgba, float* out_albedo_rgba);
+/* Filter the tracer's film with its guide films into the tracer-owned denoised image.
+ * DCRT_E_INVALID_ARG without guides rendered at the current resolution, and on a banded or
+ * partitioned tracer (its film lacks the neighbours' rows: reduce films and guides, then
+ * dcrt_tracer_denoise_device on the sums). Synchronous, on the tracer's stream. */
+DCRT_API int dcrt_tracer_denoise(dcrt_tracer* tracer, const dcrt_denoise_params* params);
+/* The same filter over caller-provided device images (width * height RGBA32F each, on the
+ * tracer's device) into d_out, which must not overlap an input (DCRT_E_INVALID_ARG). The tracer's
+ * own film is not used, so any tracer will do, e.g. rank 0 after the RCCL reduce. Synchronous. */
+DCRT_API int dcrt_tracer_denoise_device(dcrt_tracer* tracer, const dcrt_denoise_params* params, uint32_t width, uint32_t height,
+                                        const void* d_color, const void* d_normal, const void* d_albedo, void* d_out);
+/* ... and over host images (tests and tools). */
+DCRT_API int dcrt_tracer_denoise_images(dcrt_tracer* tracer, const dcrt_denoise_params* params, uint32_t width, uint32_t height,
+                                        const float* color, const float* normal, const float* albedo, float* out_rgba);
+/* The result of the last dcrt_tracer_denoise (W*H*4 floats); DCRT_E_INVALID_ARG before one, or
+ * after a resolution change. */
+DCRT_API int dcrt_tracer_read_denoised(dcrt_tracer* tracer, float* out_rgba);
+DCRT_API int dcrt_tracer_denoised_device_ptr(dcrt_tracer* tracer, void** out_ptr);
+/* dcrt_tracer_resolve_image with the denoised image in the film's place. */
+DCRT_API int dcrt_tracer_resolve_denoised(dcrt_tracer* tracer, const dcrt_postfx_params* params, uint8_t* out_rgba8,
+                                          float* out_sum_log_luminance);
+/* With ext_timing on (dcrt_tracer_set_instrumentation): the HIP-event times in ms of the kernels
+ * of the last denoise call, in launch order -- prologue, variance estimate, pass 0 .. N-1.
+ * Writes at most `capacity` entries; *out_count = the number of kernels (0 without ext_timing). */
+DCRT_API int dcrt_tracer_denoise_timings(dcrt_tracer* tracer, float* out_ms, uint32_t capacity, uint32_t* out_count);
+
 /* 24-bit BMP writer ("Save Image to File", SaveImageToFile.cpp:92-182). */
 DCRT_API int dcrt_write_bmp(const char* path, uint32_t width, uint32_t height, const uint8_t* rgba8);
 
