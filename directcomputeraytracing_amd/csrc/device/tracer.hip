@@ -25,6 +25,7 @@
 
 namespace dcrt {
 void SetLastError(const std::string& s);
+int CheckFilterParams(const dcrt_filter_params& f);   // (capi_scene.cpp: the one rule for scene and tracer)
 }
 using dcrt::SetLastError;
 using namespace dcrt::dev;
@@ -1845,6 +1846,7 @@ int dcrt_tracer::Render(uint32_t maxIterations)
 
 int dcrt_tracer::UploadFilter(const dcrt_filter_params& f)
 {
+    CHECKED(dcrt::CheckFilterParams(f));        // (refused before anything is enqueued or changed)
     HIPCHECK(hipStreamSynchronize(stream));     // the pinned staging buffer is reused
     *hFilter = MakeFilter(f);
     lastFilter = f;
@@ -2043,6 +2045,7 @@ int dcrt_tracer::Denoise(const dcrt_denoise_params& p, uint32_t w, uint32_t h, c
 // host only enqueues graphs and polls a pinned "stopped" word two graphs behind.
 int dcrt_tracer::RenderImages(uint32_t firstSeed, uint32_t count, const dcrt_filter_params& filter, uint32_t stride, bool convolve)
 {
+    CHECKED(dcrt::CheckFilterParams(filter));   // (before the seed stride, the kept slots and the sample textures change)
     seedStride = std::max<uint32_t>(1u, stride);
     keptSlots = false;
     Annotation an("RenderImages");
@@ -2170,6 +2173,7 @@ int dcrt_tracer::AccumulateImages(const void* const* pos, const void* const* val
 {
     Annotation an("SampleConvolution (image list)");
     if (!film.accum) { SetLastError("no film"); return DCRT_E_INVALID_ARG; }
+    CHECKED(dcrt::CheckFilterParams(f));
     if (count == 0) return DCRT_OK;
     if (count > sourceCap) {
         HIPCHECK(hipStreamSynchronize(stream));

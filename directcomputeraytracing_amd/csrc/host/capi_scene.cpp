@@ -14,6 +14,17 @@
 namespace dcrt {
 thread_local std::string g_lastError;
 void SetLastError(const std::string& s) { g_lastError = s; }
+
+// What a film pass can take (dcrt.h, dcrt_filter_params), for the scene and for the tracer's entry
+// points alike: a known kind -- the kernels' default case would draw anything else as a box -- and
+// a radius whose window bounds (int)floorf(c -/+ radius) are defined for every film coordinate.
+int CheckFilterParams(const dcrt_filter_params& f)
+{
+    if (f.filter > DCRT_FILTER_LANCZOS) { SetLastError("unknown reconstruction filter"); return DCRT_E_INVALID_ARG; }
+    if (!(f.radius >= 0.0f)) { SetLastError("filter radius is negative or NaN"); return DCRT_E_INVALID_ARG; }
+    if (!(f.radius < 1073741824.0f)) { SetLastError("filter radius is 2^30 or more"); return DCRT_E_INVALID_ARG; }
+    return DCRT_OK;
+}
 }  // namespace dcrt
 
 struct dcrt_scene {
@@ -211,7 +222,8 @@ DCRT_API int dcrt_scene_set_max_bounce(dcrt_scene* s, uint32_t max_bounce)
 
 DCRT_API int dcrt_scene_set_filter(dcrt_scene* s, const dcrt_filter_params* f)
 {
-    if (!s || !f || f->filter > DCRT_FILTER_LANCZOS || !(f->radius >= 0.0f)) return DCRT_E_INVALID_ARG;
+    if (!s || !f) return DCRT_E_INVALID_ARG;
+    if (const int rc = dcrt::CheckFilterParams(*f)) return rc;
     s->scene.filter = (dcrt::EFilter)f->filter;
     s->scene.filterRadius = f->radius;
     s->scene.gaussianFilterAlpha = f->gaussian_alpha;

@@ -196,7 +196,11 @@ typedef struct dcrt_frame_params {
     uint32_t features;            /* DCRT_FEATURE_* */
 } dcrt_frame_params;
 
-/* Film reconstruction (Scene.h:131-136, SampleConvolution.cpp:100-130). */
+/* Film reconstruction (Scene.h:131-136, SampleConvolution.cpp:100-130).
+   Every entry point that takes a dcrt_filter_params answers DCRT_E_INVALID_ARG (with a
+   dcrt_last_error text, the film and the device filter untouched) to a filter above
+   DCRT_FILTER_LANCZOS and to a radius that is NaN, negative or >= 2^30 (the window bounds
+   floor(c -/+ radius) must fit an int for every film coordinate). */
 #define DCRT_FILTER_BOX      0
 #define DCRT_FILTER_TRIANGLE 1
 #define DCRT_FILTER_GAUSSIAN 2
@@ -208,7 +212,7 @@ typedef struct dcrt_filter_params {
     float gaussian_alpha;
     float mitchell_b;
     float mitchell_c;
-    uint32_t lanczos_tau;
+    uint32_t lanczos_tau;         /* 0 reads as 3, the reference's default (Scene.h:136) */
 } dcrt_filter_params;
 
 /* Ray / hit records of the kernel-level boundary (WavefrontPathTracing.hlsl:3-17). */

@@ -1865,7 +1865,7 @@ static void make_filter_consts(const dcrt_filter_params* p, filter_consts* c)
         c->mf[0] = -B - 6 * C; c->mf[1] = 6 * B + 30 * C; c->mf[2] = -12 * B - 48 * C; c->mf[3] = 8 * B + 24 * C;
         c->mf[4] = 12 - 9 * B - 6 * C; c->mf[5] = -18 + 12 * B + 6 * C; c->mf[6] = 6 - 2 * B;
     } else if (p->filter == DCRT_FILTER_LANCZOS) {
-        c->tau = p->lanczos_tau;
+        c->tau = p->lanczos_tau ? p->lanczos_tau : 3;   /* 0 reads as the default (Scene.h:136), as in dcrt.h */
     }
 }
 void oracle_sample_convolution(const dcrt_filter_params* fp, uint32_t W, uint32_t H, const float* spos, const float* sval,
