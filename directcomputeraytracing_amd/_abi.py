@@ -135,6 +135,18 @@ class DenoiseParams(C.Structure):
                 ("sigma_albedo", C.c_float), ("demodulate", C.c_uint32)]
 
 
+class NoiseStats(C.Structure):
+    """dcrt_noise_stats: the half-film noise estimate of a film (dcrt.h "film noise estimate")."""
+    _fields_ = [("images", C.c_uint32), ("valid_pixels", C.c_uint32), ("converged_pixels", C.c_uint32),
+                ("mean_error", C.c_float), ("max_error", C.c_float), ("max_tile_error", C.c_float)]
+
+
+class ConvergeParams(C.Structure):
+    """dcrt_converge_params of dcrt_tracer_render_converged."""
+    _fields_ = [("threshold", C.c_float), ("target_fraction", C.c_float), ("min_images", C.c_uint32),
+                ("max_images", C.c_uint32), ("check_interval", C.c_uint32)]
+
+
 class RayStats(C.Structure):
     _fields_ = [("extension_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("new_paths", C.c_uint64),
                 ("iterations", C.c_uint64), ("images_completed", C.c_uint64)]
@@ -314,6 +326,18 @@ SIGNATURES = [
     ("dcrt_tracer_denoised_device_ptr", _I, [_P, C.POINTER(_P)]),
     ("dcrt_tracer_resolve_denoised", _I, [_P, C.POINTER(PostFxParams), C.POINTER(C.c_uint8), _FP]),
     ("dcrt_tracer_denoise_timings", _I, [_P, _FP, _U, C.POINTER(C.c_uint32)]),
+    ("dcrt_tracer_set_convergence", _I, [_P, _I]),
+    ("dcrt_tracer_film_image_count", _I, [_P, C.POINTER(C.c_uint32)]),
+    ("dcrt_tracer_half_film_device_ptr", _I, [_P, C.POINTER(_P)]),
+    ("dcrt_tracer_read_half_film", _I, [_P, _FP]),
+    ("dcrt_tracer_add_half_film_device", _I, [_P, _P]),
+    ("dcrt_tracer_noise", _I, [_P, C.c_float, C.POINTER(NoiseStats)]),
+    ("dcrt_tracer_noise_device", _I, [_P, _U, _U, _P, _P, C.c_float, _P, _P, C.POINTER(NoiseStats)]),
+    ("dcrt_tracer_film_pass_timing", _I, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    ("dcrt_tracer_noise_map_device_ptrs", _I, [_P, C.POINTER(_P), C.POINTER(_P)]),
+    ("dcrt_tracer_read_noise_maps", _I, [_P, _FP, _FP]),
+    ("dcrt_tracer_render_converged", _I, [_P, _U, C.POINTER(ConvergeParams), C.POINTER(FilterParams), C.POINTER(NoiseStats),
+                                          C.POINTER(C.c_int)]),
     ("dcrt_write_bmp", _I, [C.c_char_p, _U, _U, C.POINTER(C.c_uint8)]),
     ("dcrt_device_math_eval", _I, [_P, _I, _FP, _U, _FP]),
 ]

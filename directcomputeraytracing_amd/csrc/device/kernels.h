@@ -78,6 +78,7 @@ struct Globals {
     // CONTROL workgroups, 0 = off); cleared after that iteration.
     uint32_t staticFill, staticGrid;
     uint32_t skipFilm;        // RenderImages without the film pass: the caller convolves the images (accumulate_images)
+    uint32_t filmImageBase;   // the film's image count when this RenderImages began (film_half_kernel: image parity)
     unsigned long long extRays, shadowRays, iterations;
 };
 

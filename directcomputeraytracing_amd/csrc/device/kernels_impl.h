@@ -1640,11 +1640,17 @@ __device__ __forceinline__ void film_pixel_window(const FilterConsts& c, uint32_
 
 // posList / valList (accumulate_images): image b's sample textures sit at posList[b] / valList[b]
 // (W*H each, e.g. other pipelines' slots) instead of at slot b of this film's.
-__global__ __launch_bounds__(kFilmThreads) void film_kernel(Film film, const FilterConsts* fcon, uint32_t images, const Globals* guard,
-                                                   const float2* const* __restrict__ posList,
-                                                   const float4* const* __restrict__ valList)
+// HALF (the convergence estimate's half film, dcrt.h "film noise estimate"): a second accumulator
+// `half` takes the same additions, in the same order, for the images whose film image index
+// (firstIndex + b; under `guard` the call's base plus the images done, both from device memory:
+// the launch sits in a replayed graph) is even.
+template <bool HALF>
+__device__ __forceinline__ void film_pass(Film film, const FilterConsts* fcon, uint32_t images, const Globals* guard,
+                                          const float2* const* __restrict__ posList, const float4* const* __restrict__ valList,
+                                          float4* half, uint32_t firstIndex)
 {
     if (guard && (!guard->imageComplete || guard->skipFilm)) return;
+    const uint32_t first = HALF ? (guard ? guard->filmImageBase + guard->imagesDone : firstIndex) : 0u;
     // the images of a completed batch, in order: per pixel the same additions as one
     // film pass per image
     const uint32_t count = guard ? guard->batchImages : images;
@@ -1664,9 +1670,11 @@ __global__ __launch_bounds__(kFilmThreads) void film_kernel(Film film, const Fil
         if (film.rowOwned && !__syncthreads_or(mine)) continue;
         int xs = 0, xe = -1, ys = 0, ye = -1;
         float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        float4 hv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (mine) {
             film_pixel_window(c, px, py, W, H, &xs, &xe, &ys, &ye);
             v = film.accum[(size_t)py * W + px];
+            if (HALF) hv = half[(size_t)py * W + px];
         }
         // The tile's staged span is the union of its pixels' windows, taken from the
         // windows of its first and last pixel: floorf(p + 0.5 -/+ r) is monotone in p, so
@@ -1695,6 +1703,7 @@ __global__ __launch_bounds__(kFilmThreads) void film_kernel(Film film, const Fil
                         wsum = wsum + w;
                     }
                 v.x = v.x + sum.x; v.y = v.y + sum.y; v.z = v.z + sum.z; v.w = v.w + wsum;
+                if (HALF && !((first + b) & 1u)) { hv.x = hv.x + sum.x; hv.y = hv.y + sum.y; hv.z = hv.z + sum.z; hv.w = hv.w + wsum; }
             }
         } else {
             // staged span [txs, txe] x [tys, tye]: inside the film by construction
@@ -1767,6 +1776,7 @@ __global__ __launch_bounds__(kFilmThreads) void film_kernel(Film film, const Fil
                                 wsum = wsum + w;
                             }
                         v.x = v.x + sum.x; v.y = v.y + sum.y; v.z = v.z + sum.z; v.w = v.w + wsum;
+                        if (HALF && !((first + b) & 1u)) { hv.x = hv.x + sum.x; hv.y = hv.y + sum.y; hv.z = hv.z + sum.z; hv.w = hv.w + wsum; }
                     }
                 }
             };
@@ -1779,8 +1789,23 @@ __global__ __launch_bounds__(kFilmThreads) void film_kernel(Film film, const Fil
             }
         }
         if (mine) film.accum[(size_t)py * W + px] = v;
+        if (HALF && mine) half[(size_t)py * W + px] = hv;
         __syncthreads();   // the tile buffers are reused by the next tile
     }
+}
+
+__global__ __launch_bounds__(kFilmThreads) void film_kernel(Film film, const FilterConsts* fcon, uint32_t images, const Globals* guard,
+                                                   const float2* const* __restrict__ posList,
+                                                   const float4* const* __restrict__ valList)
+{
+    film_pass<false>(film, fcon, images, guard, posList, valList, nullptr, 0u);
+}
+// ... with the half film (convergence on: dcrt_tracer_set_convergence)
+__global__ __launch_bounds__(kFilmThreads) void film_half_kernel(Film film, const FilterConsts* fcon, uint32_t images, const Globals* guard,
+                                                        const float2* const* __restrict__ posList,
+                                                        const float4* const* __restrict__ valList, float4* half, uint32_t firstIndex)
+{
+    film_pass<true>(film, fcon, images, guard, posList, valList, half, firstIndex);
 }
 
 // film += src (dcrt_tracer_add_film_device): the films of disjoint film partitions
@@ -1810,10 +1835,11 @@ __global__ void advance_image_kernel(FrameConstants* fc, Globals* g)
 }
 
 __global__ void begin_images_kernel(Globals* g, const FrameConstants* fc, uint32_t count, uint32_t firstSeed, uint32_t batchCap,
-                                    uint32_t staticGrid, uint32_t skipFilm)
+                                    uint32_t staticGrid, uint32_t skipFilm, uint32_t filmImageBase)
 {
     if (threadIdx.x != 0) return;
     g->skipFilm = skipFilm;
+    g->filmImageBase = filmImageBase;
     g->imagesDone = 0u;
     g->imageTarget = count;
     g->seedBase = firstSeed;
@@ -1869,6 +1895,99 @@ __global__ __launch_bounds__(128) void luminance_single_kernel(const float* in, 
         __syncthreads();
     }
     if (threadIdx.x == 0) out[blockIdx.x] = acc[0];
+}
+
+// ---- film noise estimate (dcrt.h "film noise estimate"; tests/noise_ref.py restates it) -------
+constexpr int kNoiseTile = 16;
+struct NoiseTotals { uint32_t valid, converged; float total, maxError, maxTileError; };
+// One 16x16 pixel tile per workgroup: the per-pixel error e of the film against its half film,
+// the tile's sum of e (LDS tree 128 -> 1), valid / converged counts and fmaxf maximum.
+__global__ __launch_bounds__(kNoiseTile * kNoiseTile) void noise_tile_kernel(const float4* film, const float4* half, uint32_t W, uint32_t H,
+                                                                          float threshold, float* pixelMap, float* tileMap,
+                                                                          float* tileSum, float* tileMax, float* tileErr,
+                                                                          uint32_t* tileCounts)
+{
+    __shared__ float acc[kNoiseTile * kNoiseTile];
+    __shared__ float top[kNoiseTile * kNoiseTile];
+    __shared__ uint32_t cnt[2][kNoiseTile * kNoiseTile];
+    const uint32_t t = threadIdx.x;
+    const uint32_t x = blockIdx.x * kNoiseTile + (t % kNoiseTile), y = blockIdx.y * kNoiseTile + (t / kNoiseTile);
+    float e = 0.0f;
+    uint32_t valid = 0u, converged = 0u;
+    if (x < W && y < H) {
+        const size_t p = (size_t)y * W + x;
+        const float4 f = film[p], h = half[p];
+        if (f.w > 0.0f && h.w > 0.0f) {
+            valid = 1u;
+            const float cr = f.x / f.w, cg = f.y / f.w, cb = f.z / f.w;
+            const float ar = h.x / h.w, ag = h.y / h.w, ab = h.z / h.w;
+            const float d = (fabsf(cr - ar) + fabsf(cg - ag)) + fabsf(cb - ab);
+            const float s = (cr + cg) + cb;
+            const float n = sqrtf(fmaxf(s, 0.0f));
+            e = d / (n + 1e-4f);
+            converged = e <= threshold ? 1u : 0u;
+        }
+        if (pixelMap) pixelMap[p] = e;
+    }
+    acc[t] = e;
+    top[t] = fmaxf(0.0f, e);
+    cnt[0][t] = valid;
+    cnt[1][t] = converged;
+    __syncthreads();
+    for (uint32_t k = kNoiseTile * kNoiseTile / 2; k >= 1; k >>= 1) {
+        if (t < k) {
+            acc[t] = acc[t] + acc[t + k];
+            top[t] = fmaxf(top[t], top[t + k]);
+            cnt[0][t] += cnt[0][t + k];
+            cnt[1][t] += cnt[1][t + k];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        const uint32_t tile = blockIdx.y * gridDim.x + blockIdx.x;
+        const float err = cnt[0][0] ? acc[0] / (float)cnt[0][0] : 0.0f;
+        tileSum[tile] = acc[0];
+        tileMax[tile] = top[0];
+        tileErr[tile] = err;
+        tileCounts[2 * tile] = cnt[0][0];
+        tileCounts[2 * tile + 1] = cnt[1][0];
+        if (tileMap) tileMap[tile] = err;
+    }
+}
+// The whole image: integer sums of the tiles' counts, fmaxf maxima (both independent of the
+// order), and the total that luminance_single_kernel's passes left in *total. One workgroup.
+__global__ __launch_bounds__(256) void noise_finish_kernel(const float* tileMax, const float* tileErr, const uint32_t* tileCounts,
+                                                           uint32_t tiles, const float* total, NoiseTotals* out)
+{
+    __shared__ float top[2][256];
+    __shared__ uint32_t cnt[2][256];
+    const uint32_t t = threadIdx.x;
+    float m0 = 0.0f, m1 = 0.0f;
+    uint32_t v = 0u, c = 0u;
+    for (uint32_t i = t; i < tiles; i += 256u) {
+        m0 = fmaxf(m0, tileMax[i]);
+        m1 = fmaxf(m1, tileErr[i]);
+        v += tileCounts[2 * i];
+        c += tileCounts[2 * i + 1];
+    }
+    top[0][t] = m0; top[1][t] = m1; cnt[0][t] = v; cnt[1][t] = c;
+    __syncthreads();
+    for (uint32_t k = 128; k >= 1; k >>= 1) {
+        if (t < k) {
+            top[0][t] = fmaxf(top[0][t], top[0][t + k]);
+            top[1][t] = fmaxf(top[1][t], top[1][t + k]);
+            cnt[0][t] += cnt[0][t + k];
+            cnt[1][t] += cnt[1][t + k];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        out->valid = cnt[0][0];
+        out->converged = cnt[1][0];
+        out->total = total[0];
+        out->maxError = top[0][0];
+        out->maxTileError = top[1][0];
+    }
 }
 // MainPS: rgb / w -> exposure -> Reinhard -> R8G8B8A8_UNORM_SRGB (encode by host-made thresholds)
 __global__ __launch_bounds__(256) void postfx_kernel(const float4* film, uint32_t W, uint32_t H, int enabled, int autoExposure,

@@ -530,7 +530,7 @@ struct dcrt_tracer {
     bool rowProbe = false;             // the row-cost probe: MATERIAL's PROBE variant counts rays per film row
     uint32_t* dRowRays = nullptr;      // [filmH] (rowAllocs: follows the film)
     // timed launches (ext_timing): start / stop event pairs and the kernel each pair timed
-    enum TimedKind : uint8_t { kTimedCast = 0, kTimedMaterial = 1, kTimedControl = 2, kTimedKinds = 3 };
+    enum TimedKind : uint8_t { kTimedCast = 0, kTimedMaterial = 1, kTimedControl = 2, kTimedFilm = 3, kTimedKinds = 4 };
     std::vector<hipEvent_t> events;
     std::vector<uint8_t> eventKinds;   // per pair
     size_t eventsUsed = 0;
@@ -639,6 +639,28 @@ struct dcrt_tracer {
     int EnsureDenoiseWork(uint32_t w, uint32_t h);
     int Denoise(const dcrt_denoise_params& p, uint32_t w, uint32_t h, const float4* color, const float4* normal,
                 const float4* albedo, float4* out);
+    // the film noise estimate (dcrt_tracer_set_convergence / dcrt_tracer_noise*): the half film takes
+    // every other image of the film's (even film image counts); the kernels' working buffers grow
+    // with the tile count; the maps of the last dcrt_tracer_noise follow the film
+    bool convergence = false;
+    float4* halfFilm = nullptr;
+    std::vector<void*> halfAllocs, noiseAllocs, noiseMapAllocs;
+    uint32_t filmImages = 0;           // images convolved into the film since the last clear
+    uint32_t noiseTileCap = 0;
+    float *nzSum = nullptr, *nzScratch[2] = { nullptr, nullptr }, *nzMax = nullptr, *nzErr = nullptr;
+    uint32_t* nzCounts = nullptr;
+    NoiseTotals* nzTotals = nullptr;
+    float *noisePixelMap = nullptr, *noiseTileMap = nullptr;
+    bool hasNoiseMaps = false;
+    int SetConvergence(bool on);
+    int ClearFilm();
+    int LaunchFilm(uint32_t images, const Globals* guard, const float2* const* posList, const float4* const* valList,
+                   uint32_t firstIndex);
+    int Noise(uint32_t w, uint32_t h, const float4* f, const float4* hf, float threshold, float* pixelMap, float* tileMap,
+              dcrt_noise_stats* out);
+    int NoiseOwn(float threshold, dcrt_noise_stats* out);
+    int RenderConverged(uint32_t firstSeed, const dcrt_converge_params& p, const dcrt_filter_params& filter, dcrt_noise_stats* outStats,
+                        int* outConverged);
     uint32_t drainResident = 0;       // drain_kernel grid (resident workgroups)
     uint32_t drainPaths = 0;           // drain_kernel threshold (DCRT_DRAIN_PATHS; 0: no drain launches -- the default: profiles/r04_ab_virtual_drain.txt)
     int mode = 0;                      // 0 wavefront (WavefrontPathTracer), 1 megakernel (MegakernelPathTracer)
@@ -661,6 +683,9 @@ dcrt_tracer::~dcrt_tracer()
     for (hipEvent_t e : stopEvents) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : dnEvents) (void)hipEventDestroy(e);
     FreeAll(&denoiseAllocs);
+    FreeAll(&halfAllocs);
+    FreeAll(&noiseAllocs);
+    FreeAll(&noiseMapAllocs);
     if (hFilter) (void)hipHostFree(hFilter);
     if (dSourceLists) (void)hipFree(dSourceLists);
     if (hStop) (void)hipHostFree(hStop);
@@ -1386,9 +1411,19 @@ int dcrt_tracer::EnsureFilm(uint32_t w, uint32_t h)
     sampleImages = 0;
     guideNormal = guideAlbedo = denoised = nullptr;   // (they follow the film: EnsureGuides)
     guidesRendered = hasDenoised = false;
+    FreeAll(&halfAllocs);                             // (the half film and the noise maps too)
+    FreeAll(&noiseMapAllocs);
+    halfFilm = nullptr;
+    noisePixelMap = noiseTileMap = nullptr;
+    hasNoiseMaps = false;
+    filmImages = 0;
     const size_t n = (size_t)w * h;
     CHECKED(DeviceAlloc(&film.accum, n, &filmAllocs));
     HIPCHECK(hipMemsetAsync(film.accum, 0, n * sizeof(float4), stream));
+    if (convergence) {
+        CHECKED(DeviceAlloc(&halfFilm, n, &halfAllocs));
+        HIPCHECK(hipMemsetAsync(halfFilm, 0, n * sizeof(float4), stream));
+    }
     filmW = w; filmH = h;
     film.width = w; film.height = h;
     CHECKED(EnsureSamples(1));
@@ -1707,8 +1742,7 @@ int dcrt_tracer::LaunchIteration(uint32_t par, bool timed, bool sequenced)
                            dGlobals, (const SampleOut*)dSampleOut);
     }
     if (sequenced) {
-        hipLaunchKernelGGL(film_kernel, dim3(FilmGrid()), dim3(kFilmThreads), 0, stream, film, (const FilterConsts*)dFilter, 1u,
-                           (const Globals*)dGlobals, (const float2* const*)nullptr, (const float4* const*)nullptr);
+        CHECKED(LaunchFilm(1u, dGlobals, nullptr, nullptr, 0u));
         hipLaunchKernelGGL(advance_image_kernel, dim3(1), dim3(64), 0, stream, dFrame, dGlobals);
     }
     HIPCHECK(hipGetLastError());
@@ -1860,9 +1894,9 @@ int dcrt_tracer::Accumulate(const dcrt_filter_params& f)
     Annotation an("SampleConvolution");
     if (!film.accum) { SetLastError("no film"); return DCRT_E_INVALID_ARG; }
     CHECKED(UploadFilter(f));
-    hipLaunchKernelGGL(film_kernel, dim3(FilmGrid()), dim3(kFilmThreads), 0, stream, film, (const FilterConsts*)dFilter, 1u,
-                       (const Globals*)nullptr, (const float2* const*)nullptr, (const float4* const*)nullptr);
+    CHECKED(LaunchFilm(1u, nullptr, nullptr, nullptr, filmImages));
     HIPCHECK(hipGetLastError());
+    ++filmImages;
     return DCRT_OK;
 }
 
@@ -2083,9 +2117,9 @@ int dcrt_tracer::RenderImages(uint32_t firstSeed, uint32_t count, const dcrt_fil
                 hipExtLaunchKernelGGL(mk, dim3(megaResident), dim3(castBlock), castLdsFull, stream, e0, e1, 0, scene,
                                       (const FrameConstants*)dFrame, film, dGlobals, (uint32_t)(film.debugRng != nullptr));
             }
-            hipLaunchKernelGGL(film_kernel, dim3(FilmGrid()), dim3(kFilmThreads), 0, stream, film, (const FilterConsts*)dFilter, 1u,
-                               (const Globals*)nullptr, (const float2* const*)nullptr, (const float4* const*)nullptr);
+            CHECKED(LaunchFilm(1u, nullptr, nullptr, nullptr, filmImages));
             HIPCHECK(hipGetLastError());
+            ++filmImages;
         }
         HIPCHECK(hipStreamSynchronize(stream));
         imageComplete = true;
@@ -2107,7 +2141,7 @@ int dcrt_tracer::RenderImages(uint32_t firstSeed, uint32_t count, const dcrt_fil
     // static batch-start claims: one per wave of CONTROL's virtual workgroups
     const uint32_t staticGrid = poolSize / kControlBlock;
     hipLaunchKernelGGL(begin_images_kernel, dim3(1), dim3(64), 0, stream, dGlobals, (const FrameConstants*)dFrame, count, firstSeed, batch,
-                       staticGrid, convolve ? 0u : 1u);
+                       staticGrid, convolve ? 0u : 1u, filmImages);
     HIPCHECK(hipGetLastError());
     // a path needs maxBounce + 3 iterations; cap the total so a broken scene cannot spin forever
     const uint64_t maxIterations = ((uint64_t)count + 2) * (frame.max_bounce_count + 8) * (1 + (filmW * (uint64_t)filmH) / poolSize) + 64;
@@ -2159,6 +2193,7 @@ int dcrt_tracer::RenderImages(uint32_t firstSeed, uint32_t count, const dcrt_fil
     imageComplete = true;
     newImage = true;
     imagesCompleted += count;
+    if (convolve) filmImages += count;
     lastSlot = (count - 1) % batch;
     keptSlots = !convolve;
     keptImages = keptSlots ? count : 0u;
@@ -2191,11 +2226,157 @@ int dcrt_tracer::AccumulateImages(const void* const* pos, const void* const* val
     }
     CHECKED(UploadFilter(f));   // (synchronises: the list's staging below is reused safely)
     HIPCHECK(hipMemcpyAsync(dSourceLists, lists.data(), lists.size() * sizeof(void*), hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(film_kernel, dim3(FilmGrid()), dim3(kFilmThreads), 0, stream, film, (const FilterConsts*)dFilter, count,
-                       (const Globals*)nullptr, (const float2* const*)dSourceLists, (const float4* const*)(dSourceLists + count));
+    CHECKED(LaunchFilm(count, nullptr, (const float2* const*)dSourceLists, (const float4* const*)(dSourceLists + count), filmImages));
     HIPCHECK(hipGetLastError());
+    filmImages += count;
     HIPCHECK(hipStreamSynchronize(stream));   // (the host list is released on return)
     return DCRT_OK;
+}
+
+// ---- film noise estimate --------------------------------------------------------------------
+// A film pass into the film: with convergence off the kernel and the arguments of before it
+// existed; on, the instantiation that also feeds the half film (firstIndex: the film image count
+// of the pass's first image; under `guard` the kernel takes it from Globals instead).
+int dcrt_tracer::LaunchFilm(uint32_t images, const Globals* guard, const float2* const* posList, const float4* const* valList,
+                            uint32_t firstIndex)
+{
+    if (extTiming && !capturing) {
+        // timed (ext_timing): the dispatch's own timestamps, as the cast / MATERIAL / CONTROL launches'
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        CHECKED(TimedPair(kTimedFilm, &e0, &e1));
+        if (convergence && halfFilm) {
+            hipExtLaunchKernelGGL(film_half_kernel, dim3(FilmGrid()), dim3(kFilmThreads), 0, stream, e0, e1, 0, film,
+                                  (const FilterConsts*)dFilter, images, guard, posList, valList, halfFilm, firstIndex);
+        } else {
+            hipExtLaunchKernelGGL(film_kernel, dim3(FilmGrid()), dim3(kFilmThreads), 0, stream, e0, e1, 0, film,
+                                  (const FilterConsts*)dFilter, images, guard, posList, valList);
+        }
+    } else if (convergence && halfFilm) {
+        hipLaunchKernelGGL(film_half_kernel, dim3(FilmGrid()), dim3(kFilmThreads), 0, stream, film, (const FilterConsts*)dFilter, images,
+                           guard, posList, valList, halfFilm, firstIndex);
+    } else {
+        hipLaunchKernelGGL(film_kernel, dim3(FilmGrid()), dim3(kFilmThreads), 0, stream, film, (const FilterConsts*)dFilter, images,
+                           guard, posList, valList);
+    }
+    return DCRT_OK;
+}
+
+int dcrt_tracer::ClearFilm()
+{
+    if (!film.accum) return DCRT_E_INVALID_ARG;
+    const size_t bytes = (size_t)filmW * filmH * sizeof(float4);
+    HIPCHECK(hipMemsetAsync(film.accum, 0, bytes, stream));
+    if (halfFilm) HIPCHECK(hipMemsetAsync(halfFilm, 0, bytes, stream));
+    filmImages = 0;
+    return DCRT_OK;
+}
+
+int dcrt_tracer::SetConvergence(bool on)
+{
+    if (!film.accum) { SetLastError("set_convergence: no film (set the frame parameters first)"); return DCRT_E_INVALID_ARG; }
+    HIPCHECK(hipStreamSynchronize(stream));
+    if (on != convergence) InvalidateGraph();   // (the in-graph film pass is another kernel)
+    if (on && !halfFilm) CHECKED(DeviceAlloc(&halfFilm, (size_t)filmW * filmH, &halfAllocs));
+    if (!on) {
+        FreeAll(&halfAllocs);
+        halfFilm = nullptr;
+    }
+    convergence = on;
+    return ClearFilm();
+}
+
+// The noise kernels over a film and its half film (dcrt.h): tiles, the 128-group reduction of
+// the tile sums with luminance_single_kernel, counts and maxima; one copy of the totals back.
+int dcrt_tracer::Noise(uint32_t w, uint32_t h, const float4* f, const float4* hf, float threshold, float* pixelMap, float* tileMap,
+                       dcrt_noise_stats* out)
+{
+    Annotation an("Noise estimate");
+    if (!f || !hf || !out || w == 0 || h == 0 || w > 65535u || h > 65535u) return DCRT_E_INVALID_ARG;
+    if (!(threshold >= 0.0f)) { SetLastError("noise: the threshold is negative or NaN"); return DCRT_E_INVALID_ARG; }
+    const uint32_t T = (uint32_t)kNoiseTile, tilesX = (w + T - 1) / T, tilesY = (h + T - 1) / T, tiles = tilesX * tilesY;
+    if (tiles > noiseTileCap) {
+        HIPCHECK(hipStreamSynchronize(stream));
+        FreeAll(&noiseAllocs);
+        noiseTileCap = 0;
+        CHECKED(DeviceAlloc(&nzSum, tiles, &noiseAllocs));
+        CHECKED(DeviceAlloc(&nzScratch[0], (tiles + 127) / 128, &noiseAllocs));
+        CHECKED(DeviceAlloc(&nzScratch[1], (tiles + 127) / 128, &noiseAllocs));
+        CHECKED(DeviceAlloc(&nzMax, tiles, &noiseAllocs));
+        CHECKED(DeviceAlloc(&nzErr, tiles, &noiseAllocs));
+        CHECKED(DeviceAlloc(&nzCounts, (size_t)tiles * 2, &noiseAllocs));
+        CHECKED(DeviceAlloc(&nzTotals, 1, &noiseAllocs));
+        noiseTileCap = tiles;
+    }
+    hipLaunchKernelGGL(noise_tile_kernel, dim3(tilesX, tilesY), dim3(T * T), 0, stream, f, hf, w, h, threshold, pixelMap, tileMap, nzSum,
+                       nzMax, nzErr, nzCounts);
+    const float* in = nzSum;
+    uint32_t count = tiles, side = 0;
+    while (count != 1) {
+        const uint32_t groups = (count + 127) / 128;
+        hipLaunchKernelGGL(luminance_single_kernel, dim3(groups), dim3(128), 0, stream, in, count, nzScratch[side]);
+        in = nzScratch[side];
+        side ^= 1u;
+        count = groups;
+    }
+    hipLaunchKernelGGL(noise_finish_kernel, dim3(1), dim3(256), 0, stream, (const float*)nzMax, (const float*)nzErr,
+                       (const uint32_t*)nzCounts, tiles, in, nzTotals);
+    HIPCHECK(hipGetLastError());
+    NoiseTotals* host = (NoiseTotals*)hCounters;   // (pinned staging)
+    HIPCHECK(hipMemcpyAsync(host, nzTotals, sizeof(NoiseTotals), hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+    out->images = 0;
+    out->valid_pixels = host->valid;
+    out->converged_pixels = host->converged;
+    out->mean_error = host->valid ? host->total / (float)host->valid : 0.0f;
+    out->max_error = host->maxError;
+    out->max_tile_error = host->maxTileError;
+    return DCRT_OK;
+}
+
+// ... of the tracer's own film, into its own maps
+int dcrt_tracer::NoiseOwn(float threshold, dcrt_noise_stats* out)
+{
+    if (!out) return DCRT_E_INVALID_ARG;
+    if (!convergence || !halfFilm) { SetLastError("noise: convergence is off (dcrt_tracer_set_convergence)"); return DCRT_E_INVALID_ARG; }
+    if (filmImages < 2) { SetLastError("noise: the film holds fewer than 2 images"); return DCRT_E_INVALID_ARG; }
+    if (!(threshold >= 0.0f)) { SetLastError("noise: the threshold is negative or NaN"); return DCRT_E_INVALID_ARG; }
+    if (!noisePixelMap) {
+        const uint32_t T = (uint32_t)kNoiseTile;
+        CHECKED(DeviceAlloc(&noisePixelMap, (size_t)filmW * filmH, &noiseMapAllocs));
+        CHECKED(DeviceAlloc(&noiseTileMap, (size_t)((filmW + T - 1) / T) * ((filmH + T - 1) / T), &noiseMapAllocs));
+    }
+    hasNoiseMaps = false;
+    CHECKED(Noise(filmW, filmH, film.accum, halfFilm, threshold, noisePixelMap, noiseTileMap, out));
+    out->images = filmImages;
+    hasNoiseMaps = true;
+    return DCRT_OK;
+}
+
+// Render until the estimate meets the target: RenderImages between the check points (film image
+// counts min, min + interval, ..., capped at max), the image with film image count i of seed
+// firstSeed + i, so the film at count n is RenderImages(firstSeed, n)'s.
+int dcrt_tracer::RenderConverged(uint32_t firstSeed, const dcrt_converge_params& p, const dcrt_filter_params& filter,
+                                 dcrt_noise_stats* outStats, int* outConverged)
+{
+    if (!convergence || !halfFilm) { SetLastError("render_converged: convergence is off (dcrt_tracer_set_convergence)"); return DCRT_E_INVALID_ARG; }
+    if (!(p.threshold >= 0.0f) || !(p.target_fraction > 0.0f && p.target_fraction <= 1.0f) || p.min_images < 2u ||
+        p.max_images < p.min_images || p.check_interval < 1u) {
+        SetLastError("render_converged: threshold >= 0, 0 < target_fraction <= 1, 2 <= min_images <= max_images, check_interval >= 1");
+        return DCRT_E_INVALID_ARG;
+    }
+    CHECKED(dcrt::CheckFilterParams(filter));
+    *outConverged = 0;
+    for (uint64_t point = p.min_images;; point += p.check_interval) {
+        const uint32_t target = (uint32_t)std::min<uint64_t>(point, p.max_images);
+        if (filmImages < target) CHECKED(RenderImages(firstSeed + filmImages, target - filmImages, filter));
+        if (filmImages < target) { SetLastError("render_converged: the images did not reach the film"); return DCRT_E_LIMIT; }
+        CHECKED(NoiseOwn(p.threshold, outStats));
+        if ((double)outStats->converged_pixels >= (double)p.target_fraction * (double)outStats->valid_pixels) {
+            *outConverged = 1;
+            return DCRT_OK;
+        }
+        if (filmImages >= p.max_images) return DCRT_OK;
+    }
 }
 
 // ============================ C ABI ========================================
@@ -2359,9 +2540,7 @@ DCRT_API int dcrt_tracer_acquire_film_clear_trigger(dcrt_tracer* t, int* out)
 DCRT_API int dcrt_tracer_clear_film(dcrt_tracer* t)
 {
     TRACER_GUARD(t);
-    if (!t->film.accum) return DCRT_E_INVALID_ARG;
-    HIPCHECK(hipMemsetAsync(t->film.accum, 0, (size_t)t->filmW * t->filmH * sizeof(float4), t->stream));
-    return DCRT_OK;
+    return t->ClearFilm();
 }
 
 DCRT_API int dcrt_tracer_accumulate_film(dcrt_tracer* t, const dcrt_filter_params* f)
@@ -2457,6 +2636,109 @@ DCRT_API int dcrt_tracer_add_film_device(dcrt_tracer* t, const void* d_src)
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(t->stream));
     return DCRT_OK;
+}
+
+// ---- film noise estimate ----------------------------------------------------------------------
+DCRT_API int dcrt_tracer_set_convergence(dcrt_tracer* t, int enable)
+{
+    TRACER_GUARD(t);
+    return t->SetConvergence(enable != 0);
+}
+
+DCRT_API int dcrt_tracer_half_film_device_ptr(dcrt_tracer* t, void** out)
+{
+    TRACER_GUARD(t);
+    if (!out) return DCRT_E_INVALID_ARG;
+    if (!t->halfFilm) { SetLastError("no half film: convergence is off (dcrt_tracer_set_convergence)"); return DCRT_E_INVALID_ARG; }
+    *out = t->halfFilm;
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_read_half_film(dcrt_tracer* t, float* out)
+{
+    TRACER_GUARD(t);
+    if (!out) return DCRT_E_INVALID_ARG;
+    if (!t->halfFilm) { SetLastError("no half film: convergence is off (dcrt_tracer_set_convergence)"); return DCRT_E_INVALID_ARG; }
+    HIPCHECK(hipMemcpyAsync(out, t->halfFilm, (size_t)t->filmW * t->filmH * sizeof(float4), hipMemcpyDeviceToHost, t->stream));
+    HIPCHECK(hipStreamSynchronize(t->stream));
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_add_half_film_device(dcrt_tracer* t, const void* d_src)
+{
+    TRACER_GUARD(t);
+    if (!d_src) return DCRT_E_INVALID_ARG;
+    if (!t->halfFilm) { SetLastError("no half film: convergence is off (dcrt_tracer_set_convergence)"); return DCRT_E_INVALID_ARG; }
+    const uint32_t n = t->filmW * t->filmH;
+    hipLaunchKernelGGL(add_film_kernel, dim3(std::min<uint32_t>((n + 255) / 256, kMaxPersistentBlocks)), dim3(256), 0, t->stream,
+                       t->halfFilm, (const float4*)d_src, n);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(t->stream));
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_film_image_count(dcrt_tracer* t, uint32_t* out)
+{
+    TRACER_GUARD(t);
+    if (!out) return DCRT_E_INVALID_ARG;
+    *out = t->filmImages;
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_film_pass_timing(dcrt_tracer* t, uint64_t* out_launches, double* out_ms)
+{
+    TRACER_GUARD(t);
+    if (!out_launches || !out_ms) return DCRT_E_INVALID_ARG;
+    HIPCHECK(hipStreamSynchronize(t->stream));
+    CHECKED(t->CollectTimes());
+    *out_launches = t->kindLaunches[dcrt_tracer::kTimedFilm];
+    *out_ms = t->kindMs[dcrt_tracer::kTimedFilm];
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_noise(dcrt_tracer* t, float threshold, dcrt_noise_stats* out)
+{
+    TRACER_GUARD(t);
+    return t->NoiseOwn(threshold, out);
+}
+
+DCRT_API int dcrt_tracer_noise_device(dcrt_tracer* t, uint32_t width, uint32_t height, const void* d_film, const void* d_half,
+                                      float threshold, void* d_pixel_map, void* d_tile_map, dcrt_noise_stats* out)
+{
+    TRACER_GUARD(t);
+    return t->Noise(width, height, (const float4*)d_film, (const float4*)d_half, threshold, (float*)d_pixel_map, (float*)d_tile_map, out);
+}
+
+DCRT_API int dcrt_tracer_noise_map_device_ptrs(dcrt_tracer* t, void** out_pixel, void** out_tile)
+{
+    TRACER_GUARD(t);
+    if (!out_pixel || !out_tile) return DCRT_E_INVALID_ARG;
+    if (!t->hasNoiseMaps) { SetLastError("no noise maps at this resolution (dcrt_tracer_noise)"); return DCRT_E_INVALID_ARG; }
+    *out_pixel = t->noisePixelMap;
+    *out_tile = t->noiseTileMap;
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_read_noise_maps(dcrt_tracer* t, float* out_pixel, float* out_tile)
+{
+    TRACER_GUARD(t);
+    if (!out_pixel && !out_tile) return DCRT_E_INVALID_ARG;
+    if (!t->hasNoiseMaps) { SetLastError("no noise maps at this resolution (dcrt_tracer_noise)"); return DCRT_E_INVALID_ARG; }
+    const uint32_t T = (uint32_t)kNoiseTile;
+    const size_t tiles = (size_t)((t->filmW + T - 1) / T) * ((t->filmH + T - 1) / T);
+    if (out_pixel)
+        HIPCHECK(hipMemcpyAsync(out_pixel, t->noisePixelMap, (size_t)t->filmW * t->filmH * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+    if (out_tile) HIPCHECK(hipMemcpyAsync(out_tile, t->noiseTileMap, tiles * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+    HIPCHECK(hipStreamSynchronize(t->stream));
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_render_converged(dcrt_tracer* t, uint32_t first_seed, const dcrt_converge_params* p,
+                                          const dcrt_filter_params* f, dcrt_noise_stats* out_stats, int* out_converged)
+{
+    TRACER_GUARD(t);
+    if (!p || !f || !out_stats || !out_converged) return DCRT_E_INVALID_ARG;
+    return t->RenderConverged(first_seed, *p, *f, out_stats, out_converged);
 }
 
 DCRT_API int dcrt_tracer_counters(dcrt_tracer* t, dcrt_ray_stats* out)

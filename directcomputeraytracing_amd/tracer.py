@@ -313,6 +313,79 @@ class WavefrontPathTracer:
         check(self._lib.dcrt_tracer_denoise_timings(self._h, ms, 16, C.byref(n)), "DenoiseTimings")
         return [float(ms[i]) for i in range(min(16, n.value))]
 
+    # ---- film noise estimate, render until converged --------------------------------
+    def set_convergence(self, enable: bool) -> None:
+        """Keep a half film (every other image of the film's) for noise(); clears the film, the
+        half film and the film image count. Needs the frame parameters (a film)."""
+        check(self._lib.dcrt_tracer_set_convergence(self._h, 1 if enable else 0), "SetConvergence")
+
+    def film_image_count(self) -> int:
+        """Images convolved into the film since the last clear."""
+        n = C.c_uint32()
+        check(self._lib.dcrt_tracer_film_image_count(self._h, C.byref(n)), "FilmImageCount")
+        return int(n.value)
+
+    def half_film_device_ptr(self) -> int:
+        p = C.c_void_p()
+        check(self._lib.dcrt_tracer_half_film_device_ptr(self._h, C.byref(p)), "HalfFilmDevicePtr")
+        return p.value or 0
+
+    def read_half_film(self) -> np.ndarray:
+        out = np.empty((self.height, self.width, 4), np.float32)
+        check(self._lib.dcrt_tracer_read_half_film(self._h, out.ctypes.data_as(_abi._FP)), "ReadHalfFilm")
+        return out
+
+    def add_half_film_device(self, d_src: int) -> None:
+        """half film += the RGBA32F half film at device address d_src (another partition's)."""
+        check(self._lib.dcrt_tracer_add_half_film_device(self._h, C.c_void_p(d_src)), "AddHalfFilmDevice")
+
+    def noise(self, threshold: float, maps: bool = False):
+        """The half-film noise estimate of the film: a dict of dcrt_noise_stats; with maps=True
+        (stats, per-pixel e H x W, tile errors ceil(H / 16) x ceil(W / 16))."""
+        s = _abi.NoiseStats()
+        check(self._lib.dcrt_tracer_noise(self._h, float(threshold), C.byref(s)), "Noise")
+        stats = noise_stats_dict(s)
+        return (stats, *self.read_noise_maps()) if maps else stats
+
+    def read_noise_maps(self):
+        """(per-pixel e, tile errors) of the last noise()."""
+        pix = np.empty((self.height, self.width), np.float32)
+        tile = np.empty((-(-self.height // 16), -(-self.width // 16)), np.float32)
+        check(self._lib.dcrt_tracer_read_noise_maps(self._h, pix.ctypes.data_as(_abi._FP), tile.ctypes.data_as(_abi._FP)),
+              "ReadNoiseMaps")
+        return pix, tile
+
+    def noise_map_device_ptrs(self) -> tuple[int, int]:
+        pix, tile = C.c_void_p(), C.c_void_p()
+        check(self._lib.dcrt_tracer_noise_map_device_ptrs(self._h, C.byref(pix), C.byref(tile)), "NoiseMapDevicePtrs")
+        return pix.value or 0, tile.value or 0
+
+    def noise_device(self, width: int, height: int, d_film: int, d_half: int, threshold: float, d_pixel_map: int = 0,
+                     d_tile_map: int = 0) -> dict:
+        """The estimate over device images (e.g. the reduced film and half film of a multi-GPU
+        render); the map destinations are optional."""
+        s = _abi.NoiseStats()
+        check(self._lib.dcrt_tracer_noise_device(self._h, int(width), int(height), C.c_void_p(d_film), C.c_void_p(d_half),
+                                                 float(threshold), C.c_void_p(d_pixel_map or None),
+                                                 C.c_void_p(d_tile_map or None), C.byref(s)), "NoiseDevice")
+        return noise_stats_dict(s)
+
+    def film_pass_timing(self) -> tuple[int, float]:
+        """(launches, ms) of the film passes into the film since reset_stats, with ext_timing on."""
+        n, ms = C.c_uint64(), C.c_double()
+        check(self._lib.dcrt_tracer_film_pass_timing(self._h, C.byref(n), C.byref(ms)), "FilmPassTiming")
+        return int(n.value), float(ms.value)
+
+    def render_converged(self, first_seed: int, params: _abi.ConvergeParams, filter_params: _abi.FilterParams | None = None):
+        """Render images first_seed, first_seed + 1, ... until the estimate meets params' target or
+        max_images sit in the film: (stats of the last check, converged). The film is not cleared."""
+        f = filter_params or self.filter
+        s = _abi.NoiseStats()
+        done = C.c_int()
+        check(self._lib.dcrt_tracer_render_converged(self._h, int(first_seed), C.byref(params), C.byref(f), C.byref(s),
+                                                     C.byref(done)), "RenderConverged")
+        return noise_stats_dict(s), bool(done.value)
+
     # ---- statistics ----------------------------------------------------------
     def counters(self) -> dict:
         s = _abi.RayStats()
@@ -385,6 +458,10 @@ def denoise_default_params() -> _abi.DenoiseParams:
     p = _abi.DenoiseParams()
     check(_abi.load_library().dcrt_denoise_default_params(C.byref(p)), "DenoiseDefaultParams")
     return p
+
+
+def noise_stats_dict(s: _abi.NoiseStats) -> dict:
+    return {k: getattr(s, k) for k, _ in _abi.NoiseStats._fields_}
 
 
 def srgb_thresholds() -> np.ndarray:

@@ -8,6 +8,14 @@
 //               [--batch] [--point x y z r g b] [--seed-type sample-count|frame-index|fixed]
 //               [--fixed-seed N] [--iterations N] [--pool N] [--film out.f32] [--samples out.f32]
 //               [--edit N:KIND:ARGS]... [--output NAME [--iteration-threshold N]] [--denoise]
+//               [--converge THRESHOLD[:FRACTION] [--check-points MIN:INTERVAL]] [--noise-map out.bmp]
+//
+// --converge renders until the half-film noise estimate (dcrt.h "film noise estimate") says that
+// FRACTION (default 0.95) of the pixels have an error of at most THRESHOLD, checked at MIN, MIN +
+// INTERVAL, ... images (default 16:16), and at most `spp` images (dcrt_tracer_render_converged;
+// implies the --batch path). The JSON line's "images" is the count rendered, and it gains
+// "converged" and "noise". --noise-map writes a grey image of min(e / THRESHOLD, 1) per pixel
+// (code = (int)(v * 255 + 0.5); a NaN e is white).
 //
 // --denoise renders the denoiser's guide films (first-hit normal and albedo) with the seeds of the
 // film's images, filters the film with the default parameters (dcrt_tracer_denoise) and writes the
@@ -29,7 +37,9 @@
 // --batch instead hands all images to dcrt_tracer_render_images (device-side image
 // sequencing). --film writes the raw RGBA32F film (sum w*L, sum w), --samples the last image's
 // sample textures (positions W*H*2 then values W*H*4 floats). The last stdout line is JSON.
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -65,7 +75,8 @@ int Usage(const char* exe)
                  "       [--seed-type sample-count|frame-index|fixed] [--fixed-seed N] [--iterations N] [--pool N]\n"
                  "       [--film out.f32] [--samples out.f32] [--edit N:KIND:ARGS]...\n"
                  "       [--output path_tracing|normal|tangent|albedo|negative_ndotv|backface|iteration_count]\n"
-                 "       [--iteration-threshold N] [--denoise]\n",
+                 "       [--iteration-threshold N] [--denoise]\n"
+                 "       [--converge THRESHOLD[:FRACTION] [--check-points MIN:INTERVAL]] [--noise-map out.bmp]\n",
                  exe);
     return 2;
 }
@@ -178,6 +189,9 @@ int main(int argc, char** argv)
     const char* samplesPath = nullptr;
     std::vector<SEdit> edits;
     uint32_t outputType = DCRT_OUTPUT_PATH_TRACING, iterationThreshold = 20;
+    bool converge = false;
+    dcrt_converge_params convergeParams = {0.0f, 0.95f, 16u, 0u, 16u};
+    const char* noiseMapPath = nullptr;
     for (int i = 7; i < argc; ++i) {
         const bool more = i + 1 < argc;
         if (!std::strcmp(argv[i], "--batch")) {
@@ -215,6 +229,19 @@ int main(int argc, char** argv)
             if (outputType == ~0u) return Usage(argv[0]);
         } else if (!std::strcmp(argv[i], "--iteration-threshold") && more) {
             iterationThreshold = (uint32_t)std::atoi(argv[++i]);
+        } else if (!std::strcmp(argv[i], "--converge") && more) {
+            const std::vector<std::string> f = Split(argv[++i], ':');
+            if (f.size() > 2 || !ParseFloats(f[0], &convergeParams.threshold, 1) ||
+                (f.size() == 2 && !ParseFloats(f[1], &convergeParams.target_fraction, 1)))
+                return Usage(argv[0]);
+            converge = true;
+        } else if (!std::strcmp(argv[i], "--check-points") && more) {
+            const std::vector<std::string> f = Split(argv[++i], ':');
+            if (f.size() != 2) return Usage(argv[0]);
+            convergeParams.min_images = (uint32_t)std::atoi(f[0].c_str());
+            convergeParams.check_interval = (uint32_t)std::atoi(f[1].c_str());
+        } else if (!std::strcmp(argv[i], "--noise-map") && more) {
+            noiseMapPath = argv[++i];
         } else if (!std::strcmp(argv[i], "--edit") && more) {
             SEdit e;
             if (!ParseEdit(argv[++i], &e)) return Usage(argv[0]);
@@ -226,6 +253,12 @@ int main(int argc, char** argv)
     if (width == 0 || height == 0 || spp == 0 || iterations == 0) return Usage(argv[0]);
     if (batch && !edits.empty()) return Usage(argv[0]);   // (edits belong to the frame loop)
     if (denoise && outputType != DCRT_OUTPUT_PATH_TRACING) return Usage(argv[0]);   // (a view is noise-free)
+    if ((noiseMapPath && !converge) || (converge && (!edits.empty() || spp < 2))) return Usage(argv[0]);
+    if (converge) {
+        batch = true;   // (render_converged sequences the images on the device, as --batch does)
+        convergeParams.max_images = spp;
+        convergeParams.min_images = std::max(2u, std::min(convergeParams.min_images, spp));
+    }
 
     // CDirectComputeRayTracing::Init: new + Create (LaunchRendererLoop.cpp:58-64)
     CScene scene;
@@ -256,7 +289,17 @@ int main(int argc, char** argv)
     uint64_t previewFrames = 0;
     size_t editsApplied = 0;
     std::vector<uint32_t> seeds;  // frame seed of each full-resolution image, in film order
-    if (batch) {
+    uint32_t images = spp;        // images in the film (--converge: as many as it took)
+    dcrt_noise_stats noise = {};
+    int converged = 0;
+    if (converge) {
+        const dcrt_filter_params filter = MakeFilter(scene);
+        if (!Check(dcrt_tracer_set_convergence(tracer.GetTracer(), 1), "SetConvergence") ||
+            !Check(dcrt_tracer_render_converged(tracer.GetTracer(), 0, &convergeParams, &filter, &noise, &converged), "RenderConverged"))
+            return 1;
+        images = noise.images;
+        for (uint32_t s = 0; s < images; ++s) seeds.push_back(s);
+    } else if (batch) {
         const dcrt_filter_params filter = MakeFilter(scene);
         if (!Check(dcrt_tracer_clear_film(tracer.GetTracer()), "ClearFilm") ||
             !Check(dcrt_tracer_render_images(tracer.GetTracer(), 0, spp, &filter), "RenderImages"))
@@ -341,6 +384,18 @@ int main(int argc, char** argv)
         return 1;
     }
     if (!Check(dcrt_write_bmp(outPath, W, H, rgba.data()), "WriteBmp")) return 1;
+    if (noiseMapPath) {
+        std::vector<float> e(n);
+        if (!Check(dcrt_tracer_read_noise_maps(tracer.GetTracer(), e.data(), nullptr), "ReadNoiseMaps")) return 1;
+        std::vector<uint8_t> grey(n * 4);
+        for (size_t p = 0; p < n; ++p) {
+            const float v = std::fmin(e[p] / convergeParams.threshold, 1.0f);
+            const uint8_t code = v != v ? 255 : (uint8_t)(int)(v * 255.0f + 0.5f);
+            grey[4 * p] = grey[4 * p + 1] = grey[4 * p + 2] = code;
+            grey[4 * p + 3] = 255;
+        }
+        if (!Check(dcrt_write_bmp(noiseMapPath, W, H, grey.data()), "WriteBmp (noise map)")) return 1;
+    }
     dcrt_ray_stats stats;
     if (!Check(dcrt_tracer_counters(tracer.GetTracer(), &stats), "Counters")) return 1;
     const double rays = (double)(stats.extension_rays + stats.shadow_rays);
@@ -361,11 +416,20 @@ int main(int argc, char** argv)
                       (unsigned long long)up.graph_invalidations);
         editReport = buf;
     }
+    if (converge) {   // (only with --converge)
+        char buf[512];
+        std::snprintf(buf, sizeof(buf),
+                      ", \"converged\": %d, \"noise\": {\"images\": %u, \"valid_pixels\": %u, \"converged_pixels\": %u, "
+                      "\"mean_error\": %.9g, \"max_error\": %.9g, \"max_tile_error\": %.9g}",
+                      converged, noise.images, noise.valid_pixels, noise.converged_pixels, (double)noise.mean_error, (double)noise.max_error,
+                      (double)noise.max_tile_error);
+        editReport += buf;
+    }
     std::printf("{\"images\": %u, \"seconds\": %.4f, \"ms_per_spp\": %.3f, \"mrays_per_s\": %.1f, \"extension_rays\": %llu, "
                 "\"shadow_rays\": %llu, \"mode\": \"%s\", \"frames\": %llu, \"preview_frames\": %llu, \"first_seed\": %u, "
                 "\"seeds\": [%s]%s}\n",
-                spp, seconds, seconds * 1e3 / spp, rays / seconds / 1e6, (unsigned long long)stats.extension_rays,
-                (unsigned long long)stats.shadow_rays, batch ? "render_images" : "frame_loop", (unsigned long long)loop.m_FrameIndex,
+                images, seconds, seconds * 1e3 / images, rays / seconds / 1e6, (unsigned long long)stats.extension_rays,
+                (unsigned long long)stats.shadow_rays, converge ? "render_converged" : batch ? "render_images" : "frame_loop", (unsigned long long)loop.m_FrameIndex,
                 (unsigned long long)previewFrames, firstSeed, seedList.c_str(), editReport.c_str());
     return 0;
 }

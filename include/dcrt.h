@@ -737,6 +737,93 @@ DCRT_API int dcrt_tracer_resolve_denoised(dcrt_tracer* tracer, const dcrt_postfx
  * Writes at most `capacity` entries; *out_count = the number of kernels (0 without ext_timing). */
 DCRT_API int dcrt_tracer_denoise_timings(dcrt_tracer* tracer, float* out_ms, uint32_t capacity, uint32_t* out_count);
 
+/* ===== film noise estimate and render-until-converged =======================
+ * The half-buffer estimator (Dammertz et al. 2010, "A hierarchical automatic stopping condition for
+ * Monte Carlo global illumination"; Cycles' adaptive sampling uses the same): beside the film a
+ * second film, the half film, receives every other image, and the two are compared per pixel. No
+ * reference counterpart.
+ *
+ * The tracer counts the images convolved into its film since the last clear, the film image count:
+ * every film pass into the film counts (render_images / _strided with the film pass in either mode
+ * and in the output views, accumulate_film, accumulate_images); the guide films and
+ * add_film_device do not. While convergence is on, the image with 0-based count i also goes into
+ * the half film exactly when i is even -- in the same pass, over the same rows, by the same
+ * additions in the same order -- so the half film is bit for bit the film the even-counted images
+ * alone would give.
+ *
+ * All arithmetic is fp32 in exactly this order (no contraction, correctly rounded / and sqrt), so a
+ * float32 restatement matches bit for bit (tests/noise_ref.py). Per pixel, f = film, h = half film:
+ *   valid = f.w > 0 && h.w > 0 (a NaN weight is invalid);  c = f.rgb / f.w, a = h.rgb / h.w;
+ *   d = (|c.r - a.r| + |c.g - a.g|) + |c.b - a.b|;  s = (c.r + c.g) + c.b;
+ *   n = sqrt(fmaxf(s, 0))  (negative filter lobes can make s negative);
+ *   e = valid ? d / (n + 1e-4f) : 0.  A valid pixel is converged when e <= threshold (a NaN e is
+ *   valid and not converged).
+ * Per 16 x 16 pixel tile (thread t = ty * 16 + tx): acc[t] = e (0 outside the image); for k = 128,
+ * 64 .. 1: if t < k, acc[t] = acc[t] + acc[t + k]; the tile's valid and converged counts are
+ * integers, its maximum is fmaxf over its e from 0 (NaN ignored); tile error = tile sum /
+ * (float)valid count, 0 without a valid pixel.
+ * Whole image: the tile sums (row-major tiles) in groups of 128 consecutive values, zero padded,
+ * each reduced by the tree 64 .. 1 as above, repeated until one value remains (the luminance
+ * reduction's order); counts summed as integers; max_error = fmaxf of the tile maxima,
+ * max_tile_error = fmaxf of the tile errors, both from 0. */
+typedef struct dcrt_noise_stats {
+    uint32_t images;            /* film image count (0 from dcrt_tracer_noise_device)     */
+    uint32_t valid_pixels, converged_pixels;
+    float mean_error;           /* total / (float)valid_pixels; 0 when none              */
+    float max_error, max_tile_error;
+} dcrt_noise_stats;
+/* enable != 0 allocates the half film (W x H RGBA32F, 16 B per pixel, only while enabled); 0 frees
+ * it. Either way the film and the half film are cleared, the film image count is reset and, on a
+ * change, the captured graphs are dropped. Needs a film (frame parameters), as dcrt_tracer_clear_film
+ * does; a later resolution change resizes the half film with the film. Default: off, and then
+ * every film pass is the kernel it was before this existed. dcrt_tracer_clear_film clears both
+ * films and resets the count. */
+DCRT_API int dcrt_tracer_set_convergence(dcrt_tracer* tracer, int enable);
+DCRT_API int dcrt_tracer_film_image_count(dcrt_tracer* tracer, uint32_t* out_images);
+/* The half film: DCRT_E_INVALID_ARG while convergence is off. add_half_film_device is
+ * dcrt_tracer_add_film_device on the half film (the half films of disjoint partitions or bands sum
+ * as their films do). */
+DCRT_API int dcrt_tracer_half_film_device_ptr(dcrt_tracer* tracer, void** out_ptr);
+DCRT_API int dcrt_tracer_read_half_film(dcrt_tracer* tracer, float* out_rgba);                 /* W*H*4 floats */
+DCRT_API int dcrt_tracer_add_half_film_device(dcrt_tracer* tracer, const void* d_src);
+/* The estimate over the tracer's film and half film, on its stream; the one synchronisation is the
+ * copy of the statistics. DCRT_E_INVALID_ARG with convergence off, with fewer than 2 film images,
+ * or for a negative or NaN threshold. On a banded or partitioned tracer the rows it does not own
+ * have weight 0 and are invalid. */
+DCRT_API int dcrt_tracer_noise(dcrt_tracer* tracer, float threshold, dcrt_noise_stats* out_stats);
+/* ... over caller-provided device images (width * height RGBA32F each, on the tracer's device);
+ * the maps (width * height floats: e per pixel; ceil(width / 16) * ceil(height / 16) floats: tile
+ * errors, row-major) are optional. The tracer's own film is not used: any tracer will do, e.g.
+ * rank 0 after the reduce, or one without a scene. */
+DCRT_API int dcrt_tracer_noise_device(dcrt_tracer* tracer, uint32_t width, uint32_t height, const void* d_film, const void* d_half,
+                                      float threshold, void* d_pixel_map_or_null, void* d_tile_map_or_null,
+                                      dcrt_noise_stats* out_stats);
+/* The maps of the last dcrt_tracer_noise; DCRT_E_INVALID_ARG before one, or after a resolution
+ * change. read_noise_maps takes a null pointer for a map it should skip (not for both). */
+/* With ext_timing on (dcrt_tracer_set_instrumentation): launches and summed HIP-event time in ms
+ * of the film passes into the film since dcrt_tracer_reset_stats (the in-graph pass is launched
+ * every iteration and returns at once unless a batch completed). */
+DCRT_API int dcrt_tracer_film_pass_timing(dcrt_tracer* tracer, uint64_t* out_launches, double* out_ms);
+DCRT_API int dcrt_tracer_noise_map_device_ptrs(dcrt_tracer* tracer, void** out_pixel_map, void** out_tile_map);
+DCRT_API int dcrt_tracer_read_noise_maps(dcrt_tracer* tracer, float* out_pixel_map, float* out_tile_map);
+typedef struct dcrt_converge_params {
+    float threshold;          /* per-pixel e                                                       */
+    float target_fraction;    /* stop when converged_pixels >= target_fraction * valid_pixels
+                                 (compared in double); in (0, 1]                                   */
+    uint32_t min_images;      /* first check point, >= 2                                           */
+    uint32_t max_images;      /* >= min_images                                                     */
+    uint32_t check_interval;  /* >= 1                                                              */
+} dcrt_converge_params;
+/* Render until the estimate meets the target. The check points are the film image counts
+ * min_images, min_images + check_interval, ..., capped at max_images; between them it renders with
+ * dcrt_tracer_render_images, the image with film image count i from seed first_seed + i, so the
+ * film it leaves at count n is bit for bit that of dcrt_tracer_render_images(first_seed, n). It
+ * stops at the first check point that meets the target (*out_converged = 1) or at max_images
+ * (0); *out_stats is the last estimate. The film is not cleared: the caller does that. Refuses
+ * what dcrt_tracer_noise and dcrt_tracer_render_images refuse, and parameters out of range. */
+DCRT_API int dcrt_tracer_render_converged(dcrt_tracer* tracer, uint32_t first_seed, const dcrt_converge_params* params,
+                                          const dcrt_filter_params* filter, dcrt_noise_stats* out_stats, int* out_converged);
+
 /* 24-bit BMP writer ("Save Image to File", SaveImageToFile.cpp:92-182). */
 DCRT_API int dcrt_write_bmp(const char* path, uint32_t width, uint32_t height, const uint8_t* rgba8);
 
