@@ -15,7 +15,7 @@ LIB_PATH = PKG_DIR / "libdcrt.so"
 
 # ---- status codes / flags (dcrt.h) -----------------------------------------
 DCRT_OK = 0
-ABI_VERSION = 2          # DCRT_ABI_VERSION: load_library refuses a libdcrt.so of another
+ABI_VERSION = 3          # DCRT_ABI_VERSION: load_library refuses a libdcrt.so of another
 ERRORS = {-1: "DCRT_E_INVALID_ARG", -2: "DCRT_E_HIP", -3: "DCRT_E_NO_SCENE", -4: "DCRT_E_IO",
           -5: "DCRT_E_LIMIT", -6: "DCRT_E_NO_DEVICE"}
 LIGHT_INDEX_INVALID = 0xFFFFFFFF
@@ -172,7 +172,13 @@ class TracerInfo(C.Structure):
                 ("material_generic", C.c_uint32), ("pair_traversal", C.c_uint32), ("control_grid", C.c_uint32),
                 ("material_grid", C.c_uint32), ("cast_grid", C.c_uint32), ("material_lds", C.c_uint32),
                 ("cast_identity", C.c_uint32), ("stack_lds_rows", C.c_uint32), ("ring_rows", C.c_uint32),
-                ("cast_waves_per_cu", C.c_uint32)]
+                ("cast_waves_per_cu", C.c_uint32), ("shadow_cells", C.c_uint32), ("shadow_cell_max_leaves", C.c_uint32),
+                ("shadow_cell_mean_leaves", C.c_float)]
+
+
+class ShadowCellsInfo(C.Structure):
+    _fields_ = [("resolution", C.c_uint32), ("leaf_count", C.c_uint32), ("node_count", C.c_uint32),
+                ("max_leaves", C.c_uint32), ("mean_leaves", C.c_float), ("r0", C.c_float)]
 
 
 class UploadStats(C.Structure):
@@ -312,6 +318,10 @@ SIGNATURES = [
     ("dcrt_tracer_trace_rays", _I, [_P, C.POINTER(Ray), _U, C.POINTER(RayHit), _U]),
     ("dcrt_tracer_occluded", _I, [_P, C.POINTER(Ray), _U, C.POINTER(C.c_uint32), _U]),
     ("dcrt_tracer_trace_rays_device", _I, [_P, _P, _U, _P, _U]),
+    ("dcrt_tracer_trace_occlusion_cells", _I, [_P, C.POINTER(Ray), _U, C.POINTER(C.c_uint32), _U]),
+    ("dcrt_shadow_cells_build", _I, [C.POINTER(FlatScene), _U, C.POINTER(ShadowCellsInfo), C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint32), C.POINTER(BVHNode), _U]),
+    ("dcrt_shadow_cell_indices", _I, [_U, _FP, _U, C.POINTER(C.c_uint32)]),
     ("dcrt_scene_get_postfx_params", _I, [_P, C.POINTER(PostFxParams)]),
     ("dcrt_srgb_encode_thresholds", _I, [_FP]),
     ("dcrt_tracer_resolve_image", _I, [_P, C.POINTER(PostFxParams), C.POINTER(C.c_uint8), _FP]),

@@ -7,6 +7,7 @@
 
 #include "../../../include/dcrt.h"
 #include "dmath.h"
+#include "../host/shadow_cells.h"
 
 namespace dcrt {
 namespace dev {
@@ -94,6 +95,13 @@ struct DeviceScene {
     // MATERIAL's LDS scene copy (material_kernel<CAPS, true>, small scenes): the material and
     // light counts it copies (0 when the variant is not used)
     uint32_t ldsMaterials, ldsLights;
+    // The point light's direction-cell table (cells_occluded; shadow_cells.h builds it): a cube map
+    // of shadowRes^2 cells per face around the light, per cell the 64-bit set of triangle leaves a
+    // shadow ray of that direction can reach, and per leaf a packed word (cells_leaf_word). Null /
+    // 0 when the scene has no table.
+    const uint64_t* shadowCells;
+    const uint32_t* shadowLeaves;   // kCellWords words
+    uint32_t shadowRes;
 };
 
 // MATERIAL's LDS scene copy, in 16-B units: triVerts (3 T), triShade (6 T), the forward
@@ -847,6 +855,93 @@ DEV bool trav_leaf(const DeviceScene& sc, TravState& s, bool watertight, uint32_
             if (test(p)) return true;
     }
     return trav_pop<IDENT, RING>(sc, s, lds, stack_stride<ALL_CACHED>(shift), shift);
+}
+
+// ---- the point light's direction cells (shadow_cells.h) ---------------------------------------
+// The cell of direction w = -d, seen from the light: the cube face of w's dominant axis, then the
+// two other components over it. (inv = 1/d: the division by |w[z]| is a product with |inv[z]|; the
+// table's margin covers the rounding, shadow_cells.cpp ShadowCellIndex restates this.)
+DEV uint32_t cells_index(uint32_t R, V3 d, V3 inv)
+{
+    const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
+    int z = ax >= ay ? 0 : 1;
+    z = (z == 0 ? ax : ay) >= az ? z : 2;
+    int x = z + 1; x = x == 3 ? 0 : x;
+    int y = x + 1; y = y == 3 ? 0 : y;
+    const float s = -fabsf(comp(inv, z)), half = 0.5f * (float)R;
+    const float fu = (comp(d, x) * s + 1.0f) * half, fv = (comp(d, y) * s + 1.0f) * half;
+    const uint32_t iu = fu >= 0.0f ? min(R - 1u, (uint32_t)fu) : 0u;
+    const uint32_t iv = fv >= 0.0f ? min(R - 1u, (uint32_t)fv) : 0u;
+    const uint32_t face = 2u * (uint32_t)z + (comp(d, z) > 0.0f ? 1u : 0u);
+    return (face * R + iv) * R + iu;
+}
+
+// The occlusion bit of shadow ray (o, d, tMax) of a scene with a cell table, by the kernels over
+// the entry-free node order (ALL_CACHED, IDENT, FLAT; `leafWords`: the table's leaf words in LDS).
+// The reference's any-hit walk reaches a leaf exactly when the leaf's box and every box above it
+// pass the slab test with the ray's constant tMax, and answers with the OR of the reached leaves'
+// triangle tests; a box that holds the leaf's box component-wise passes whenever the leaf's does,
+// so per leaf of the cell's mask this runs the leaf's slab test and its guards' (shadow_cells.h), and
+// per leaf that passes trav_leaf's triangle test of an any-hit lane, operand for operand. A ray with a non-finite
+// 1/d component (NaN slabs: the implication above fails) walks the BVH as the cast does.
+DEV bool cells_occluded(const DeviceScene& sc, float4 o4, float4 d4, bool watertight, uint32_t* lds, uint32_t shift,
+                        const uint32_t* leafWords)
+{
+    const V3 o = mk(o4.x, o4.y, o4.z), d = mk(d4.x, d4.y, d4.z);
+    const float tMax = o4.w;
+    const V3 inv = inv_dir(d);
+    const float big = inf();
+    if (__builtin_expect(!(fabsf(inv.x) < big && fabsf(inv.y) < big && fabsf(inv.z) < big), 0)) {
+        TravState s;
+        TraversalStats st = {};
+        trav_init(s, o, d, 0.0f, tMax);
+        s.anyHit = true;
+        for (;;) {
+            if (trav_visit<false, true, kLayoutFlat, false, true, false>(sc, s, lds, shift, st)) break;
+            if (s.parked && trav_leaf<true, false, false, false, true, true, false, true>(sc, s, watertight, lds, shift, st)) break;
+        }
+        return s.found;
+    }
+    uint64_t mask = global_load_u64(sc.shadowCells, cells_index(sc.shadowRes, d, inv));
+    const float4* c = scene_cache(sc, lds - threadIdx.x, shift);
+    // (the instance-space ray of an identity instance, as trav_leaf forms it)
+    const V3 spO = mk(o.x + 0.0f, o.y + 0.0f, o.z + 0.0f), spD = mk(d.x + 0.0f, d.y + 0.0f, d.z + 0.0f);
+    Shear sh = {};
+    if (watertight) sh = make_shear_rot(spD, spO, inv);
+    const float4* tris = c + sc.cachedNodes * 2u;
+    // Two loops, so that a wave's lanes stay together: the box tests of every leaf of the mask first
+    // (a lane's triangle test would otherwise hold up the lanes still testing boxes), then the
+    // triangle tests of the leaves whose boxes passed, until the first hit.
+    uint64_t reached = 0ull;
+    while (mask != 0ull) {
+        const uint32_t k = (uint32_t)__builtin_ctzll(mask);
+        mask &= mask - 1ull;
+        const uint32_t word = leafWords[k];
+        const uint32_t leaf = word & kCellNodeMask;
+        bool pass = ray_aabb_raw(o, inv, 0.0f, tMax, c[leaf * 2u], c[leaf * 2u + 1u]);
+        if (__builtin_expect(pass && (word >> kCellNodeBits) != 0u, 0)) {
+            const uint32_t* guard = leafWords + (word >> (kCellNodeBits + kCellCountBits));
+            for (uint32_t g = (word >> kCellNodeBits) & kCellCountMask; pass && g != 0u; --g, ++guard)
+                pass = ray_aabb_raw(o, inv, 0.0f, tMax, c[*guard * 2u], c[*guard * 2u + 1u]);
+        }
+        reached |= pass ? 1ull << k : 0ull;
+    }
+    while (reached != 0ull) {
+        const uint32_t k = (uint32_t)__builtin_ctzll(reached);
+        reached &= reached - 1ull;
+        const uint32_t p = asu(c[(leafWords[k] & kCellNodeMask) * 2u + 1u].z);
+        float t, u, v; bool bf, h;
+        if (watertight) {
+            const float4* q = tris + __umul24(p, kRotTriFloat4) + __umul24((uint32_t)sh.kz, 3u);
+            h = tri_watertight_rot(sh, 0.0f, tMax, q[0], q[1], q[2], &t, &u, &v, &bf);
+        } else {
+            const float4* q = tris + __umul24(p, kRotTriFloat4) + 6u;   // permutation z = 2 is the identity
+            const float4 q0 = q[0], q1 = q[1], q2 = q[2];
+            h = tri_moller(spO, spD, 0.0f, tMax, mk(q0.x, q0.y, q0.z), mk(q1.x, q1.y, q1.z), mk(q2.x, q2.y, q2.z), &t, &u, &v, &bf);
+        }
+        if (h) return true;
+    }
+    return false;
 }
 
 // ---- texture emulation ----------------------------------------------------------

@@ -950,11 +950,12 @@ __device__ __forceinline__ void emit_hit(const PathPool& pool, uint32_t item, co
 }
 // The shadow cast's result where MATERIAL asked for it: the continuing path's next
 // extension-queue position, or its finish-queue position (kDestFinish)
-__device__ __forceinline__ void emit_occlusion(const PathPool& pool, uint32_t dest, const TravState& s)
+__device__ __forceinline__ void emit_occlusion(const PathPool& pool, uint32_t dest, bool found)
 {
     uint32_t* dst = (dest & kDestFinish) ? pool.finHit : pool.shadowHit;
-    dst[dest & ~kDestFinish] = s.found ? 1u : 0u;
+    dst[dest & ~kDestFinish] = found ? 1u : 0u;
 }
+__device__ __forceinline__ void emit_occlusion(const PathPool& pool, uint32_t dest, const TravState& s) { emit_occlusion(pool, dest, s.found); }
 
 // OPACITY: the ALLOW_ANYHIT_SHADER variant (a separate instantiation, so the default
 // kernels carry none of its state).
@@ -1049,7 +1050,11 @@ __global__ __launch_bounds__(256) DCRT_CAST_OCCUPANCY void shadow_kernel(PathPoo
 // RING: the traversal stack as an LDS window over a per-lane global column (ring_maintain), for
 // scenes whose whole stack would cost LDS occupancy (tracer.hip UploadScene).
 // FLAT: the cache-only IDENT kernel over the entry-free node order (tracer.hip EntryFreeLayout)
-template <bool INSTR, bool OPACITY, bool ALL_CACHED, bool PAIR, bool IDENT = false, bool RING = false, bool FLAT = false>
+// CELLS (with FLAT, a scene with a direction-cell table, shadow_cells.h): every wave first streams
+// through its share of the shadow queue, one ray per lane, testing only the leaves of the ray's
+// cell (cells_occluded: the reference's occlusion bit), then traces the extension queue alone
+template <bool INSTR, bool OPACITY, bool ALL_CACHED, bool PAIR, bool IDENT = false, bool RING = false, bool FLAT = false,
+          bool CELLS = false>
 __global__ __launch_bounds__(256)
 #ifndef DCRT_GLOBAL_CAST_WAVES_PER_EU
 #define DCRT_GLOBAL_CAST_WAVES_PER_EU DCRT_CAST_WAVES_PER_EU   // (the global-memory, non-pair kernel; A/B)
@@ -1059,6 +1064,10 @@ __attribute__((amdgpu_waves_per_eu(ALL_CACHED && !OPACITY && !INSTR ? (IDENT ? D
                                                                      Counters* nextCnt, Globals* g, unsigned long long* instr)
 {
     extern __shared__ uint32_t stackMem[];
+    static_assert(!CELLS || (FLAT && ALL_CACHED && IDENT && !INSTR && !OPACITY && !PAIR && !RING), "CELLS: the entry-free cache-only kernel");
+    // (CELLS: the table's leaf words behind the scene cache, stored before its barrier)
+    uint32_t* leafWords = (uint32_t*)(scene_cache(sc, stackMem, block_shift()) + sc.cachedNodes * 2u + sc.cachedTris * kRotTriFloat4);
+    if (CELLS && threadIdx.x < kCellWords) leafWords[threadIdx.x] = sc.shadowLeaves[threadIdx.x];
     scene_cache_load<ALL_CACHED>(sc, stackMem, block_shift());
     QueueMap qe, qs;
     qmap(cnt, kQExt, &qe);
@@ -1104,6 +1113,35 @@ __attribute__((amdgpu_waves_per_eu(ALL_CACHED && !OPACITY && !INSTR ? (IDENT ? D
             st, DCRT_WAVE_TAG(g));
         const unsigned long long r = wave_sum(rays);
         if ((threadIdx.x & 63u) == 0 && r) atomicAdd(&g->extRays, r);
+    } else if constexpr (CELLS) {
+        // The shadow queue, in the groups of 64 items the round-robin deal below hands out: a
+        // plain loop, every lane busy (no stack, no refill hand-over, no parking)
+        const uint32_t wavesPerBlock = blockDim.x >> 6, waves = gridDim.x * wavesPerBlock;
+        const uint32_t waveId = blockIdx.x * wavesPerBlock + (threadIdx.x >> 6);
+        const bool watertight = (fc->features & DCRT_FEATURE_WATERTIGHT) != 0;
+        auto shadowSection = [&]() __attribute__((always_inline)) {
+            for (uint32_t i = (waveId << 6) + (threadIdx.x & 63u); i < nShadow; i += waves << 6) {
+                const float4* r = ext_rec(shRec, qpos(pool.recCap, qs, i));
+                const float4 o = r[0], d = r[1];
+                emit_occlusion(pool, asu(d.w), cells_occluded(sc, o, d, watertight, stackMem + threadIdx.x, block_shift(), leafWords));
+            }
+        };
+#ifndef DCRT_CELLS_LAST
+#define DCRT_CELLS_LAST 0   // (A/B: the shadow section after the extension rays)
+#endif
+        if (!DCRT_CELLS_LAST) shadowSection();
+        persistent_trace<false, INSTR, OPACITY, false, ALL_CACHED, PAIR, kLayout, IDENT, RING, FLAT>(
+            sc, nExt, fc->features, fc->refillLanes, fc->parkLanes, stackMem + threadIdx.x, block_shift(),
+            [&](uint32_t i) __attribute__((always_inline)) { return qpos(pool.recCap, qe, i); },
+            [&](uint32_t i, uint32_t v, TravState& s) __attribute__((always_inline)) {
+                const float4* r = ext_rec(extRec, v);
+                const float4 o = r[0], d = r[1];
+                trav_init(s, mk(o.x, o.y, o.z), mk(d.x, d.y, d.z), 0.0f, inf());
+                return i;   // the result goes to the ray's queue item
+            },
+            [&](uint32_t item, const TravState& s) __attribute__((always_inline)) { emit_hit(pool, item, s); },
+            st, DCRT_WAVE_TAG(g));
+        if (DCRT_CELLS_LAST) shadowSection();
     } else {
     // (node order: the pair kernels run on pair-ordered scenes, the other non-counting ones on
     // PackBVH-ordered ones -- tracer.hip takes both from castPair -- the counting ones on either)
@@ -1558,6 +1596,25 @@ __global__ __launch_bounds__(256) void batch_trace_kernel(DeviceScene sc, const 
         },
         st);
     if (INSTR) flush_stats(st, instr);
+}
+
+// The merged cast's streaming shadow section over a caller's ray batch (tests): cast_kernel<..., CELLS>'s
+// LDS layout and device function, one ray per lane
+__global__ __launch_bounds__(256) void cells_occlusion_kernel(DeviceScene sc, const dcrt_ray* rays, uint32_t n, uint32_t features,
+                                                               uint32_t* occluded)
+{
+    extern __shared__ uint32_t stackMem[];
+    uint32_t* leafWords = (uint32_t*)(scene_cache(sc, stackMem, block_shift()) + sc.cachedNodes * 2u + sc.cachedTris * kRotTriFloat4);
+    if (threadIdx.x < kCellWords) leafWords[threadIdx.x] = sc.shadowLeaves[threadIdx.x];
+    scene_cache_load<true>(sc, stackMem, block_shift());
+    const bool watertight = (features & DCRT_FEATURE_WATERTIGHT) != 0;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const dcrt_ray r = rays[i];
+        const bool occ = cells_occluded(sc, make_float4(r.origin[0], r.origin[1], r.origin[2], r.t_max),
+                                        make_float4(r.direction[0], r.direction[1], r.direction[2], 0.0f), watertight,
+                                        stackMem + threadIdx.x, block_shift(), leafWords);
+        occluded[i] = occ ? 1u : 0u;
+    }
 }
 
 __global__ void math_eval_kernel(int function, const float* x, uint32_t n, float* y)
@@ -2372,6 +2429,7 @@ template __global__ void cast_kernel<false, false, false, true>(PathPool, Device
 template __global__ void cast_kernel<false, true, false, true>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
 template __global__ void cast_kernel<false, false, true, false, true>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
 template __global__ void cast_kernel<false, false, true, false, true, false, true>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
+template __global__ void cast_kernel<false, false, true, false, true, false, true, true>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
 template __global__ void cast_kernel<true, false, true, false, true>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
 template __global__ void cast_kernel<false, false, false, false, true>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
 template __global__ void cast_kernel<true, false, false, false, true>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);

@@ -28,6 +28,7 @@ void SetLastError(const std::string& s);
 int CheckFilterParams(const dcrt_filter_params& f);   // (capi_scene.cpp: the one rule for scene and tracer)
 }
 using dcrt::SetLastError;
+using dcrt::ShadowCells;
 using namespace dcrt::dev;
 
 #define HIPCHECK(expr)                                                                              \
@@ -172,9 +173,12 @@ using CastFn = void (*)(PathPool, DeviceScene, const FrameConstants*, Counters*,
 // x pair-expanding traversal (the non-counting kernels of scenes not in the LDS cache) x the
 // world ray in every space (IDENT) x the spilling stack window (RING: non-counting, opaque,
 // global-memory kernels)
-CastFn CastKernel(bool instr, bool opacity, bool allCached, bool pair, bool ident = false, bool ring = false, bool flat = false)
+// x the entry-free node order (FLAT) x the point light's direction cells for its shadow rays (CELLS)
+CastFn CastKernel(bool instr, bool opacity, bool allCached, bool pair, bool ident = false, bool ring = false, bool flat = false,
+                  bool cells = false)
 {
-    if (flat && ident && allCached && !opacity && !instr && !ring) return cast_kernel<false, false, true, false, true, false, true>;
+    if (flat && ident && allCached && !opacity && !instr && !ring)
+        return cells ? cast_kernel<false, false, true, false, true, false, true, true> : cast_kernel<false, false, true, false, true, false, true>;
     if (ring && !instr && !opacity && !allCached) {
         if (pair) return cast_kernel<false, false, false, true, false, true>;
         return ident ? cast_kernel<false, false, false, false, true, true> : cast_kernel<false, false, false, false, false, true>;
@@ -464,6 +468,19 @@ struct dcrt_tracer {
     bool castFlat = false;             // the cache-only IDENT cast runs on the entry-free node order (EntryFreeLayout)
     DeviceScene sceneFlat{};           // the scene as that kernel sees it (its nodes, one more stack row)
     size_t castLdsFlat = 0;
+    // The point light's direction cells (shadow_cells.h) of a castFlat scene: sceneFlat.shadowRes != 0
+    // while the table stands. cellsRes: the resolution asked for (0: off, or the leaf words did not
+    // fit the cast's LDS without costing occupancy); the device buffers hold any table of it; the
+    // host copies of the geometry rebuild it when the lights change (RebuildShadowCells).
+    uint32_t cellsRes = 0;
+    uint64_t* dCells = nullptr;
+    uint32_t* dCellLeaves = nullptr;
+    ShadowCells cells;
+    std::vector<dcrt_bvh_node> cellNodes;
+    std::vector<dcrt_vertex> cellVertices;
+    std::vector<uint32_t> cellTriangles;
+    std::vector<dcrt_float4x3> cellTransforms;
+    int RebuildShadowCells();
     uint32_t castPerCU = 0;            // resident cast workgroups per CU
     bool castAllCached = false;        // the scene fits the LDS cache: cast_kernel<., ., true, .>
     bool castPair = false;             // trav_visit_pair: the scene outgrows an XCD's L2 (UploadScene)
@@ -971,6 +988,7 @@ int dcrt_tracer::UpdateLights(const dcrt_light* lights, uint32_t count)
     uploadStats.shading_bytes += (uint64_t)count * sizeof(dcrt_light);
     ++uploadStats.light_updates;
     CHECKED(RederiveShading());
+    CHECKED(RebuildShadowCells());
     HIPCHECK(hipStreamSynchronize(stream));
     return DCRT_OK;
 }
@@ -986,6 +1004,38 @@ int dcrt_tracer::UpdateInstanceFlags(const uint32_t* flags, uint32_t count)
     HIPCHECK(hipStreamSynchronize(stream));
     uploadStats.shading_bytes += (uint64_t)count * sizeof(uint32_t);
     ++uploadStats.instance_flag_updates;
+    CHECKED(RebuildShadowCells());   // (the flags enter no mask today: the any-hit kernels keep the BVH)
+    return DCRT_OK;
+}
+
+// The direction-cell table for the current lights (UploadScene, UpdateLights, UpdateInstanceFlags):
+// built on the host from the copies UploadScene kept, written into the buffers it allocated. A moved
+// light changes the buffers' contents only; a table that appears or goes changes the kernel and its
+// DeviceScene, so the captured graphs are dropped.
+int dcrt_tracer::RebuildShadowCells()
+{
+    if (!castFlat || !cellsRes) return DCRT_OK;
+    dcrt_flat_scene s{};
+    s.vertices = cellVertices.data();
+    s.vertex_count = (uint32_t)cellVertices.size();
+    s.triangles = cellTriangles.data();
+    s.triangle_count = (uint32_t)(cellTriangles.size() / 3);
+    s.instance_transforms = cellTransforms.data();
+    s.instance_count = (uint32_t)(cellTransforms.size() / 2);
+    s.lights = hostLights.data();
+    s.light_count = (uint32_t)hostLights.size();
+    dcrt::BuildShadowCells(cellNodes.data(), cellNodes.size(), s, cellsRes, &cells);
+    const uint32_t before = sceneFlat.shadowRes;
+    HIPCHECK(hipStreamSynchronize(stream));
+    if (cells.resolution) {
+        HIPCHECK(hipMemcpyAsync(dCells, cells.cells.data(), cells.cells.size() * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        HIPCHECK(hipMemcpyAsync(dCellLeaves, cells.leafWords.data(), dcrt::kCellWords * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        HIPCHECK(hipStreamSynchronize(stream));
+    }
+    sceneFlat.shadowCells = cells.resolution ? dCells : nullptr;
+    sceneFlat.shadowLeaves = cells.resolution ? dCellLeaves : nullptr;
+    sceneFlat.shadowRes = cells.resolution;
+    if (before != sceneFlat.shadowRes) InvalidateGraph();
     return DCRT_OK;
 }
 
@@ -1314,6 +1364,10 @@ int dcrt_tracer::UploadScene(const dcrt_flat_scene& s)
         // step per node visit), where its nodes, the triangles and one more stack row still fit
         // the LDS the IDENT kernel runs at (DCRT_FLAT_CAST=0: off, A/B and tests)
         castFlat = false;
+        cellsRes = 0;
+        dCells = nullptr;        // (sceneAllocs: freed above)
+        dCellLeaves = nullptr;
+        cells = ShadowCells{};
         bool flatWanted = true;
         if (const char* e = std::getenv("DCRT_FLAT_CAST")) flatWanted = std::atoi(e) != 0;
         if (flatWanted && castAllCached && castIdent && mergedCasts && d.singlePrimLeaves) {
@@ -1338,6 +1392,31 @@ int dcrt_tracer::UploadScene(const dcrt_flat_scene& s)
                     sceneFlat.stackRows = d.stackSize + 3u;
                     castLdsFlat = flatLds;
                     castFlat = true;
+                    // The point light's direction cells for this kernel's shadow rays (RebuildShadowCells
+                    // decides per light set): the leaf words go behind the scene cache, where they and the
+                    // CELLS kernel's registers leave the occupancy alone. DCRT_SHADOW_CELLS = the cube
+                    // map's resolution R (0: off).
+#ifndef DCRT_SHADOW_CELLS
+#define DCRT_SHADOW_CELLS 32
+#endif
+                    uint32_t wanted = DCRT_SHADOW_CELLS;
+                    if (const char* e = std::getenv("DCRT_SHADOW_CELLS")) wanted = (uint32_t)std::max(0, std::min((int)dcrt::kCellMaxRes, std::atoi(e)));
+                    const size_t cellsLds = flatLds + dcrt::kCellWords * sizeof(uint32_t);
+                    int plainPerCU = 0, cellsPerCU = 0;
+                    if (wanted) {
+                        CHECKED(castOccupancy(CastKernel(false, false, true, false, true, false, true), cellsLds, &plainPerCU));
+                        CHECKED(castOccupancy(CastKernel(false, false, true, false, true, false, true, true), cellsLds, &cellsPerCU));
+                    }
+                    if (wanted && std::min(plainPerCU, cellsPerCU) >= flatPerCU && cellsLds <= 65536) {
+                        cellsRes = wanted;
+                        castLdsFlat = cellsLds;
+                        CHECKED(DeviceAlloc(&dCells, (size_t)6 * cellsRes * cellsRes, &sceneAllocs));
+                        CHECKED(DeviceAlloc(&dCellLeaves, dcrt::kCellWords, &sceneAllocs));
+                        cellNodes = flat;
+                        cellVertices.assign(s.vertices, s.vertices + s.vertex_count);
+                        cellTriangles.assign(s.triangles, s.triangles + (size_t)s.triangle_count * 3);
+                        cellTransforms.assign(s.instance_transforms, s.instance_transforms + (size_t)s.instance_count * 2);
+                    }
                 }
             }
         }
@@ -1394,6 +1473,7 @@ int dcrt_tracer::UploadScene(const dcrt_flat_scene& s)
             sceneRing.spill = spill;
         }
     }
+    CHECKED(RebuildShadowCells());
     HIPCHECK(hipStreamSynchronize(stream));
     hasScene = true;
     newImage = true;
@@ -1721,7 +1801,7 @@ int dcrt_tracer::LaunchIteration(uint32_t par, bool timed, bool sequenced)
         const bool ring = ringRows != 0 && !instrCounters && !opacity;   // (the ring kernel; the counting and
                                                                         // any-hit kernels keep the whole stack)
         const bool flat = castFlat && !instrCounters && !opacity;
-        auto cast = CastKernel(instrCounters, opacity, castAllCached, castPair, castIdent, ring, flat);
+        auto cast = CastKernel(instrCounters, opacity, castAllCached, castPair, castIdent, ring, flat, flat && sceneFlat.shadowRes != 0u);
         hipExtLaunchKernelGGL(cast, dim3(castGrid), dim3(castBlock), flat ? castLdsFlat : ring ? castLds : castLdsFull, stream, e0,
                               e1, 0, pool, flat ? sceneFlat : ring ? sceneRing : scene,
                               (const FrameConstants*)dFrame, cnt, next, dGlobals, dInstr);
@@ -2786,6 +2866,10 @@ DCRT_API int dcrt_tracer_get_info(dcrt_tracer* t, dcrt_tracer_info* out)
     out->stack_lds_rows = t->hasScene ? (t->ringRows ? t->ringRows : t->castFlat ? t->sceneFlat.stackRows : t->scene.stackRows) : 0u;
     out->ring_rows = t->hasScene ? t->ringRows : 0u;
     out->cast_waves_per_cu = t->castPerCU * (t->castBlock / 64u);
+    const bool cells = t->hasScene && t->castFlat && t->sceneFlat.shadowRes != 0u;
+    out->shadow_cells = cells ? t->sceneFlat.shadowRes : 0u;
+    out->shadow_cell_max_leaves = cells ? t->cells.maxLeaves : 0u;
+    out->shadow_cell_mean_leaves = cells ? t->cells.meanLeaves : 0.0f;
     return DCRT_OK;
 }
 
@@ -2913,6 +2997,70 @@ DCRT_API int dcrt_tracer_occluded(dcrt_tracer* t, const dcrt_ray* rays, uint32_t
     if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
     FreeAll(&tmp);
     return rc;
+}
+
+DCRT_API int dcrt_tracer_trace_occlusion_cells(dcrt_tracer* t, const dcrt_ray* rays, uint32_t n, uint32_t* out, uint32_t features)
+{
+    TRACER_GUARD(t);
+    if ((!rays || !out) && n) return DCRT_E_INVALID_ARG;
+    if (!t->hasScene || !t->castFlat || t->sceneFlat.shadowRes == 0u) {
+        SetLastError("the uploaded scene has no direction-cell table" + (t->cells.reason.empty() ? std::string() : ": " + t->cells.reason));
+        return DCRT_E_NO_SCENE;
+    }
+    if (n == 0) return DCRT_OK;
+    std::vector<void*> tmp;
+    dcrt_ray* dr = nullptr; uint32_t* dOcc = nullptr;
+    CHECKED(DeviceAlloc(&dr, n, &tmp));
+    CHECKED(DeviceAlloc(&dOcc, n, &tmp));
+    int rc = DCRT_OK;
+    if (hipMemcpyAsync(dr, rays, (size_t)n * sizeof(dcrt_ray), hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    if (rc == DCRT_OK) {
+        const uint32_t grid = std::min<uint32_t>((n + t->castBlock - 1) / t->castBlock, t->castResident);
+        hipLaunchKernelGGL(cells_occlusion_kernel, dim3(grid), dim3(t->castBlock), t->castLdsFlat, t->stream, t->sceneFlat, (const dcrt_ray*)dr, n,
+                           features, dOcc);
+        if (hipGetLastError() != hipSuccess) rc = DCRT_E_HIP;
+    }
+    if (rc == DCRT_OK && hipMemcpyAsync(out, dOcc, (size_t)n * 4, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    FreeAll(&tmp);
+    return rc;
+}
+
+DCRT_API int dcrt_shadow_cells_build(const dcrt_flat_scene* s, uint32_t resolution, dcrt_shadow_cells_info* info, uint64_t* outCells,
+                                     uint32_t* outLeafWords, dcrt_bvh_node* outNodes, uint32_t nodeCapacity)
+{
+    if (!s || !info || !s->bvh_nodes || !s->vertices || !s->triangles || !s->instance_transforms || s->bvh_node_count == 0 ||
+        resolution > dcrt::kCellMaxRes) {
+        SetLastError("dcrt_shadow_cells_build: incomplete scene or resolution above the limit");
+        return DCRT_E_INVALID_ARG;
+    }
+    *info = dcrt_shadow_cells_info{};
+    std::vector<dcrt_bvh_node> flat;
+    ShadowCells cells;
+    if (!EntryFreeLayout(*s, &flat)) cells.reason = "no entry-free node order (a leaf with several triangles, or a malformed tree)";
+    else dcrt::BuildShadowCells(flat.data(), flat.size(), *s, resolution ? resolution : (uint32_t)DCRT_SHADOW_CELLS, &cells);
+    if (!cells.resolution) {
+        SetLastError("no direction-cell table: " + cells.reason);
+        return DCRT_OK;
+    }
+    if (outNodes && nodeCapacity < flat.size()) { SetLastError("dcrt_shadow_cells_build: node capacity too small"); return DCRT_E_INVALID_ARG; }
+    info->resolution = cells.resolution;
+    info->leaf_count = cells.leafCount;
+    info->node_count = (uint32_t)flat.size();
+    info->max_leaves = cells.maxLeaves;
+    info->mean_leaves = cells.meanLeaves;
+    info->r0 = (float)cells.r0;
+    if (outCells) std::memcpy(outCells, cells.cells.data(), cells.cells.size() * sizeof(uint64_t));
+    if (outLeafWords) std::memcpy(outLeafWords, cells.leafWords.data(), dcrt::kCellWords * sizeof(uint32_t));
+    if (outNodes) std::memcpy(outNodes, flat.data(), flat.size() * sizeof(dcrt_bvh_node));
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_shadow_cell_indices(uint32_t resolution, const float* w, uint32_t count, uint32_t* out)
+{
+    if (resolution == 0u || resolution > dcrt::kCellMaxRes || ((!w || !out) && count)) return DCRT_E_INVALID_ARG;
+    for (uint32_t i = 0; i < count; ++i) out[i] = dcrt::ShadowCellIndex(resolution, w + (size_t)i * 3);
+    return DCRT_OK;
 }
 
 DCRT_API int dcrt_tracer_trace_rays_device(dcrt_tracer* t, const void* d_rays, uint32_t n, void* d_hits, uint32_t features)

@@ -215,6 +215,34 @@ class Scene:
         check(self._lib.dcrt_scene_get_flat(self._h, C.byref(f)), "GetFlat")
         return f
 
+    def shadow_cells(self, resolution: int = 0) -> dict | None:
+        """The point light's direction-cell table as upload_scene would build it for this scene
+        (dcrt_shadow_cells_build, host only): {"resolution", "cells" [6, R, R] uint64 leaf masks,
+        "leaf_words" [128], "nodes" [n, 8] uint32 entry-free nodes, "leaf_count", "mean_leaves",
+        "max_leaves", "r0"}, or None when the scene is not eligible."""
+        f = self.flat()
+        info = _abi.ShadowCellsInfo()
+        check(self._lib.dcrt_shadow_cells_build(C.byref(f), int(resolution), C.byref(info), None, None, None, 0), "ShadowCellsBuild")
+        if info.resolution == 0:
+            return None
+        R = info.resolution
+        cells = np.zeros((6, R, R), np.uint64)
+        words = np.zeros(128, np.uint32)
+        nodes = np.zeros((info.node_count, 8), np.uint32)
+        check(self._lib.dcrt_shadow_cells_build(C.byref(f), int(resolution), C.byref(info), cells.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                words.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                nodes.ctypes.data_as(C.POINTER(_abi.BVHNode)), info.node_count), "ShadowCellsBuild")
+        return {"resolution": R, "cells": cells, "leaf_words": words, "nodes": nodes, "leaf_count": info.leaf_count,
+                "mean_leaves": info.mean_leaves, "max_leaves": info.max_leaves, "r0": info.r0}
+
+    def shadow_cell_indices(self, resolution: int, w: np.ndarray) -> np.ndarray:
+        """Cells (flat indices into "cells") of directions w [n, 3], from the light to the ray."""
+        w = np.ascontiguousarray(w, np.float32).reshape(-1, 3)
+        out = np.zeros(len(w), np.uint32)
+        check(self._lib.dcrt_shadow_cell_indices(int(resolution), w.ctypes.data_as(C.POINTER(C.c_float)), len(w),
+                                                 out.ctypes.data_as(C.POINTER(C.c_uint32))), "ShadowCellIndices")
+        return out
+
     def postfx_params(self) -> _abi.PostFxParams:
         """Scene.h:181-185 defaults, EV100 from the camera (PostProcessing.cpp:39-42)."""
         p = _abi.PostFxParams()

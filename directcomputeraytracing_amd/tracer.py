@@ -441,6 +441,17 @@ class WavefrontPathTracer:
                                              out.ctypes.data_as(C.POINTER(C.c_uint32)), int(features)), "Occluded")
         return out
 
+    def occluded_cells(self, rays: np.ndarray, features: int = _abi.FEATURE_DEFAULT) -> np.ndarray:
+        """Occlusion bits of shadow rays towards the scene's point light through the merged cast's
+        direction-cell section (dcrt_tracer_trace_occlusion_cells); `occluded` is its comparison
+        partner. Raises when the scene has no table (info()["shadow_cells"] == 0)."""
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        out = np.zeros(len(rays), np.uint32)
+        check(self._lib.dcrt_tracer_trace_occlusion_cells(self._h, rays.ctypes.data_as(C.POINTER(_abi.Ray)), len(rays),
+                                                          out.ctypes.data_as(C.POINTER(C.c_uint32)), int(features)),
+              "TraceOcclusionCells")
+        return out
+
     def trace_rays_device(self, d_rays: int, count: int, d_hits: int, features: int = _abi.FEATURE_DEFAULT) -> None:
         check(self._lib.dcrt_tracer_trace_rays_device(self._h, C.c_void_p(d_rays), int(count), C.c_void_p(d_hits),
                                                       int(features)), "TraceRaysDevice")

@@ -298,6 +298,10 @@ typedef struct dcrt_tracer_info {
     uint32_t ring_rows;           /* 0, or the LDS window (rows) of a spilling traversal stack: deeper
                                      entries live in a per-lane global column              */
     uint32_t cast_waves_per_cu;   /* resident waves per CU of the launched cast kernel      */
+    uint32_t shadow_cells;        /* 0, or R: the merged cast tests shadow rays against the point light's
+                                     6 * R * R direction cells (dcrt_shadow_cells_build) instead of walking the BVH */
+    uint32_t shadow_cell_max_leaves;   /* leaves in the fullest cell, and the mean over the cells */
+    float shadow_cell_mean_leaves;
 } dcrt_tracer_info;
 
 typedef struct dcrt_tracer dcrt_tracer;
@@ -305,12 +309,13 @@ typedef struct dcrt_scene dcrt_scene;
 
 /* ===== version / device ================================================== */
 /* ABI version of this header: bumped whenever a struct changes size or an entry point its
- * meaning (2: dcrt_tracer_info grew cast_waves_per_cu / ring_rows / stack_lds_rows). A caller
+ * meaning (2: dcrt_tracer_info grew cast_waves_per_cu / ring_rows / stack_lds_rows; 3: it grew
+ * shadow_cells / shadow_cell_max_leaves / shadow_cell_mean_leaves). A caller
  * compiled against another header checks dcrt_abi_version() == DCRT_ABI_VERSION before it
  * passes any struct (a smaller dcrt_tracer_info would be written past its end). Added entry
  * points with structs of their own (the scene updates, the output views, the film denoiser)
  * leave it as it is: nothing an older caller passes has changed. */
-#define DCRT_ABI_VERSION 2
+#define DCRT_ABI_VERSION 3
 DCRT_API int dcrt_abi_version(void);
 DCRT_API const char* dcrt_version(void);
 DCRT_API const char* dcrt_last_error(void);
@@ -643,6 +648,36 @@ DCRT_API int dcrt_tracer_occluded(dcrt_tracer* tracer, const dcrt_ray* rays, uin
 /* Device-resident variant for timing: rays/hits already in HBM, launched on the tracer stream. */
 DCRT_API int dcrt_tracer_trace_rays_device(dcrt_tracer* tracer, const void* d_rays, uint32_t count, void* d_hits,
                                            uint32_t features);
+
+/* ===== the point light's direction-cell table (shadow rays of one-point-light scenes) ===== */
+/* The occlusion bits of shadow rays through the device function of the merged cast's streaming
+ * shadow section. The rays must be built the way MATERIAL builds them -- origin
+ * OffsetRayOrigin(P), direction normalize(L - P), t_max = |L - P| for the scene's point light L --
+ * since the table is keyed by direction; dcrt_tracer_occluded is the comparison partner.
+ * DCRT_E_NO_SCENE when the uploaded scene has no table (dcrt_tracer_info.shadow_cells == 0). */
+DCRT_API int dcrt_tracer_trace_occlusion_cells(dcrt_tracer* tracer, const dcrt_ray* rays, uint32_t count,
+                                               uint32_t* out_occluded, uint32_t features);
+typedef struct dcrt_shadow_cells_info {
+    uint32_t resolution;      /* R: 6 * R * R cells; 0: the scene is not eligible              */
+    uint32_t leaf_count;      /* triangle leaves (bits of a mask in use)                       */
+    uint32_t node_count;      /* nodes of the entry-free array                                 */
+    uint32_t max_leaves;      /* most leaves in one cell                                       */
+    float mean_leaves;        /* mean leaves per cell                                          */
+    float r0;                 /* no triangle may come closer to the light than this            */
+} dcrt_shadow_cells_info;
+/* The table as upload_scene builds it for a flat scene, on the host (needs no device): the cell
+ * masks (6 * R * R words, or NULL), the 128 leaf words (or NULL: word k < leaf_count = leaf k's node |
+ * its guard count << 10 | the index of its first guard word << 16; a guard word is the node of an
+ * ancestor whose box is tested beside the leaf's) and the entry-free nodes they index (up to
+ * node_capacity; or NULL).
+ * resolution 0 = the default. An ineligible scene answers DCRT_OK with out_info->resolution == 0
+ * and the reason in dcrt_last_error(). The cell of a direction: dcrt_shadow_cell_indices. */
+DCRT_API int dcrt_shadow_cells_build(const dcrt_flat_scene* scene, uint32_t resolution, dcrt_shadow_cells_info* out_info,
+                                     uint64_t* out_cells, uint32_t* out_leaf_words, dcrt_bvh_node* out_nodes,
+                                     uint32_t node_capacity);
+/* Cells (indices into the masks) of `count` directions w (3 floats each), pointing from the light to
+ * the ray: the negated ray directions. */
+DCRT_API int dcrt_shadow_cell_indices(uint32_t resolution, const float* w, uint32_t count, uint32_t* out_cells);
 
 /* ===== post-processing + image output (PostProcessing.cpp, PostProcessings.hlsl,
  *       SumLuminance.hlsl, SaveImageToFile.cpp) ============================== */
