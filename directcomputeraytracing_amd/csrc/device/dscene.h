@@ -114,7 +114,7 @@ __host__ __device__ inline uint32_t material_lds_bytes(uint32_t T, uint32_t I, u
 
 // Node orders on the device. kLayoutFlat is PackBVH's depth-first order, as in the flat
 // scene: an interior node's left child is node + 1 and its `right` field the right child.
-// kLayoutPairs (tracer.hip PairLayout, taken for scenes beyond an XCD's L2: the pair
+// kLayoutPairs (bvh_layout.h PairLayout, taken for scenes beyond an XCD's L2: the pair
 // traversal's kernels) puts the two children side by side -- one 64-B line, fetched together
 // when trav_visit_pair expands a node -- with `right` holding the left child's index, and the
 // levels nearest the roots first (the prefix the LDS scene cache holds). kLayoutScene reads
@@ -750,7 +750,7 @@ DEV bool trav_visit_pair(const DeviceScene& sc, TravState& s, uint32_t* lds, uin
 // Phase B: the parked leaf's work. TLAS leaf: move the ray into the instance and
 // continue at its BLAS root. BLAS leaf: test triangles [ref, ref + count), then pop.
 // LANE_ANY: any-hit is a per-lane choice (s.anyHit), for the merged ray-cast kernel
-// FLAT (the entry-free node order of the cache-only IDENT kernel, tracer.hip EntryFreeLayout): no
+// FLAT (the entry-free node order of the cache-only IDENT kernel, bvh_layout.h EntryFreeLayout): no
 // TLAS leaves -- a leaf is a BLAS triangle leaf whose count field holds its instance + 1
 template <bool ANY_HIT, bool INSTR, bool OPACITY = false, bool LANE_ANY = false, bool ALL_CACHED = false, bool IDENT = false,
           bool RING = false, bool FLAT = false>

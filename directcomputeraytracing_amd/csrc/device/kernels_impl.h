@@ -1049,7 +1049,7 @@ __global__ __launch_bounds__(256) DCRT_CAST_OCCUPANCY void shadow_kernel(PathPoo
 #endif
 // RING: the traversal stack as an LDS window over a per-lane global column (ring_maintain), for
 // scenes whose whole stack would cost LDS occupancy (tracer.hip UploadScene).
-// FLAT: the cache-only IDENT kernel over the entry-free node order (tracer.hip EntryFreeLayout)
+// FLAT: the cache-only IDENT kernel over the entry-free node order (bvh_layout.h EntryFreeLayout)
 // CELLS (with FLAT, a scene with a direction-cell table, shadow_cells.h): every wave first streams
 // through its share of the shadow queue, one ray per lane, testing only the leaves of the ray's
 // cell (cells_occluded: the reference's occlusion bit), then traces the extension queue alone
@@ -1144,7 +1144,7 @@ __attribute__((amdgpu_waves_per_eu(ALL_CACHED && !OPACITY && !INSTR ? (IDENT ? D
         if (DCRT_CELLS_LAST) shadowSection();
     } else {
     // (node order: the pair kernels run on pair-ordered scenes, the other non-counting ones on
-    // PackBVH-ordered ones -- tracer.hip takes both from castPair -- the counting ones on either)
+    // PackBVH-ordered ones -- tracer.hip's cast plan takes both from `pair` -- the counting ones on either)
     persistent_trace<false, INSTR, OPACITY, true, ALL_CACHED, PAIR, kLayout, IDENT, RING, FLAT>(
         sc, nExt + nShadow, fc->features, fc->refillLanes, fc->parkLanes, stackMem + threadIdx.x, block_shift(),
         [&](uint32_t i) __attribute__((always_inline)) {
@@ -2417,22 +2417,32 @@ template __global__ void shadow_kernel<false, false>(PathPool, DeviceScene, cons
 template __global__ void shadow_kernel<false, true>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
 template __global__ void shadow_kernel<true, false>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
 template __global__ void shadow_kernel<true, true>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
-template __global__ void cast_kernel<false, false, false, false>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
-template __global__ void cast_kernel<false, false, true, false>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
-template __global__ void cast_kernel<false, true, false, false>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
-template __global__ void cast_kernel<false, true, true, false>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
-template __global__ void cast_kernel<true, false, false, false>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
-template __global__ void cast_kernel<true, false, true, false>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
-template __global__ void cast_kernel<true, true, false, false>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
-template __global__ void cast_kernel<true, true, true, false>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
-template __global__ void cast_kernel<false, false, false, true>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
-template __global__ void cast_kernel<false, true, false, true>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
-template __global__ void cast_kernel<false, false, true, false, true>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
-template __global__ void cast_kernel<false, false, true, false, true, false, true>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
-template __global__ void cast_kernel<false, false, true, false, true, false, true, true>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
-template __global__ void cast_kernel<true, false, true, false, true>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
-template __global__ void cast_kernel<false, false, false, false, true>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
-template __global__ void cast_kernel<true, false, false, false, true>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
+// The compiled cast_kernel variants (INSTR, OPACITY, ALL_CACHED, PAIR, IDENT, RING, FLAT, CELLS): this one list
+// instantiates them and is the table that tracer.hip's CastKernel() picks from, in this order.
+#define DCRT_CAST_VARIANTS(X)                                   \
+    X(false, false, false, false, false, false, false, false)   \
+    X(false, false, true, false, false, false, false, false)    \
+    X(false, true, false, false, false, false, false, false)    \
+    X(false, true, true, false, false, false, false, false)     \
+    X(true, false, false, false, false, false, false, false)    \
+    X(true, false, true, false, false, false, false, false)     \
+    X(true, true, false, false, false, false, false, false)     \
+    X(true, true, true, false, false, false, false, false)      \
+    X(false, false, false, true, false, false, false, false)    \
+    X(false, true, false, true, false, false, false, false)     \
+    X(false, false, true, false, true, false, false, false)     \
+    X(false, false, true, false, true, false, true, false)      \
+    X(false, false, true, false, true, false, true, true)       \
+    X(true, false, true, false, true, false, false, false)      \
+    X(false, false, false, false, true, false, false, false)    \
+    X(true, false, false, false, true, false, false, false)     \
+    X(false, false, false, false, false, true, false, false)    \
+    X(false, false, false, false, true, true, false, false)     \
+    X(false, false, false, true, false, true, false, false)
+#define DCRT_INSTANTIATE_CAST(...) \
+    template __global__ void cast_kernel<__VA_ARGS__>(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
+DCRT_CAST_VARIANTS(DCRT_INSTANTIATE_CAST)
+#undef DCRT_INSTANTIATE_CAST
 template __global__ void megakernel<false>(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t);
 template __global__ void megakernel<true>(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t);
 template __global__ void view_kernel<false>(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t, uint32_t, uint32_t);

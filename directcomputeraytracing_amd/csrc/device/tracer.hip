@@ -21,12 +21,15 @@
 #include <vector>
 
 #include "../../../include/dcrt.h"
+#include "../host/bvh_layout.h"
+#include "../host/film_rows.h"
 #include "kernels_impl.h"
 
 namespace dcrt {
 void SetLastError(const std::string& s);
 int CheckFilterParams(const dcrt_filter_params& f);   // (capi_scene.cpp: the one rule for scene and tracer)
 }
+using dcrt::FilterSupportRows;
 using dcrt::SetLastError;
 using dcrt::ShadowCells;
 using namespace dcrt::dev;
@@ -111,10 +114,6 @@ FilterConsts MakeFilter(const dcrt_filter_params& p)   // SampleConvolution.cpp:
     return c;
 }
 
-// Rows beyond its own that a film row's SampleConvolution window reaches
-// (SampleConvolution.hlsl:77-81), with the kernel's float arithmetic
-// (film_pixel_window): floor(r + 0.5) in exact arithmetic, one more where py + 0.5 + r
-// rounds up to the next integer (r just below k + 0.5).
 // roctx ranges around the host-side passes, named like the reference's PIX annotations
 // (SCOPED_RENDER_ANNOTATION, WavefrontPathTracer.cpp:443-1083): visible in rocprofv3
 // --marker-trace next to the kernels. rocprofiler-sdk's roctx (the one rocprofv3 intercepts;
@@ -154,43 +153,149 @@ struct Annotation {
     }
 };
 
-uint32_t FilterSupportRows(float r, uint32_t H)
+// A cast_kernel variant, by its template parameters: instrumented counts x ALLOW_ANYHIT_SHADER x
+// whole scene in the LDS cache x pair-expanding traversal (the non-counting kernels of scenes not
+// in the LDS cache) x the world ray in every space (IDENT) x the spilling stack window (RING:
+// non-counting, opaque, global-memory kernels) x the entry-free node order (FLAT) x the point
+// light's direction cells for its shadow rays (CELLS)
+struct CastVariant {
+    bool instr, opacity, allCached, pair, ident, ring, flat, cells;
+};
+using CastFn = void (*)(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
+
+// The compiled kernel for what a launch asks for (DCRT_CAST_VARIANTS, kernels_impl.h). Not every
+// combination is compiled; the fall-back drops, in this order, what the others rule out: FLAT is
+// the cache-only IDENT kernel, CELLS goes with FLAT; RING, the counting and the any-hit kernels
+// keep PackBVH's or the pair order; IDENT has no any-hit kernel and no pair kernel but the ring's.
+CastFn CastKernel(const CastVariant& want)
 {
-    if (!(r < (float)H)) return H;
-    uint32_t rows = 0;
-    for (uint32_t py = 0; py < H; ++py) {
-        const float cy = (float)py + 0.5f;
-        int ys = (int)std::floor(cy - r), ye = (int)std::floor(cy + r);
-        ys = std::max(ys, 0);
-        ye = std::min(ye, (int)H - 1);
-        rows = std::max<uint32_t>(rows, (uint32_t)std::max(ye - (int)py, (int)py - ys));
+    CastVariant v = want;
+    v.flat = v.flat && v.ident && v.allCached && !v.opacity && !v.instr && !v.ring;
+    v.cells = v.cells && v.flat;
+    v.ring = v.ring && !v.instr && !v.opacity && !v.allCached;
+    if (v.flat) {
+        v.pair = false;
+    } else if (v.ring) {
+        v.ident = v.ident && !v.pair;
+    } else {
+        v.ident = v.ident && !v.opacity && (v.allCached || v.instr || !v.pair);
+        v.pair = v.pair && !v.ident && !v.instr && !v.allCached;
     }
-    return rows;
+    struct Row { CastVariant v; CastFn fn; };
+#define DCRT_CAST_ROW(...) { { __VA_ARGS__ }, cast_kernel<__VA_ARGS__> },
+    static const Row table[] = { DCRT_CAST_VARIANTS(DCRT_CAST_ROW) };
+#undef DCRT_CAST_ROW
+    for (const Row& r : table) {
+        if (r.v.instr == v.instr && r.v.opacity == v.opacity && r.v.allCached == v.allCached && r.v.pair == v.pair &&
+            r.v.ident == v.ident && r.v.ring == v.ring && r.v.flat == v.flat && r.v.cells == v.cells)
+            return r.fn;
+    }
+    return nullptr;   // (no input gets here: the fall-back above ends on a compiled variant)
 }
 
-using CastFn = void (*)(PathPool, DeviceScene, const FrameConstants*, Counters*, Counters*, Globals*, unsigned long long*);
-// cast_kernel variant: instrumented counts x ALLOW_ANYHIT_SHADER x whole scene in the LDS cache
-// x pair-expanding traversal (the non-counting kernels of scenes not in the LDS cache) x the
-// world ray in every space (IDENT) x the spilling stack window (RING: non-counting, opaque,
-// global-memory kernels)
-// x the entry-free node order (FLAT) x the point light's direction cells for its shadow rays (CELLS)
-CastFn CastKernel(bool instr, bool opacity, bool allCached, bool pair, bool ident = false, bool ring = false, bool flat = false,
-                  bool cells = false)
+// ---- DCRT_* knobs: one reader per moment they are read at, one struct each -- the list of knobs,
+// with their defaults (A/B experiments and tests; the static ones sit with their code:
+// DCRT_MAX_BATCH, DCRT_BATCH_POOL_LIMIT, DCRT_ROCTX, DCRT_DENOISE_PASS) ------------------------
+int EnvInt(const char* name, int unset)
 {
-    if (flat && ident && allCached && !opacity && !instr && !ring)
-        return cells ? cast_kernel<false, false, true, false, true, false, true, true> : cast_kernel<false, false, true, false, true, false, true>;
-    if (ring && !instr && !opacity && !allCached) {
-        if (pair) return cast_kernel<false, false, false, true, false, true>;
-        return ident ? cast_kernel<false, false, false, false, true, true> : cast_kernel<false, false, false, false, false, true>;
+    const char* e = std::getenv(name);
+    return e ? std::atoi(e) : unset;
+}
+bool EnvFlag(const char* name, bool unset)
+{
+    const char* e = std::getenv(name);
+    return e ? std::atoi(e) != 0 : unset;
+}
+
+struct CreateKnobs {
+    bool mergedCasts = true;           // one cast_kernel per iteration (DCRT_SPLIT_CASTS=1: EXT then SHADOW)
+    bool virtualStart = true;          // virtual batch starts where the cast kernel has them (DCRT_VIRTUAL_START=0: off)
+    uint32_t drainPaths = 0;           // drain_kernel threshold (DCRT_DRAIN_PATHS; 0: no drain launches -- the default: profiles/r04_ab_virtual_drain.txt)
+    // cast-kernel refill / park thresholds (persistent_trace): refill when 36 lanes are idle
+    // in the LDS-only kernel, 28 in the global-memory one (round 3 sweep with the adaptive
+    // park threshold); park at 24 (profiles/r01_tune_sweep.txt); DCRT_TRAVERSAL_TUNE=
+    // "refill,park" overrides both
+    uint32_t refillLanes = 36, parkLanes = 24;
+    bool tuneOverride = false;
+    // DCRT_CONTROL_GRID / DCRT_MATERIAL_GRID = k: k x resident; 0: one workgroup per virtual
+    // workgroup. 2x / 4x resident (two A/B passes of the default bench on cornell / spaceship / coffee,
+    // ms/spp: one workgroup per virtual workgroup 2.40 / 2.84 / 2.96; 1x / 1x 2.28-2.38 /
+    // 2.63 / 3.02; 1x / 4x 2.37 / 2.58 / 2.95; 2x / 4x 2.35-2.38 / 2.54 / 2.92; 4x / 4x
+    // 2.37 / 2.55 / 2.95; 2x / 8x 2.37-2.39 / 2.55 / 2.92)
+    uint32_t controlGridMul = 2, materialGridMul = 4;
+};
+CreateKnobs ReadCreateKnobs()
+{
+    CreateKnobs k;
+    k.mergedCasts = !EnvFlag("DCRT_SPLIT_CASTS", false);
+    k.virtualStart = EnvFlag("DCRT_VIRTUAL_START", true);
+    k.drainPaths = (uint32_t)std::max(0, EnvInt("DCRT_DRAIN_PATHS", 0));
+    if (const char* tune = std::getenv("DCRT_TRAVERSAL_TUNE")) {
+        unsigned r = 0, p = 0;
+        if (std::sscanf(tune, "%u,%u", &r, &p) == 2 && r >= 1 && r <= 64 && p >= 1 && p <= 64) {
+            k.refillLanes = r;
+            k.parkLanes = p;
+            k.tuneOverride = true;
+        }
     }
-    if (ident && allCached && !opacity) return instr ? cast_kernel<true, false, true, false, true> : cast_kernel<false, false, true, false, true>;
-    if (ident && !opacity && (instr || !pair)) return instr ? cast_kernel<true, false, false, false, true> : cast_kernel<false, false, false, false, true>;
-    static const CastFn table[8] = {
-        cast_kernel<false, false, false, false>, cast_kernel<false, false, true, false>, cast_kernel<false, true, false, false>,
-        cast_kernel<false, true, true, false>, cast_kernel<true, false, false, false>, cast_kernel<true, false, true, false>,
-        cast_kernel<true, true, false, false>, cast_kernel<true, true, true, false>};
-    if (pair && !instr && !allCached) return opacity ? cast_kernel<false, true, false, true> : cast_kernel<false, false, false, true>;
-    return table[(instr ? 4 : 0) + (opacity ? 2 : 0) + (allCached ? 1 : 0)];
+    k.controlGridMul = (uint32_t)std::max(0, EnvInt("DCRT_CONTROL_GRID", (int)k.controlGridMul));
+    k.materialGridMul = (uint32_t)std::max(0, EnvInt("DCRT_MATERIAL_GRID", (int)k.materialGridMul));
+    return k;
+}
+
+#ifndef DCRT_CAST_LDS_RESERVE
+#define DCRT_CAST_LDS_RESERVE 12288   // (A/B: coffee -2 to -3 %, lamp -1 %; profiles/r04_ab_round4.txt)
+#endif
+struct UploadKnobs {
+    uint32_t castBlock = 0;            // DCRT_CAST_BLOCK = 64 / 128 / 256, at most the block the stack allows (else: that block)
+    bool noLdsCache = false;           // DCRT_NO_LDS_CACHE=1: no LDS scene cache
+    int pairTraversal = -1;            // DCRT_PAIR_TRAVERSAL=0/1 forces trav_visit_pair off / on (-1: by the scene's size)
+    uint32_t topNodes = 4096;          // DCRT_TOP_NODES: PairLayout's breadth-first prefix
+    bool nodeQuads = true;             // DCRT_NODE_QUADS=0: PairLayout without quads (profiles/r06_ab_log.md: spaceship -1.6 %, close framing -0.1 / -1.4 %)
+    bool identCast = true;             // DCRT_IDENT_CAST=0: no IDENT kernel
+    int stackRing = -1;                // DCRT_STACK_RING = K (a power of two, 8..64) forces a ring window of K rows, 0: never (-1: where it gains occupancy)
+    size_t castLdsReserve = DCRT_CAST_LDS_RESERVE;   // DCRT_CAST_LDS_RESERVE: bytes per CU the LDS cache leaves free
+    uint32_t skipRoot = 1;             // DCRT_SKIP_ROOT: trav_skip_root's levels of sure hits taken without their box tests (0..16)
+    bool ldsTrim = true;               // DCRT_LDS_TRIM=0: the cache is not trimmed to the LDS granule
+    bool flatCast = true;              // DCRT_FLAT_CAST=0: no entry-free node order
+    bool flatMerge = true;             // DCRT_FLAT_MERGE=0: every TLAS leaf over an empty node
+    uint32_t shadowCells = dcrt::kCellDefaultRes;   // DCRT_SHADOW_CELLS = the direction cells' cube map resolution R (0: off)
+    int castBlocksPerCU = 0;           // DCRT_CAST_BLOCKS_PER_CU: fewer resident cast workgroups per CU than fit
+    int castGridMul = 0;               // DCRT_CAST_GRID_MUL = k (2..16): k x resident, workgroups retire in k rounds
+};
+UploadKnobs ReadUploadKnobs()
+{
+    UploadKnobs k;
+    k.castBlock = (uint32_t)EnvInt("DCRT_CAST_BLOCK", 0);
+    k.noLdsCache = EnvFlag("DCRT_NO_LDS_CACHE", false);
+    if (std::getenv("DCRT_PAIR_TRAVERSAL")) k.pairTraversal = EnvFlag("DCRT_PAIR_TRAVERSAL", false) ? 1 : 0;
+    k.topNodes = (uint32_t)EnvInt("DCRT_TOP_NODES", (int)k.topNodes);
+    k.nodeQuads = EnvFlag("DCRT_NODE_QUADS", true);
+    k.identCast = EnvFlag("DCRT_IDENT_CAST", true);
+    k.stackRing = EnvInt("DCRT_STACK_RING", -1);
+    if (std::getenv("DCRT_CAST_LDS_RESERVE")) k.castLdsReserve = (size_t)std::max(0, EnvInt("DCRT_CAST_LDS_RESERVE", 0));
+    k.skipRoot = (uint32_t)std::max(0, std::min(16, EnvInt("DCRT_SKIP_ROOT", (int)k.skipRoot)));
+    k.ldsTrim = EnvFlag("DCRT_LDS_TRIM", true);
+    k.flatCast = EnvFlag("DCRT_FLAT_CAST", true);
+    k.flatMerge = EnvFlag("DCRT_FLAT_MERGE", true);
+    k.shadowCells = (uint32_t)std::max(0, std::min((int)dcrt::kCellMaxRes, EnvInt("DCRT_SHADOW_CELLS", (int)k.shadowCells)));
+    k.castBlocksPerCU = EnvInt("DCRT_CAST_BLOCKS_PER_CU", 0);
+    k.castGridMul = EnvInt("DCRT_CAST_GRID_MUL", 0);
+    return k;
+}
+
+struct ShadingKnobs {
+    bool materialGeneric = false;      // DCRT_MATERIAL_GENERIC=1: always the generic MATERIAL variant
+    uint32_t materialLds = 16384;      // DCRT_MATERIAL_LDS = bytes budget of MATERIAL's LDS scene copy, 0: off
+    bool materialLdsPartial = true;    // DCRT_MATERIAL_LDS_PARTIAL=0: no mode 2 (everything but the triangles)
+};
+ShadingKnobs ReadShadingKnobs()
+{
+    ShadingKnobs k;
+    k.materialGeneric = EnvFlag("DCRT_MATERIAL_GENERIC", false);
+    k.materialLds = (uint32_t)std::max(0, EnvInt("DCRT_MATERIAL_LDS", (int)k.materialLds));
+    k.materialLdsPartial = EnvFlag("DCRT_MATERIAL_LDS_PARTIAL", true);
+    return k;
 }
 
 // Workgroups per CU that a workgroup's LDS allocation allows. hipOccupancyMaxActiveBlocksPerMultiprocessor
@@ -213,219 +318,48 @@ int LdsResident(size_t lds, const void* kernel = nullptr)
     return lds ? (int)(g_ldsPerCU / ((lds + kLdsGranule - 1) / kLdsGranule * kLdsGranule)) : 1 << 20;
 }
 
-// The LDS stack depth traversal of the uploaded tree needs: the most interior nodes on
-// any root-to-leaf path through a TLAS leaf into its BLAS (each descent pushes the far
-// child; BVHAccel.inc.hlsl:143-154). Children lie after their parent (depth-first
-// layout), BLAS roots after the TLAS; anything else is malformed (false).
-bool RequiredTraversalStack(const dcrt_flat_scene& s, uint32_t* out)
-{
-    const uint32_t n = s.bvh_node_count;
-    *out = 0;
-    if (n == 0) return true;
-    std::vector<uint32_t> blasDepth(n, UINT32_MAX);   // memo: deepest path below a BLAS root
-    // every node is reached at most once per walk: a tree. A node reached twice (a child
-    // shared between parents, a cycle) is malformed -- and would make the walk exponential
-    std::vector<uint32_t> seen(n, UINT32_MAX);        // the walk that last reached the node
-    uint32_t walkId = 0;
-    struct Item { uint32_t node, depth; };
-    std::vector<Item> todo;
-    auto walk = [&](uint32_t root, bool tlas, uint32_t* deepest) {
-        ++walkId;
-        todo.assign(1, { root, 0u });
-        *deepest = 0;
-        while (!todo.empty()) {
-            const Item it = todo.back();
-            todo.pop_back();
-            if (seen[it.node] == walkId) return false;
-            seen[it.node] = walkId;
-            const dcrt_bvh_node& nd = s.bvh_nodes[it.node];
-            if (nd.misc >= 4u) {   // a leaf
-                uint32_t d = it.depth;
-                if (tlas && (nd.misc & 4u)) {
-                    const uint32_t b = nd.right_child_or_prim_index;
-                    if (b >= n || b < s.tlas_node_count) return false;
-                    d += blasDepth[b];
-                }
-                *deepest = std::max(*deepest, d);
-                continue;
-            }
-            const uint32_t right = nd.right_child_or_prim_index;
-            if (it.node + 1 >= n || right <= it.node || right >= n) return false;
-            todo.push_back({ it.node + 1, it.depth + 1 });
-            todo.push_back({ right, it.depth + 1 });
-        }
-        return true;
-    };
-    // BLAS roots: the TLAS leaves' targets
-    for (uint32_t i = 0; i < std::min(s.tlas_node_count, n); ++i) {
-        const dcrt_bvh_node& nd = s.bvh_nodes[i];
-        if (!(nd.misc & 4u)) continue;
-        const uint32_t b = nd.right_child_or_prim_index;
-        if (b >= n || b < s.tlas_node_count) return false;
-        if (blasDepth[b] != UINT32_MAX) continue;
-        uint32_t d = 0;
-        if (!walk(b, false, &d)) return false;
-        blasDepth[b] = d;
-    }
-    return walk(0, true, out);
-}
+// What a launch of the cast needs
+struct CastLaunch {
+    CastFn kernel;
+    size_t lds;                        // dynamic LDS bytes
+    const DeviceScene& scene;
+    uint32_t resident;                 // persistent grid: resident workgroups on the whole chip
+};
 
-// The child-pair node order (dscene.h kLayoutPairs): an interior node's two children
-// adjacent, its `right` field the first child's device index, a TLAS leaf's the BLAS root's.
-// The levels nearest the roots come first -- the TLAS root and every BLAS root, breadth-first
-// until at least `topNodes` nodes are placed: what the LDS scene cache (a prefix) and the L2
-// hold -- then every subtree below them depth-first by child pairs. Each root gets a padded
-// slot, so every pair starts at an even index (one 64-B aligned line). Traversal follows the
-// tree, not the indices: hits, node counts and stack depths are those of the flat order.
-// quads (the default; DCRT_NODE_QUADS=0: off): below the top levels the children pairs of a node's two children
-// sit side by side in one 128-B aligned line (a padded half where a child is a leaf), so the
-// fetch that expands one child brings its sibling's children into L2 with it; otherwise a
-// node's left child's pair follows the node's own pair depth-first.
-// Call after RequiredTraversalStack (which checks every reference); false if a node would be
-// placed twice (a child shared between parents).
-bool PairLayout(const dcrt_flat_scene& s, uint32_t topNodes, std::vector<dcrt_bvh_node>* out, bool quads = false)
-{
-    constexpr uint32_t kNone = UINT32_MAX;
-    const dcrt_bvh_node* nd = s.bvh_nodes;
-    std::vector<uint32_t> pos(s.bvh_node_count, kNone);   // flat index -> device index
-    std::vector<uint32_t> order;                          // device index -> flat index (kNone: padding)
-    order.reserve((size_t)s.bvh_node_count + 64);
-    auto isLeaf = [&](uint32_t i) { return nd[i].misc >= 4u; };
-    auto place = [&](uint32_t i) {
-        if (pos[i] != kNone) return false;
-        pos[i] = (uint32_t)order.size();
-        order.push_back(i);
-        return true;
-    };
-    // an interior node's children, left then right, at the next (even) device index
-    auto placeChildren = [&](uint32_t p) { return place(p + 1) && place(nd[p].right_child_or_prim_index); };
-    std::vector<uint32_t> level, next, stack;
-    auto addRoot = [&](uint32_t r) {
-        if (pos[r] != kNone) return;   // a BLAS shared by several instances
-        place(r);
-        order.push_back(kNone);
-        if (!isLeaf(r)) level.push_back(r);
-    };
-    addRoot(0);
-    for (uint32_t i = 0; i < std::min(s.tlas_node_count, s.bvh_node_count); ++i)
-        if ((nd[i].misc & 4u) && nd[i].misc >= 4u) addRoot(nd[i].right_child_or_prim_index);
-    while (!level.empty() && order.size() < topNodes) {
-        next.clear();
-        for (const uint32_t p : level) {
-            if (!placeChildren(p)) return false;
-            if (!isLeaf(p + 1)) next.push_back(p + 1);
-            if (!isLeaf(nd[p].right_child_or_prim_index)) next.push_back(nd[p].right_child_or_prim_index);
-        }
-        level.swap(next);
-    }
-    for (const uint32_t root : level) {
-        stack.assign(1, root);
-        if (quads) {
-            // stack: nodes whose children are placed; expanding one places its children's pairs
-            if (!placeChildren(root)) return false;
-            while (!stack.empty()) {
-                const uint32_t p = stack.back();
-                stack.pop_back();
-                const uint32_t c0 = p + 1, c1 = nd[p].right_child_or_prim_index;
-                if (isLeaf(c0) && isLeaf(c1)) continue;
-                while (order.size() & 3u) order.push_back(kNone);   // one 128-B line
-                if (!isLeaf(c0) && !placeChildren(c0)) return false;
-                if (!isLeaf(c1) && !placeChildren(c1)) return false;
-                if (!isLeaf(c1)) stack.push_back(c1);
-                if (!isLeaf(c0)) stack.push_back(c0);   // the left subtree first
-            }
-            continue;
-        }
-        while (!stack.empty()) {
-            const uint32_t p = stack.back();
-            stack.pop_back();
-            if (!placeChildren(p)) return false;
-            if (!isLeaf(nd[p].right_child_or_prim_index)) stack.push_back(nd[p].right_child_or_prim_index);
-            if (!isLeaf(p + 1)) stack.push_back(p + 1);   // the left subtree's pairs first
-        }
-    }
-    out->assign(order.size(), dcrt_bvh_node{});
-    for (size_t k = 0; k < order.size(); ++k) {
-        if (order[k] == kNone) continue;
-        dcrt_bvh_node v = nd[order[k]];
-        if (v.misc < 4u) v.right_child_or_prim_index = pos[order[k] + 1];
-        else if (v.misc & 4u) v.right_child_or_prim_index = pos[v.right_child_or_prim_index];
-        (*out)[k] = v;
-    }
-    return true;
-}
+// How the uploaded scene is cast (PlanCast, SizeGrids): the one place that says which cast_kernel
+// variant runs, on which copy of the scene and with how much LDS.
+struct CastPlan {
+    uint32_t block = 256;              // workgroup size of every traversal kernel
+    uint32_t perCU = 0;                // resident workgroups per CU of the shipped kernel
+    bool allCached = false;            // the scene fits the LDS cache: cast_kernel's ALL_CACHED
+    bool pair = false;                 // trav_visit_pair: the scene outgrows an XCD's L2
+    bool ident = false;                // no instance space (every instance the identity: dscene.h IDENT)
+    bool flat = false;                 // the cache-only IDENT cast runs on the entry-free node order (EntryFreeLayout)
+    uint32_t ringRows = 0;             // the ring cast kernel's LDS stack window (0: whole stack in LDS)
+    // The point light's direction cells (shadow_cells.h) of a flat scene: the resolution asked for
+    // (0: off, or the leaf words did not fit the cast's LDS without costing occupancy).
+    // sceneFlat.shadowRes != 0 while a table stands (RebuildShadowCells).
+    uint32_t cellsRes = 0;
+    // a workgroup's dynamic LDS: the stack rows in front of the scene cache
+    size_t ldsWholeStack = 0;          // stackSize + 2 rows: every kernel but the ring and the flat cast
+    size_t ldsRing = 0;                // ringRows rows (ringRows != 0)
+    size_t ldsFlat = 0;                // stackSize + 3 rows, the entry-free nodes, the cells' leaf words
+    DeviceScene scene{};               // the uploaded scene (the PackBVH or the pair node order)
+    DeviceScene sceneRing{};           // ... as the ring cast kernel sees it (stackRows = ringRows, spill column)
+    DeviceScene sceneFlat{};           // ... as the flat cast kernel sees it (its nodes, one more stack row, the cells)
+    uint32_t resident[2][2] = {};      // [instr][opacity] persistent grids; [0][0]: the shipped kernel's
 
-// The entry-free node order of the cache-only IDENT kernel (cast_kernel<..., FLAT>; every instance's
-// inverse exactly the identity, single-triangle leaves). A TLAS leaf whose box is its BLAS root's bit
-// for bit is replaced by (a copy of) that root: the root's visit would repeat the leaf's box test with
-// the same world ray and tMax (IDENT), so skipping it changes no hit. Any other TLAS leaf becomes an interior node (misc 3:
-// its near child is taken by negMask bit 3, the front-to-back flag) whose children are an empty node
-// and a copy of its instance's BLAS; the BLAS triangle leaves carry instance + 1 in their count field.
-// The kernel then has no BLAS-entry step in its node visit: the TLAS leaf's box is tested as before,
-// the BLAS root is visited next (or after the empty node, which no ray hits: all its planes are +inf,
-// so its slab interval is empty or starts at +inf), and hits, their order and their tMax are the
-// reference's bit for bit -- the empty node adds a visit and a stack entry (the kernel's stack has
-// one row more), no triangle test. (The counting kernels keep PackBVH's order and their counts are
-// the reference's.) False if a leaf holds more than one triangle.
-bool EntryFreeLayout(const dcrt_flat_scene& s, std::vector<dcrt_bvh_node>* out, bool merge = true)
-{
-    const dcrt_bvh_node* nd = s.bvh_nodes;
-    const uint32_t n = s.bvh_node_count;
-    out->clear();
-    out->reserve((size_t)n + 2u * s.instance_count);
-    bool ok = true;
-    // (explicit stack: (node, instance + 1 or 0 in the TLAS, the slot whose `right` field takes it))
-    struct Item { uint32_t node, inst1, parent; };
-    std::vector<Item> todo{{0u, 0u, UINT32_MAX}};
-    while (!todo.empty() && ok) {
-        const Item it = todo.back();
-        todo.pop_back();
-        if (it.node >= n) { ok = false; break; }
-        const uint32_t idx = (uint32_t)out->size();
-        if (it.parent != UINT32_MAX) (*out)[it.parent].right_child_or_prim_index = idx;
-        dcrt_bvh_node v = nd[it.node];
-        if (it.inst1 == 0u && (v.misc & 0x4u)) {
-            const uint32_t inst = (v.misc >> 3) & DCRT_BVHNODE_MISC_MASK_PRIMITIVE_COUNT;
-            const uint32_t blas = v.right_child_or_prim_index;
-            if (merge && blas < n && inst + 1u <= DCRT_BVHNODE_MISC_MASK_PRIMITIVE_COUNT &&
-                std::memcmp(v.bbox_min, nd[blas].bbox_min, sizeof(v.bbox_min)) == 0 &&
-                std::memcmp(v.bbox_max, nd[blas].bbox_max, sizeof(v.bbox_max)) == 0) {
-                // the BLAS root's box is the TLAS leaf's bit for bit (an identity instance's bounds
-                // usually are): its visit would repeat the leaf's test with the same ray and tMax,
-                // so the root takes the leaf's place and the ray enters with no visit of its own
-                todo.push_back({blas, inst + 1u, it.parent});
-                continue;
-            }
-        }
-        if (it.inst1 == 0u && (v.misc & 0x4u)) {
-            // TLAS leaf -> interior node: left child the empty node, right child the BLAS copy
-            const uint32_t inst = (v.misc >> 3) & DCRT_BVHNODE_MISC_MASK_PRIMITIVE_COUNT;
-            if (inst + 1u > DCRT_BVHNODE_MISC_MASK_PRIMITIVE_COUNT) { ok = false; break; }
-            const uint32_t blas = v.right_child_or_prim_index;
-            v.misc = 3u;
-            out->push_back(v);
-            dcrt_bvh_node empty{};
-            const float inf = std::numeric_limits<float>::infinity();
-            empty.bbox_min[0] = empty.bbox_min[1] = empty.bbox_min[2] = inf;
-            empty.bbox_max[0] = empty.bbox_max[1] = empty.bbox_max[2] = inf;
-            empty.misc = 0u;
-            out->push_back(empty);
-            todo.push_back({blas, inst + 1u, idx});
-        } else if (v.misc >= 4u) {
-            // BLAS triangle leaf (a TLAS-level triangle leaf cannot exist)
-            if (it.inst1 == 0u || ((v.misc >> 3) & DCRT_BVHNODE_MISC_MASK_PRIMITIVE_COUNT) != 1u) { ok = false; break; }
-            v.misc = (v.misc & 0x7u) | (it.inst1 << 3);
-            out->push_back(v);
-        } else {
-            // interior: the left child (node + 1) right behind it, the right child after its subtree
-            out->push_back(v);
-            todo.push_back({v.right_child_or_prim_index, it.inst1, idx});
-            todo.push_back({it.node + 1u, it.inst1, UINT32_MAX});
-        }
-        if (out->size() > (size_t)n * 4u + 64u) { ok = false; break; }   // (a malformed tree: refuse)
+    // The cast of a frame with or without counters and ALLOW_ANYHIT_SHADER. The ring and the flat
+    // kernel are non-counting and opaque (the counting and any-hit kernels keep the whole stack
+    // and the plain scene); the cells go with the flat kernel while a table stands.
+    CastLaunch Launch(bool instr, bool opacity) const
+    {
+        const bool useFlat = flat && !instr && !opacity, useRing = ringRows != 0 && !instr && !opacity;
+        const CastVariant v{ instr, opacity, allCached, pair, ident, useRing, useFlat, useFlat && sceneFlat.shadowRes != 0u };
+        return { CastKernel(v), useFlat ? ldsFlat : useRing ? ldsRing : ldsWholeStack, useFlat ? sceneFlat : useRing ? sceneRing : scene,
+                 resident[instr][opacity] };
     }
-    return ok && !out->empty();
-}
+};
 
 }  // namespace
 
@@ -433,24 +367,20 @@ struct dcrt_tracer {
     int device = 0;
     hipStream_t stream = nullptr;
     bool ownsStream = false;
+    uint32_t cuCount = 1;              // compute units (the persistent grids' factor)
+    CreateKnobs knobs;
+    uint32_t iterationsPerRender = kDefaultIterations;
+    bool debugRng = false;
+    int mode = 0;                      // 0 wavefront (WavefrontPathTracer), 1 megakernel (MegakernelPathTracer)
+    // the "Output" view (dcrt_tracer_set_output): anything but PATH_TRACING renders first hits
+    dcrt_output_params output{ DCRT_OUTPUT_PATH_TRACING, 20u };
+
+    // ---- path pool ----
     uint32_t poolSize = 0;
     // CONTROL / MATERIAL grids (ResidentGrid): workgroups that loop over the pool's 256-slot
     // "virtual workgroups" vb = blockIdx.x + round * gridDim.x
     uint32_t controlGrid = 0, materialGrid = 0;
-    uint32_t materialLds = 0;          // MATERIAL's dynamic LDS: the scene copy's bytes (0: the global-memory variant)
-    uint32_t materialLdsMode = 0;      // material_kernel<CAPS, mode>: 0 no copy, 1 whole shading data, 2 all but the triangles
-    bool castIdent = false;            // cache-only cast kernel without instance space (every instance the identity: dscene.h IDENT)
-    uint32_t iterationsPerRender = kDefaultIterations;
-    bool debugRng = false;
-    // cast-kernel refill / park thresholds (persistent_trace): refill when 36 lanes are idle
-    // in the LDS-only kernel, 28 in the global-memory one (round 3 sweep with the adaptive
-    // park threshold); park at 24 (profiles/r01_tune_sweep.txt); DCRT_TRAVERSAL_TUNE=
-    // "refill,park" overrides both
-    uint32_t refillLanes = 36, parkLanes = 24;
-    bool tuneOverride = false;
-    uint64_t imagesCompleted = 0;                // since the last ResetStats (counters())
-
-    std::vector<void*> poolAllocs, sceneAllocs, filmAllocs, sampleAllocs, rowAllocs;
+    std::vector<void*> poolAllocs;
     PathPool pool{};                   // (queue pointers set per launch: LaunchIteration)
     float4* extRecs = nullptr;         // 2 parities x kShards x recCap extension-ray records (2 float4)
     PathStateA* stateRecsA = nullptr;  // 2 parities x kShards x recCap path state halves
@@ -458,36 +388,21 @@ struct dcrt_tracer {
     uint32_t* shadowHits = nullptr;    // 2 parities x kShards x recCap shadow results
     FinishRec* finRecs = nullptr;      // 2 parities x kFinShards x pool.finCap
     uint32_t* finHits = nullptr;       // 2 parities x kFinShards x pool.finCap
-    DeviceScene scene{};
+    FrameConstants* dFrame = nullptr;
+    Counters* dCounters = nullptr;     // [2]
+    Globals* dGlobals = nullptr;
+    Counters* hCounters = nullptr;     // pinned [2]
+    dcrt_bxdf_luts* dLuts = nullptr;
+
+    // ---- scene and cast plan ----
+    std::vector<void*> sceneAllocs;
     bool hasScene = false;
-    uint32_t castBlock = 256;
-    size_t castLds = 0;
-    size_t castLdsFull = 0;            // the layout of every kernel but the ring cast: stackSize + 2 rows + the cache
-    uint32_t ringRows = 0;             // the ring cast kernel's LDS stack window (0: whole stack in LDS)
-    DeviceScene sceneRing{};           // the scene as the ring cast kernel sees it (stackRows = ringRows, spill column)
-    bool castFlat = false;             // the cache-only IDENT cast runs on the entry-free node order (EntryFreeLayout)
-    DeviceScene sceneFlat{};           // the scene as that kernel sees it (its nodes, one more stack row)
-    size_t castLdsFlat = 0;
-    // The point light's direction cells (shadow_cells.h) of a castFlat scene: sceneFlat.shadowRes != 0
-    // while the table stands. cellsRes: the resolution asked for (0: off, or the leaf words did not
-    // fit the cast's LDS without costing occupancy); the device buffers hold any table of it; the
-    // host copies of the geometry rebuild it when the lights change (RebuildShadowCells).
-    uint32_t cellsRes = 0;
-    uint64_t* dCells = nullptr;
-    uint32_t* dCellLeaves = nullptr;
-    ShadowCells cells;
-    std::vector<dcrt_bvh_node> cellNodes;
-    std::vector<dcrt_vertex> cellVertices;
-    std::vector<uint32_t> cellTriangles;
-    std::vector<dcrt_float4x3> cellTransforms;
-    int RebuildShadowCells();
-    uint32_t castPerCU = 0;            // resident cast workgroups per CU
-    bool castAllCached = false;        // the scene fits the LDS cache: cast_kernel<., ., true, .>
-    bool castPair = false;             // trav_visit_pair: the scene outgrows an XCD's L2 (UploadScene)
-    bool mergedCasts = true;           // one cast_kernel per iteration (DCRT_SPLIT_CASTS=1: EXT then SHADOW)
-    bool virtualStart = true;          // virtual batch starts where the cast kernel has them (DCRT_VIRTUAL_START=0: off)
+    CastPlan plan;
+    dcrt_upload_stats uploadStats{};
     uint32_t sceneCaps = kCapAll;      // what the uploaded scene uses (kCap* of dscene.h)
     uint32_t materialCaps = kCapAll;   // the MATERIAL variant launched for it
+    uint32_t materialLds = 0;          // MATERIAL's dynamic LDS: the scene copy's bytes (0: the global-memory variant)
+    uint32_t materialLdsMode = 0;      // material_kernel<CAPS, mode>: 0 no copy, 1 whole shading data, 2 all but the triangles
     // The arrays the partial updates replace (UpdateMaterials / UpdateLights / UpdateInstanceFlags):
     // their device buffers, and host copies of the two that DeriveShading reads. The lights
     // buffer holds DCRT_MAX_LIGHT_COUNT entries, so a changed count never moves it.
@@ -496,54 +411,65 @@ struct dcrt_tracer {
     uint32_t* dInstanceFlags = nullptr;
     std::vector<dcrt_material> hostMaterials;
     std::vector<dcrt_light> hostLights;
-    uint32_t cuCount = 1;              // compute units (the persistent grids' factor)
-    dcrt_upload_stats uploadStats{};
+    // The direction cells of a plan.cellsRes scene: the device buffers hold any table of that
+    // resolution; the host copies of the geometry rebuild it when the lights change (RebuildShadowCells).
+    uint64_t* dCells = nullptr;
+    uint32_t* dCellLeaves = nullptr;
+    ShadowCells cells;
+    std::vector<dcrt_bvh_node> cellNodes;
+    std::vector<dcrt_vertex> cellVertices;
+    std::vector<uint32_t> cellTriangles;
+    std::vector<dcrt_float4x3> cellTransforms;
+    uint32_t megaResident = 0;         // persistent megakernel grid
+    uint32_t viewResident = 0;         // persistent view_kernel grid
+    uint32_t viewResidentOpacity = 0;  // the same for the ALLOW_ANYHIT_SHADER variant
+    uint32_t drainResident = 0;        // drain_kernel grid (resident workgroups)
 
-    dcrt_bxdf_luts* dLuts = nullptr;
+    // ---- film, its rows and the sample textures ----
+    std::vector<void*> filmAllocs, sampleAllocs, rowAllocs;
     Film film{};
     uint32_t filmW = 0, filmH = 0;
     uint32_t rowCount = 0;             // rows this tracer path-traces (film.rowY)
     uint32_t bandCount = 0;            // ceil(rowCount / 8): block rows of an image
+    dcrt_film_partition partition{ 1, 0, 64, 0 };
+    std::vector<uint32_t> bands;       // explicit film bands [y0, y1) pairs (dcrt_tracer_set_film_bands), or empty
     uint32_t sampleImages = 0;         // images the sample textures hold (batch capacity)
     uint32_t batchImages = 0;          // RenderImages batch size (0: automatic)
     uint32_t lastSlot = 0;             // sample slot of the last completed image
     uint32_t seedStride = 1;           // RenderImages: image k has frame seed first + k * seedStride
     bool keptSlots = false;            // the last RenderImages left image k's samples in slot k (no film pass)
     uint32_t keptImages = 0;
-    void** dSourceLists = nullptr;     // accumulate_images: device copies of the caller's pointer lists
-    uint32_t sourceCap = 0;
-    dcrt_film_partition partition{ 1, 0, 64, 0 };
-    std::vector<uint32_t> bands;       // explicit film bands [y0, y1) pairs (dcrt_tracer_set_film_bands), or empty
-
-    dcrt_frame_params frame{};
-    bool hasFrame = false;
-    FrameConstants* dFrame = nullptr;
-    Counters* dCounters = nullptr;     // [2]
-    Globals* dGlobals = nullptr;
     SampleOut* dSampleOut = nullptr;   // MATERIAL's copy of the sample pointers (EnsureSamples)
     SampleOut hSampleOut = {};
-    unsigned long long* dInstr = nullptr;   // [8]
-    Counters* hCounters = nullptr;     // pinned [2]
-
-    bool newImage = true;
-    bool capturing = false;            // LaunchIteration is being captured into a graph (no host annotations)
-    bool imageComplete = false;
+    void** dSourceLists = nullptr;     // accumulate_images: device copies of the caller's pointer lists
+    uint32_t sourceCap = 0;
+    FilterConsts* dFilter = nullptr;
+    FilterConsts* hFilter = nullptr;   // pinned staging
+    dcrt_filter_params lastFilter{};   // the reconstruction filter on the device (UploadFilter)
+    bool hasFilter = false;
+    uint32_t filmImages = 0;           // images convolved into the film since the last clear
     bool filmClearTrigger = false;
-    uint32_t parity = 0;
 
-    // graphs of `iters` iterations (even), rebuilt when launch parameters change;
-    // [0] = plain iterations (Render), [1] = with the guarded film pass and image
-    // advance (RenderImages)
+    // ---- the image in flight and the captured graphs ----
+    dcrt_frame_params frame{};
+    bool hasFrame = false;
+    bool newImage = true;
+    bool imageComplete = false;
+    uint32_t parity = 0;
+    uint64_t imagesCompleted = 0;      // since the last ResetStats (counters())
+    bool capturing = false;            // LaunchIteration is being captured into a graph (no host annotations)
+    // graphs of `iters` iterations (even), rebuilt when launch parameters change
     struct GraphCache {
         hipGraphExec_t exec = nullptr;
         uint32_t iters = 0;
     } graphs[3];   // unsequenced (Render), sequenced (RenderImages), sequenced tail chunks
-    FilterConsts* dFilter = nullptr;
-    FilterConsts* hFilter = nullptr;   // pinned staging
     uint32_t* hStop = nullptr;         // pinned [4][2]: Globals::stopped, imagesDone per poll
     hipEvent_t stopEvents[4] = {};
+
+    // ---- instrumentation ----
     bool instrCounters = false;
     bool extTiming = false;
+    unsigned long long* dInstr = nullptr;   // [8]
     bool rowProbe = false;             // the row-cost probe: MATERIAL's PROBE variant counts rays per film row
     uint32_t* dRowRays = nullptr;      // [filmH] (rowAllocs: follows the film)
     // timed launches (ext_timing): start / stop event pairs and the kernel each pair timed
@@ -553,6 +479,107 @@ struct dcrt_tracer {
     size_t eventsUsed = 0;
     double kindMs[kTimedKinds] = {};
     uint64_t kindLaunches[kTimedKinds] = {};
+
+    // ---- the film denoiser (dcrt_tracer_render_guides / dcrt_tracer_denoise*): two guide films and the
+    // denoised image follow the film (filmAllocs); the working images follow the denoised size ----
+    float4* guideNormal = nullptr;
+    float4* guideAlbedo = nullptr;
+    float4* denoised = nullptr;
+    bool guidesRendered = false, hasDenoised = false;
+    std::vector<void*> denoiseAllocs;
+    float4* dnWork[2] = { nullptr, nullptr };   // (c.rgb, var), ping-pong
+    float4* dnNormal = nullptr;        // decoded guides (n.xyz, 0), (a.xyz, 0)
+    float4* dnAlbedo = nullptr;
+    uint32_t dnW = 0, dnH = 0;
+    std::vector<hipEvent_t> dnEvents;  // ext_timing: one event per kernel boundary of the last denoise
+    uint32_t dnEventsUsed = 0;
+
+    // ---- the film noise estimate (dcrt_tracer_set_convergence / dcrt_tracer_noise*): the half film takes
+    // every other image of the film's (even film image counts); the kernels' working buffers grow
+    // with the tile count; the maps of the last dcrt_tracer_noise follow the film ----
+    bool convergence = false;
+    float4* halfFilm = nullptr;
+    std::vector<void*> halfAllocs, noiseAllocs, noiseMapAllocs;
+    uint32_t noiseTileCap = 0;
+    float *nzSum = nullptr, *nzScratch[2] = { nullptr, nullptr }, *nzMax = nullptr, *nzErr = nullptr;
+    uint32_t* nzCounts = nullptr;
+    NoiseTotals* nzTotals = nullptr;
+    float *noisePixelMap = nullptr, *noiseTileMap = nullptr;
+    bool hasNoiseMaps = false;
+
+    ~dcrt_tracer();
+    int Create(const dcrt_tracer_config& cfg);
+    int BuildLuts();
+    // scene
+    int UploadScene(const dcrt_flat_scene& s);
+    int UploadArrays(const dcrt_flat_scene& s, std::vector<uint32_t>* identity);
+    int PlanCast(const dcrt_flat_scene& s, const UploadKnobs& k, const std::vector<uint32_t>& identity);
+    int PlanFlatCast(const dcrt_flat_scene& s, const UploadKnobs& k);
+    int SizeGrids(const UploadKnobs& k);
+    int CastOccupancy(CastFn k, size_t lds, int* out);
+    void DeriveShading();
+    int DeriveDrainGrid();
+    int RederiveShading();
+    int UpdateMaterials(const dcrt_material* materials, uint32_t count);
+    int UpdateLights(const dcrt_light* lights, uint32_t count);
+    int UpdateInstanceFlags(const uint32_t* flags, uint32_t count);
+    int RebuildShadowCells();
+    int CheckFrameLights() const;
+    // film
+    int SetFrame(const dcrt_frame_params& p);
+    int SetPartition(const dcrt_film_partition& p);
+    int SetBands(const uint32_t* b, uint32_t count, uint32_t halo);
+    int EnsureFilm(uint32_t w, uint32_t h);
+    int BuildRows();
+    int UploadSampleOut();
+    int SetRowProbe(bool on);
+    int EnsureSamples(uint32_t images);
+    int UploadFilter(const dcrt_filter_params& f);
+    int ClearFilm();
+    int LaunchFilm(uint32_t images, const Globals* guard, const float2* const* posList, const float4* const* valList,
+                   uint32_t firstIndex);
+    int AccumulateImages(const void* const* pos, const void* const* val, uint32_t count, const dcrt_filter_params& filter);
+    int Accumulate(const dcrt_filter_params& filter);
+    // rendering
+    uint32_t AutoBatch(uint32_t count) const;
+    int BeginImage();
+    int LaunchIteration(uint32_t par, bool timed, bool sequenced);
+    int LaunchGraph(bool sequenced, uint32_t iters);
+    int BuildGraph(bool sequenced, uint32_t iters);
+    int PrepareImages(uint32_t count);
+    int RunIterations(uint32_t n);
+    int ReadCompletion(bool* complete);
+    int Render(uint32_t maxIterations);
+    int LaunchView();
+    int LaunchView(uint32_t type, const Film& target);
+    int RenderImages(uint32_t firstSeed, uint32_t count, const dcrt_filter_params& filter, uint32_t stride = 1,
+                     bool convolve = true);
+    // denoiser, noise estimate
+    int EnsureGuides();
+    int RenderGuides(uint32_t firstSeed, uint32_t count);
+    int EnsureDenoiseWork(uint32_t w, uint32_t h);
+    int Denoise(const dcrt_denoise_params& p, uint32_t w, uint32_t h, const float4* color, const float4* normal,
+                const float4* albedo, float4* out);
+    int SetConvergence(bool on);
+    int Noise(uint32_t w, uint32_t h, const float4* f, const float4* hf, float threshold, float* pixelMap, float* tileMap,
+              dcrt_noise_stats* out);
+    int NoiseOwn(float threshold, dcrt_noise_stats* out);
+    int RenderConverged(uint32_t firstSeed, const dcrt_converge_params& p, const dcrt_filter_params& filter, dcrt_noise_stats* outStats,
+                        int* outConverged);
+
+    // One device array of the scene: allocated (sceneAllocs), filled from `src` and counted in `*counted`
+    template <typename T>
+    int Upload(T** dst, const T* src, size_t count, uint64_t* counted, size_t capacity = 0)
+    {
+        T* p = nullptr;
+        CHECKED(DeviceAlloc(&p, std::max(count, capacity), &sceneAllocs));
+        if (count && src) {
+            HIPCHECK(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, stream));
+            *counted += count * sizeof(T);
+        }
+        *dst = p;
+        return DCRT_OK;
+    }
     int TimedPair(TimedKind kind, hipEvent_t* e0, hipEvent_t* e1)
     {
         while (events.size() < eventsUsed + 2) {
@@ -577,42 +604,6 @@ struct dcrt_tracer {
         eventsUsed = 0;
         return DCRT_OK;
     }
-
-    ~dcrt_tracer();
-    int Create(const dcrt_tracer_config& cfg);
-    int BuildLuts();
-    int UploadScene(const dcrt_flat_scene& s);
-    void DeriveShading();
-    int DeriveDrainGrid();
-    int RederiveShading();
-    int UpdateMaterials(const dcrt_material* materials, uint32_t count);
-    int UpdateLights(const dcrt_light* lights, uint32_t count);
-    int UpdateInstanceFlags(const uint32_t* flags, uint32_t count);
-    int CheckFrameLights() const;
-    int SetFrame(const dcrt_frame_params& p);
-    int SetPartition(const dcrt_film_partition& p);
-    int SetBands(const uint32_t* b, uint32_t count, uint32_t halo);
-    int EnsureFilm(uint32_t w, uint32_t h);
-    int BuildRows();
-    int UploadSampleOut();
-    int SetRowProbe(bool on);
-    int EnsureSamples(uint32_t images);
-    uint32_t AutoBatch(uint32_t count) const;
-    int BeginImage();
-    int LaunchIteration(uint32_t par, bool timed, bool sequenced);
-    int LaunchGraph(bool sequenced, uint32_t iters);
-    int BuildGraph(bool sequenced, uint32_t iters);
-    int PrepareImages(uint32_t count);
-    int RunIterations(uint32_t n);
-    int UploadFilter(const dcrt_filter_params& f);
-    int ReadCompletion(bool* complete);
-    int Render(uint32_t maxIterations);
-    int LaunchView();
-    int LaunchView(uint32_t type, const Film& target);
-    int RenderImages(uint32_t firstSeed, uint32_t count, const dcrt_filter_params& filter, uint32_t stride = 1,
-                     bool convolve = true);
-    int AccumulateImages(const void* const* pos, const void* const* val, uint32_t count, const dcrt_filter_params& filter);
-    int Accumulate(const dcrt_filter_params& filter);
     void InvalidateGraph()
     {
         for (const GraphCache& g : graphs)
@@ -628,66 +619,6 @@ struct dcrt_tracer {
     {
         const uint32_t T = (uint32_t)kFilmTile;
         return std::max<uint32_t>(1u, std::min<uint32_t>(((filmW + T - 1) / T) * ((filmH + T - 1) / T), 8u * kMaxPersistentBlocks * (256u / kFilmThreads)));
-    }
-    uint32_t castResident = 0;         // persistent cast grid: resident workgroups on the whole chip
-    uint32_t castResidentOpacity = 0;  // the same for the ALLOW_ANYHIT_SHADER variant
-    uint32_t megaResident = 0;         // persistent megakernel grid
-    uint32_t viewResident = 0;         // persistent view_kernel grid
-    uint32_t viewResidentOpacity = 0;  // the same for the ALLOW_ANYHIT_SHADER variant
-    // the "Output" view (dcrt_tracer_set_output): anything but PATH_TRACING renders first hits
-    dcrt_output_params output{ DCRT_OUTPUT_PATH_TRACING, 20u };
-    // the film denoiser (dcrt_tracer_render_guides / dcrt_tracer_denoise*): two guide films and the
-    // denoised image follow the film (filmAllocs); the working images follow the denoised size
-    float4* guideNormal = nullptr;
-    float4* guideAlbedo = nullptr;
-    float4* denoised = nullptr;
-    bool guidesRendered = false, hasDenoised = false;
-    dcrt_filter_params lastFilter{};   // the reconstruction filter on the device (UploadFilter)
-    bool hasFilter = false;
-    std::vector<void*> denoiseAllocs;
-    float4* dnWork[2] = { nullptr, nullptr };   // (c.rgb, var), ping-pong
-    float4* dnNormal = nullptr;        // decoded guides (n.xyz, 0), (a.xyz, 0)
-    float4* dnAlbedo = nullptr;
-    uint32_t dnW = 0, dnH = 0;
-    std::vector<hipEvent_t> dnEvents;  // ext_timing: one event per kernel boundary of the last denoise
-    uint32_t dnEventsUsed = 0;
-    int EnsureGuides();
-    int RenderGuides(uint32_t firstSeed, uint32_t count);
-    int EnsureDenoiseWork(uint32_t w, uint32_t h);
-    int Denoise(const dcrt_denoise_params& p, uint32_t w, uint32_t h, const float4* color, const float4* normal,
-                const float4* albedo, float4* out);
-    // the film noise estimate (dcrt_tracer_set_convergence / dcrt_tracer_noise*): the half film takes
-    // every other image of the film's (even film image counts); the kernels' working buffers grow
-    // with the tile count; the maps of the last dcrt_tracer_noise follow the film
-    bool convergence = false;
-    float4* halfFilm = nullptr;
-    std::vector<void*> halfAllocs, noiseAllocs, noiseMapAllocs;
-    uint32_t filmImages = 0;           // images convolved into the film since the last clear
-    uint32_t noiseTileCap = 0;
-    float *nzSum = nullptr, *nzScratch[2] = { nullptr, nullptr }, *nzMax = nullptr, *nzErr = nullptr;
-    uint32_t* nzCounts = nullptr;
-    NoiseTotals* nzTotals = nullptr;
-    float *noisePixelMap = nullptr, *noiseTileMap = nullptr;
-    bool hasNoiseMaps = false;
-    int SetConvergence(bool on);
-    int ClearFilm();
-    int LaunchFilm(uint32_t images, const Globals* guard, const float2* const* posList, const float4* const* valList,
-                   uint32_t firstIndex);
-    int Noise(uint32_t w, uint32_t h, const float4* f, const float4* hf, float threshold, float* pixelMap, float* tileMap,
-              dcrt_noise_stats* out);
-    int NoiseOwn(float threshold, dcrt_noise_stats* out);
-    int RenderConverged(uint32_t firstSeed, const dcrt_converge_params& p, const dcrt_filter_params& filter, dcrt_noise_stats* outStats,
-                        int* outConverged);
-    uint32_t drainResident = 0;       // drain_kernel grid (resident workgroups)
-    uint32_t drainPaths = 0;           // drain_kernel threshold (DCRT_DRAIN_PATHS; 0: no drain launches -- the default: profiles/r04_ab_virtual_drain.txt)
-    int mode = 0;                      // 0 wavefront (WavefrontPathTracer), 1 megakernel (MegakernelPathTracer)
-    uint32_t castResidentInstr = 0;    // the same for the counting kernels (whole stack: castLdsFull)
-    uint32_t castResidentInstrOpacity = 0;
-    uint32_t CastGrid(uint32_t block, bool opacity) const
-    {
-        const uint32_t resident = instrCounters ? (opacity ? castResidentInstrOpacity : castResidentInstr)
-                                                : (opacity ? castResidentOpacity : castResident);
-        return std::min<uint32_t>((poolSize + block - 1) / block, resident);
     }
 };
 
@@ -738,17 +669,7 @@ int dcrt_tracer::Create(const dcrt_tracer_config& cfg)
     poolSize = (poolSize + kControlBlock - 1) / kControlBlock * kControlBlock;
     iterationsPerRender = cfg.iterations_per_render ? cfg.iterations_per_render : kDefaultIterations;
     debugRng = cfg.debug_rng != 0;
-    if (const char* split = std::getenv("DCRT_SPLIT_CASTS")) mergedCasts = std::atoi(split) == 0;
-    if (const char* vs = std::getenv("DCRT_VIRTUAL_START")) virtualStart = std::atoi(vs) != 0;
-    if (const char* dp = std::getenv("DCRT_DRAIN_PATHS")) drainPaths = (uint32_t)std::max(0, std::atoi(dp));
-    if (const char* tune = std::getenv("DCRT_TRAVERSAL_TUNE")) {
-        unsigned r = 0, p = 0;
-        if (std::sscanf(tune, "%u,%u", &r, &p) == 2 && r >= 1 && r <= 64 && p >= 1 && p <= 64) {
-            refillLanes = r;
-            parkLanes = p;
-            tuneOverride = true;
-        }
-    }
+    knobs = ReadCreateKnobs();
     // pool arrays are addressed through 32-bit byte offsets (slot(): at most 16 B per slot), and
     // one parity's extension-ray records and path-state halves (ext_rec(), state_at(): 32 B at
     // position q = shard * recCap + entry) as well; this check bounds the pool at 2^26 slots,
@@ -772,28 +693,22 @@ int dcrt_tracer::Create(const dcrt_tracer_config& cfg)
         // pool cost the dispatch of P / 256 workgroups (2^26 slots: 262144 workgroups,
         // CONTROL 91 us and MATERIAL 57 us with nothing to do). The grids hold what is
         // resident instead, a multiple of kShards (= kFinShards), so a workgroup's virtual
-        // workgroups all belong to its own shard: vb mod kShards = blockIdx.x mod kShards.
-        // DCRT_CONTROL_GRID / DCRT_MATERIAL_GRID = k: k x resident; 0: one workgroup per virtual
-        // workgroup (A/B overrides).
+        // workgroups all belong to its own shard: vb mod kShards = blockIdx.x mod kShards
+        // (knobs.controlGridMul / materialGridMul x resident; 0: one workgroup per virtual workgroup).
         hipDeviceProp_t prop;
         HIPCHECK(hipGetDeviceProperties(&prop, device));
         if (prop.maxSharedMemoryPerMultiProcessor > 0) g_ldsPerCU = prop.maxSharedMemoryPerMultiProcessor;
         int cPerCU = 0, mPerCU = 0;
         HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&cPerCU, control_kernel, (int)kControlBlock, 0));
         HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&mPerCU, material_kernel<kCapAll, 0>, (int)kMaterialBlock, 0));
-        auto resident = [&](int perCU, const char* knob, uint32_t mul) {
-            if (const char* g = std::getenv(knob)) mul = (uint32_t)std::max(0, std::atoi(g));
+        auto resident = [&](int perCU, uint32_t mul) {
             if (mul == 0) return V;
             const uint64_t r = (uint64_t)std::max(1, perCU) * (uint64_t)std::max(1, prop.multiProcessorCount) * mul;
             const uint32_t g = (uint32_t)std::max<uint64_t>(kShards, r / kShards * kShards);
             return std::min(g, V);   // (= V: one round, any V)
         };
-        // 2x / 4x resident (two A/B passes of the default bench on cornell / spaceship / coffee,
-        // ms/spp: one workgroup per virtual workgroup 2.40 / 2.84 / 2.96; 1x / 1x 2.28-2.38 /
-        // 2.63 / 3.02; 1x / 4x 2.37 / 2.58 / 2.95; 2x / 4x 2.35-2.38 / 2.54 / 2.92; 4x / 4x
-        // 2.37 / 2.55 / 2.95; 2x / 8x 2.37-2.39 / 2.55 / 2.92)
-        controlGrid = resident(cPerCU, "DCRT_CONTROL_GRID", 2);
-        materialGrid = resident(mPerCU, "DCRT_MATERIAL_GRID", 4);
+        controlGrid = resident(cPerCU, knobs.controlGridMul);
+        materialGrid = resident(mPerCU, knobs.materialGridMul);
         static_assert(kFinShards == kShards, "MATERIAL's grid is a multiple of both shard counts");
     }
     // The extension queue's shard s receives the new paths of CONTROL's virtual workgroups
@@ -898,6 +813,8 @@ static int ValidateInstanceFlags(const uint32_t* flags, uint32_t count)
 // partial updates both come here.
 void dcrt_tracer::DeriveShading()
 {
+    const ShadingKnobs k = ReadShadingKnobs();
+    const DeviceScene& scene = plan.scene;
     const uint32_t materialCount = (uint32_t)hostMaterials.size(), lightCount = (uint32_t)hostLights.size();
     // MATERIAL variant: the smallest compiled one whose capabilities cover the scene
     sceneCaps = scene.envCube ? kCapEnvCube : 0u;
@@ -909,23 +826,16 @@ void dcrt_tracer::DeriveShading()
     }
     for (const dcrt_light& l : hostLights) sceneCaps |= (l.flags & 0xFu) << kCapLightShift;
     materialCaps = (sceneCaps & ~kCapOpaqueDelta) == 0u ? kCapOpaqueDelta : kCapAll;
-    if (const char* g = std::getenv("DCRT_MATERIAL_GENERIC")) {   // A/B: always the generic variant
-        if (std::atoi(g)) materialCaps = kCapAll;
-    }
+    if (k.materialGeneric) materialCaps = kCapAll;
     // MATERIAL's LDS scene copy (material_kernel<CAPS, mode>): the whole shading data of a small
-    // scene (mode 1), else everything but the triangles (mode 2) -- DCRT_MATERIAL_LDS = bytes
-    // budget, 0: off; DCRT_MATERIAL_LDS_PARTIAL=0: no mode 2
-    uint32_t budget = 16384;
-    if (const char* e = std::getenv("DCRT_MATERIAL_LDS")) budget = (uint32_t)std::max(0, std::atoi(e));
-    bool partial = true;
-    if (const char* e = std::getenv("DCRT_MATERIAL_LDS_PARTIAL")) partial = std::atoi(e) != 0;
+    // scene (mode 1), else everything but the triangles (mode 2)
     const bool counts = scene.triangleCount > 0 && scene.triangleCount < (1u << 20) && scene.instanceCount < (1u << 20) &&
                         materialCount < (1u << 20) && lightCount < (1u << 20);
     const uint64_t whole = material_lds_bytes(scene.triangleCount, scene.instanceCount, materialCount, lightCount);
     const uint64_t rest = material_lds_bytes(0u, scene.instanceCount, materialCount, lightCount);
-    materialLdsMode = !counts ? 0u : whole <= budget ? 1u : (partial && rest <= budget ? 2u : 0u);
+    materialLdsMode = !counts ? 0u : whole <= k.materialLds ? 1u : (k.materialLdsPartial && rest <= k.materialLds ? 2u : 0u);
     materialLds = materialLdsMode == 1 ? (uint32_t)whole : materialLdsMode == 2 ? (uint32_t)rest : 0u;
-    for (DeviceScene* d : { &scene, &sceneFlat, &sceneRing }) {   // (the two variants' copies: unused ones are rewritten with the next upload)
+    for (DeviceScene* d : { &plan.scene, &plan.sceneFlat, &plan.sceneRing }) {   // (the two variants' copies: unused ones are rewritten with the next upload)
         d->ldsMaterials = materialLdsMode ? materialCount : 0u;
         d->ldsLights = materialLdsMode ? lightCount : 0u;
     }
@@ -937,8 +847,8 @@ int dcrt_tracer::DeriveDrainGrid()
     const void* fn = materialCaps == kCapOpaqueDelta ? (const void*)drain_kernel<kCapOpaqueDelta> : (const void*)drain_kernel<kCapAll>;
     int drainPerCU = 0;
     HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&drainPerCU, materialCaps == kCapOpaqueDelta ? drain_kernel<kCapOpaqueDelta> : drain_kernel<kCapAll>,
-                                                          (int)castBlock, castLdsFull));
-    drainResident = (uint32_t)std::max(1, std::min(drainPerCU, LdsResident(castLdsFull, fn))) * cuCount;
+                                                          (int)plan.block, plan.ldsWholeStack));
+    drainResident = (uint32_t)std::max(1, std::min(drainPerCU, LdsResident(plan.ldsWholeStack, fn))) * cuCount;
     return DCRT_OK;
 }
 
@@ -948,11 +858,11 @@ int dcrt_tracer::DeriveDrainGrid()
 int dcrt_tracer::RederiveShading()
 {
     const uint32_t caps = materialCaps, mode = materialLdsMode, lds = materialLds, grid = drainResident;
-    const uint32_t ldsM = scene.ldsMaterials, ldsL = scene.ldsLights;
+    const uint32_t ldsM = plan.scene.ldsMaterials, ldsL = plan.scene.ldsLights;
     DeriveShading();
     if (materialCaps != caps) CHECKED(DeriveDrainGrid());
     if (materialCaps != caps || materialLdsMode != mode || materialLds != lds || drainResident != grid ||
-        scene.ldsMaterials != ldsM || scene.ldsLights != ldsL) {
+        plan.scene.ldsMaterials != ldsM || plan.scene.ldsLights != ldsL) {
         HIPCHECK(hipStreamSynchronize(stream));
         InvalidateGraph();
     }
@@ -998,7 +908,7 @@ int dcrt_tracer::UpdateInstanceFlags(const uint32_t* flags, uint32_t count)
     Annotation an("UpdateInstanceFlags");
     if (!hasScene) { SetLastError("no scene uploaded"); return DCRT_E_NO_SCENE; }
     CHECKED(ValidateInstanceFlags(flags, count));
-    if (count != scene.instanceCount) { SetLastError("instance count differs from the uploaded scene's"); return DCRT_E_INVALID_ARG; }
+    if (count != plan.scene.instanceCount) { SetLastError("instance count differs from the uploaded scene's"); return DCRT_E_INVALID_ARG; }
     // nothing is derived from the flags; the copy is done on return (the caller's array is free)
     HIPCHECK(hipMemcpyAsync(dInstanceFlags, flags, (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     HIPCHECK(hipStreamSynchronize(stream));
@@ -1014,7 +924,8 @@ int dcrt_tracer::UpdateInstanceFlags(const uint32_t* flags, uint32_t count)
 // DeviceScene, so the captured graphs are dropped.
 int dcrt_tracer::RebuildShadowCells()
 {
-    if (!castFlat || !cellsRes) return DCRT_OK;
+    if (!plan.flat || !plan.cellsRes) return DCRT_OK;
+    DeviceScene& sceneFlat = plan.sceneFlat;
     dcrt_flat_scene s{};
     s.vertices = cellVertices.data();
     s.vertex_count = (uint32_t)cellVertices.size();
@@ -1024,7 +935,7 @@ int dcrt_tracer::RebuildShadowCells()
     s.instance_count = (uint32_t)(cellTransforms.size() / 2);
     s.lights = hostLights.data();
     s.light_count = (uint32_t)hostLights.size();
-    dcrt::BuildShadowCells(cellNodes.data(), cellNodes.size(), s, cellsRes, &cells);
+    dcrt::BuildShadowCells(cellNodes.data(), cellNodes.size(), s, plan.cellsRes, &cells);
     const uint32_t before = sceneFlat.shadowRes;
     HIPCHECK(hipStreamSynchronize(stream));
     if (cells.resolution) {
@@ -1053,6 +964,22 @@ int dcrt_tracer::CheckFrameLights() const
 int dcrt_tracer::UploadScene(const dcrt_flat_scene& s)
 {
     Annotation an("UploadScene");
+    const UploadKnobs k = ReadUploadKnobs();   // (per upload: tests set the variables between uploads)
+    std::vector<uint32_t> identity;
+    CHECKED(UploadArrays(s, &identity));
+    CHECKED(PlanCast(s, k, identity));
+    CHECKED(SizeGrids(k));
+    CHECKED(RebuildShadowCells());
+    HIPCHECK(hipStreamSynchronize(stream));
+    hasScene = true;
+    newImage = true;
+    return DCRT_OK;
+}
+
+// UploadScene's first job: the flat scene checked, the last one's buffers freed, every array but
+// the BVH nodes on the device and plan.scene pointing at them. `identity`: IdentityInstances(s).
+int dcrt_tracer::UploadArrays(const dcrt_flat_scene& s, std::vector<uint32_t>* identity)
+{
     if (!s.vertices || !s.triangles || !s.bvh_nodes || !s.material_ids || !s.instance_transforms ||
         !s.instance_light_indices || !s.instance_material_overrides || s.triangle_count == 0 ||
         s.bvh_node_count == 0 || s.instance_count == 0 || ValidateMaterials(s.materials, s.material_count) != DCRT_OK ||
@@ -1067,29 +994,19 @@ int dcrt_tracer::UploadScene(const dcrt_flat_scene& s)
     hasScene = false;
     ++uploadStats.scene_uploads;
     DeviceScene d{};
-    uint64_t* uploaded = &uploadStats.geometry_bytes;   // (shading_bytes around the three arrays an edit replaces)
-    auto upload = [&](auto** dst, const auto* src, size_t count, size_t capacity = 0) -> int {
-        using T = std::remove_const_t<std::remove_pointer_t<decltype(src)>>;
-        T* p = nullptr;
-        CHECKED(DeviceAlloc(&p, std::max(count, capacity), &sceneAllocs));
-        if (count && src) {
-            HIPCHECK(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, stream));
-            *uploaded += count * sizeof(T);
-        }
-        *dst = p;
-        return DCRT_OK;
-    };
+    // (shading_bytes: the three arrays an edit replaces)
+    uint64_t* const geometry = &uploadStats.geometry_bytes;
+    uint64_t* const shading = &uploadStats.shading_bytes;
     dcrt_vertex* vtx = nullptr;
     uint32_t* tris = nullptr;
-    dcrt_bvh_node* nodes = nullptr;
     dcrt_float4x3* xf = nullptr;
-    CHECKED(upload(&vtx, s.vertices, s.vertex_count));
-    CHECKED(upload(&tris, s.triangles, (size_t)s.triangle_count * 3));
+    CHECKED(Upload(&vtx, s.vertices, s.vertex_count, geometry));
+    CHECKED(Upload(&tris, s.triangles, (size_t)s.triangle_count * 3, geometry));
     // the traversal pushes without a bound check: refuse a stack size below what the
     // uploaded tree needs (TLAS leaf depth + BLAS depth, Scene.cpp:199-207); the walk also
     // checks every node reference
     uint32_t stackNeed = 0;
-    if (!RequiredTraversalStack(s, &stackNeed)) { SetLastError("malformed BVH node references"); return DCRT_E_INVALID_ARG; }
+    if (!dcrt::RequiredTraversalStack(s, &stackNeed)) { SetLastError("malformed BVH node references"); return DCRT_E_INVALID_ARG; }
     if (s.bvh_traversal_stack_size < stackNeed) {
         SetLastError("bvh_traversal_stack_size " + std::to_string(s.bvh_traversal_stack_size) +
                      " is below the uploaded BVH's depth " + std::to_string(stackNeed));
@@ -1097,32 +1014,18 @@ int dcrt_tracer::UploadScene(const dcrt_flat_scene& s)
     }
     uint32_t* mids = nullptr; uint32_t* lidx = nullptr; uint32_t* iflags = nullptr; uint32_t* ovr = nullptr;
     dcrt_material* mats = nullptr; dcrt_light* lights = nullptr;
-    CHECKED(upload(&mids, s.material_ids, s.triangle_count));
-    CHECKED(upload(&xf, s.instance_transforms, (size_t)s.instance_count * 2));
-    CHECKED(upload(&lidx, s.instance_light_indices, s.instance_count));
-    uploaded = &uploadStats.shading_bytes;
-    CHECKED(upload(&iflags, s.instance_flags, s.instance_count));
-    uploaded = &uploadStats.geometry_bytes;
-    CHECKED(upload(&ovr, s.instance_material_overrides, s.instance_count));
-    // instances whose world->instance matrix is exactly the identity (every OBJ shape):
-    // traversal then reuses the world ray instead of transforming it (bit-identical
-    // when no ray component is zero, which the kernel checks per ray)
-    std::vector<uint32_t> identity(s.instance_count, 0u);
-    for (uint32_t i = 0; i < s.instance_count; ++i) {
-        const float* m = s.instance_transforms[s.instance_count + i].m;
-        bool id = true;
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 4; ++c) id = id && m[r * 4 + c] == (r == c ? 1.0f : 0.0f);
-        identity[i] = id ? 1u : 0u;
-    }
+    CHECKED(Upload(&mids, s.material_ids, s.triangle_count, geometry));
+    CHECKED(Upload(&xf, s.instance_transforms, (size_t)s.instance_count * 2, geometry));
+    CHECKED(Upload(&lidx, s.instance_light_indices, s.instance_count, geometry));
+    CHECKED(Upload(&iflags, s.instance_flags, s.instance_count, shading));
+    CHECKED(Upload(&ovr, s.instance_material_overrides, s.instance_count, geometry));
+    *identity = dcrt::IdentityInstances(s);
     uint32_t* ident = nullptr;
-    CHECKED(upload(&ident, identity.data(), s.instance_count));
-    uploaded = &uploadStats.shading_bytes;
-    CHECKED(upload(&mats, s.materials, s.material_count));
+    CHECKED(Upload(&ident, (const uint32_t*)identity->data(), s.instance_count, geometry));
+    CHECKED(Upload(&mats, s.materials, s.material_count, shading));
     // (room for DCRT_MAX_LIGHT_COUNT lights, 5000 x 28 B as the reference allocates: UpdateLights
     // changes the count in place)
-    CHECKED(upload(&lights, s.lights, s.light_count, DCRT_MAX_LIGHT_COUNT));
-    uploaded = &uploadStats.geometry_bytes;
+    CHECKED(Upload(&lights, s.lights, s.light_count, shading, DCRT_MAX_LIGHT_COUNT));
     dMaterials = mats;
     dLights = lights;
     dInstanceFlags = iflags;
@@ -1151,16 +1054,16 @@ int dcrt_tracer::UploadScene(const dcrt_flat_scene& s)
     }
     if (blob.empty()) blob.resize(4, 0);
     TextureDesc* dDescs = nullptr; uint8_t* dBlob = nullptr; float* dSrgb = nullptr;
-    CHECKED(upload(&dDescs, descs.data(), descs.size()));
-    CHECKED(upload(&dBlob, blob.data(), blob.size()));
+    CHECKED(Upload(&dDescs, (const TextureDesc*)descs.data(), descs.size(), geometry));
+    CHECKED(Upload(&dBlob, (const uint8_t*)blob.data(), blob.size(), geometry));
     float srgb[256];
     for (int i = 0; i < 256; ++i) {
         const double c = i / 255.0;
         srgb[i] = (float)(c <= 0.04045 ? c / 12.92 : std::pow((c + 0.055) / 1.055, 2.4));
     }
-    CHECKED(upload(&dSrgb, srgb, 256));
+    CHECKED(Upload(&dSrgb, (const float*)srgb, 256, geometry));
     float* dEnv = nullptr;
-    if (s.env_cube_rgb && s.env_cube_size) CHECKED(upload(&dEnv, s.env_cube_rgb, (size_t)6 * s.env_cube_size * s.env_cube_size * 3));
+    if (s.env_cube_rgb && s.env_cube_size) CHECKED(Upload(&dEnv, s.env_cube_rgb, (size_t)6 * s.env_cube_size * s.env_cube_size * 3, geometry));
     d.triVerts = triVerts;
     d.triShade = triShade;
     d.vertices = vtx;
@@ -1187,296 +1090,260 @@ int dcrt_tracer::UploadScene(const dcrt_flat_scene& s)
     d.instanceCount = s.instance_count;
     d.triangleCount = s.triangle_count;
     d.stackSize = std::max<uint32_t>(s.bvh_traversal_stack_size, 1u);
-    // BLAS leaves (no TLAS-leaf bit, a primitive count) all with one triangle
-    d.singlePrimLeaves = 1u;
-    for (uint32_t i = 0; i < s.bvh_node_count; ++i) {
-        const uint32_t misc = s.bvh_nodes[i].misc;
-        if (!(misc & 0x4u) && ((misc >> 3) & DCRT_BVHNODE_MISC_MASK_PRIMITIVE_COUNT) > 1u) { d.singlePrimLeaves = 0u; break; }
-    }
-    scene = d;
-    // the MATERIAL variant and its LDS scene copy (the later copies of d carry the two counts on)
+    d.singlePrimLeaves = dcrt::SingleTriangleLeaves(s) ? 1u : 0u;
+    plan.scene = d;
+    // the MATERIAL variant and its LDS scene copy (plan.scene carries the two counts on)
     DeriveShading();
-    d.ldsMaterials = scene.ldsMaterials;
-    d.ldsLights = scene.ldsLights;
+    return DCRT_OK;
+}
+
+// Resident workgroups per CU of a cast kernel with `lds` bytes of dynamic LDS: registers and
+// LDS (gfx950's 1280-B allocation granule, LdsResident). Split casts run extension_kernel's.
+int dcrt_tracer::CastOccupancy(CastFn k, size_t lds, int* out)
+{
+    int n = 0;
+    if (knobs.mergedCasts) HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, (int)plan.block, lds));
+    else HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, extension_kernel<false, false>, (int)plan.block, lds));
+    *out = std::min(n, LdsResident(lds, knobs.mergedCasts ? (const void*)k : (const void*)extension_kernel<false, false>));
+    return DCRT_OK;
+}
+
+// UploadScene's second job: the cast's workgroup size, its LDS scene cache, which traversal the
+// scene gets (pair / ident / ring / flat / cells), and the node order that goes with it, uploaded.
+int dcrt_tracer::PlanCast(const dcrt_flat_scene& s, const UploadKnobs& k, const std::vector<uint32_t>& identity)
+{
+    DeviceScene d = plan.scene;
     // LDS stack: [stackSize + 2][block] u32 (two spare rows per lane, see stack_at in
     // dscene.h); keep a workgroup's stack <= 32 KiB
-    castBlock = 256;
-    while (castBlock > 64 && (size_t)(d.stackSize + 2) * castBlock * 4 > 32768) castBlock >>= 1;
-    if (const char* e = std::getenv("DCRT_CAST_BLOCK")) {   // (A/B: 64 / 128 / 256, at most the default)
-        const uint32_t v = (uint32_t)std::atoi(e);
-        if ((v == 64 || v == 128 || v == 256) && v <= castBlock) castBlock = v;
-    }
+    plan.block = 256;
+    while (plan.block > 64 && (size_t)(d.stackSize + 2) * plan.block * 4 > 32768) plan.block >>= 1;
+    if ((k.castBlock == 64 || k.castBlock == 128 || k.castBlock == 256) && k.castBlock <= plan.block) plan.block = k.castBlock;
     d.stackRows = d.stackSize + 2u;
     d.ringRows = 0u;
     d.spill = nullptr;
-    ringRows = 0;
-    castLds = (size_t)(d.stackSize + 2) * castBlock * 4;
-    if (castLds > 65536) { SetLastError("BVH traversal stack too deep for LDS"); return DCRT_E_LIMIT; }
-    // resident workgroups per CU of a cast kernel with `lds` bytes of dynamic LDS: registers and
-    // LDS (gfx950's 1280-B allocation granule, LdsResident)
-    auto castOccupancy = [&](CastFn k, size_t lds, int* out) -> int {
-        int n = 0;
-        if (mergedCasts) HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, (int)castBlock, lds));
-        else HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, extension_kernel<false, false>, (int)castBlock, lds));
-        *out = std::min(n, LdsResident(lds, mergedCasts ? (const void*)k : (const void*)extension_kernel<false, false>));
-        return DCRT_OK;
+    plan.ringRows = 0;
+    const size_t wholeStack = (size_t)(d.stackSize + 2) * plan.block * 4;
+    if (wholeStack > 65536) { SetLastError("BVH traversal stack too deep for LDS"); return DCRT_E_LIMIT; }
+    // LDS scene cache in what the cast kernel's register-limited occupancy leaves of the
+    // CU's 160 KiB per workgroup: BVH nodes first, then pre-gathered triangles
+    int regPerCU = 0;
+    CHECKED(CastOccupancy(CastKernel(CastVariant{}), wholeStack, &regPerCU));
+    const size_t perBlock = (g_ldsPerCU / (size_t)std::max(1, regPerCU)) & ~(size_t)15;
+    size_t budget = wholeStack < perBlock ? perBlock - wholeStack : 0;
+    uint32_t nodeCount = s.bvh_node_count;
+    d.cachedNodes = (uint32_t)std::min<size_t>(nodeCount, budget / 32);
+    d.cachedTris = (uint32_t)std::min<size_t>(s.triangle_count, (budget - d.cachedNodes * 32) / 48);
+    if (k.noLdsCache) d.cachedNodes = d.cachedTris = 0;
+    // (the LDS-only variant assumes 256-thread workgroups: its stack stride is a constant)
+    // (the cache-only variant keeps three permuted copies of every triangle: 144 B each)
+    plan.allCached = plan.block == 256 && d.cachedNodes == nodeCount && d.cachedTris == s.triangle_count &&
+                     (size_t)d.cachedNodes * 32 + (size_t)s.triangle_count * 144 + (size_t)s.instance_count * 64 <= budget;
+    d.cachedInstances = plan.allCached ? s.instance_count : 0u;
+    // trav_visit_pair where the traversal's fetches miss L2: nodes + triangles beyond an
+    // XCD's 4 MiB L2
+    plan.pair = !plan.allCached && (size_t)nodeCount * 32 + (size_t)s.triangle_count * 48 > ((size_t)4 << 20);
+    if (k.pairTraversal >= 0) plan.pair = !plan.allCached && k.pairTraversal != 0;
+    // the node order goes with it (dscene.h kLayoutPairs: the pair kernels assume it, the
+    // other non-counting cast kernels assume PackBVH's)
+    std::vector<dcrt_bvh_node> pairNodes;
+    if (plan.pair) {
+        if (!dcrt::PairLayout(s, k.topNodes, &pairNodes, k.nodeQuads)) { SetLastError("malformed BVH: a node with two parents"); return DCRT_E_INVALID_ARG; }
+        nodeCount = (uint32_t)pairNodes.size();
+    }
+    std::vector<dcrt_bvh_node> devNodes = plan.pair ? std::move(pairNodes) : std::vector<dcrt_bvh_node>(s.bvh_nodes, s.bvh_nodes + nodeCount);
+    // every instance the identity: the cache-only kernel keeps no instance space (IDENT)
+    plan.ident = (plan.allCached || !plan.pair) && knobs.mergedCasts && s.instance_count > 0;
+    plan.ident = plan.ident && dcrt::AllInstancesBitwiseIdentity(s) && k.identCast;
+    // a non-counting, opaque kernel this scene could run
+    auto candidate = [&](bool ring, bool flat = false, bool cells = false) {
+        return CastKernel({ false, false, plan.allCached, plan.pair, plan.ident, ring, flat, cells });
     };
-    {
-        // LDS scene cache in what the cast kernel's register-limited occupancy leaves of the
-        // CU's 160 KiB per workgroup: BVH nodes first, then pre-gathered triangles
-        int regPerCU = 0;
-        CHECKED(castOccupancy(cast_kernel<false, false, false, false>, castLds, &regPerCU));
-        const size_t perBlock = (g_ldsPerCU / (size_t)std::max(1, regPerCU)) & ~(size_t)15;
-        size_t budget = castLds < perBlock ? perBlock - castLds : 0;
-        uint32_t nodeCount = s.bvh_node_count;
+    // The spilling stack (cast_kernel's RING: an LDS window of K rows over a per-lane global
+    // column, kernels_impl.h ring_maintain) where the whole stack costs the launched kernel
+    // resident workgroups: a deep BVH (spaceship: 30 entries = 32 KiB per 256-lane workgroup,
+    // 4 workgroups per CU where its registers allow 6). A forced K below the scene's depth spills (tests).
+    if (!plan.allCached && knobs.mergedCasts) {
+        const int forced = k.stackRing;
+        const uint32_t K = forced > 0 ? (uint32_t)forced : 16u;
+        // (the window must take a batch of kVisitsPerCheck visits after a refill to half: kMinRingRows)
+        const bool validK = K >= std::max(8u, kMinRingRows) && K <= 64u && (K & (K - 1u)) == 0u;
+        if (forced > 0 && !validK) {
+            SetLastError("DCRT_STACK_RING: a power of two in [max(8, 2 * (visits per check + 1)), 64]");
+            return DCRT_E_INVALID_ARG;
+        }
+        if (forced > 0) {
+            plan.ringRows = K;
+        } else if (forced < 0 && validK && K < d.stackSize + 2u) {
+            int whole = 0, ring = 0;
+            CHECKED(CastOccupancy(candidate(false), wholeStack, &whole));
+            CHECKED(CastOccupancy(candidate(true), (size_t)K * plan.block * 4, &ring));
+            if (ring > whole) plan.ringRows = K;
+        }
+    }
+    // A scene the cache does not hold whole: the cache leaves `reserve` bytes of each CU's LDS
+    // free, so workgroups of the other pipeline's kernels (MATERIAL, CONTROL) can be resident
+    // beside the cast's -- with the cache sized to the last byte they could not
+    const size_t reserve = std::min<size_t>(k.castLdsReserve, g_ldsPerCU);
+    const CastFn launched = candidate(plan.ringRows != 0);
+    // the launched kernel's stack bytes: the ring window, or the whole stack
+    const size_t stackLds = plan.ringRows ? (size_t)plan.ringRows * plan.block * 4 : wholeStack;
+    if (!plan.allCached) {
+        // the cache budget from the occupancy of the kernel that launches
+        int perCU = 0;
+        CHECKED(CastOccupancy(launched, stackLds, &perCU));
+        const size_t perBlockR = ((g_ldsPerCU - reserve) / (size_t)std::max(1, perCU)) & ~(size_t)15;
+        budget = stackLds < perBlockR ? perBlockR - stackLds : 0;
         d.cachedNodes = (uint32_t)std::min<size_t>(nodeCount, budget / 32);
         d.cachedTris = (uint32_t)std::min<size_t>(s.triangle_count, (budget - d.cachedNodes * 32) / 48);
-        bool noCache = false;
-        if (const char* off = std::getenv("DCRT_NO_LDS_CACHE")) noCache = std::atoi(off) != 0;   // A/B experiments, tests
-        if (noCache) d.cachedNodes = d.cachedTris = 0;
-        // (the LDS-only variant assumes 256-thread workgroups: its stack stride is a constant)
-        // (the cache-only variant keeps three permuted copies of every triangle: 144 B each)
-        castAllCached = castBlock == 256 && d.cachedNodes == nodeCount && d.cachedTris == s.triangle_count &&
-                        (size_t)d.cachedNodes * 32 + (size_t)s.triangle_count * 144 + (size_t)s.instance_count * 64 <= budget;
-        d.cachedInstances = castAllCached ? s.instance_count : 0u;
-        // trav_visit_pair where the traversal's fetches miss L2: nodes + triangles beyond an
-        // XCD's 4 MiB L2 (DCRT_PAIR_TRAVERSAL=0/1 forces it off / on, A/B and tests)
-        castPair = !castAllCached && (size_t)nodeCount * 32 + (size_t)s.triangle_count * 48 > ((size_t)4 << 20);
-        if (const char* pv = std::getenv("DCRT_PAIR_TRAVERSAL")) castPair = !castAllCached && std::atoi(pv) != 0;
-        // the node order goes with it (dscene.h kLayoutPairs: the pair kernels assume it, the
-        // other non-counting cast kernels assume PackBVH's)
-        std::vector<dcrt_bvh_node> pairNodes;
-        if (castPair) {
-            uint32_t topNodes = 4096;
-            if (const char* e = std::getenv("DCRT_TOP_NODES")) topNodes = (uint32_t)std::atoi(e);   // A/B experiments
-            // quads (profiles/r06_ab_log.md: spaceship -1.6 %, close framing -0.1 / -1.4 %)
-            bool quads = true;
-            if (const char* e = std::getenv("DCRT_NODE_QUADS")) quads = std::atoi(e) != 0;   // A/B experiments
-            if (!PairLayout(s, topNodes, &pairNodes, quads)) { SetLastError("malformed BVH: a node with two parents"); return DCRT_E_INVALID_ARG; }
-            nodeCount = (uint32_t)pairNodes.size();
-        }
-        std::vector<dcrt_bvh_node> devNodes = castPair ? std::move(pairNodes) : std::vector<dcrt_bvh_node>(s.bvh_nodes, s.bvh_nodes + nodeCount);
-        // every instance the identity: the cache-only kernel keeps no instance space (IDENT;
-        // DCRT_IDENT_CAST=0: off, A/B)
-        // (bitwise: +1 and +0 entries only -- with a -0 entry the transform of a -0 component could
-        // stay -0, where IDENT's o + 0 gives +0)
-        castIdent = (castAllCached || !castPair) && mergedCasts && s.instance_count > 0;
-        for (uint32_t i = 0; castIdent && i < s.instance_count; ++i) {
-            const float* m = s.instance_transforms[s.instance_count + i].m;
-            for (int r = 0; r < 3; ++r)
-                for (int c = 0; c < 4; ++c) {
-                    uint32_t bits;
-                    std::memcpy(&bits, &m[r * 4 + c], 4);
-                    castIdent = castIdent && bits == (r == c ? 0x3F800000u : 0u);
-                }
-        }
-        if (const char* e = std::getenv("DCRT_IDENT_CAST")) castIdent = castIdent && std::atoi(e) != 0;
-        // The spilling stack (cast_kernel<..., RING>: an LDS window of K rows over a per-lane global
-        // column, kernels_impl.h ring_maintain) where the whole stack costs the launched kernel
-        // resident workgroups: a deep BVH (spaceship: 30 entries = 32 KiB per 256-lane workgroup,
-        // 4 workgroups per CU where its registers allow 6). DCRT_STACK_RING = K (a power of two,
-        // 8..64) forces a window of K rows (tests: K below the scene's depth spills), 0: never.
-        if (!castAllCached && mergedCasts) {
-            int forced = -1;
-            if (const char* e = std::getenv("DCRT_STACK_RING")) forced = std::atoi(e);
-            const uint32_t K = forced > 0 ? (uint32_t)forced : 16u;
-            // (the window must take a batch of kVisitsPerCheck visits after a refill to half: kMinRingRows)
-            const bool validK = K >= std::max(8u, kMinRingRows) && K <= 64u && (K & (K - 1u)) == 0u;
-            if (forced > 0 && !validK) {
-                SetLastError("DCRT_STACK_RING: a power of two in [max(8, 2 * (visits per check + 1)), 64]");
-                return DCRT_E_INVALID_ARG;
-            }
-            if (forced > 0) {
-                ringRows = K;
-            } else if (forced < 0 && validK && K < d.stackSize + 2u) {
-                int whole = 0, ring = 0;
-                CHECKED(castOccupancy(CastKernel(false, false, false, castPair, castIdent, false), castLds, &whole));
-                CHECKED(castOccupancy(CastKernel(false, false, false, castPair, castIdent, true), (size_t)K * castBlock * 4, &ring));
-                if (ring > whole) ringRows = K;
-            }
-        }
-        // A scene the cache does not hold whole: the cache leaves `reserve` bytes of each CU's LDS
-        // free, so workgroups of the other pipeline's kernels (MATERIAL, CONTROL) can be resident
-        // beside the cast's -- with the cache sized to the last byte they could not
-        // (DCRT_CAST_LDS_RESERVE, bytes per CU)
-#ifndef DCRT_CAST_LDS_RESERVE
-#define DCRT_CAST_LDS_RESERVE 12288   // (A/B: coffee -2 to -3 %, lamp -1 %; profiles/r04_ab_round4.txt)
-#endif
-        size_t reserve = DCRT_CAST_LDS_RESERVE;
-        if (const char* e = std::getenv("DCRT_CAST_LDS_RESERVE")) reserve = (size_t)std::max(0, std::atoi(e));
-        reserve = std::min<size_t>(reserve, g_ldsPerCU);
-        const CastFn launched = CastKernel(false, false, castAllCached, castPair, castIdent, ringRows != 0);
-        // the launched kernel's stack bytes: the ring window, or the whole stack
-        const size_t stackLds = ringRows ? (size_t)ringRows * castBlock * 4 : castLds;
-        if (!castAllCached) {
-            // the cache budget from the occupancy of the kernel that launches
-            int perCU = 0;
-            CHECKED(castOccupancy(launched, stackLds, &perCU));
-            const size_t perBlockR = ((g_ldsPerCU - reserve) / (size_t)std::max(1, perCU)) & ~(size_t)15;
-            budget = stackLds < perBlockR ? perBlockR - stackLds : 0;
-            d.cachedNodes = (uint32_t)std::min<size_t>(nodeCount, budget / 32);
-            d.cachedTris = (uint32_t)std::min<size_t>(s.triangle_count, (budget - d.cachedNodes * 32) / 48);
-            if (noCache) d.cachedNodes = d.cachedTris = 0;
-        }
-        // the cache-only kernels enter identity instances' BLASes in phase A (dscene.h
-        // kMiscIdentityLeaf): TLAS leaves carry the flag in their otherwise unused axis bits
-        if (castAllCached || castIdent) {
-            for (dcrt_bvh_node& n : devNodes) {
-                if (!(n.misc & 0x4u)) continue;
-                const uint32_t inst = (n.misc >> 3) & DCRT_BVHNODE_MISC_MASK_PRIMITIVE_COUNT;
-                n.misc = (n.misc & ~0x3u) | (inst < s.instance_count && identity[inst] ? kMiscIdentityLeaf : 0u);
-            }
-        }
-        CHECKED(upload(&nodes, devNodes.data(), nodeCount));
-        HIPCHECK(hipStreamSynchronize(stream));   // (devNodes ends with this block)
-        d.nodes = (const float4*)nodes;
-        d.nodeCount = nodeCount;
-        d.pairLayout = castPair ? 1u : 0u;
-        // trav_skip_root: levels of sure hits taken at a ray's start without their box tests
-        d.skipRoot = 1u;
-        if (const char* e = std::getenv("DCRT_SKIP_ROOT")) d.skipRoot = (uint32_t)std::max(0, std::min(16, std::atoi(e)));   // (A/B, tests)
-        const size_t cacheBytes = [&] { return (size_t)d.cachedNodes * 32 + (size_t)d.cachedTris * (castAllCached ? 144 : 48) + (size_t)d.cachedInstances * 64; }();
-        size_t launchLds = stackLds + cacheBytes;
-        // The budget above divides 160 KiB evenly among the workgroups the registers allow; the
-        // LDS is allocated in granules (and the kernel's static LDS comes on top), so the cache
-        // could cost a workgroup per CU (the spaceship pair kernel ran 5 of its 6). Trim the
-        // cache -- triangles first, then nodes, a granule at a time -- until the launched kernel
-        // keeps the occupancy the stack alone allows.
-        bool trim = true;
-        if (const char* e = std::getenv("DCRT_LDS_TRIM")) trim = std::atoi(e) != 0;   // (A/B)
-        if (!castAllCached && trim) {
-            int target = 0, now = 0;
-            CHECKED(castOccupancy(launched, stackLds, &target));
-            for (;;) {
-                CHECKED(castOccupancy(launched, launchLds, &now));
-                if (now >= target || (d.cachedTris == 0 && d.cachedNodes == 0)) break;
-                if (d.cachedTris > 0) d.cachedTris -= std::min<uint32_t>(d.cachedTris, 11);   // 528 B
-                else d.cachedNodes -= std::min<uint32_t>(d.cachedNodes, 16);                  // 512 B
-                launchLds = stackLds + (size_t)d.cachedNodes * 32 + (size_t)d.cachedTris * 48;
-            }
-        }
-        scene = d;
-        // every kernel but the ring cast launches with the whole stack (stackSize + 2 rows) in
-        // front of the same cache
-        castLdsFull = castLds + (launchLds - stackLds);
-        castLds = launchLds;
-        // The entry-free node order for the cache-only IDENT kernel (EntryFreeLayout: no BLAS-entry
-        // step per node visit), where its nodes, the triangles and one more stack row still fit
-        // the LDS the IDENT kernel runs at (DCRT_FLAT_CAST=0: off, A/B and tests)
-        castFlat = false;
-        cellsRes = 0;
-        dCells = nullptr;        // (sceneAllocs: freed above)
-        dCellLeaves = nullptr;
-        cells = ShadowCells{};
-        bool flatWanted = true;
-        if (const char* e = std::getenv("DCRT_FLAT_CAST")) flatWanted = std::atoi(e) != 0;
-        if (flatWanted && castAllCached && castIdent && mergedCasts && d.singlePrimLeaves) {
-            std::vector<dcrt_bvh_node> flat;
-            bool merge = true;   // (DCRT_FLAT_MERGE=0: every TLAS leaf over an empty node -- tests)
-            if (const char* e = std::getenv("DCRT_FLAT_MERGE")) merge = std::atoi(e) != 0;
-            if (EntryFreeLayout(s, &flat, merge)) {
-                const size_t flatLds = (size_t)(d.stackSize + 3u) * castBlock * 4 + flat.size() * 32 + (size_t)s.triangle_count * 144;
-                int identPerCU = 0, flatPerCU = 0;
-                CHECKED(castOccupancy(CastKernel(false, false, true, false, true, false), castLds, &identPerCU));
-                CHECKED(castOccupancy(CastKernel(false, false, true, false, true, false, true), flatLds, &flatPerCU));
-                if (flatPerCU >= identPerCU && flatLds <= 65536) {
-                    dcrt_bvh_node* fn = nullptr;
-                    CHECKED(upload(&fn, flat.data(), flat.size()));
-                    HIPCHECK(hipStreamSynchronize(stream));   // (flat ends with this block)
-                    sceneFlat = scene;
-                    sceneFlat.nodes = (const float4*)fn;
-                    sceneFlat.nodeCount = (uint32_t)flat.size();
-                    sceneFlat.cachedNodes = (uint32_t)flat.size();
-                    sceneFlat.cachedInstances = 0u;
-                    sceneFlat.stackSize = d.stackSize + 1u;
-                    sceneFlat.stackRows = d.stackSize + 3u;
-                    castLdsFlat = flatLds;
-                    castFlat = true;
-                    // The point light's direction cells for this kernel's shadow rays (RebuildShadowCells
-                    // decides per light set): the leaf words go behind the scene cache, where they and the
-                    // CELLS kernel's registers leave the occupancy alone. DCRT_SHADOW_CELLS = the cube
-                    // map's resolution R (0: off).
-#ifndef DCRT_SHADOW_CELLS
-#define DCRT_SHADOW_CELLS 32
-#endif
-                    uint32_t wanted = DCRT_SHADOW_CELLS;
-                    if (const char* e = std::getenv("DCRT_SHADOW_CELLS")) wanted = (uint32_t)std::max(0, std::min((int)dcrt::kCellMaxRes, std::atoi(e)));
-                    const size_t cellsLds = flatLds + dcrt::kCellWords * sizeof(uint32_t);
-                    int plainPerCU = 0, cellsPerCU = 0;
-                    if (wanted) {
-                        CHECKED(castOccupancy(CastKernel(false, false, true, false, true, false, true), cellsLds, &plainPerCU));
-                        CHECKED(castOccupancy(CastKernel(false, false, true, false, true, false, true, true), cellsLds, &cellsPerCU));
-                    }
-                    if (wanted && std::min(plainPerCU, cellsPerCU) >= flatPerCU && cellsLds <= 65536) {
-                        cellsRes = wanted;
-                        castLdsFlat = cellsLds;
-                        CHECKED(DeviceAlloc(&dCells, (size_t)6 * cellsRes * cellsRes, &sceneAllocs));
-                        CHECKED(DeviceAlloc(&dCellLeaves, dcrt::kCellWords, &sceneAllocs));
-                        cellNodes = flat;
-                        cellVertices.assign(s.vertices, s.vertices + s.vertex_count);
-                        cellTriangles.assign(s.triangles, s.triangles + (size_t)s.triangle_count * 3);
-                        cellTransforms.assign(s.instance_transforms, s.instance_transforms + (size_t)s.instance_count * 2);
-                    }
-                }
-            }
+        if (k.noLdsCache) d.cachedNodes = d.cachedTris = 0;
+    }
+    // the cache-only kernels enter identity instances' BLASes in phase A (dscene.h
+    // kMiscIdentityLeaf): TLAS leaves carry the flag in their otherwise unused axis bits
+    if (plan.allCached || plan.ident) {
+        for (dcrt_bvh_node& n : devNodes) {
+            if (!(n.misc & 0x4u)) continue;
+            const uint32_t inst = (n.misc >> 3) & DCRT_BVHNODE_MISC_MASK_PRIMITIVE_COUNT;
+            n.misc = (n.misc & ~0x3u) | (inst < s.instance_count && identity[inst] ? kMiscIdentityLeaf : 0u);
         }
     }
-    {
-        // The persistent traversal kernels run exactly one resident wave of workgroups.
-        hipDeviceProp_t prop;
-        HIPCHECK(hipGetDeviceProperties(&prop, device));
-        int perCU = 0;
-        if (castFlat) CHECKED(castOccupancy(CastKernel(false, false, true, false, true, false, true), castLdsFlat, &perCU));
-        else CHECKED(castOccupancy(CastKernel(false, false, castAllCached, castPair, castIdent, ringRows != 0), castLds, &perCU));
-        if (const char* b = std::getenv("DCRT_CAST_BLOCKS_PER_CU")) {   // tuning experiments
-            const int v = std::atoi(b);
-            if (v >= 1 && v < perCU) perCU = v;
-        }
-        castPerCU = (uint32_t)std::max(1, perCU);
-        castResident = castPerCU * (uint32_t)std::max(1, prop.multiProcessorCount);
-        if (const char* m = std::getenv("DCRT_CAST_GRID_MUL")) {   // (A/B: k x resident, workgroups retire in k rounds)
-            const int k = std::atoi(m);
-            if (k >= 2 && k <= 16) castResident *= (uint32_t)k;
-        }
-        int opacityPerCU = 0;
-        CHECKED(castOccupancy(CastKernel(false, true, castAllCached, castPair), castLdsFull, &opacityPerCU));
-        castResidentOpacity = (uint32_t)std::max(1, std::min(opacityPerCU, perCU)) * (uint32_t)std::max(1, prop.multiProcessorCount);
-        // the counting kernels keep the whole stack (castLdsFull): their own resident grid, so an
-        // instrumented run has no second partial round of workgroups the shipped kernel lacks
-        int instrPerCU = 0, instrOpacityPerCU = 0;
-        CHECKED(castOccupancy(CastKernel(true, false, castAllCached, castPair, castIdent, false), castLdsFull, &instrPerCU));
-        CHECKED(castOccupancy(CastKernel(true, true, castAllCached, castPair), castLdsFull, &instrOpacityPerCU));
-        castResidentInstr = (uint32_t)std::max(1, std::min(instrPerCU, perCU)) * (uint32_t)std::max(1, prop.multiProcessorCount);
-        castResidentInstrOpacity = (uint32_t)std::max(1, std::min(instrOpacityPerCU, perCU)) * (uint32_t)std::max(1, prop.multiProcessorCount);
-        int megaPerCU = 0;
-        HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&megaPerCU, megakernel<false>, (int)castBlock, castLdsFull));
-        megaResident = (uint32_t)std::max(1, std::min(megaPerCU, LdsResident(castLdsFull, (const void*)megakernel<false>))) *
-                       (uint32_t)std::max(1, prop.multiProcessorCount);
-        // the first-hit view kernel: the megakernel's launch shape, its own register budget
-        int viewPerCU = 0, viewOpacityPerCU = 0;
-        HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&viewPerCU, view_kernel<false>, (int)castBlock, castLdsFull));
-        HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&viewOpacityPerCU, view_kernel<true>, (int)castBlock, castLdsFull));
-        viewResident = (uint32_t)std::max(1, std::min(viewPerCU, LdsResident(castLdsFull, (const void*)view_kernel<false>))) *
-                       (uint32_t)std::max(1, prop.multiProcessorCount);
-        viewResidentOpacity = (uint32_t)std::max(1, std::min(viewOpacityPerCU, LdsResident(castLdsFull, (const void*)view_kernel<true>))) *
-                              (uint32_t)std::max(1, prop.multiProcessorCount);
-        cuCount = (uint32_t)std::max(1, prop.multiProcessorCount);
-        CHECKED(DeriveDrainGrid());
-        if (ringRows) {
-            // the spill columns: stackSize entries per lane of the persistent ring grid
-            uint32_t* spill = nullptr;
-            CHECKED(DeviceAlloc(&spill, (size_t)castResident * castBlock * scene.stackSize, &sceneAllocs));
-            HIPCHECK(hipMemsetAsync(spill, 0, (size_t)castResident * castBlock * scene.stackSize * 4, stream));
-            sceneRing = scene;
-            sceneRing.stackRows = ringRows;
-            sceneRing.ringRows = ringRows;
-            sceneRing.spill = spill;
+    dcrt_bvh_node* nodes = nullptr;
+    CHECKED(Upload(&nodes, (const dcrt_bvh_node*)devNodes.data(), nodeCount, &uploadStats.geometry_bytes));
+    HIPCHECK(hipStreamSynchronize(stream));   // (devNodes ends with this function)
+    d.nodes = (const float4*)nodes;
+    d.nodeCount = nodeCount;
+    d.pairLayout = plan.pair ? 1u : 0u;
+    d.skipRoot = k.skipRoot;
+    const size_t cacheBytes = (size_t)d.cachedNodes * 32 + (size_t)d.cachedTris * (plan.allCached ? 144 : 48) + (size_t)d.cachedInstances * 64;
+    size_t launchLds = stackLds + cacheBytes;
+    // The budget above divides 160 KiB evenly among the workgroups the registers allow; the
+    // LDS is allocated in granules (and the kernel's static LDS comes on top), so the cache
+    // could cost a workgroup per CU (the spaceship pair kernel ran 5 of its 6). Trim the
+    // cache -- triangles first, then nodes, a granule at a time -- until the launched kernel
+    // keeps the occupancy the stack alone allows.
+    if (!plan.allCached && k.ldsTrim) {
+        int target = 0, now = 0;
+        CHECKED(CastOccupancy(launched, stackLds, &target));
+        for (;;) {
+            CHECKED(CastOccupancy(launched, launchLds, &now));
+            if (now >= target || (d.cachedTris == 0 && d.cachedNodes == 0)) break;
+            if (d.cachedTris > 0) d.cachedTris -= std::min<uint32_t>(d.cachedTris, 11);   // 528 B
+            else d.cachedNodes -= std::min<uint32_t>(d.cachedNodes, 16);                  // 512 B
+            launchLds = stackLds + (size_t)d.cachedNodes * 32 + (size_t)d.cachedTris * 48;
         }
     }
-    CHECKED(RebuildShadowCells());
-    HIPCHECK(hipStreamSynchronize(stream));
-    hasScene = true;
-    newImage = true;
+    plan.scene = d;
+    // every kernel but the ring cast launches with the whole stack in front of the same cache
+    plan.ldsWholeStack = wholeStack + (launchLds - stackLds);
+    plan.ldsRing = plan.ringRows ? launchLds : 0;
+    return PlanFlatCast(s, k);
+}
+
+// ... and its last part: the entry-free node order for the cache-only IDENT kernel (EntryFreeLayout:
+// no BLAS-entry step per node visit), where its nodes, the triangles and one more stack row still
+// fit the LDS the IDENT kernel runs at; with it the buffers of the point light's direction cells.
+int dcrt_tracer::PlanFlatCast(const dcrt_flat_scene& s, const UploadKnobs& k)
+{
+    const DeviceScene& d = plan.scene;
+    plan.flat = false;
+    plan.cellsRes = 0;
+    dCells = nullptr;        // (sceneAllocs: freed by UploadArrays)
+    dCellLeaves = nullptr;
+    cells = ShadowCells{};
+    if (!(k.flatCast && plan.allCached && plan.ident && knobs.mergedCasts && d.singlePrimLeaves)) return DCRT_OK;
+    std::vector<dcrt_bvh_node> flat;
+    if (!dcrt::EntryFreeLayout(s, &flat, k.flatMerge)) return DCRT_OK;
+    auto kernel = [&](bool flatOrder, bool cellTable) { return CastKernel({ false, false, true, false, true, false, flatOrder, cellTable }); };
+    const size_t flatLds = (size_t)(d.stackSize + 3u) * plan.block * 4 + flat.size() * 32 + (size_t)s.triangle_count * 144;
+    int identPerCU = 0, flatPerCU = 0;
+    CHECKED(CastOccupancy(kernel(false, false), plan.ldsWholeStack, &identPerCU));
+    CHECKED(CastOccupancy(kernel(true, false), flatLds, &flatPerCU));
+    if (!(flatPerCU >= identPerCU && flatLds <= 65536)) return DCRT_OK;
+    dcrt_bvh_node* fn = nullptr;
+    CHECKED(Upload(&fn, (const dcrt_bvh_node*)flat.data(), flat.size(), &uploadStats.geometry_bytes));
+    HIPCHECK(hipStreamSynchronize(stream));   // (flat ends with this function)
+    plan.sceneFlat = plan.scene;
+    plan.sceneFlat.nodes = (const float4*)fn;
+    plan.sceneFlat.nodeCount = (uint32_t)flat.size();
+    plan.sceneFlat.cachedNodes = (uint32_t)flat.size();
+    plan.sceneFlat.cachedInstances = 0u;
+    plan.sceneFlat.stackSize = d.stackSize + 1u;
+    plan.sceneFlat.stackRows = d.stackSize + 3u;
+    plan.ldsFlat = flatLds;
+    plan.flat = true;
+    // The point light's direction cells for this kernel's shadow rays (RebuildShadowCells
+    // decides per light set): the leaf words go behind the scene cache, where they and the
+    // CELLS kernel's registers leave the occupancy alone.
+    const uint32_t wanted = k.shadowCells;
+    const size_t cellsLds = flatLds + dcrt::kCellWords * sizeof(uint32_t);
+    int plainPerCU = 0, cellsPerCU = 0;
+    if (wanted) {
+        CHECKED(CastOccupancy(kernel(true, false), cellsLds, &plainPerCU));
+        CHECKED(CastOccupancy(kernel(true, true), cellsLds, &cellsPerCU));
+    }
+    if (wanted && std::min(plainPerCU, cellsPerCU) >= flatPerCU && cellsLds <= 65536) {
+        plan.cellsRes = wanted;
+        plan.ldsFlat = cellsLds;
+        CHECKED(DeviceAlloc(&dCells, (size_t)6 * plan.cellsRes * plan.cellsRes, &sceneAllocs));
+        CHECKED(DeviceAlloc(&dCellLeaves, dcrt::kCellWords, &sceneAllocs));
+        cellNodes = flat;
+        cellVertices.assign(s.vertices, s.vertices + s.vertex_count);
+        cellTriangles.assign(s.triangles, s.triangles + (size_t)s.triangle_count * 3);
+        cellTransforms.assign(s.instance_transforms, s.instance_transforms + (size_t)s.instance_count * 2);
+    }
+    return DCRT_OK;
+}
+
+// UploadScene's third job: the persistent grids -- the traversal kernels run exactly one resident
+// wave of workgroups -- and the ring cast's spill columns, which take the shipped grid's size.
+int dcrt_tracer::SizeGrids(const UploadKnobs& k)
+{
+    hipDeviceProp_t prop;
+    HIPCHECK(hipGetDeviceProperties(&prop, device));
+    cuCount = (uint32_t)std::max(1, prop.multiProcessorCount);
+    // (no cell table stands yet -- RebuildShadowCells follows -- so a flat plan is sized by the plain
+    // FLAT kernel: PlanFlatCast saw to it that the CELLS kernel keeps that occupancy)
+    const CastLaunch shipped = plan.Launch(false, false);
+    int perCU = 0;
+    CHECKED(CastOccupancy(shipped.kernel, shipped.lds, &perCU));
+    // the two tuning knobs act on the shipped kernel's grid only
+    if (k.castBlocksPerCU >= 1 && k.castBlocksPerCU < perCU) perCU = k.castBlocksPerCU;
+    plan.perCU = (uint32_t)std::max(1, perCU);
+    plan.resident[0][0] = plan.perCU * cuCount;
+    if (k.castGridMul >= 2 && k.castGridMul <= 16) plan.resident[0][0] *= (uint32_t)k.castGridMul;
+    // the any-hit and the counting kernels keep the whole stack: their own resident grids, so an
+    // instrumented run has no second partial round of workgroups the shipped kernel lacks
+    for (const bool instr : { false, true }) {
+        for (const bool opacity : { false, true }) {
+            if (!instr && !opacity) continue;
+            const CastLaunch other = plan.Launch(instr, opacity);
+            int own = 0;
+            CHECKED(CastOccupancy(other.kernel, other.lds, &own));
+            plan.resident[instr][opacity] = (uint32_t)std::max(1, std::min(own, perCU)) * cuCount;
+        }
+    }
+    const uint32_t block = plan.block;
+    const size_t lds = plan.ldsWholeStack;
+    int megaPerCU = 0;
+    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&megaPerCU, megakernel<false>, (int)block, lds));
+    megaResident = (uint32_t)std::max(1, std::min(megaPerCU, LdsResident(lds, (const void*)megakernel<false>))) * cuCount;
+    // the first-hit view kernel: the megakernel's launch shape, its own register budget
+    int viewPerCU = 0, viewOpacityPerCU = 0;
+    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&viewPerCU, view_kernel<false>, (int)block, lds));
+    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&viewOpacityPerCU, view_kernel<true>, (int)block, lds));
+    viewResident = (uint32_t)std::max(1, std::min(viewPerCU, LdsResident(lds, (const void*)view_kernel<false>))) * cuCount;
+    viewResidentOpacity = (uint32_t)std::max(1, std::min(viewOpacityPerCU, LdsResident(lds, (const void*)view_kernel<true>))) * cuCount;
+    CHECKED(DeriveDrainGrid());
+    if (plan.ringRows) {
+        // the spill columns: stackSize entries per lane of the persistent ring grid
+        const size_t words = (size_t)plan.resident[0][0] * block * plan.scene.stackSize;
+        uint32_t* spill = nullptr;
+        CHECKED(DeviceAlloc(&spill, words, &sceneAllocs));
+        HIPCHECK(hipMemsetAsync(spill, 0, words * 4, stream));
+        plan.sceneRing = plan.scene;
+        plan.sceneRing.stackRows = plan.ringRows;
+        plan.sceneRing.ringRows = plan.ringRows;
+        plan.sceneRing.spill = spill;
+    }
     return DCRT_OK;
 }
 
@@ -1729,14 +1596,14 @@ int dcrt_tracer::BeginImage()
 #ifndef DCRT_REFILL_GLOBAL
 #define DCRT_REFILL_GLOBAL 28
 #endif
-    fc.refillLanes = tuneOverride || castAllCached ? refillLanes : DCRT_REFILL_GLOBAL;
-    fc.parkLanes = parkLanes;
+    fc.refillLanes = knobs.tuneOverride || plan.allCached ? knobs.refillLanes : DCRT_REFILL_GLOBAL;
+    fc.parkLanes = knobs.parkLanes;
     // virtual batch starts (control_kernel): the merged cast kernels carry the camera-ray fetch;
     // not with ALLOW_ANYHIT_SHADER (NEW_PATH's opacity draw)
-    fc.virtualStart = virtualStart && mergedCasts && !(frame.features & DCRT_FEATURE_ALLOW_ANYHIT) ? 1u : 0u;
+    fc.virtualStart = knobs.virtualStart && knobs.mergedCasts && !(frame.features & DCRT_FEATURE_ALLOW_ANYHIT) ? 1u : 0u;
     // drain completion (drain_kernel): not with ALLOW_ANYHIT_SHADER, and not while the cast
     // kernels are instrumented (the roofline leg's counts and launch times are the wavefront's)
-    fc.drainPaths = !(frame.features & DCRT_FEATURE_ALLOW_ANYHIT) && !instrCounters && !extTiming && !rowProbe ? drainPaths : 0u;
+    fc.drainPaths = !(frame.features & DCRT_FEATURE_ALLOW_ANYHIT) && !instrCounters && !extTiming && !rowProbe ? knobs.drainPaths : 0u;
     hipLaunchKernelGGL(set_frame_kernel, dim3(1), dim3(1), 0, stream, dFrame, fc);
     const uint32_t total = fc.blocksPerImage;
     const uint32_t idleThreads = std::max<uint32_t>(poolSize, 2u * (uint32_t)(sizeof(Counters) / 4));
@@ -1772,7 +1639,8 @@ int dcrt_tracer::LaunchIteration(uint32_t par, bool timed, bool sequenced)
     pool.finHit = finHits + (size_t)par * kFinShards * pool.finCap;
     pool.finHitPrev = finHits + (size_t)(par ^ 1u) * kFinShards * pool.finCap;
     const bool opacity = (frame.features & DCRT_FEATURE_ALLOW_ANYHIT) != 0;
-    const uint32_t castGrid = CastGrid(castBlock, opacity);
+    const CastLaunch cast = plan.Launch(instrCounters, opacity);
+    const uint32_t castBlock = plan.block, castGrid = std::min<uint32_t>((poolSize + castBlock - 1) / castBlock, cast.resident);
     // Timed launches take their start/stop timestamps from the dispatch itself
     // (hipExtLaunchKernelGGL), so the duration is the kernel's, as rocprofv3 reports it.
     hipEvent_t c0 = nullptr, c1 = nullptr, m0 = nullptr, m1 = nullptr, e0 = nullptr, e1 = nullptr;
@@ -1791,34 +1659,28 @@ int dcrt_tracer::LaunchIteration(uint32_t par, bool timed, bool sequenced)
     if (timed) CHECKED(TimedPair(kTimedMaterial, &m0, &m1));
     {
         Annotation a("Material", !capturing);
-        hipExtLaunchKernelGGL(material, dim3(materialGrid), dim3(kMaterialBlock), rowProbe ? 0u : materialLds, stream, m0, m1, 0, pool, scene,
+        hipExtLaunchKernelGGL(material, dim3(materialGrid), dim3(kMaterialBlock), rowProbe ? 0u : materialLds, stream, m0, m1, 0, pool, plan.scene,
                               (const FrameConstants*)dFrame, cnt, (const Counters*)next, (const SampleOut*)dSampleOut);
     }
     if (timed) CHECKED(TimedPair(kTimedCast, &e0, &e1));
-    // kernel variant: instrumented counts x ALLOW_ANYHIT_SHADER
-    Annotation castAnnotation(mergedCasts ? "Extension + shadow ray cast" : "Extension ray cast, shadow ray cast", !capturing);
-    if (mergedCasts) {
-        const bool ring = ringRows != 0 && !instrCounters && !opacity;   // (the ring kernel; the counting and
-                                                                        // any-hit kernels keep the whole stack)
-        const bool flat = castFlat && !instrCounters && !opacity;
-        auto cast = CastKernel(instrCounters, opacity, castAllCached, castPair, castIdent, ring, flat, flat && sceneFlat.shadowRes != 0u);
-        hipExtLaunchKernelGGL(cast, dim3(castGrid), dim3(castBlock), flat ? castLdsFlat : ring ? castLds : castLdsFull, stream, e0,
-                              e1, 0, pool, flat ? sceneFlat : ring ? sceneRing : scene,
+    Annotation castAnnotation(knobs.mergedCasts ? "Extension + shadow ray cast" : "Extension ray cast, shadow ray cast", !capturing);
+    if (knobs.mergedCasts) {
+        hipExtLaunchKernelGGL(cast.kernel, dim3(castGrid), dim3(castBlock), cast.lds, stream, e0, e1, 0, pool, cast.scene,
                               (const FrameConstants*)dFrame, cnt, next, dGlobals, dInstr);
     } else {
         auto ext = instrCounters ? (opacity ? extension_kernel<true, true> : extension_kernel<true, false>)
                                  : (opacity ? extension_kernel<false, true> : extension_kernel<false, false>);
         auto shadow = instrCounters ? (opacity ? shadow_kernel<true, true> : shadow_kernel<true, false>)
                                     : (opacity ? shadow_kernel<false, true> : shadow_kernel<false, false>);
-        hipExtLaunchKernelGGL(ext, dim3(castGrid), dim3(castBlock), castLdsFull, stream, e0, e1, 0, pool, scene,
+        hipExtLaunchKernelGGL(ext, dim3(castGrid), dim3(castBlock), cast.lds, stream, e0, e1, 0, pool, cast.scene,
                               (const FrameConstants*)dFrame, (const Counters*)cnt, dGlobals, dInstr);
-        hipLaunchKernelGGL(shadow, dim3(castGrid), dim3(castBlock), castLdsFull, stream, pool, scene, (const FrameConstants*)dFrame, cnt,
+        hipLaunchKernelGGL(shadow, dim3(castGrid), dim3(castBlock), cast.lds, stream, pool, cast.scene, (const FrameConstants*)dFrame, cnt,
                            next, dGlobals, dInstr);
     }
-    if (drainPaths) {
+    if (knobs.drainPaths) {
         // (returns at once unless the batch's last paths are few enough: fc.drainPaths)
         auto drain = materialCaps == kCapOpaqueDelta ? drain_kernel<kCapOpaqueDelta> : drain_kernel<kCapAll>;
-        hipLaunchKernelGGL(drain, dim3(drainResident), dim3(castBlock), castLdsFull, stream, pool, scene, (const FrameConstants*)dFrame, cnt,
+        hipLaunchKernelGGL(drain, dim3(drainResident), dim3(castBlock), plan.ldsWholeStack, stream, pool, plan.scene, (const FrameConstants*)dFrame, cnt,
                            dGlobals, (const SampleOut*)dSampleOut);
     }
     if (sequenced) {
@@ -1923,7 +1785,7 @@ int dcrt_tracer::LaunchView(uint32_t type, const Film& target)
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (extTiming) CHECKED(TimedPair(kTimedCast, &e0, &e1));
     auto vk = opacity ? view_kernel<true> : view_kernel<false>;
-    hipExtLaunchKernelGGL(vk, dim3(opacity ? viewResidentOpacity : viewResident), dim3(castBlock), castLdsFull, stream, e0, e1, 0, scene,
+    hipExtLaunchKernelGGL(vk, dim3(opacity ? viewResidentOpacity : viewResident), dim3(plan.block), plan.ldsWholeStack, stream, e0, e1, 0, plan.scene,
                           (const FrameConstants*)dFrame, target, dGlobals, (uint32_t)(target.debugRng != nullptr), type,
                           output.iteration_threshold);
     HIPCHECK(hipGetLastError());
@@ -2194,7 +2056,7 @@ int dcrt_tracer::RenderImages(uint32_t firstSeed, uint32_t count, const dcrt_fil
                 hipEvent_t e0 = nullptr, e1 = nullptr;
                 if (extTiming) CHECKED(TimedPair(kTimedCast, &e0, &e1));
                 auto mk = (frame.features & DCRT_FEATURE_ALLOW_ANYHIT) ? megakernel<true> : megakernel<false>;
-                hipExtLaunchKernelGGL(mk, dim3(megaResident), dim3(castBlock), castLdsFull, stream, e0, e1, 0, scene,
+                hipExtLaunchKernelGGL(mk, dim3(megaResident), dim3(plan.block), plan.ldsWholeStack, stream, e0, e1, 0, plan.scene,
                                       (const FrameConstants*)dFrame, film, dGlobals, (uint32_t)(film.debugRng != nullptr));
             }
             CHECKED(LaunchFilm(1u, nullptr, nullptr, nullptr, filmImages));
@@ -2314,9 +2176,9 @@ int dcrt_tracer::AccumulateImages(const void* const* pos, const void* const* val
 }
 
 // ---- film noise estimate --------------------------------------------------------------------
-// A film pass into the film: with convergence off the kernel and the arguments of before it
-// existed; on, the instantiation that also feeds the half film (firstIndex: the film image count
-// of the pass's first image; under `guard` the kernel takes it from Globals instead).
+// A film pass into the film: film_kernel, or with convergence on the kernel that also feeds the
+// half film (firstIndex: the film image count of the pass's first image; under `guard` the kernel
+// takes it from Globals instead).
 int dcrt_tracer::LaunchFilm(uint32_t images, const Globals* guard, const float2* const* posList, const float4* const* valList,
                             uint32_t firstIndex)
 {
@@ -2850,24 +2712,26 @@ DCRT_API int dcrt_tracer_get_info(dcrt_tracer* t, dcrt_tracer_info* out)
 {
     TRACER_GUARD(t);
     if (!out) return DCRT_E_INVALID_ARG;
+    const CastPlan& plan = t->plan;
+    const CastLaunch shipped = plan.Launch(false, false);
     out->path_pool_size = t->poolSize;
-    out->scene_in_lds = t->hasScene && t->castAllCached ? 1u : 0u;
-    out->cached_nodes = t->hasScene ? t->scene.cachedNodes : 0u;
-    out->cached_triangles = t->hasScene ? t->scene.cachedTris : 0u;
-    out->cast_block = t->castBlock;
-    out->traversal_stack = t->hasScene ? t->scene.stackSize : 0u;
+    out->scene_in_lds = t->hasScene && plan.allCached ? 1u : 0u;
+    out->cached_nodes = t->hasScene ? plan.scene.cachedNodes : 0u;
+    out->cached_triangles = t->hasScene ? plan.scene.cachedTris : 0u;
+    out->cast_block = plan.block;
+    out->traversal_stack = t->hasScene ? plan.scene.stackSize : 0u;
     out->material_generic = t->materialCaps == kCapAll ? 1u : 0u;
-    out->pair_traversal = t->hasScene && t->castPair ? 1u : 0u;
+    out->pair_traversal = t->hasScene && plan.pair ? 1u : 0u;
     out->control_grid = t->controlGrid;
     out->material_grid = t->materialGrid;
-    out->cast_grid = t->castResident;
+    out->cast_grid = shipped.resident;
     out->material_lds = t->materialLds;
-    out->cast_identity = t->castIdent ? (t->castFlat ? 2u : 1u) : 0u;
-    out->stack_lds_rows = t->hasScene ? (t->ringRows ? t->ringRows : t->castFlat ? t->sceneFlat.stackRows : t->scene.stackRows) : 0u;
-    out->ring_rows = t->hasScene ? t->ringRows : 0u;
-    out->cast_waves_per_cu = t->castPerCU * (t->castBlock / 64u);
-    const bool cells = t->hasScene && t->castFlat && t->sceneFlat.shadowRes != 0u;
-    out->shadow_cells = cells ? t->sceneFlat.shadowRes : 0u;
+    out->cast_identity = plan.ident ? (plan.flat ? 2u : 1u) : 0u;
+    out->stack_lds_rows = t->hasScene ? shipped.scene.stackRows : 0u;
+    out->ring_rows = t->hasScene ? plan.ringRows : 0u;
+    out->cast_waves_per_cu = plan.perCU * (plan.block / 64u);
+    const bool cells = t->hasScene && shipped.scene.shadowRes != 0u;   // (the flat scene's, while a table stands)
+    out->shadow_cells = cells ? shipped.scene.shadowRes : 0u;
     out->shadow_cell_max_leaves = cells ? t->cells.maxLeaves : 0u;
     out->shadow_cell_mean_leaves = cells ? t->cells.meanLeaves : 0.0f;
     return DCRT_OK;
@@ -2878,11 +2742,12 @@ DCRT_API int dcrt_tracer_debug_ring_spills(dcrt_tracer* t, uint64_t* out)
     TRACER_GUARD(t);
     if (!out) return DCRT_E_INVALID_ARG;
     *out = 0;
-    if (!t->hasScene || !t->ringRows) return DCRT_OK;
-    const size_t n = (size_t)t->castResident * t->castBlock * t->scene.stackSize;
+    const CastLaunch shipped = t->plan.Launch(false, false);
+    if (!t->hasScene || !shipped.scene.spill) return DCRT_OK;   // (the ring cast's scene alone has spill columns)
+    const size_t n = (size_t)shipped.resident * t->plan.block * shipped.scene.stackSize;
     std::vector<uint32_t> h(n);
     HIPCHECK(hipStreamSynchronize(t->stream));
-    HIPCHECK(hipMemcpy(h.data(), t->sceneRing.spill, n * 4, hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(h.data(), shipped.scene.spill, n * 4, hipMemcpyDeviceToHost));
     for (const uint32_t w : h) *out += w != 0u;
     return DCRT_OK;
 }
@@ -2955,12 +2820,14 @@ DCRT_API int dcrt_tracer_set_luts(dcrt_tracer* t, const dcrt_bxdf_luts* luts)
 static int TraceBatch(dcrt_tracer* t, const dcrt_ray* d_rays, uint32_t n, dcrt_ray_hit* d_hits, uint32_t* d_occ, bool any, uint32_t features)
 {
     if (!t->hasScene) { SetLastError("no scene uploaded"); return DCRT_E_NO_SCENE; }
-    const uint32_t grid = std::min<uint32_t>((n + t->castBlock - 1) / t->castBlock, t->castResident);
+    // (the plain scene with the whole stack, on the shipped kernel's grid)
+    const CastPlan& plan = t->plan;
+    const uint32_t grid = std::min<uint32_t>((n + plan.block - 1) / plan.block, plan.resident[0][0]);
     if (n == 0) return DCRT_OK;
     unsigned long long* instr = t->instrCounters ? t->dInstr : nullptr;
     auto kernel = any ? (instr ? batch_trace_kernel<true, true> : batch_trace_kernel<true, false>)
                       : (instr ? batch_trace_kernel<false, true> : batch_trace_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(t->castBlock), t->castLdsFull, t->stream, t->scene, d_rays, n, features, d_hits, d_occ, instr);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(plan.block), plan.ldsWholeStack, t->stream, plan.scene, d_rays, n, features, d_hits, d_occ, instr);
     HIPCHECK(hipGetLastError());
     return DCRT_OK;
 }
@@ -3003,7 +2870,8 @@ DCRT_API int dcrt_tracer_trace_occlusion_cells(dcrt_tracer* t, const dcrt_ray* r
 {
     TRACER_GUARD(t);
     if ((!rays || !out) && n) return DCRT_E_INVALID_ARG;
-    if (!t->hasScene || !t->castFlat || t->sceneFlat.shadowRes == 0u) {
+    const CastLaunch shipped = t->plan.Launch(false, false);
+    if (!t->hasScene || shipped.scene.shadowRes == 0u) {
         SetLastError("the uploaded scene has no direction-cell table" + (t->cells.reason.empty() ? std::string() : ": " + t->cells.reason));
         return DCRT_E_NO_SCENE;
     }
@@ -3015,8 +2883,8 @@ DCRT_API int dcrt_tracer_trace_occlusion_cells(dcrt_tracer* t, const dcrt_ray* r
     int rc = DCRT_OK;
     if (hipMemcpyAsync(dr, rays, (size_t)n * sizeof(dcrt_ray), hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
     if (rc == DCRT_OK) {
-        const uint32_t grid = std::min<uint32_t>((n + t->castBlock - 1) / t->castBlock, t->castResident);
-        hipLaunchKernelGGL(cells_occlusion_kernel, dim3(grid), dim3(t->castBlock), t->castLdsFlat, t->stream, t->sceneFlat, (const dcrt_ray*)dr, n,
+        const uint32_t block = t->plan.block, grid = std::min<uint32_t>((n + block - 1) / block, shipped.resident);
+        hipLaunchKernelGGL(cells_occlusion_kernel, dim3(grid), dim3(block), shipped.lds, t->stream, shipped.scene, (const dcrt_ray*)dr, n,
                            features, dOcc);
         if (hipGetLastError() != hipSuccess) rc = DCRT_E_HIP;
     }
@@ -3024,43 +2892,6 @@ DCRT_API int dcrt_tracer_trace_occlusion_cells(dcrt_tracer* t, const dcrt_ray* r
     if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
     FreeAll(&tmp);
     return rc;
-}
-
-DCRT_API int dcrt_shadow_cells_build(const dcrt_flat_scene* s, uint32_t resolution, dcrt_shadow_cells_info* info, uint64_t* outCells,
-                                     uint32_t* outLeafWords, dcrt_bvh_node* outNodes, uint32_t nodeCapacity)
-{
-    if (!s || !info || !s->bvh_nodes || !s->vertices || !s->triangles || !s->instance_transforms || s->bvh_node_count == 0 ||
-        resolution > dcrt::kCellMaxRes) {
-        SetLastError("dcrt_shadow_cells_build: incomplete scene or resolution above the limit");
-        return DCRT_E_INVALID_ARG;
-    }
-    *info = dcrt_shadow_cells_info{};
-    std::vector<dcrt_bvh_node> flat;
-    ShadowCells cells;
-    if (!EntryFreeLayout(*s, &flat)) cells.reason = "no entry-free node order (a leaf with several triangles, or a malformed tree)";
-    else dcrt::BuildShadowCells(flat.data(), flat.size(), *s, resolution ? resolution : (uint32_t)DCRT_SHADOW_CELLS, &cells);
-    if (!cells.resolution) {
-        SetLastError("no direction-cell table: " + cells.reason);
-        return DCRT_OK;
-    }
-    if (outNodes && nodeCapacity < flat.size()) { SetLastError("dcrt_shadow_cells_build: node capacity too small"); return DCRT_E_INVALID_ARG; }
-    info->resolution = cells.resolution;
-    info->leaf_count = cells.leafCount;
-    info->node_count = (uint32_t)flat.size();
-    info->max_leaves = cells.maxLeaves;
-    info->mean_leaves = cells.meanLeaves;
-    info->r0 = (float)cells.r0;
-    if (outCells) std::memcpy(outCells, cells.cells.data(), cells.cells.size() * sizeof(uint64_t));
-    if (outLeafWords) std::memcpy(outLeafWords, cells.leafWords.data(), dcrt::kCellWords * sizeof(uint32_t));
-    if (outNodes) std::memcpy(outNodes, flat.data(), flat.size() * sizeof(dcrt_bvh_node));
-    return DCRT_OK;
-}
-
-DCRT_API int dcrt_shadow_cell_indices(uint32_t resolution, const float* w, uint32_t count, uint32_t* out)
-{
-    if (resolution == 0u || resolution > dcrt::kCellMaxRes || ((!w || !out) && count)) return DCRT_E_INVALID_ARG;
-    for (uint32_t i = 0; i < count; ++i) out[i] = dcrt::ShadowCellIndex(resolution, w + (size_t)i * 3);
-    return DCRT_OK;
 }
 
 DCRT_API int dcrt_tracer_trace_rays_device(dcrt_tracer* t, const void* d_rays, uint32_t n, void* d_hits, uint32_t features)

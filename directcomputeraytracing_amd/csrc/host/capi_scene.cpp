@@ -9,7 +9,9 @@
 #include <string>
 
 #include "../../../include/dcrt.h"
+#include "bvh_layout.h"
 #include "scene.h"
+#include "shadow_cells.h"
 
 namespace dcrt {
 thread_local std::string g_lastError;
@@ -39,7 +41,9 @@ struct dcrt_scene {
     bool HasCube() const { return scene.hasEnvironmentLight && scene.environmentLight.cubeSize != 0; }
 };
 
+using dcrt::EntryFreeLayout;
 using dcrt::SetLastError;
+using dcrt::ShadowCells;
 
 #define DCRT_GUARD_BEGIN try {
 #define DCRT_GUARD_END                                   \
@@ -601,6 +605,43 @@ DCRT_API int dcrt_xml_dump_tree(const char* path, char* out, uint32_t capacity, 
     }
     return dump.size() <= capacity ? DCRT_OK : DCRT_E_LIMIT;
     DCRT_GUARD_END
+}
+
+DCRT_API int dcrt_shadow_cells_build(const dcrt_flat_scene* s, uint32_t resolution, dcrt_shadow_cells_info* info, uint64_t* outCells,
+                                     uint32_t* outLeafWords, dcrt_bvh_node* outNodes, uint32_t nodeCapacity)
+{
+    if (!s || !info || !s->bvh_nodes || !s->vertices || !s->triangles || !s->instance_transforms || s->bvh_node_count == 0 ||
+        resolution > dcrt::kCellMaxRes) {
+        SetLastError("dcrt_shadow_cells_build: incomplete scene or resolution above the limit");
+        return DCRT_E_INVALID_ARG;
+    }
+    *info = dcrt_shadow_cells_info{};
+    std::vector<dcrt_bvh_node> flat;
+    ShadowCells cells;
+    if (!EntryFreeLayout(*s, &flat)) cells.reason = "no entry-free node order (a leaf with several triangles, or a malformed tree)";
+    else dcrt::BuildShadowCells(flat.data(), flat.size(), *s, resolution ? resolution : dcrt::kCellDefaultRes, &cells);
+    if (!cells.resolution) {
+        SetLastError("no direction-cell table: " + cells.reason);
+        return DCRT_OK;
+    }
+    if (outNodes && nodeCapacity < flat.size()) { SetLastError("dcrt_shadow_cells_build: node capacity too small"); return DCRT_E_INVALID_ARG; }
+    info->resolution = cells.resolution;
+    info->leaf_count = cells.leafCount;
+    info->node_count = (uint32_t)flat.size();
+    info->max_leaves = cells.maxLeaves;
+    info->mean_leaves = cells.meanLeaves;
+    info->r0 = (float)cells.r0;
+    if (outCells) std::memcpy(outCells, cells.cells.data(), cells.cells.size() * sizeof(uint64_t));
+    if (outLeafWords) std::memcpy(outLeafWords, cells.leafWords.data(), dcrt::kCellWords * sizeof(uint32_t));
+    if (outNodes) std::memcpy(outNodes, flat.data(), flat.size() * sizeof(dcrt_bvh_node));
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_shadow_cell_indices(uint32_t resolution, const float* w, uint32_t count, uint32_t* out)
+{
+    if (resolution == 0u || resolution > dcrt::kCellMaxRes || ((!w || !out) && count)) return DCRT_E_INVALID_ARG;
+    for (uint32_t i = 0; i < count; ++i) out[i] = dcrt::ShadowCellIndex(resolution, w + (size_t)i * 3);
+    return DCRT_OK;
 }
 
 }  // extern "C"

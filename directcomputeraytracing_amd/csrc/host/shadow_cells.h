@@ -24,6 +24,7 @@ constexpr uint32_t kCellWords = 128;
 constexpr uint32_t kCellNodeBits = 10, kCellNodeMask = (1u << kCellNodeBits) - 1u;
 constexpr uint32_t kCellCountBits = 6, kCellCountMask = (1u << kCellCountBits) - 1u;
 constexpr uint32_t kCellMaxRes = 64;        // 6 * 64 * 64 masks = 192 KiB
+constexpr uint32_t kCellDefaultRes = 32;    // the tracer's table (DCRT_SHADOW_CELLS) and dcrt_shadow_cells_build's
 // Cells a mask is dilated by on every side. The margin only has to cover a ray's distance from the
 // light (r0, BuildShadowCells) and the rounding of the cell arithmetic; a wider one puts more leaves
 // into every mask, a narrower one keeps the light further from every triangle.
@@ -47,7 +48,7 @@ struct ShadowCells {
 // (dscene.h cells_index). Rounding differences fall inside the table's margin.
 uint32_t ShadowCellIndex(uint32_t R, const float w[3]);
 
-// Builds the table for entry-free nodes `nodes` (tracer.hip EntryFreeLayout) of flat scene `s`.
+// Builds the table for entry-free nodes `nodes` (bvh_layout.h EntryFreeLayout) of flat scene `s`.
 // Leaves `out->resolution` 0 when the scene is not eligible: more or other lights than one point
 // light, an instance whose inverse is not bitwise the identity, more than kCellLeaves leaves, more
 // guards than the leaf words hold, a triangle closer to the light than r0.

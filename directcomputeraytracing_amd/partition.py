@@ -177,7 +177,7 @@ def pipeline_pool(pool: int, rows: int, width: int, images: int, max_batch: int 
 
 def halo_for_radius(radius: float, height: int = 65535) -> int:
     """Rows of support beyond a pixel row that SampleConvolution gathers (SampleConvolution.hlsl:77-81),
-    in the kernel's float32 arithmetic over the film's rows (dcrt_tracer FilterSupportRows): floor(r + 0.5),
+    in the kernel's float32 arithmetic over the film's rows (film_rows.h FilterSupportRows): floor(r + 0.5),
     or one more where py + 0.5 + r rounds up to an integer (r just below k + 0.5)."""
     r = np.float32(radius)
     if not r < height:

@@ -519,7 +519,7 @@ def test_identity_cast_kernel_bit_exact(native_lib, golden_luts, monkeypatch, ca
     """The cast kernel without instance space (every instance's inverse exactly the identity, as
     for every OBJ shape: IDENT in dscene.h) against the kernel that keeps it (DCRT_IDENT_CAST=0),
     as the cache-only kernel and (DCRT_NO_LDS_CACHE=1) as the global-memory one -- and the cache-only
-    one over the entry-free node order (FLAT, tracer.hip EntryFreeLayout: cast_identity 2) against
+    one over the entry-free node order (FLAT, bvh_layout.h EntryFreeLayout: cast_identity 2) against
     it over PackBVH's (DCRT_FLAT_CAST=0): the same samples, RNG state, film and ray counts bit for
     bit, and the instrumented traversal counts (node visits, triangle tests, BLAS entries) equal."""
     from directcomputeraytracing_amd import FILTER_BOX, FilterParams, WavefrontPathTracer
@@ -905,7 +905,7 @@ def test_stack_ring_and_split_casts_bit_exact(native_lib, golden_luts, oracle_mo
 @pytest.mark.parametrize("scene_name", ["cornell", "xml_mix"])
 def test_pair_order_trace_rays_and_megakernel_bit_exact(native_lib, golden_luts, oracle_mod, monkeypatch, scene_name):
     """The kernels that read the node order from the scene (trace_rays' batch kernel, the
-    megakernel) on the child-pair order (tracer.hip PairLayout: forced here with the LDS cache
+    megakernel) on the child-pair order (bvh_layout.h PairLayout: forced here with the LDS cache
     off), against the oracle on PackBVH's order."""
     from conftest import GOLDEN
     from directcomputeraytracing_amd import Scene, WavefrontPathTracer
