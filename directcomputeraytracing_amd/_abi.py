@@ -147,6 +147,12 @@ class ConvergeParams(C.Structure):
                 ("max_images", C.c_uint32), ("check_interval", C.c_uint32)]
 
 
+class AdaptiveReport(C.Structure):
+    """dcrt_adaptive_report of dcrt_tracer_render_adaptive."""
+    _fields_ = [("images", C.c_uint32), ("check_points", C.c_uint32), ("pixel_samples", C.c_uint64),
+                ("active_blocks", C.c_uint32), ("total_blocks", C.c_uint32)]
+
+
 class RayStats(C.Structure):
     _fields_ = [("extension_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("new_paths", C.c_uint64),
                 ("iterations", C.c_uint64), ("images_completed", C.c_uint64)]
@@ -348,6 +354,14 @@ SIGNATURES = [
     ("dcrt_tracer_read_noise_maps", _I, [_P, _FP, _FP]),
     ("dcrt_tracer_render_converged", _I, [_P, _U, C.POINTER(ConvergeParams), C.POINTER(FilterParams), C.POINTER(NoiseStats),
                                           C.POINTER(C.c_int)]),
+    ("dcrt_tracer_set_adaptive", _I, [_P, _I]),
+    ("dcrt_tracer_set_sample_blocks", _I, [_P, C.POINTER(C.c_uint32), _U]),
+    ("dcrt_tracer_get_sample_blocks", _I, [_P, C.POINTER(C.c_uint32), _U, C.POINTER(C.c_uint32)]),
+    ("dcrt_tracer_update_sample_blocks", _I, [_P, C.c_float, _U, C.POINTER(C.c_uint32)]),
+    ("dcrt_tracer_sample_blocks_device", _I, [_P, _U, _U, _P, _P, C.c_float, _U, _P, _P, C.POINTER(C.c_uint32)]),
+    ("dcrt_tracer_adaptive_timings", _I, [_P, _FP, _FP, _FP]),
+    ("dcrt_tracer_render_adaptive", _I, [_P, _U, C.POINTER(ConvergeParams), _U, C.POINTER(FilterParams), C.POINTER(NoiseStats),
+                                         C.POINTER(C.c_int), C.POINTER(AdaptiveReport)]),
     ("dcrt_write_bmp", _I, [C.c_char_p, _U, _U, C.POINTER(C.c_uint8)]),
     ("dcrt_device_math_eval", _I, [_P, _I, _FP, _U, _FP]),
 ]

@@ -320,6 +320,9 @@ struct Film {
     float4* accum;            // W*H RGBA32F (sum w*L, sum w)
     const uint32_t* rowY;     // the rows this tracer path-traces (8 per block row), ascending
     const uint32_t* rowOwned; // per film row: 1 if this tracer convolves it (nullptr: all rows)
+    // adaptive sampling (dcrt_tracer_set_adaptive): the blocks of an image that still start paths,
+    // band * blocksX + bx ascending, fc.blocksPerImage of them (nullptr: every block)
+    const uint32_t* blockList;
     uint32_t width, height, rowCount;
 };
 
@@ -372,12 +375,15 @@ DEV Rng new_path(const FrameConstants& fc, uint32_t p, V3* o, V3* d)
 }
 
 // Pixel of lane `lane` in claimed block `block` of the batch: image, then 8-row group,
-// then 8-column block. False for lanes outside the film or past the last rendered row.
+// then 8-column block (block k of an image is film.blockList[k] under adaptive sampling: a
+// wave-uniform branch on a kernel argument, one scalar load when it is taken). False for lanes
+// outside the film or past the last rendered row.
 DEV bool block_pixel(const FrameConstants& fc, const Film& film, uint32_t block, uint32_t lane, uint32_t* px, uint32_t* py,
                      uint32_t* image)
 {
     *image = block / fc.blocksPerImage;
-    const uint32_t local = block - *image * fc.blocksPerImage;
+    uint32_t local = block - *image * fc.blocksPerImage;
+    if (film.blockList) local = film.blockList[local];
     const uint32_t band = local / fc.blocksX, bx = local - band * fc.blocksX;
     const uint32_t ri = band * kBlockH + lane / kBlockW;
     *px = bx * kBlockW + (lane % kBlockW);

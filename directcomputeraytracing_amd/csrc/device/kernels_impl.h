@@ -1957,6 +1957,19 @@ __global__ __launch_bounds__(128) void luminance_single_kernel(const float* in, 
 // ---- film noise estimate (dcrt.h "film noise estimate"; tests/noise_ref.py restates it) -------
 constexpr int kNoiseTile = 16;
 struct NoiseTotals { uint32_t valid, converged; float total, maxError, maxTileError; };
+// A pixel's error e of the film value f against the half film's h (dcrt.h): false, and e left
+// alone, for an invalid pixel (either weight not positive).
+__device__ __forceinline__ bool noise_pixel_error(float4 f, float4 h, float* e)
+{
+    if (!(f.w > 0.0f && h.w > 0.0f)) return false;
+    const float cr = f.x / f.w, cg = f.y / f.w, cb = f.z / f.w;
+    const float ar = h.x / h.w, ag = h.y / h.w, ab = h.z / h.w;
+    const float d = (fabsf(cr - ar) + fabsf(cg - ag)) + fabsf(cb - ab);
+    const float s = (cr + cg) + cb;
+    const float n = sqrtf(fmaxf(s, 0.0f));
+    *e = d / (n + 1e-4f);
+    return true;
+}
 // One 16x16 pixel tile per workgroup: the per-pixel error e of the film against its half film,
 // the tile's sum of e (LDS tree 128 -> 1), valid / converged counts and fmaxf maximum.
 __global__ __launch_bounds__(kNoiseTile * kNoiseTile) void noise_tile_kernel(const float4* film, const float4* half, uint32_t W, uint32_t H,
@@ -1973,15 +1986,8 @@ __global__ __launch_bounds__(kNoiseTile * kNoiseTile) void noise_tile_kernel(con
     uint32_t valid = 0u, converged = 0u;
     if (x < W && y < H) {
         const size_t p = (size_t)y * W + x;
-        const float4 f = film[p], h = half[p];
-        if (f.w > 0.0f && h.w > 0.0f) {
+        if (noise_pixel_error(film[p], half[p], &e)) {
             valid = 1u;
-            const float cr = f.x / f.w, cg = f.y / f.w, cb = f.z / f.w;
-            const float ar = h.x / h.w, ag = h.y / h.w, ab = h.z / h.w;
-            const float d = (fabsf(cr - ar) + fabsf(cg - ag)) + fabsf(cb - ab);
-            const float s = (cr + cg) + cb;
-            const float n = sqrtf(fmaxf(s, 0.0f));
-            e = d / (n + 1e-4f);
             converged = e <= threshold ? 1u : 0u;
         }
         if (pixelMap) pixelMap[p] = e;
@@ -2046,6 +2052,110 @@ __global__ __launch_bounds__(256) void noise_finish_kernel(const float* tileMax,
         out->maxTileError = top[1][0];
     }
 }
+
+// ---- adaptive sampling (dcrt.h "adaptive sampling"; tests/adaptive_ref.py restates it) --------
+// One flag per 8x8 pixel block of a W x H film: 1 while some film pixel within `margin` pixels of
+// the block is not converged -- invalid, or !(e <= threshold), so a NaN e counts -- else 0. One
+// wave per block, its lanes striding over the block's window (clamped to the film), leaving at
+// the first chunk that holds such a pixel. No barrier: a wave past the last block just returns.
+__global__ __launch_bounds__(256) void sample_mask_kernel(const float4* film, const float4* half, uint32_t W, uint32_t H, float threshold,
+                                                          uint32_t margin, uint32_t blocksX, uint32_t blocks, uint32_t* flags)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t b = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (b >= blocks) return;
+    const uint32_t by = b / blocksX, bx = b - by * blocksX;
+    const uint32_t bx0 = bx * kBlockW, by0 = by * kBlockH;
+    const uint32_t x0 = bx0 > margin ? bx0 - margin : 0u, y0 = by0 > margin ? by0 - margin : 0u;
+    const uint32_t x1 = (uint32_t)min((unsigned long long)bx0 + (kBlockW - 1u) + margin, (unsigned long long)W - 1u);
+    const uint32_t y1 = (uint32_t)min((unsigned long long)by0 + (kBlockH - 1u) + margin, (unsigned long long)H - 1u);
+    const uint32_t ww = x1 - x0 + 1u, n = ww * (y1 - y0 + 1u);   // (<= W * H <= 65535^2: base + 64 cannot wrap)
+    uint32_t active = 0u;
+    for (uint32_t base = 0; base < n; base += 64u) {
+        const uint32_t i = base + lane;
+        bool noisy = false;
+        if (i < n) {
+            const uint32_t wy = i / ww, wx = i - wy * ww;
+            const size_t p = (size_t)(y0 + wy) * W + (x0 + wx);
+            float e = 0.0f;
+            noisy = !noise_pixel_error(film[p], half[p], &e) || !(e <= threshold);
+        }
+        if (__ballot(noisy) != 0ull) { active = 1u; break; }
+    }
+    if (lane == 0) flags[b] = active;
+}
+
+// The flags' ascending list of active blocks: one workgroup walks the flags 256 at a time, a
+// wave ballot + mbcnt gives each active block its place in its wave, an LDS scan of the four wave
+// counts its place in the chunk. out[0] = the count, out[1] = the in-film pixels of the listed
+// blocks (the paths an image starts; partial edge blocks count their pixels inside the film).
+__global__ __launch_bounds__(256) void compact_blocks_kernel(const uint32_t* flags, uint32_t blocks, uint32_t blocksX, uint32_t W, uint32_t H,
+                                                             uint32_t* list, uint32_t* out)
+{
+    __shared__ uint32_t ws[4];
+    __shared__ uint32_t pix[4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t base = 0u, pixels = 0u;
+    for (uint32_t start = 0; start < blocks; start += 256u) {
+        const uint32_t i = start + threadIdx.x;
+        const bool a = i < blocks && flags[i] != 0u;
+        const unsigned long long m = __ballot(a);
+        const uint32_t x = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        if (lane == 0) ws[wave] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t off = 0u, total = 0u;
+        for (uint32_t w = 0; w < 4u; ++w) {
+            const uint32_t c = ws[w];
+            off += w < wave ? c : 0u;
+            total += c;
+        }
+        if (a) {
+            list[base + off + x] = i;
+            const uint32_t by = i / blocksX, bx = i - by * blocksX;
+            pixels += min(kBlockW, W - bx * kBlockW) * min(kBlockH, H - by * kBlockH);
+        }
+        base += total;
+        __syncthreads();   // (ws is rewritten by the next chunk)
+    }
+    const uint32_t s = (uint32_t)wave_sum(pixels);   // (<= W * H < 2^32)
+    if (lane == 0) pix[wave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        out[0] = base;
+        out[1] = (pix[0] + pix[1]) + (pix[2] + pix[3]);
+    }
+}
+
+// Every block active: flags 1, list 0 .. blocks-1 (the list before any mask, and after a clear)
+__global__ void all_blocks_kernel(uint32_t* flags, uint32_t* list, uint32_t blocks)
+{
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < blocks; i += gridDim.x * blockDim.x) {
+        flags[i] = 1u;
+        list[i] = i;
+    }
+}
+
+// The sentinel sample -- position (+inf, +inf), value 0, which every reconstruction filter weighs
+// with exactly +0 -- into the pixels of the inactive blocks of `slots` sample images, so that a
+// film pass over the slots adds nothing for the pixels no path was started in.
+__global__ __launch_bounds__(256) void fill_inactive_samples_kernel(float2* pos, float4* val, const uint32_t* flags, uint32_t W, uint32_t H,
+                                                                    uint32_t blocksX, uint32_t slots)
+{
+    const uint32_t total = W * H;
+    const float2 sp = make_float2(inf(), inf());
+    const float4 sv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (unsigned long long pp = blockIdx.x * blockDim.x + threadIdx.x; pp < total; pp += gridDim.x * blockDim.x) {
+        const uint32_t p = (uint32_t)pp;
+        const uint32_t y = p / W, x = p - y * W;
+        if (flags[(y / kBlockH) * blocksX + x / kBlockW] != 0u) continue;
+        for (uint32_t s = 0; s < slots; ++s) {
+            const size_t q = (size_t)s * total + p;
+            pos[q] = sp;
+            val[q] = sv;
+        }
+    }
+}
+
 // MainPS: rgb / w -> exposure -> Reinhard -> R8G8B8A8_UNORM_SRGB (encode by host-made thresholds)
 __global__ __launch_bounds__(256) void postfx_kernel(const float4* film, uint32_t W, uint32_t H, int enabled, int autoExposure,
                                                      float ev100, float maxWhiteSqr, const float* sumLogLum,

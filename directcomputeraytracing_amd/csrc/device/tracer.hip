@@ -507,6 +507,34 @@ struct dcrt_tracer {
     float *noisePixelMap = nullptr, *noiseTileMap = nullptr;
     bool hasNoiseMaps = false;
 
+    // ---- adaptive sampling (dcrt_tracer_set_adaptive): one flag per 8x8 block of the film and the
+    // ascending list of the active ones, both with room for every block (adaptiveAllocs: they
+    // follow the film's size); RenderImages' kernels get `dBlockList` and the list's length as
+    // blocksPerImage, every other launch the plain film. maskAllocs: sample_blocks_device's
+    // scratch (the count words, flags when the caller passes none) ----
+    bool adaptive = false;
+    std::vector<void*> adaptiveAllocs, maskAllocs;
+    uint32_t* dBlockFlags = nullptr;
+    uint32_t* dBlockList = nullptr;
+    uint32_t* dMaskCount = nullptr;    // [2]: compact_blocks_kernel's count and in-film pixels
+    uint32_t* dMaskFlags = nullptr;
+    uint32_t maskFlagCap = 0;
+    uint32_t blockTotal = 0;           // blocks of the film: blocksX * ceil(H / 8)
+    uint32_t listCount = 0;            // active blocks
+    uint32_t listPixels = 0;           // their pixels inside the film: the paths an image starts
+    bool inactiveFilled = false;       // every slot's inactive pixels hold the sentinel sample
+    bool listFrame = false;            // BeginImage: the frame constants' blocksPerImage is the list's length
+    uint64_t pathsSkipped = 0;         // pixels the lists left out since the last ResetStats (counters())
+    // ext_timing: events around the last mask, compaction and fill kernels (dcrt_tracer_adaptive_timings)
+    hipEvent_t adEvents[5] = {};
+    bool adMaskTimed = false, adFillTimed = false;
+    int AdaptiveEvents()
+    {
+        for (hipEvent_t& e : adEvents)
+            if (!e) HIPCHECK(hipEventCreate(&e));
+        return DCRT_OK;
+    }
+
     ~dcrt_tracer();
     int Create(const dcrt_tracer_config& cfg);
     int BuildLuts();
@@ -566,6 +594,18 @@ struct dcrt_tracer {
     int NoiseOwn(float threshold, dcrt_noise_stats* out);
     int RenderConverged(uint32_t firstSeed, const dcrt_converge_params& p, const dcrt_filter_params& filter, dcrt_noise_stats* outStats,
                         int* outConverged);
+    // adaptive sampling
+    int SetAdaptive(bool on);
+    int AllocBlockList();
+    int ResetBlockList();
+    int SetSampleBlocks(const uint32_t* blocks, uint32_t count);
+    int GetSampleBlocks(uint32_t* out, uint32_t capacity, uint32_t* outCount);
+    int SampleBlocks(uint32_t w, uint32_t h, const float4* f, const float4* hf, float threshold, uint32_t margin, uint32_t* flags,
+                     uint32_t* list, uint32_t* outCount, uint32_t* outPixels);
+    int UpdateSampleBlocks(float threshold, uint32_t margin, uint32_t* outActive);
+    int FillInactive();
+    int RenderAdaptive(uint32_t firstSeed, const dcrt_converge_params& p, uint32_t margin, const dcrt_filter_params& filter,
+                       dcrt_noise_stats* outStats, int* outConverged, dcrt_adaptive_report* report);
 
     // One device array of the scene: allocated (sceneAllocs), filled from `src` and counted in `*counted`
     template <typename T>
@@ -630,10 +670,13 @@ dcrt_tracer::~dcrt_tracer()
     for (hipEvent_t e : events) (void)hipEventDestroy(e);
     for (hipEvent_t e : stopEvents) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : dnEvents) (void)hipEventDestroy(e);
+    for (hipEvent_t e : adEvents) if (e) (void)hipEventDestroy(e);
     FreeAll(&denoiseAllocs);
     FreeAll(&halfAllocs);
     FreeAll(&noiseAllocs);
     FreeAll(&noiseMapAllocs);
+    FreeAll(&adaptiveAllocs);
+    FreeAll(&maskAllocs);
     if (hFilter) (void)hipHostFree(hFilter);
     if (dSourceLists) (void)hipFree(dSourceLists);
     if (hStop) (void)hipHostFree(hStop);
@@ -1374,7 +1417,8 @@ int dcrt_tracer::EnsureFilm(uint32_t w, uint32_t h)
     filmW = w; filmH = h;
     film.width = w; film.height = h;
     CHECKED(EnsureSamples(1));
-    return BuildRows();
+    CHECKED(BuildRows());
+    return adaptive ? AllocBlockList() : DCRT_OK;   // (a new resolution: its own blocks, all of them active)
 }
 
 // Sample textures for `images` images (a RenderImages batch); grows only.
@@ -1396,6 +1440,7 @@ int dcrt_tracer::EnsureSamples(uint32_t images)
     HIPCHECK(hipMemcpyAsync(dSampleOut, &hSampleOut, sizeof(SampleOut), hipMemcpyHostToDevice, stream));
     HIPCHECK(hipStreamSynchronize(stream));
     sampleImages = images;
+    inactiveFilled = false;   // (adaptive sampling: the new slots hold no sentinel samples)
     return DCRT_OK;
 }
 
@@ -1414,7 +1459,9 @@ uint32_t dcrt_tracer::AutoBatch(uint32_t count) const
     if (b == 0) {
         // the slots an image takes: whole 8x8 pixel blocks (a wave each), partial bands and
         // columns included, so a batch that "fits" never waits for slots to free up
-        const uint64_t pixels = std::max<uint64_t>(1, (uint64_t)bandCount * kBlockH * ((filmW + kBlockW - 1) / kBlockW) * kBlockW);
+        // (adaptive sampling: the listed blocks alone)
+        const uint64_t blocks = adaptive ? listCount : (uint64_t)bandCount * ((filmW + kBlockW - 1) / kBlockW);
+        const uint64_t pixels = std::max<uint64_t>(1, blocks * kBlockH * kBlockW);
         b = (uint32_t)std::min<uint64_t>(cap, std::max<uint64_t>(1, poolSize / pixels));
         if (!BatchPoolLimit()) b = cap;
         // equal batches: as many batches as the cap needs, each as large as the others (a
@@ -1534,6 +1581,7 @@ int dcrt_tracer::SetPartition(const dcrt_film_partition& p)
         SetLastError("invalid film partition");
         return DCRT_E_INVALID_ARG;
     }
+    if (adaptive && p.world_size > 1) { SetLastError("adaptive sampling is on: the film cannot be partitioned"); return DCRT_E_INVALID_ARG; }
     partition = p;
     bands.clear();
     if (filmW) {
@@ -1552,6 +1600,7 @@ int dcrt_tracer::SetPartition(const dcrt_film_partition& p)
 int dcrt_tracer::SetBands(const uint32_t* b, uint32_t count, uint32_t halo)
 {
     if (count == 0 || !b) { SetLastError("no film bands"); return DCRT_E_INVALID_ARG; }
+    if (adaptive) { SetLastError("adaptive sampling is on: the film cannot be cut into bands"); return DCRT_E_INVALID_ARG; }
     for (uint32_t i = 0; i < count; ++i) {
         if (b[2 * i] >= b[2 * i + 1] || (i > 0 && b[2 * i] < b[2 * i - 1])) {
             SetLastError("film bands: ascending, disjoint, non-empty [y0, y1) ranges");
@@ -1592,7 +1641,8 @@ int dcrt_tracer::BeginImage()
     fc.features = frame.features;
     fc.blocksX = (frame.resolution[0] + kBlockW - 1) / kBlockW;
     fc.bandCount = bandCount;
-    fc.blocksPerImage = fc.blocksX * bandCount;
+    // (adaptive sampling: an image of RenderImages is its listed blocks, film.blockList)
+    fc.blocksPerImage = listFrame ? listCount : fc.blocksX * bandCount;
 #ifndef DCRT_REFILL_GLOBAL
 #define DCRT_REFILL_GLOBAL 28
 #endif
@@ -1647,7 +1697,10 @@ int dcrt_tracer::LaunchIteration(uint32_t par, bool timed, bool sequenced)
     if (timed) CHECKED(TimedPair(kTimedControl, &c0, &c1));
     {
         Annotation a("Control", !capturing);
-        hipExtLaunchKernelGGL(control_kernel, dim3(controlGrid), dim3(kControlBlock), 0, stream, c0, c1, 0, pool, film,
+        // (RenderImages' iterations claim from the block list while adaptive sampling is on)
+        Film claims = film;
+        claims.blockList = sequenced && adaptive ? dBlockList : nullptr;
+        hipExtLaunchKernelGGL(control_kernel, dim3(controlGrid), dim3(kControlBlock), 0, stream, c0, c1, 0, pool, claims,
                               (const FrameConstants*)dFrame, cnt, (const Counters*)next, dGlobals, (uint32_t)(film.debugRng != nullptr));
     }
     auto material = rowProbe ? material_kernel<kCapAll, 0, true>
@@ -1797,6 +1850,7 @@ int dcrt_tracer::Render(uint32_t maxIterations)
     if (!hasScene) { SetLastError("no scene uploaded"); return DCRT_E_NO_SCENE; }
     if (!hasFrame) { SetLastError("no frame parameters"); return DCRT_E_INVALID_ARG; }
     CHECKED(CheckFrameLights());
+    inactiveFilled = false;   // (a progressive or view image fills slot 0 in every block)
     if (output.output_type != DCRT_OUTPUT_PATH_TRACING) {
         // a view image is one launch: the whole image of the current frame seed, complete on return
         keptSlots = false;   // (slot 0 is this image's now)
@@ -1878,6 +1932,7 @@ int dcrt_tracer::RenderGuides(uint32_t firstSeed, uint32_t count)
     HIPCHECK(hipMemsetAsync(guideAlbedo, 0, n * sizeof(float4), stream));
     guidesRendered = false;
     keptSlots = false;   // (slot 0 holds the last guide image now)
+    inactiveFilled = false;
     lastSlot = 0;
     const uint32_t seed = frame.frame_seed;
     int rc = DCRT_OK;
@@ -2041,15 +2096,26 @@ int dcrt_tracer::RenderImages(uint32_t firstSeed, uint32_t count, const dcrt_fil
     // MegakernelPathTracer::Render: one persistent launch + SampleConvolution per image -- the
     // path-tracing megakernel, or the first-hit kernel of the selected output view
     const bool view = output.output_type != DCRT_OUTPUT_PATH_TRACING;
+    // adaptive sampling: the path-traced images start paths in the listed blocks only (the views
+    // run over every block)
+    const bool listed = adaptive && !view;
+    if (listed && listCount == 0) { SetLastError("adaptive sampling: nothing left to sample (the block list is empty)"); return DCRT_E_INVALID_ARG; }
     if (view || mode == 1) {
         if (!convolve) {
             SetLastError(view ? "an output view convolves every image" : "the megakernel mode convolves every image");
             return DCRT_E_INVALID_ARG;
         }
         CHECKED(UploadFilter(filter));
+        if (listed) CHECKED(FillInactive());
+        if (view) inactiveFilled = false;   // (slot 0 gets a whole view image)
+        Film claims = film;
+        claims.blockList = listed ? dBlockList : nullptr;
         for (uint32_t img = 0; img < count; ++img) {
             frame.frame_seed = firstSeed + img * seedStride;
-            CHECKED(BeginImage());
+            listFrame = listed;
+            const int rc = BeginImage();
+            listFrame = false;
+            CHECKED(rc);
             if (view) {
                 CHECKED(LaunchView());
             } else {
@@ -2057,7 +2123,7 @@ int dcrt_tracer::RenderImages(uint32_t firstSeed, uint32_t count, const dcrt_fil
                 if (extTiming) CHECKED(TimedPair(kTimedCast, &e0, &e1));
                 auto mk = (frame.features & DCRT_FEATURE_ALLOW_ANYHIT) ? megakernel<true> : megakernel<false>;
                 hipExtLaunchKernelGGL(mk, dim3(megaResident), dim3(plan.block), plan.ldsWholeStack, stream, e0, e1, 0, plan.scene,
-                                      (const FrameConstants*)dFrame, film, dGlobals, (uint32_t)(film.debugRng != nullptr));
+                                      (const FrameConstants*)dFrame, claims, dGlobals, (uint32_t)(film.debugRng != nullptr));
             }
             CHECKED(LaunchFilm(1u, nullptr, nullptr, nullptr, filmImages));
             HIPCHECK(hipGetLastError());
@@ -2067,6 +2133,7 @@ int dcrt_tracer::RenderImages(uint32_t firstSeed, uint32_t count, const dcrt_fil
         imageComplete = true;
         newImage = true;
         imagesCompleted += count;
+        if (listed) pathsSkipped += (uint64_t)count * ((uint64_t)rowCount * filmW - listPixels);
         return DCRT_OK;
     }
     uint32_t batch = AutoBatch(count);
@@ -2079,7 +2146,11 @@ int dcrt_tracer::RenderImages(uint32_t firstSeed, uint32_t count, const dcrt_fil
     CHECKED(EnsureSamples(batch));
     frame.frame_seed = firstSeed;
     CHECKED(UploadFilter(filter));
-    CHECKED(BeginImage());
+    if (listed) CHECKED(FillInactive());   // (after EnsureSamples: the slots the film pass reads)
+    listFrame = listed;
+    const int began = BeginImage();
+    listFrame = false;
+    CHECKED(began);
     // static batch-start claims: one per wave of CONTROL's virtual workgroups
     const uint32_t staticGrid = poolSize / kControlBlock;
     hipLaunchKernelGGL(begin_images_kernel, dim3(1), dim3(64), 0, stream, dGlobals, (const FrameConstants*)dFrame, count, firstSeed, batch,
@@ -2135,6 +2206,7 @@ int dcrt_tracer::RenderImages(uint32_t firstSeed, uint32_t count, const dcrt_fil
     imageComplete = true;
     newImage = true;
     imagesCompleted += count;
+    if (listed) pathsSkipped += (uint64_t)count * ((uint64_t)rowCount * filmW - listPixels);
     if (convolve) filmImages += count;
     lastSlot = (count - 1) % batch;
     keptSlots = !convolve;
@@ -2210,6 +2282,7 @@ int dcrt_tracer::ClearFilm()
     HIPCHECK(hipMemsetAsync(film.accum, 0, bytes, stream));
     if (halfFilm) HIPCHECK(hipMemsetAsync(halfFilm, 0, bytes, stream));
     filmImages = 0;
+    if (adaptive) CHECKED(ResetBlockList());   // (an empty film is noisy everywhere)
     return DCRT_OK;
 }
 
@@ -2319,6 +2392,219 @@ int dcrt_tracer::RenderConverged(uint32_t firstSeed, const dcrt_converge_params&
         }
         if (filmImages >= p.max_images) return DCRT_OK;
     }
+}
+
+// ---- adaptive sampling (dcrt.h "adaptive sampling") -----------------------------------------
+// The flag and list buffers of the film's blocks (room for every block, so film.blockList is one
+// pointer while the resolution stands), the list set to every block.
+int dcrt_tracer::AllocBlockList()
+{
+    HIPCHECK(hipStreamSynchronize(stream));
+    InvalidateGraph();   // (captured CONTROL launches hold the old list pointer)
+    FreeAll(&adaptiveAllocs);
+    dBlockFlags = dBlockList = nullptr;
+    blockTotal = ((filmW + kBlockW - 1) / kBlockW) * ((filmH + kBlockH - 1) / kBlockH);
+    CHECKED(DeviceAlloc(&dBlockFlags, blockTotal, &adaptiveAllocs));
+    CHECKED(DeviceAlloc(&dBlockList, blockTotal, &adaptiveAllocs));
+    return ResetBlockList();
+}
+
+int dcrt_tracer::ResetBlockList()
+{
+    hipLaunchKernelGGL(all_blocks_kernel, dim3(std::min<uint32_t>((blockTotal + 255) / 256, kMaxPersistentBlocks)), dim3(256), 0, stream,
+                       dBlockFlags, dBlockList, blockTotal);
+    HIPCHECK(hipGetLastError());
+    listCount = blockTotal;
+    listPixels = filmW * filmH;
+    inactiveFilled = false;
+    return DCRT_OK;
+}
+
+int dcrt_tracer::SetAdaptive(bool on)
+{
+    if (!film.accum) { SetLastError("set_adaptive: no film (set the frame parameters first)"); return DCRT_E_INVALID_ARG; }
+    if (on && (partition.world_size > 1 || !bands.empty())) {
+        SetLastError("set_adaptive: not on a partitioned or banded film");
+        return DCRT_E_INVALID_ARG;
+    }
+    HIPCHECK(hipStreamSynchronize(stream));
+    if (on == adaptive) return on ? ResetBlockList() : DCRT_OK;
+    InvalidateGraph();   // (the in-graph CONTROL launches take another Film)
+    adaptive = on;
+    if (on) return AllocBlockList();
+    FreeAll(&adaptiveAllocs);
+    dBlockFlags = dBlockList = nullptr;
+    blockTotal = listCount = listPixels = 0;
+    return DCRT_OK;
+}
+
+int dcrt_tracer::SetSampleBlocks(const uint32_t* blocks, uint32_t count)
+{
+    if (!adaptive) { SetLastError("set_sample_blocks: adaptive sampling is off (dcrt_tracer_set_adaptive)"); return DCRT_E_INVALID_ARG; }
+    if (count > blockTotal || (count && !blocks)) { SetLastError("set_sample_blocks: more blocks than the film has"); return DCRT_E_INVALID_ARG; }
+    const uint32_t blocksX = (filmW + kBlockW - 1) / kBlockW;
+    std::vector<uint32_t> flags(blockTotal, 0u);
+    uint64_t pixels = 0;
+    for (uint32_t i = 0; i < count; ++i) {
+        if (blocks[i] >= blockTotal || (i > 0 && blocks[i] <= blocks[i - 1])) {
+            SetLastError("set_sample_blocks: block indices are strictly ascending and below blocksX * ceil(H / 8)");
+            return DCRT_E_INVALID_ARG;
+        }
+        flags[blocks[i]] = 1u;
+        const uint32_t by = blocks[i] / blocksX, bx = blocks[i] - by * blocksX;
+        pixels += (uint64_t)std::min(kBlockW, filmW - bx * kBlockW) * std::min(kBlockH, filmH - by * kBlockH);
+    }
+    HIPCHECK(hipStreamSynchronize(stream));
+    HIPCHECK(hipMemcpy(dBlockFlags, flags.data(), (size_t)blockTotal * 4, hipMemcpyHostToDevice));
+    if (count) HIPCHECK(hipMemcpy(dBlockList, blocks, (size_t)count * 4, hipMemcpyHostToDevice));
+    listCount = count;
+    listPixels = (uint32_t)pixels;
+    inactiveFilled = false;
+    return DCRT_OK;
+}
+
+int dcrt_tracer::GetSampleBlocks(uint32_t* out, uint32_t capacity, uint32_t* outCount)
+{
+    if (!adaptive) { SetLastError("get_sample_blocks: adaptive sampling is off (dcrt_tracer_set_adaptive)"); return DCRT_E_INVALID_ARG; }
+    if (!outCount || (capacity && !out)) return DCRT_E_INVALID_ARG;
+    *outCount = listCount;
+    const uint32_t n = std::min(capacity, listCount);
+    if (n) {
+        HIPCHECK(hipMemcpyAsync(out, dBlockList, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+        HIPCHECK(hipStreamSynchronize(stream));
+    }
+    return DCRT_OK;
+}
+
+// sample_mask_kernel + compact_blocks_kernel over a film and its half film; the copy of the count
+// (and the listed blocks' pixels) is the one synchronisation.
+int dcrt_tracer::SampleBlocks(uint32_t w, uint32_t h, const float4* f, const float4* hf, float threshold, uint32_t margin, uint32_t* flags,
+                              uint32_t* list, uint32_t* outCount, uint32_t* outPixels)
+{
+    Annotation an("Sample blocks");
+    if (!f || !hf || !list || !outCount || w == 0 || h == 0 || w > 65535u || h > 65535u) return DCRT_E_INVALID_ARG;
+    if (!(threshold >= 0.0f)) { SetLastError("sample blocks: the threshold is negative or NaN"); return DCRT_E_INVALID_ARG; }
+    const uint32_t blocksX = (w + kBlockW - 1) / kBlockW, blocks = blocksX * ((h + kBlockH - 1) / kBlockH);
+    if (!dMaskCount || (!flags && blocks > maskFlagCap)) {
+        HIPCHECK(hipStreamSynchronize(stream));
+        FreeAll(&maskAllocs);
+        dMaskCount = dMaskFlags = nullptr;
+        maskFlagCap = 0;
+        CHECKED(DeviceAlloc(&dMaskCount, 2, &maskAllocs));
+        if (!flags) {
+            CHECKED(DeviceAlloc(&dMaskFlags, blocks, &maskAllocs));
+            maskFlagCap = blocks;
+        }
+    }
+    if (!flags) flags = dMaskFlags;
+    adMaskTimed = false;
+    if (extTiming) {
+        CHECKED(AdaptiveEvents());
+        HIPCHECK(hipEventRecord(adEvents[0], stream));
+    }
+    hipLaunchKernelGGL(sample_mask_kernel, dim3((blocks + 3) / 4), dim3(256), 0, stream, f, hf, w, h, threshold, margin, blocksX, blocks, flags);
+    if (extTiming) HIPCHECK(hipEventRecord(adEvents[1], stream));
+    hipLaunchKernelGGL(compact_blocks_kernel, dim3(1), dim3(256), 0, stream, (const uint32_t*)flags, blocks, blocksX, w, h, list, dMaskCount);
+    if (extTiming) {
+        HIPCHECK(hipEventRecord(adEvents[2], stream));
+        adMaskTimed = true;
+    }
+    HIPCHECK(hipGetLastError());
+    uint32_t* host = (uint32_t*)hCounters;   // (pinned staging)
+    HIPCHECK(hipMemcpyAsync(host, dMaskCount, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+    *outCount = host[0];
+    if (outPixels) *outPixels = host[1];
+    return DCRT_OK;
+}
+
+// ... of the tracer's own film and half film into its own list
+int dcrt_tracer::UpdateSampleBlocks(float threshold, uint32_t margin, uint32_t* outActive)
+{
+    if (!adaptive) { SetLastError("update_sample_blocks: adaptive sampling is off (dcrt_tracer_set_adaptive)"); return DCRT_E_INVALID_ARG; }
+    if (!convergence || !halfFilm) { SetLastError("update_sample_blocks: convergence is off (dcrt_tracer_set_convergence)"); return DCRT_E_INVALID_ARG; }
+    if (filmImages < 2) { SetLastError("update_sample_blocks: the film holds fewer than 2 images"); return DCRT_E_INVALID_ARG; }
+    if (!(threshold >= 0.0f)) { SetLastError("update_sample_blocks: the threshold is negative or NaN"); return DCRT_E_INVALID_ARG; }
+    if (margin == 0xFFFFFFFFu) {
+        if (!hasFilter) { SetLastError("update_sample_blocks: no film pass has set the filter the default margin follows"); return DCRT_E_INVALID_ARG; }
+        margin = FilterSupportRows(lastFilter.radius, filmH);
+    }
+    uint32_t count = 0, pixels = 0;
+    CHECKED(SampleBlocks(filmW, filmH, film.accum, halfFilm, threshold, margin, dBlockFlags, dBlockList, &count, &pixels));
+    listCount = count;
+    listPixels = pixels;
+    inactiveFilled = false;
+    if (outActive) *outActive = count;
+    return DCRT_OK;
+}
+
+// The sentinel sample into every slot's inactive pixels. It runs before a listed RenderImages
+// whenever a slot's inactive pixels may hold older samples: the list changed, EnsureSamples
+// allocated or grew the slots, or a progressive / view / guide image went through slot 0.
+int dcrt_tracer::FillInactive()
+{
+    if (inactiveFilled) return DCRT_OK;
+    if (listCount < blockTotal) {
+        const uint32_t n = filmW * filmH;
+        adFillTimed = false;
+        if (extTiming) {
+            CHECKED(AdaptiveEvents());
+            HIPCHECK(hipEventRecord(adEvents[3], stream));
+        }
+        hipLaunchKernelGGL(fill_inactive_samples_kernel, dim3(std::min<uint32_t>((n + 255) / 256, 8u * kMaxPersistentBlocks)), dim3(256), 0, stream,
+                           film.samplePosition, film.sampleValue, (const uint32_t*)dBlockFlags, filmW, filmH, (filmW + kBlockW - 1) / kBlockW,
+                           sampleImages);
+        HIPCHECK(hipGetLastError());
+        if (extTiming) {
+            HIPCHECK(hipEventRecord(adEvents[4], stream));
+            adFillTimed = true;
+        }
+    }
+    inactiveFilled = true;
+    return DCRT_OK;
+}
+
+// RenderConverged's loop with the block list rebuilt at every check point that goes on: the list
+// is a function of the film, the half film, the threshold and the margin alone, so a block whose
+// neighbourhood turns noisy again wakes up. The call starts on every block.
+int dcrt_tracer::RenderAdaptive(uint32_t firstSeed, const dcrt_converge_params& p, uint32_t margin, const dcrt_filter_params& filter,
+                                dcrt_noise_stats* outStats, int* outConverged, dcrt_adaptive_report* report)
+{
+    if (!adaptive) { SetLastError("render_adaptive: adaptive sampling is off (dcrt_tracer_set_adaptive)"); return DCRT_E_INVALID_ARG; }
+    if (!convergence || !halfFilm) { SetLastError("render_adaptive: convergence is off (dcrt_tracer_set_convergence)"); return DCRT_E_INVALID_ARG; }
+    if (!(p.threshold >= 0.0f) || !(p.target_fraction > 0.0f && p.target_fraction <= 1.0f) || p.min_images < 2u ||
+        p.max_images < p.min_images || p.check_interval < 1u) {
+        SetLastError("render_adaptive: threshold >= 0, 0 < target_fraction <= 1, 2 <= min_images <= max_images, check_interval >= 1");
+        return DCRT_E_INVALID_ARG;
+    }
+    CHECKED(dcrt::CheckFilterParams(filter));
+    if (margin == 0xFFFFFFFFu) margin = FilterSupportRows(filter.radius, filmH);
+    CHECKED(ResetBlockList());
+    *outConverged = 0;
+    dcrt_adaptive_report rep{};
+    rep.total_blocks = blockTotal;
+    rep.active_blocks = listCount;
+    int rc = DCRT_OK;
+    for (uint64_t point = p.min_images; rc == DCRT_OK; point += p.check_interval) {
+        const uint32_t target = (uint32_t)std::min<uint64_t>(point, p.max_images);
+        if (filmImages < target) {
+            const uint32_t n = target - filmImages;
+            rc = RenderImages(firstSeed + filmImages, n, filter);
+            if (rc != DCRT_OK) break;
+            rep.images += n;
+            rep.pixel_samples += (uint64_t)n * listPixels;
+        }
+        if (filmImages < target) { SetLastError("render_adaptive: the images did not reach the film"); rc = DCRT_E_LIMIT; break; }
+        rc = NoiseOwn(p.threshold, outStats);
+        if (rc != DCRT_OK) break;
+        ++rep.check_points;
+        if ((double)outStats->converged_pixels >= (double)p.target_fraction * (double)outStats->valid_pixels) { *outConverged = 1; break; }
+        if (filmImages >= p.max_images) break;
+        rc = UpdateSampleBlocks(p.threshold, margin, &rep.active_blocks);
+        if (rc == DCRT_OK && rep.active_blocks == 0u) { *outConverged = 1; break; }
+    }
+    if (report) *report = rep;
+    return rc;
 }
 
 // ============================ C ABI ========================================
@@ -2683,6 +2969,62 @@ DCRT_API int dcrt_tracer_render_converged(dcrt_tracer* t, uint32_t first_seed, c
     return t->RenderConverged(first_seed, *p, *f, out_stats, out_converged);
 }
 
+// ---- adaptive sampling ------------------------------------------------------------------------
+DCRT_API int dcrt_tracer_set_adaptive(dcrt_tracer* t, int enable)
+{
+    TRACER_GUARD(t);
+    return t->SetAdaptive(enable != 0);
+}
+
+DCRT_API int dcrt_tracer_set_sample_blocks(dcrt_tracer* t, const uint32_t* blocks, uint32_t count)
+{
+    TRACER_GUARD(t);
+    return t->SetSampleBlocks(blocks, count);
+}
+
+DCRT_API int dcrt_tracer_get_sample_blocks(dcrt_tracer* t, uint32_t* out, uint32_t capacity, uint32_t* out_count)
+{
+    TRACER_GUARD(t);
+    return t->GetSampleBlocks(out, capacity, out_count);
+}
+
+DCRT_API int dcrt_tracer_update_sample_blocks(dcrt_tracer* t, float threshold, uint32_t margin, uint32_t* out_active)
+{
+    TRACER_GUARD(t);
+    return t->UpdateSampleBlocks(threshold, margin, out_active);
+}
+
+DCRT_API int dcrt_tracer_sample_blocks_device(dcrt_tracer* t, uint32_t width, uint32_t height, const void* d_film, const void* d_half,
+                                              float threshold, uint32_t margin, void* d_flags, void* d_list, uint32_t* out_count)
+{
+    TRACER_GUARD(t);
+    return t->SampleBlocks(width, height, (const float4*)d_film, (const float4*)d_half, threshold, margin, (uint32_t*)d_flags,
+                           (uint32_t*)d_list, out_count, nullptr);
+}
+
+DCRT_API int dcrt_tracer_adaptive_timings(dcrt_tracer* t, float* out_mask_ms, float* out_compact_ms, float* out_fill_ms)
+{
+    TRACER_GUARD(t);
+    if (!out_mask_ms || !out_compact_ms || !out_fill_ms) return DCRT_E_INVALID_ARG;
+    *out_mask_ms = *out_compact_ms = *out_fill_ms = 0.0f;
+    HIPCHECK(hipStreamSynchronize(t->stream));
+    if (t->adMaskTimed) {
+        HIPCHECK(hipEventElapsedTime(out_mask_ms, t->adEvents[0], t->adEvents[1]));
+        HIPCHECK(hipEventElapsedTime(out_compact_ms, t->adEvents[1], t->adEvents[2]));
+    }
+    if (t->adFillTimed) HIPCHECK(hipEventElapsedTime(out_fill_ms, t->adEvents[3], t->adEvents[4]));
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_render_adaptive(dcrt_tracer* t, uint32_t first_seed, const dcrt_converge_params* p, uint32_t margin,
+                                         const dcrt_filter_params* f, dcrt_noise_stats* out_stats, int* out_converged,
+                                         dcrt_adaptive_report* out_report)
+{
+    TRACER_GUARD(t);
+    if (!p || !f || !out_stats || !out_converged) return DCRT_E_INVALID_ARG;
+    return t->RenderAdaptive(first_seed, *p, margin, *f, out_stats, out_converged, out_report);
+}
+
 DCRT_API int dcrt_tracer_counters(dcrt_tracer* t, dcrt_ray_stats* out)
 {
     TRACER_GUARD(t);
@@ -2693,7 +3035,8 @@ DCRT_API int dcrt_tracer_counters(dcrt_tracer* t, dcrt_ray_stats* out)
     out->extension_rays = g.extRays;
     out->shadow_rays = g.shadowRays;
     // every rendered pixel (film rows of this tracer, halo included) starts one path per image
-    out->new_paths = t->imagesCompleted * (uint64_t)t->rowCount * t->filmW;
+    // (less the pixels of the blocks an adaptive block list left out)
+    out->new_paths = t->imagesCompleted * (uint64_t)t->rowCount * t->filmW - t->pathsSkipped;
     out->iterations = g.iterations;
     out->images_completed = t->imagesCompleted;
     return DCRT_OK;
@@ -2782,6 +3125,7 @@ DCRT_API int dcrt_tracer_reset_stats(dcrt_tracer* t)
     HIPCHECK(hipStreamSynchronize(t->stream));
     g.extRays = g.shadowRays = g.iterations = 0;
     t->imagesCompleted = 0;
+    t->pathsSkipped = 0;
     HIPCHECK(hipMemcpyAsync(t->dGlobals, &g, sizeof(Globals), hipMemcpyHostToDevice, t->stream));
     HIPCHECK(hipStreamSynchronize(t->stream));
     t->eventsUsed = 0;

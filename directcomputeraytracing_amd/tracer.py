@@ -386,6 +386,63 @@ class WavefrontPathTracer:
                                                      C.byref(done)), "RenderConverged")
         return noise_stats_dict(s), bool(done.value)
 
+    # ---- adaptive sampling: trace only the film blocks that are still noisy ---------
+    FILTER_MARGIN = 0xFFFFFFFF   # margin: the filter's window rows
+
+    def set_adaptive(self, enable: bool) -> None:
+        """Keep a list of active 8 x 8 film blocks (index by * ceil(W / 8) + bx) that render_images
+        starts paths in; set to every block. Needs a film; not on a partitioned or banded tracer."""
+        check(self._lib.dcrt_tracer_set_adaptive(self._h, 1 if enable else 0), "SetAdaptive")
+
+    def set_sample_blocks(self, blocks) -> None:
+        """The active blocks: strictly ascending indices; an empty list leaves nothing to sample."""
+        b = np.ascontiguousarray(blocks, np.uint32).ravel()
+        check(self._lib.dcrt_tracer_set_sample_blocks(self._h, b.ctypes.data_as(C.POINTER(C.c_uint32)), b.size), "SetSampleBlocks")
+
+    def get_sample_blocks(self) -> np.ndarray:
+        n = C.c_uint32()
+        check(self._lib.dcrt_tracer_get_sample_blocks(self._h, None, 0, C.byref(n)), "GetSampleBlocks")
+        out = np.empty(n.value, np.uint32)
+        check(self._lib.dcrt_tracer_get_sample_blocks(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size, C.byref(n)),
+              "GetSampleBlocks")
+        return out
+
+    def update_sample_blocks(self, threshold: float, margin: int = FILTER_MARGIN) -> int:
+        """Rebuild the list from the film and the half film: the blocks with a pixel within `margin`
+        pixels that is invalid or whose error is not <= threshold. Returns the list's length."""
+        n = C.c_uint32()
+        check(self._lib.dcrt_tracer_update_sample_blocks(self._h, float(threshold), int(margin), C.byref(n)), "UpdateSampleBlocks")
+        return int(n.value)
+
+    def sample_blocks_device(self, width: int, height: int, d_film: int, d_half: int, threshold: float, margin: int,
+                             d_list: int, d_flags: int = 0) -> int:
+        """The same over device images: the ascending list at d_list (room for every block), one
+        uint32 flag per block at d_flags if given. Returns the count."""
+        n = C.c_uint32()
+        check(self._lib.dcrt_tracer_sample_blocks_device(self._h, int(width), int(height), C.c_void_p(d_film), C.c_void_p(d_half),
+                                                         float(threshold), int(margin), C.c_void_p(d_flags or None),
+                                                         C.c_void_p(d_list), C.byref(n)), "SampleBlocksDevice")
+        return int(n.value)
+
+    def adaptive_timings(self) -> dict:
+        """HIP-event ms of the last mask, compaction and sentinel-fill kernels, with ext_timing on."""
+        ms = [C.c_float(), C.c_float(), C.c_float()]
+        check(self._lib.dcrt_tracer_adaptive_timings(self._h, *[C.byref(m) for m in ms]), "AdaptiveTimings")
+        return {"mask_ms": ms[0].value, "compact_ms": ms[1].value, "fill_ms": ms[2].value}
+
+    def render_adaptive(self, first_seed: int, params: _abi.ConvergeParams, margin: int = FILTER_MARGIN,
+                        filter_params: _abi.FilterParams | None = None):
+        """render_converged that rebuilds the block list at every check point and renders only the
+        listed blocks: (stats of the last check, converged, report dict). Starts on every block;
+        the film is not cleared, and the list stays as the last check point left it."""
+        f = filter_params or self.filter
+        s = _abi.NoiseStats()
+        done = C.c_int()
+        r = _abi.AdaptiveReport()
+        check(self._lib.dcrt_tracer_render_adaptive(self._h, int(first_seed), C.byref(params), int(margin), C.byref(f), C.byref(s),
+                                                    C.byref(done), C.byref(r)), "RenderAdaptive")
+        return noise_stats_dict(s), bool(done.value), {k: int(getattr(r, k)) for k, _ in _abi.AdaptiveReport._fields_}
+
     # ---- statistics ----------------------------------------------------------
     def counters(self) -> dict:
         s = _abi.RayStats()

@@ -9,6 +9,14 @@
 //               [--fixed-seed N] [--iterations N] [--pool N] [--film out.f32] [--samples out.f32]
 //               [--edit N:KIND:ARGS]... [--output NAME [--iteration-threshold N]] [--denoise]
 //               [--converge THRESHOLD[:FRACTION] [--check-points MIN:INTERVAL]] [--noise-map out.bmp]
+//               [--adaptive THRESHOLD:FRACTION[:MARGIN]] [--sample-map out.bmp]
+//
+// --adaptive runs like --converge (the same check points, --noise-map, "converged" and "noise"),
+// but through dcrt_tracer_render_adaptive: after every check point only the 8 x 8 pixel blocks
+// within MARGIN pixels (default: the filter's window rows) of a pixel that is still over
+// THRESHOLD go on being traced (dcrt.h "adaptive sampling"). The JSON line gains "adaptive".
+// --sample-map writes the film's weight over its maximum as a grey image, the per-pixel sampling
+// density (code = (int)(v * 255 + 0.5)); it works with any mode.
 //
 // --converge renders until the half-film noise estimate (dcrt.h "film noise estimate") says that
 // FRACTION (default 0.95) of the pixels have an error of at most THRESHOLD, checked at MIN, MIN +
@@ -76,7 +84,8 @@ int Usage(const char* exe)
                  "       [--film out.f32] [--samples out.f32] [--edit N:KIND:ARGS]...\n"
                  "       [--output path_tracing|normal|tangent|albedo|negative_ndotv|backface|iteration_count]\n"
                  "       [--iteration-threshold N] [--denoise]\n"
-                 "       [--converge THRESHOLD[:FRACTION] [--check-points MIN:INTERVAL]] [--noise-map out.bmp]\n",
+                 "       [--converge THRESHOLD[:FRACTION] [--check-points MIN:INTERVAL]] [--noise-map out.bmp]\n"
+                 "       [--adaptive THRESHOLD:FRACTION[:MARGIN]] [--sample-map out.bmp]\n",
                  exe);
     return 2;
 }
@@ -192,6 +201,9 @@ int main(int argc, char** argv)
     bool converge = false;
     dcrt_converge_params convergeParams = {0.0f, 0.95f, 16u, 0u, 16u};
     const char* noiseMapPath = nullptr;
+    bool adaptive = false;
+    uint32_t adaptiveMargin = 0xFFFFFFFFu;   // (the filter's window rows)
+    const char* sampleMapPath = nullptr;
     for (int i = 7; i < argc; ++i) {
         const bool more = i + 1 < argc;
         if (!std::strcmp(argv[i], "--batch")) {
@@ -235,6 +247,15 @@ int main(int argc, char** argv)
                 (f.size() == 2 && !ParseFloats(f[1], &convergeParams.target_fraction, 1)))
                 return Usage(argv[0]);
             converge = true;
+        } else if (!std::strcmp(argv[i], "--adaptive") && more) {
+            const std::vector<std::string> f = Split(argv[++i], ':');
+            if (f.size() < 2 || f.size() > 3 || !ParseFloats(f[0], &convergeParams.threshold, 1) ||
+                !ParseFloats(f[1], &convergeParams.target_fraction, 1))
+                return Usage(argv[0]);
+            if (f.size() == 3) adaptiveMargin = (uint32_t)std::atoi(f[2].c_str());
+            converge = adaptive = true;
+        } else if (!std::strcmp(argv[i], "--sample-map") && more) {
+            sampleMapPath = argv[++i];
         } else if (!std::strcmp(argv[i], "--check-points") && more) {
             const std::vector<std::string> f = Split(argv[++i], ':');
             if (f.size() != 2) return Usage(argv[0]);
@@ -292,7 +313,18 @@ int main(int argc, char** argv)
     uint32_t images = spp;        // images in the film (--converge: as many as it took)
     dcrt_noise_stats noise = {};
     int converged = 0;
-    if (converge) {
+    dcrt_adaptive_report adaptiveReport = {};
+    if (adaptive) {
+        const dcrt_filter_params filter = MakeFilter(scene);
+        if (!Check(dcrt_tracer_set_convergence(tracer.GetTracer(), 1), "SetConvergence") ||
+            !Check(dcrt_tracer_set_adaptive(tracer.GetTracer(), 1), "SetAdaptive") ||
+            !Check(dcrt_tracer_render_adaptive(tracer.GetTracer(), 0, &convergeParams, adaptiveMargin, &filter, &noise, &converged,
+                                               &adaptiveReport),
+                   "RenderAdaptive"))
+            return 1;
+        images = noise.images;
+        for (uint32_t s = 0; s < images; ++s) seeds.push_back(s);
+    } else if (converge) {
         const dcrt_filter_params filter = MakeFilter(scene);
         if (!Check(dcrt_tracer_set_convergence(tracer.GetTracer(), 1), "SetConvergence") ||
             !Check(dcrt_tracer_render_converged(tracer.GetTracer(), 0, &convergeParams, &filter, &noise, &converged), "RenderConverged"))
@@ -396,6 +428,19 @@ int main(int argc, char** argv)
         }
         if (!Check(dcrt_write_bmp(noiseMapPath, W, H, grey.data()), "WriteBmp (noise map)")) return 1;
     }
+    if (sampleMapPath) {
+        std::vector<float> film(n * 4);
+        if (!Check(dcrt_tracer_read_film(tracer.GetTracer(), film.data()), "ReadFilm")) return 1;
+        float top = 0.0f;
+        for (size_t p = 0; p < n; ++p) top = std::fmax(top, film[4 * p + 3]);
+        std::vector<uint8_t> grey(n * 4);
+        for (size_t p = 0; p < n; ++p) {
+            const float v = top > 0.0f ? std::fmin(std::fmax(film[4 * p + 3], 0.0f) / top, 1.0f) : 0.0f;
+            grey[4 * p] = grey[4 * p + 1] = grey[4 * p + 2] = (uint8_t)(int)(v * 255.0f + 0.5f);
+            grey[4 * p + 3] = 255;
+        }
+        if (!Check(dcrt_write_bmp(sampleMapPath, W, H, grey.data()), "WriteBmp (sample map)")) return 1;
+    }
     dcrt_ray_stats stats;
     if (!Check(dcrt_tracer_counters(tracer.GetTracer(), &stats), "Counters")) return 1;
     const double rays = (double)(stats.extension_rays + stats.shadow_rays);
@@ -425,11 +470,20 @@ int main(int argc, char** argv)
                       (double)noise.max_tile_error);
         editReport += buf;
     }
+    if (adaptive) {   // (only with --adaptive)
+        char buf[256];
+        std::snprintf(buf, sizeof(buf),
+                      ", \"adaptive\": {\"images\": %u, \"check_points\": %u, \"pixel_samples\": %llu, \"active_blocks\": %u, "
+                      "\"total_blocks\": %u}",
+                      adaptiveReport.images, adaptiveReport.check_points, (unsigned long long)adaptiveReport.pixel_samples,
+                      adaptiveReport.active_blocks, adaptiveReport.total_blocks);
+        editReport += buf;
+    }
     std::printf("{\"images\": %u, \"seconds\": %.4f, \"ms_per_spp\": %.3f, \"mrays_per_s\": %.1f, \"extension_rays\": %llu, "
                 "\"shadow_rays\": %llu, \"mode\": \"%s\", \"frames\": %llu, \"preview_frames\": %llu, \"first_seed\": %u, "
                 "\"seeds\": [%s]%s}\n",
                 images, seconds, seconds * 1e3 / images, rays / seconds / 1e6, (unsigned long long)stats.extension_rays,
-                (unsigned long long)stats.shadow_rays, converge ? "render_converged" : batch ? "render_images" : "frame_loop", (unsigned long long)loop.m_FrameIndex,
+                (unsigned long long)stats.shadow_rays, adaptive ? "render_adaptive" : converge ? "render_converged" : batch ? "render_images" : "frame_loop", (unsigned long long)loop.m_FrameIndex,
                 (unsigned long long)previewFrames, firstSeed, seedList.c_str(), editReport.c_str());
     return 0;
 }

@@ -859,6 +859,68 @@ typedef struct dcrt_converge_params {
 DCRT_API int dcrt_tracer_render_converged(dcrt_tracer* tracer, uint32_t first_seed, const dcrt_converge_params* params,
                                           const dcrt_filter_params* filter, dcrt_noise_stats* out_stats, int* out_converged);
 
+/* ===== adaptive sampling: trace only the film blocks that are still noisy ====
+ * The film is cut into 8 x 8 pixel blocks, blocksX = ceil(W / 8) per row, block index by * blocksX
+ * + bx. While adaptive sampling is on, the tracer keeps a strictly ascending list of active blocks,
+ * and dcrt_tracer_render_images / _strided (wavefront and megakernel mode, with or without the film
+ * pass) start one path per image in the in-film pixels of the listed blocks only. Every other
+ * pixel of the image's sample textures holds the sentinel sample -- position (+inf, +inf), value
+ * 0 -- to which all five reconstruction filters give the weight +0, so the film pass over them
+ * is bit for bit the film of the traced samples alone (tests/adaptive_ref.py). With the film pass
+ * off, the kept slots hold the sentinel too, so dcrt_tracer_accumulate_images on another tracer
+ * gives the same film. The output views, dcrt_tracer_render_guides and the progressive
+ * dcrt_tracer_render ignore the list. dcrt_ray_stats.new_paths counts the pixels started. No
+ * reference counterpart.
+ *
+ * A block is active when some film pixel (x, y) with bx*8 - m <= x <= bx*8 + 7 + m and by*8 - m
+ * <= y <= by*8 + 7 + m (m = the margin, in pixels) is not converged: invalid, or !(e <= threshold)
+ * with valid and e of the film noise estimate above (a NaN e is not converged). The margin keeps
+ * every block sampling that a noisy pixel's filter window reaches. */
+typedef struct dcrt_adaptive_report {
+    uint32_t images;          /* images rendered by the call                                       */
+    uint32_t check_points;    /* noise estimates taken                                             */
+    uint64_t pixel_samples;   /* paths started: the sum over the images of their listed pixels     */
+    uint32_t active_blocks;   /* the list's length on return                                       */
+    uint32_t total_blocks;    /* blocksX * ceil(H / 8)                                             */
+} dcrt_adaptive_report;
+/* enable != 0 allocates the flag and list buffers (4 B each per block, only while enabled) and sets
+ * the list to every block; 0 frees them. On a change the captured graphs are dropped. Needs a film
+ * (frame parameters); DCRT_E_INVALID_ARG on a partitioned or banded tracer, and while it is on
+ * dcrt_tracer_set_film_partition (world_size > 1) and dcrt_tracer_set_film_bands are refused.
+ * Default: off, and then every launch is what it was before this existed. A resolution change and
+ * dcrt_tracer_clear_film (dcrt_tracer_set_convergence clears too) reset the list to every block. */
+DCRT_API int dcrt_tracer_set_adaptive(dcrt_tracer* tracer, int enable);
+/* The list from host memory: strictly ascending, every index < blocksX * ceil(H / 8), else
+ * DCRT_E_INVALID_ARG with the list untouched. count 0 is legal: nothing is left to sample, and
+ * dcrt_tracer_render_images then returns DCRT_E_INVALID_ARG before anything is launched. */
+DCRT_API int dcrt_tracer_set_sample_blocks(dcrt_tracer* tracer, const uint32_t* blocks, uint32_t count);
+/* Writes at most `capacity` indices; *out_count = the list's length. */
+DCRT_API int dcrt_tracer_get_sample_blocks(dcrt_tracer* tracer, uint32_t* out_blocks, uint32_t capacity, uint32_t* out_count);
+/* The list rebuilt from the tracer's own film and half film, on its stream; the one
+ * synchronisation is the copy of the count. Refuses what dcrt_tracer_noise refuses. margin
+ * 0xFFFFFFFF: the window rows of the last film pass's filter (what the halo check uses). */
+DCRT_API int dcrt_tracer_update_sample_blocks(dcrt_tracer* tracer, float threshold, uint32_t margin, uint32_t* out_active);
+/* The same kernels over caller-provided device images (width * height RGBA32F each): one uint32
+ * flag per block (optional) and the ascending list (room for every block). Any tracer will do,
+ * adaptive or not, with or without a scene. */
+DCRT_API int dcrt_tracer_sample_blocks_device(dcrt_tracer* tracer, uint32_t width, uint32_t height, const void* d_film,
+                                              const void* d_half, float threshold, uint32_t margin, void* d_flags_or_null,
+                                              void* d_list, uint32_t* out_count);
+/* With ext_timing on (dcrt_tracer_set_instrumentation): the HIP-event times in ms of the last mask
+ * kernel, the last compaction kernel (update_sample_blocks / sample_blocks_device) and the last
+ * sentinel fill of the sample slots; 0 for one that has not run with ext_timing on. */
+DCRT_API int dcrt_tracer_adaptive_timings(dcrt_tracer* tracer, float* out_mask_ms, float* out_compact_ms, float* out_fill_ms);
+/* dcrt_tracer_render_converged with the block list in the loop. It starts on every block; at each
+ * check point (as there) it renders up to the point's film image count, the image with count i
+ * from seed first_seed + i, takes the estimate, stops with *out_converged = 1 if the target is
+ * met or with 0 at max_images, else rebuilds the list (update_sample_blocks(threshold, margin);
+ * margin 0xFFFFFFFF: the window rows of `filter`) and stops with 1 if it is empty. The list is
+ * rebuilt from every block each time, so blocks can wake up again; it stays in place on return
+ * (dcrt_tracer_clear_film resets it). out_report may be null. */
+DCRT_API int dcrt_tracer_render_adaptive(dcrt_tracer* tracer, uint32_t first_seed, const dcrt_converge_params* params,
+                                         uint32_t margin, const dcrt_filter_params* filter, dcrt_noise_stats* out_stats,
+                                         int* out_converged, dcrt_adaptive_report* out_report_or_null);
+
 /* 24-bit BMP writer ("Save Image to File", SaveImageToFile.cpp:92-182). */
 DCRT_API int dcrt_write_bmp(const char* path, uint32_t width, uint32_t height, const uint8_t* rgba8);
 
