@@ -222,6 +222,11 @@ class ObjMaterial(C.Structure):
                 ("albedo_texture_index", C.c_int32), ("opacity_texture_index", C.c_int32)]
 
 
+class BsdfProbeMaterial(C.Structure):
+    _fields_ = [("type", C.c_uint32), ("albedo", C.c_float * 3), ("ior", C.c_float * 3), ("alpha", C.c_float),
+                ("two_sided", C.c_uint32), ("multiscattering", C.c_uint32), ("internal_scattering_mode", C.c_uint32)]
+
+
 OBJ_SCENE_LAYOUT = 1
 
 # Every symbol include/dcrt.h declares: (name, restype, argtypes)
@@ -364,6 +369,8 @@ SIGNATURES = [
                                          C.POINTER(C.c_int), C.POINTER(AdaptiveReport)]),
     ("dcrt_write_bmp", _I, [C.c_char_p, _U, _U, C.POINTER(C.c_uint8)]),
     ("dcrt_device_math_eval", _I, [_P, _I, _FP, _U, _FP]),
+    ("dcrt_device_bsdf_eval", _I, [_P, C.POINTER(BsdfProbeMaterial), _U, _FP, _FP, _U, _FP, _FP]),
+    ("dcrt_device_bsdf_sample", _I, [_P, C.POINTER(BsdfProbeMaterial), _U, _FP, _FP, _U, _FP, _FP, _FP, C.POINTER(C.c_uint32)]),
 ]
 
 _lib = None

@@ -1632,6 +1632,57 @@ __global__ void math_eval_kernel(int function, const float* x, uint32_t n, float
     }
 }
 
+// One material's BSDF at a caller's directions (tests): MATERIAL's bsdf_frame / evaluate_bsdf /
+// evaluate_bsdf_pdf / sample_bsdf in the frame n = (0,0,1), t = (1,0,0). Of `sc` only the LUTs are read.
+__device__ __forceinline__ Intersection bsdf_probe_intersection(const dcrt_bsdf_probe_material& m)
+{
+    Intersection it;
+    it.albedo = mk(m.albedo[0], m.albedo[1], m.albedo[2]);
+    it.alpha = m.alpha;
+    it.position = mk(0.0f, 0.0f, 0.0f);
+    it.normal = mk(0.0f, 0.0f, 1.0f);
+    it.tangent = mk(1.0f, 0.0f, 0.0f);
+    it.geometryNormal = mk(0.0f, 0.0f, 1.0f);
+    it.ior = mk(m.ior[0], m.ior[1], m.ior[2]);
+    it.isTwoSided = m.two_sided != 0;
+    it.backface = false;
+    it.multiscattering = m.multiscattering != 0;
+    it.internalScatteringMode = m.internal_scattering_mode;
+    it.materialType = m.type;
+    it.lightIndex = DCRT_LIGHT_INDEX_INVALID;
+    it.triangleIndex = 0;
+    return it;
+}
+__global__ void bsdf_eval_kernel(DeviceScene sc, dcrt_bsdf_probe_material m, uint32_t features, const float* wi, const float* wo,
+                                 uint32_t n, float* f, float* pdf)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const bool vndf = (features & DCRT_FEATURE_GGX_SAMPLE_VNDF) != 0;
+    const Intersection it = bsdf_probe_intersection(m);
+    const V3 a = mk(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]), b = mk(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]);
+    const BsdfFrame bf = bsdf_frame(sc, b, it);
+    const V3 v = evaluate_bsdf(sc, vndf, a, bf, it);
+    f[3 * i] = v.x; f[3 * i + 1] = v.y; f[3 * i + 2] = v.z;
+    pdf[i] = evaluate_bsdf_pdf(sc, vndf, a, bf, it);
+}
+__global__ void bsdf_sample_kernel(DeviceScene sc, dcrt_bsdf_probe_material m, uint32_t features, const float* wo, const float* u,
+                                   uint32_t n, float* wi, float* f, float* pdf, uint32_t* delta)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const bool vndf = (features & DCRT_FEATURE_GGX_SAMPLE_VNDF) != 0;
+    const Intersection it = bsdf_probe_intersection(m);
+    const V3 b = mk(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]);
+    const BsdfFrame bf = bsdf_frame(sc, b, it);
+    V3 w, v; float p; bool d;
+    sample_bsdf(sc, vndf, bf, u[3 * i], u[3 * i + 1], u[3 * i + 2], it, &w, &v, &p, &d);
+    wi[3 * i] = w.x; wi[3 * i + 1] = w.y; wi[3 * i + 2] = w.z;
+    f[3 * i] = v.x; f[3 * i + 1] = v.y; f[3 * i + 2] = v.z;
+    pdf[i] = p;
+    delta[i] = d ? 1u : 0u;
+}
+
 // ---- SampleConvolution ----------------------------------------------------------------
 struct FilterConsts { float radius, gaussianAlpha, gaussianExp, mf[7]; uint32_t tau, kind; };
 

@@ -3481,6 +3481,76 @@ DCRT_API int dcrt_device_math_eval(dcrt_tracer* t, int function, const float* x,
     return rc;
 }
 
+// A DeviceScene with nothing but the tracer's current LUTs (the BSDF probe kernels read no more).
+static DeviceScene LutOnlyScene(const dcrt_tracer* t)
+{
+    DeviceScene d{};
+    d.lutBrdf = t->dLuts->brdf;
+    d.lutBrdfAvg = t->dLuts->brdf_avg;
+    d.lutBrdfDielectric = t->dLuts->brdf_dielectric;
+    d.lutBrdfDielectricAvg = t->dLuts->brdf_dielectric_avg;
+    d.lutBsdf = t->dLuts->bsdf;
+    d.lutBsdfAvg = t->dLuts->bsdf_avg;
+    return d;
+}
+
+DCRT_API int dcrt_device_bsdf_eval(dcrt_tracer* t, const dcrt_bsdf_probe_material* m, uint32_t features, const float* wi,
+                                   const float* wo, uint32_t n, float* f, float* pdf)
+{
+    TRACER_GUARD(t);
+    if (!m || ((!wi || !wo || !f || !pdf) && n)) return DCRT_E_INVALID_ARG;
+    std::vector<void*> tmp;
+    float *dwi = nullptr, *dwo = nullptr, *df = nullptr, *dpdf = nullptr;
+    CHECKED(DeviceAlloc(&dwi, (size_t)n * 3, &tmp));
+    CHECKED(DeviceAlloc(&dwo, (size_t)n * 3, &tmp));
+    CHECKED(DeviceAlloc(&df, (size_t)n * 3, &tmp));
+    CHECKED(DeviceAlloc(&dpdf, n, &tmp));
+    int rc = DCRT_OK;
+    if (hipMemcpyAsync(dwi, wi, (size_t)n * 12, hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    if (rc == DCRT_OK && hipMemcpyAsync(dwo, wo, (size_t)n * 12, hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    if (rc == DCRT_OK && n) {
+        hipLaunchKernelGGL(bsdf_eval_kernel, dim3((n + 255) / 256), dim3(256), 0, t->stream, LutOnlyScene(t), *m, features,
+                           (const float*)dwi, (const float*)dwo, n, df, dpdf);
+        if (hipGetLastError() != hipSuccess) rc = DCRT_E_HIP;
+    }
+    if (rc == DCRT_OK && hipMemcpyAsync(f, df, (size_t)n * 12, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    if (rc == DCRT_OK && hipMemcpyAsync(pdf, dpdf, (size_t)n * 4, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    FreeAll(&tmp);
+    return rc;
+}
+
+DCRT_API int dcrt_device_bsdf_sample(dcrt_tracer* t, const dcrt_bsdf_probe_material* m, uint32_t features, const float* wo,
+                                     const float* u, uint32_t n, float* wi, float* f, float* pdf, uint32_t* delta)
+{
+    TRACER_GUARD(t);
+    if (!m || ((!wo || !u || !wi || !f || !pdf || !delta) && n)) return DCRT_E_INVALID_ARG;
+    std::vector<void*> tmp;
+    float *dwo = nullptr, *du = nullptr, *dwi = nullptr, *df = nullptr, *dpdf = nullptr;
+    uint32_t* ddelta = nullptr;
+    CHECKED(DeviceAlloc(&dwo, (size_t)n * 3, &tmp));
+    CHECKED(DeviceAlloc(&du, (size_t)n * 3, &tmp));
+    CHECKED(DeviceAlloc(&dwi, (size_t)n * 3, &tmp));
+    CHECKED(DeviceAlloc(&df, (size_t)n * 3, &tmp));
+    CHECKED(DeviceAlloc(&dpdf, n, &tmp));
+    CHECKED(DeviceAlloc(&ddelta, n, &tmp));
+    int rc = DCRT_OK;
+    if (hipMemcpyAsync(dwo, wo, (size_t)n * 12, hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    if (rc == DCRT_OK && hipMemcpyAsync(du, u, (size_t)n * 12, hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    if (rc == DCRT_OK && n) {
+        hipLaunchKernelGGL(bsdf_sample_kernel, dim3((n + 255) / 256), dim3(256), 0, t->stream, LutOnlyScene(t), *m, features,
+                           (const float*)dwo, (const float*)du, n, dwi, df, dpdf, ddelta);
+        if (hipGetLastError() != hipSuccess) rc = DCRT_E_HIP;
+    }
+    if (rc == DCRT_OK && hipMemcpyAsync(wi, dwi, (size_t)n * 12, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    if (rc == DCRT_OK && hipMemcpyAsync(f, df, (size_t)n * 12, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    if (rc == DCRT_OK && hipMemcpyAsync(pdf, dpdf, (size_t)n * 4, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    if (rc == DCRT_OK && hipMemcpyAsync(delta, ddelta, (size_t)n * 4, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    FreeAll(&tmp);
+    return rc;
+}
+
 }  // extern "C"
 
 #ifdef DCRT_WAVE_TIMELINE

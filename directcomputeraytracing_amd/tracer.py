@@ -520,6 +520,49 @@ class WavefrontPathTracer:
                                               y.ctypes.data_as(_abi._FP)), "MathEval")
         return y
 
+    def bsdf_eval(self, material: _abi.BsdfProbeMaterial, wi: np.ndarray, wo: np.ndarray,
+                  features: int = _abi.FEATURE_DEFAULT):
+        """MATERIAL's evaluate_bsdf / evaluate_bsdf_pdf of one material in the frame n = (0,0,1),
+        t = (1,0,0) with the current LUTs: (N, 3) f and (N,) pdf for (N, 3) direction pairs."""
+        wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
+        wo = np.ascontiguousarray(wo, np.float32).reshape(-1, 3)
+        if len(wi) != len(wo):
+            raise ValueError("bsdf_eval: wi and wo differ in length")
+        f = np.zeros_like(wi)
+        pdf = np.zeros(len(wi), np.float32)
+        fp = _abi._FP
+        check(self._lib.dcrt_device_bsdf_eval(self._h, C.byref(material), int(features), wi.ctypes.data_as(fp),
+                                              wo.ctypes.data_as(fp), len(wi), f.ctypes.data_as(fp), pdf.ctypes.data_as(fp)),
+              "BsdfEval")
+        return f, pdf
+
+    def bsdf_sample(self, material: _abi.BsdfProbeMaterial, wo: np.ndarray, u: np.ndarray,
+                    features: int = _abi.FEATURE_DEFAULT):
+        """MATERIAL's sample_bsdf likewise: for (N, 3) wo and (N, 3) numbers (sx, sy, sel), the
+        sampled wi (N, 3), f (N, 3), pdf (N,) and delta flags (N,)."""
+        wo = np.ascontiguousarray(wo, np.float32).reshape(-1, 3)
+        u = np.ascontiguousarray(u, np.float32).reshape(-1, 3)
+        if len(wo) != len(u):
+            raise ValueError("bsdf_sample: wo and u differ in length")
+        wi = np.zeros_like(wo)
+        f = np.zeros_like(wo)
+        pdf = np.zeros(len(wo), np.float32)
+        delta = np.zeros(len(wo), np.uint32)
+        fp = _abi._FP
+        check(self._lib.dcrt_device_bsdf_sample(self._h, C.byref(material), int(features), wo.ctypes.data_as(fp),
+                                                u.ctypes.data_as(fp), len(wo), wi.ctypes.data_as(fp), f.ctypes.data_as(fp),
+                                                pdf.ctypes.data_as(fp), delta.ctypes.data_as(C.POINTER(C.c_uint32))),
+              "BsdfSample")
+        return wi, f, pdf, delta.astype(bool)
+
+
+def bsdf_probe_material(type, albedo=(1.0, 1.0, 1.0), alpha=0.5, ior=1.5, two_sided=False, multiscattering=False,
+                        internal_scattering=0) -> _abi.BsdfProbeMaterial:
+    """A probe material for bsdf_eval / bsdf_sample; a scalar ior fills all three channels."""
+    ior3 = (float(ior),) * 3 if np.isscalar(ior) else tuple(float(x) for x in ior)
+    return _abi.BsdfProbeMaterial(int(type), (C.c_float * 3)(*albedo), (C.c_float * 3)(*ior3), float(alpha), int(two_sided),
+                                  int(multiscattering), int(internal_scattering))
+
 
 def denoise_default_params() -> _abi.DenoiseParams:
     """dcrt_denoise_default_params: 5 iterations, sigmas 4 / 0.2 / 0.1, demodulation on (no device needed)."""

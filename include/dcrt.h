@@ -161,7 +161,13 @@ typedef struct dcrt_flat_scene {
     uint32_t bvh_traversal_stack_size;      /* CScene::m_BVHTraversalStackSize */
 } dcrt_flat_scene;
 
-/* The six R16_UNORM BxDF lookup tables (BxDFTexturesBuilding.cpp:171-175,265-270,379-384). */
+/* The six R16_UNORM BxDF lookup tables (BxDFTexturesBuilding.cpp:171-175,265-270,379-384). Main
+ * tables: the directional albedo at cos = max(x * 0.032258, 0.0001), alpha = y * step (0.032258
+ * for brdf, 0.066667 for the arrays), ior = 1 + (slice % 16) * 0.133333; slices 0-15 see the
+ * boundary from outside ("leaving"), 16-31 from the dense side ("entering"). Each *_avg texel is
+ * the cosine-weighted average of one row of its main table by the trapezoid rule over the 32
+ * columns, 2 / 31 * (f(0) * 0.0001 / 2 + sum_{i=1..30} f(i) * (i * 0.032258) + f(31) / 2), taken
+ * on the float table before it is clamped; row (slice, alpha) goes to [slice / 16][slice % 16][alpha]. */
 #define DCRT_LUT_BRDF_COUNT            (32 * 32)
 #define DCRT_LUT_BRDF_AVG_COUNT        (32)
 #define DCRT_LUT_BRDF_DIELECTRIC_COUNT (32 * 16 * 32)
@@ -927,6 +933,26 @@ DCRT_API int dcrt_write_bmp(const char* path, uint32_t width, uint32_t height, c
 /* Deterministic transcendental helpers shared by kernels (parity tests): function 0 sin, 1 cos,
    2 exp, 3 atan, 4 log (the det_* polynomials), 5 the fast reciprocal rcp_ieee, 6 IEEE 1/x. */
 DCRT_API int dcrt_device_math_eval(dcrt_tracer* tracer, int function, const float* x, uint32_t count, float* out_y);
+
+/* One material's BSDF at chosen directions (tests): MATERIAL's own bsdf_frame / evaluate_bsdf /
+   evaluate_bsdf_pdf / sample_bsdf in the frame normal = geometric normal = (0,0,1), tangent =
+   (1,0,0), with the tracer's current LUTs (dcrt_tracer_set_luts); no scene is needed. albedo holds
+   a conductor's k. Of `features` only DCRT_FEATURE_GGX_SAMPLE_VNDF is read. */
+typedef struct dcrt_bsdf_probe_material {
+    uint32_t type;                        /* DCRT_MATERIAL_TYPE_* */
+    float albedo[3];
+    float ior[3];
+    float alpha;
+    uint32_t two_sided, multiscattering;
+    uint32_t internal_scattering_mode;    /* DCRT_INTERNAL_SCATTERING_* */
+} dcrt_bsdf_probe_material;               /* 44 bytes */
+/* count (wi, wo) pairs, 3 floats each: f (3 per pair) and pdf. */
+DCRT_API int dcrt_device_bsdf_eval(dcrt_tracer* tracer, const dcrt_bsdf_probe_material* material, uint32_t features,
+                                   const float* wi, const float* wo, uint32_t count, float* out_f, float* out_pdf);
+/* count wo and (sx, sy, sel) triples: wi, f (3 each), pdf and the delta flag (0 / 1). */
+DCRT_API int dcrt_device_bsdf_sample(dcrt_tracer* tracer, const dcrt_bsdf_probe_material* material, uint32_t features,
+                                     const float* wo, const float* u, uint32_t count, float* out_wi, float* out_f,
+                                     float* out_pdf, uint32_t* out_delta);
 
 #ifdef __cplusplus
 }

@@ -1674,7 +1674,7 @@ static isect bsdf_test_isect(const oracle_bsdf_material* m)
     it.normal = V3(0.0f, 0.0f, 1.0f);
     it.geometryNormal = V3(0.0f, 0.0f, 1.0f);
     it.tangent = V3(1.0f, 0.0f, 0.0f);
-    it.ior = V3(m->ior, 1.0f, 1.0f);
+    it.ior = V3(m->ior[0], m->ior[1], m->ior[2]);
     it.isTwoSided = m->two_sided;
     it.multiscattering = m->multiscattering;
     it.internalScatteringMode = m->internal_scattering;
@@ -1682,10 +1682,11 @@ static isect bsdf_test_isect(const oracle_bsdf_material* m)
     it.lightIndex = DCRT_LIGHT_INDEX_INVALID;
     return it;
 }
-void oracle_bsdf_eval(const dcrt_bxdf_luts* luts, const oracle_bsdf_material* m, const float* wi, const float* wo,
-                      uint32_t count, float* f_out, float* pdf_out)
+void oracle_bsdf_eval(const dcrt_bxdf_luts* luts, const oracle_bsdf_material* m, uint32_t features, const float* wi,
+                      const float* wo, uint32_t count, float* f_out, float* pdf_out)
 {
     g_luts = luts;
+    g_vndf = (features & DCRT_FEATURE_GGX_SAMPLE_VNDF) != 0;
     const isect it = bsdf_test_isect(m);
     for (uint32_t i = 0; i < count; ++i) {
         const v3 a = V3(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]), b = V3(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]);
@@ -1694,10 +1695,11 @@ void oracle_bsdf_eval(const dcrt_bxdf_luts* luts, const oracle_bsdf_material* m,
         pdf_out[i] = evaluate_bsdf_pdf(a, b, &it);
     }
 }
-void oracle_bsdf_sample(const dcrt_bxdf_luts* luts, const oracle_bsdf_material* m, const float* wo, const float* u,
-                        uint32_t count, float* wi_out, float* f_out, float* pdf_out, int* delta_out)
+void oracle_bsdf_sample(const dcrt_bxdf_luts* luts, const oracle_bsdf_material* m, uint32_t features, const float* wo,
+                        const float* u, uint32_t count, float* wi_out, float* f_out, float* pdf_out, int* delta_out)
 {
     g_luts = luts;
+    g_vndf = (features & DCRT_FEATURE_GGX_SAMPLE_VNDF) != 0;
     const isect it = bsdf_test_isect(m);
     for (uint32_t i = 0; i < count; ++i) {
         const v3 b = V3(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]);

@@ -77,19 +77,20 @@ void oracle_math_eval(int function, const float* x, uint32_t count, float* y);
 /* One material's BSDF (BSDFs.inc.hlsl EvaluateBSDF / EvaluateBSDFPdf / SampleBSDF) in the frame
    normal = geometric normal = (0,0,1), tangent = (1,0,0), for the BxDF physics pins
    (tests/test_bsdf_pins.py). material: type, albedo[3], alpha, ior, two-sided, multiscattering,
-   internal scattering mode. eval: f (3 per pair) and pdf for `count` (wi, wo) pairs; sample: for
+   internal scattering mode (albedo holds a conductor's k). Of `features` only
+   DCRT_FEATURE_GGX_SAMPLE_VNDF is read. eval: f (3 per pair) and pdf for `count` (wi, wo) pairs; sample: for
    `count` wo and (sx, sy, sel) triples, wi, f, pdf and the delta flag. */
 typedef struct oracle_bsdf_material {
     uint32_t type;
     float albedo[3];
-    float alpha, ior;
+    float alpha, ior[3];
     int two_sided, multiscattering;
     uint32_t internal_scattering;
 } oracle_bsdf_material;
-void oracle_bsdf_eval(const dcrt_bxdf_luts* luts, const oracle_bsdf_material* m, const float* wi, const float* wo,
-                      uint32_t count, float* f_out, float* pdf_out);
-void oracle_bsdf_sample(const dcrt_bxdf_luts* luts, const oracle_bsdf_material* m, const float* wo, const float* u,
-                        uint32_t count, float* wi_out, float* f_out, float* pdf_out, int* delta_out);
+void oracle_bsdf_eval(const dcrt_bxdf_luts* luts, const oracle_bsdf_material* m, uint32_t features, const float* wi,
+                      const float* wo, uint32_t count, float* f_out, float* pdf_out);
+void oracle_bsdf_sample(const dcrt_bxdf_luts* luts, const oracle_bsdf_material* m, uint32_t features, const float* wo,
+                        const float* u, uint32_t count, float* wi_out, float* f_out, float* pdf_out, int* delta_out);
 
 /* Post-processing (PostProcessings.hlsl, SumLuminance.hlsl): tone-mapped sRGB8 RGBA. */
 float oracle_sum_log_luminance(const float* film_rgba, uint32_t width, uint32_t height);

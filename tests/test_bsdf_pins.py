@@ -134,9 +134,8 @@ def test_white_furnace_bounds(oracle_mod, golden_luts):
     white, energy-conserving material (albedo 1 diffuse base under a dielectric coat; a
     conductor with eta -> 0 and k = 0, whose Fresnel term is 1), within 5 standard errors; at
     high roughness the single-scattering conductor loses energy (about 0.39 of it remains at
-    alpha 0.9) and the Kulla-Conty term restores it to 1 within 0.01. (The test entry takes
-    one eta: a conductor's other two channels have eta = 1, k = 0 and reflect nothing, so
-    only channel x is checked for it.)"""
+    alpha 0.9) and the Kulla-Conty term restores it to 1 within 0.01. (Channel x is checked for
+    the conductor; a scalar ior gives the other two the same eta.)"""
     rng = np.random.default_rng(6)
     n = 200_000
     wo = np.broadcast_to(np.array([0.6, 0.0, 0.8], np.float32), (n, 3))
