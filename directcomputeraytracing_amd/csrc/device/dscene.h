@@ -112,6 +112,12 @@ __host__ __device__ inline uint32_t material_lds_bytes(uint32_t T, uint32_t I, u
     return 16u * (9u * T + 3u * I) + 4u * (2u * I + 13u * M + 7u * L);
 }
 
+// What MATERIAL's fused variant (material_kernel's FUSED) copies behind the shading copy, at the next
+// 16-B boundary, for cells_occluded_cached: the entry-free nodes (2 float4 each), the rotated triangle
+// copies (9 float4 each), the cell table's leaf words.
+__host__ __device__ inline uint32_t material_cells_lds_bytes(uint32_t nodes, uint32_t T) { return 32u * nodes + 144u * T + 4u * kCellWords; }
+__host__ __device__ inline uint32_t material_cells_lds_offset(uint32_t shadingBytes) { return (shadingBytes + 15u) & ~15u; }
+
 // Node orders on the device. kLayoutFlat is PackBVH's depth-first order, as in the flat
 // scene: an interior node's left child is node + 1 and its `right` field the right child.
 // kLayoutPairs (bvh_layout.h PairLayout, taken for scenes beyond an XCD's L2: the pair
@@ -178,6 +184,15 @@ DEV float4 global_load4(const float4* g, size_t i)
 constexpr uint32_t kRotTriFloat4 = 9;   // float4 per triangle: 3 permutations x 3 vertices
 template <bool ROTATED>
 DEV uint32_t cache_tri_float4() { return ROTATED ? kRotTriFloat4 : 3u; }
+// float4 i of the rotated copies: triangle i / 9, permutation (i mod 9) / 3, vertex i mod 3
+DEV float4 rot_tri_float4(const float4* triVerts, uint32_t i)
+{
+    const uint32_t tri = i / kRotTriFloat4, r = i - tri * kRotTriFloat4, z = r / 3u, k = r - z * 3u;
+    const float4 q = triVerts[(size_t)tri * 3 + k];
+    const float v[3] = {q.x, q.y, q.z};
+    const uint32_t x = z == 2u ? 0u : z + 1u, y = x == 2u ? 0u : x + 1u;
+    return make_float4(v[x], v[y], v[z], q.w);
+}
 
 // Every thread of the block: fill the cache, then a barrier.
 template <bool ROTATED = false>
@@ -188,11 +203,7 @@ DEV void scene_cache_load(const DeviceScene& sc, uint32_t* stackMem, uint32_t sh
     for (uint32_t i = threadIdx.x; i < nn; i += blockDim.x) c[i] = sc.nodes[i];
     for (uint32_t i = threadIdx.x; i < nt; i += blockDim.x) {
         if (ROTATED) {
-            const uint32_t tri = i / kRotTriFloat4, r = i - tri * kRotTriFloat4, z = r / 3u, k = r - z * 3u;
-            const float4 q = sc.triVerts[(size_t)tri * 3 + k];
-            const float v[3] = {q.x, q.y, q.z};
-            const uint32_t x = z == 2u ? 0u : z + 1u, y = x == 2u ? 0u : x + 1u;
-            c[nn + i] = make_float4(v[x], v[y], v[z], q.w);
+            c[nn + i] = rot_tri_float4(sc.triVerts, i);
         } else {
             c[nn + i] = sc.triVerts[i];
         }
@@ -876,39 +887,31 @@ DEV uint32_t cells_index(uint32_t R, V3 d, V3 inv)
     return (face * R + iv) * R + iu;
 }
 
-// The occlusion bit of shadow ray (o, d, tMax) of a scene with a cell table, by the kernels over
-// the entry-free node order (ALL_CACHED, IDENT, FLAT; `leafWords`: the table's leaf words in LDS).
+// A shadow ray the cells answer: every component of 1/d finite (a NaN slab breaks the implication
+// cells_occluded_cached rests on)
+DEV bool cells_finite(V3 inv)
+{
+    const float big = inf();
+    return fabsf(inv.x) < big && fabsf(inv.y) < big && fabsf(inv.z) < big;
+}
+
+// The occlusion bit of shadow ray (o, d, tMax), inv = inv_dir(d) finite (cells_finite), of a scene
+// with a cell table: `cells` / R the table's masks in global memory, `c` the entry-free node array,
+// `tris` the rotated triangle copies and `leafWords` the table's leaf words, all three in LDS (the
+// cast's scene cache; MATERIAL's fused variant keeps its own copy).
 // The reference's any-hit walk reaches a leaf exactly when the leaf's box and every box above it
 // pass the slab test with the ray's constant tMax, and answers with the OR of the reached leaves'
 // triangle tests; a box that holds the leaf's box component-wise passes whenever the leaf's does,
 // so per leaf of the cell's mask this runs the leaf's slab test and its guards' (shadow_cells.h), and
-// per leaf that passes trav_leaf's triangle test of an any-hit lane, operand for operand. A ray with a non-finite
-// 1/d component (NaN slabs: the implication above fails) walks the BVH as the cast does.
-DEV bool cells_occluded(const DeviceScene& sc, float4 o4, float4 d4, bool watertight, uint32_t* lds, uint32_t shift,
-                        const uint32_t* leafWords)
+// per leaf that passes trav_leaf's triangle test of an any-hit lane, operand for operand.
+DEV bool cells_occluded_cached(const uint64_t* cells, uint32_t R, V3 o, V3 d, float tMax, V3 inv, bool watertight, const float4* c,
+                               const float4* tris, const uint32_t* leafWords)
 {
-    const V3 o = mk(o4.x, o4.y, o4.z), d = mk(d4.x, d4.y, d4.z);
-    const float tMax = o4.w;
-    const V3 inv = inv_dir(d);
-    const float big = inf();
-    if (__builtin_expect(!(fabsf(inv.x) < big && fabsf(inv.y) < big && fabsf(inv.z) < big), 0)) {
-        TravState s;
-        TraversalStats st = {};
-        trav_init(s, o, d, 0.0f, tMax);
-        s.anyHit = true;
-        for (;;) {
-            if (trav_visit<false, true, kLayoutFlat, false, true, false>(sc, s, lds, shift, st)) break;
-            if (s.parked && trav_leaf<true, false, false, false, true, true, false, true>(sc, s, watertight, lds, shift, st)) break;
-        }
-        return s.found;
-    }
-    uint64_t mask = global_load_u64(sc.shadowCells, cells_index(sc.shadowRes, d, inv));
-    const float4* c = scene_cache(sc, lds - threadIdx.x, shift);
+    uint64_t mask = global_load_u64(cells, cells_index(R, d, inv));
     // (the instance-space ray of an identity instance, as trav_leaf forms it)
     const V3 spO = mk(o.x + 0.0f, o.y + 0.0f, o.z + 0.0f), spD = mk(d.x + 0.0f, d.y + 0.0f, d.z + 0.0f);
     Shear sh = {};
     if (watertight) sh = make_shear_rot(spD, spO, inv);
-    const float4* tris = c + sc.cachedNodes * 2u;
     // Two loops, so that a wave's lanes stay together: the box tests of every leaf of the mask first
     // (a lane's triangle test would otherwise hold up the lanes still testing boxes), then the
     // triangle tests of the leaves whose boxes passed, until the first hit.
@@ -942,6 +945,31 @@ DEV bool cells_occluded(const DeviceScene& sc, float4 o4, float4 d4, bool watert
         if (h) return true;
     }
     return false;
+}
+
+// The occlusion bit of shadow ray (o, d, tMax) of a scene with a cell table, by the kernels over
+// the entry-free node order (ALL_CACHED, IDENT, FLAT; `leafWords`: the table's leaf words in LDS):
+// cells_occluded_cached over the cast's scene cache. A ray with a non-finite 1/d component walks the
+// BVH as the cast does.
+DEV bool cells_occluded(const DeviceScene& sc, float4 o4, float4 d4, bool watertight, uint32_t* lds, uint32_t shift,
+                        const uint32_t* leafWords)
+{
+    const V3 o = mk(o4.x, o4.y, o4.z), d = mk(d4.x, d4.y, d4.z);
+    const float tMax = o4.w;
+    const V3 inv = inv_dir(d);
+    if (__builtin_expect(!cells_finite(inv), 0)) {
+        TravState s;
+        TraversalStats st = {};
+        trav_init(s, o, d, 0.0f, tMax);
+        s.anyHit = true;
+        for (;;) {
+            if (trav_visit<false, true, kLayoutFlat, false, true, false>(sc, s, lds, shift, st)) break;
+            if (s.parked && trav_leaf<true, false, false, false, true, true, false, true>(sc, s, watertight, lds, shift, st)) break;
+        }
+        return s.found;
+    }
+    const float4* c = scene_cache(sc, lds - threadIdx.x, shift);
+    return cells_occluded_cached(sc.shadowCells, sc.shadowRes, o, d, tMax, inv, watertight, c, c + sc.cachedNodes * 2u, leafWords);
 }
 
 // ---- texture emulation ----------------------------------------------------------

@@ -18,7 +18,10 @@ constexpr uint32_t kFlagTerminate = 0x20000000u;
 constexpr uint32_t kFlagDelta = 0x10000000u;           // the path's last BSDF lobe was a delta (SPathAccumulation.isDelta)
 constexpr uint32_t kFlagFirst = 0x08000000u;           // a new path's state record holds NEW_PATH's rng only (PathStateA)
 constexpr uint32_t kFlagShadowPending = 0x04000000u;   // the path cast a shadow ray last pass: its result is at its position
-constexpr uint32_t kBlockW = 8, kBlockH = 8;           // one wave64 = one 8x8 pixel block
+// the path's last shadow ray was tested by MATERIAL itself (its FUSED variant) and is occluded: no
+// result to fetch (an unoccluded one sets neither bit)
+constexpr uint32_t kFlagShadowResolved = 0x02000000u;
+constexpr uint32_t kBlockW = 8, kBlockH = 8;          // one wave64 = one 8x8 pixel block
 #ifndef DCRT_CONTROL_BLOCK
 #define DCRT_CONTROL_BLOCK 256
 #endif
@@ -51,13 +54,24 @@ constexpr uint32_t kNoPixel = 0xFFFFFFFFu;             // a virtual item (path s
 // And one more: nonzero = drain_kernel completed every path this iteration's queues held (the
 // next MATERIAL / CONTROL pass has nothing to take from them)
 constexpr uint32_t kDrainedWord = kCounterWords + 1;
+// And kShards more: the shadow rays MATERIAL's FUSED variant tested itself, one add per workgroup
+// to its shard's word -- the shadow queue then counts only the rays that took the queue, and
+// end_iteration accounts for both
+constexpr uint32_t kInlineShadowWord = kCounterWords + 2;
+constexpr uint32_t kCounterLines = kCounterWords + 2 + kShards;
 // Extension-queue entry bit: the path's first MATERIAL pass follows (set by NEW_PATH), whose
 // Li, light sampling result and throughput are the NEW_PATH constants, not stored or loaded
 constexpr uint32_t kEntryFirst = 0x80000000u;
 
 struct Counters {        // one set per iteration parity
-    uint32_t w[(kCounterWords + 2) * kShardStride];
+    uint32_t w[kCounterLines * kShardStride];
 };
+DEV uint32_t inline_shadow_rays(const Counters* c)
+{
+    uint32_t t = 0;
+    for (uint32_t s = 0; s < kShards; ++s) t += c->w[(kInlineShadowWord + s) * kShardStride];
+    return t;
+}
 DEV uint32_t virtual_items(const Counters* c) { return c->w[kVirtualWord * kShardStride]; }
 DEV bool drained(const Counters* c) { return c->w[kDrainedWord * kShardStride] != 0u; }
 struct Globals {
@@ -151,6 +165,20 @@ struct FrameConstants {
     uint32_t virtualStart;           // batch starts use the virtual extension queue (kVirtualWord)
     uint32_t drainPaths;             // drain_kernel completes the live paths once at most this many remain (0: off)
     uint32_t seedStride;             // image b of a batch has frame seed frameSeed + b * seedStride (interleaved pipelines)
+    // MATERIAL's FUSED variant tests a shadow ray itself only if (path slot & mask) == 0; the others
+    // take the shadow queue. 0 but for DCRT_FUSED_SHADOW's test value, which mixes the two routes in a wave.
+    uint32_t shadowInlineMask;
+};
+
+// What MATERIAL's FUSED variant reads of the flat cast's scene (CastPlan::sceneFlat) for
+// cells_occluded_cached: the entry-free node array -- the order the cell table's leaf words index --
+// and the table. Zero for every other variant.
+struct ShadowInline {
+    const float4* nodes;
+    const uint64_t* cells;
+    const uint32_t* leaves;
+    uint32_t nodeCount;
+    uint32_t res;
 };
 // The frame seed of image `image` of the current batch (RenderImages: frameSeed is the batch's first)
 DEV uint32_t image_seed(const FrameConstants& fc, uint32_t image) { return fc.frameSeed + __umul24(image, fc.seedStride); }

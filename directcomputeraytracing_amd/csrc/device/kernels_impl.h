@@ -419,14 +419,16 @@ static_assert(DCRT_MATERIAL_BLOCK % 64 == 0 && DCRT_MATERIAL_BLOCK <= 960, "MATE
 // unbounded): it then spills 3 VGPRs and still gains, coffee 3.12 -> 3.02, lamp 7.78 ->
 // 7.62 ms/spp (three / two A/B passes). The scene-specialised variants reach 5 waves by
 // themselves (95 VGPRs); held to 5 the compiler schedules them into 91 and the Cornell
-// bench loses 2 % (2.393 -> 2.447, four passes), so they are left unbounded.
+// bench loses 2 % (2.393 -> 2.447, four passes), so they are left unbounded. The FUSED
+// variants are held to 5 as well: unbounded, the Cornell one takes 98 VGPRs (4 waves); held,
+// 94 with no scratch (tools/vgprs.sh).
 #ifndef DCRT_MATERIAL_WAVES_PER_EU
 #define DCRT_MATERIAL_WAVES_PER_EU 5
 #endif
 #ifndef DCRT_MATERIAL_OD_WAVES_PER_EU
 #define DCRT_MATERIAL_OD_WAVES_PER_EU 1   // (the opaque / delta-light variants: the compiler's choice)
 #endif
-#define DCRT_MATERIAL_OCCUPANCY __attribute__((amdgpu_waves_per_eu(CAPS == kCapAll ? DCRT_MATERIAL_WAVES_PER_EU : DCRT_MATERIAL_OD_WAVES_PER_EU, 8)))
+#define DCRT_MATERIAL_OCCUPANCY __attribute__((amdgpu_waves_per_eu(CAPS == kCapAll || FUSED ? DCRT_MATERIAL_WAVES_PER_EU : DCRT_MATERIAL_OD_WAVES_PER_EU, 8)))
 // CAPS: the scene capabilities this variant is compiled for (kCapAll = any scene; see
 // kCapOpaqueDelta in dscene.h and dcrt_tracer::UploadScene).
 // SCENE_LDS: the scene arrays MATERIAL's shading reads per item are copied into LDS by each
@@ -436,14 +438,21 @@ static_assert(DCRT_MATERIAL_BLOCK % 64 == 0 && DCRT_MATERIAL_BLOCK <= 960, "MATE
 // (larger scenes: the hit -> triangle fetch stays global, the triangle -> material one and the
 // light sample's reads become LDS reads); 0: none.
 // PROBE: counts the rays per film row (the row-cost probe); launched only while it is on.
-template <uint32_t CAPS, int SCENE_LDS, bool PROBE = false>
+// FUSED (with SCENE_LDS == 1; launched exactly when the cast is cast_kernel's CELLS variant): a shadow
+// ray whose 1/d is finite is tested here, against the point light's direction cells
+// (cells_occluded_cached, the function the cast calls, over this workgroup's own LDS copy of what it
+// reads: `si`), instead of travelling through the shadow queue -- no 32-B record, no result word. Its
+// answer goes into the path's flags (kFlagShadowResolved) or, for a path that ends here, straight to
+// finHit at its finish-queue position. A ray with a non-finite 1/d component takes the queue as before.
+template <uint32_t CAPS, int SCENE_LDS, bool PROBE = false, bool FUSED = false>
 __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void material_kernel(PathPool pool, DeviceScene sc, const FrameConstants* __restrict__ fcr, Counters* cnt,
-                                                                             const Counters* prev, const SampleOut* __restrict__ sampleOut)
+                                                                             const Counters* prev, const SampleOut* __restrict__ sampleOut, ShadowInline si)
 {
+    static_assert(!FUSED || (SCENE_LDS == 1 && !PROBE), "FUSED: beside the whole LDS shading copy");
 #if defined(DCRT_MATERIAL_PRIO) && DCRT_MATERIAL_PRIO > 0
     __builtin_amdgcn_s_setprio(DCRT_MATERIAL_PRIO);   // (A/B: issue priority over a co-resident cast)
 #endif
-    __shared__ uint32_t sm[96];
+    __shared__ uint32_t sm[96 + (FUSED ? 1 : 0)];
     // the work list: the previous iteration's extension queue (its rays have been cast) -- or
     // a batch start's virtual queue (item i = path slot i, kVirtualWord)
     QueueMap qm;
@@ -458,6 +467,12 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
     // the plain pointer they were vector loads, each waited on at once, several dependent round
     // trips per round.
     const FrameConstants& fcv = *fcr;
+    // (FUSED) the cells' LDS copy, and the shadow rays tested here: counted per wave, added per workgroup
+    const float4* cellNodes = nullptr;
+    const float4* cellTris = nullptr;
+    const uint32_t* cellLeaves = nullptr;
+    uint32_t& inlineTotal = sm[FUSED ? 96 : 0];
+    uint32_t inlineRays = 0;
     if constexpr (SCENE_LDS != 0) {
         extern __shared__ float4 sceneLds[];
         if (blockIdx.x * blockDim.x >= count) return;   // (no item: no copy)
@@ -476,6 +491,20 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
         for (uint32_t i = threadIdx.x; i < I; i += blockDim.x) { li[i] = sc.instanceLightIndices[i]; ov[i] = sc.overrides[i]; }
         for (uint32_t i = threadIdx.x; i < 13u * sc.ldsMaterials; i += blockDim.x) mt[i] = ((const uint32_t*)sc.materials)[i];
         for (uint32_t i = threadIdx.x; i < 7u * sc.ldsLights; i += blockDim.x) lt[i] = ((const uint32_t*)sc.lights)[i];
+        if constexpr (FUSED) {
+            // behind the shading copy (material_cells_lds_offset): the cast's scene cache of the flat
+            // scene, as scene_cache_load<true> fills it, then the leaf words
+            float4* cn = sceneLds + (material_cells_lds_offset(material_lds_bytes(T, I, sc.ldsMaterials, sc.ldsLights)) >> 4);
+            float4* ct = cn + 2u * si.nodeCount;
+            uint32_t* cl = (uint32_t*)(ct + kRotTriFloat4 * T);
+            for (uint32_t i = threadIdx.x; i < 2u * si.nodeCount; i += blockDim.x) cn[i] = si.nodes[i];
+            for (uint32_t i = threadIdx.x; i < kRotTriFloat4 * T; i += blockDim.x) ct[i] = rot_tri_float4(sc.triVerts, i);
+            for (uint32_t i = threadIdx.x; i < kCellWords; i += blockDim.x) cl[i] = si.leaves[i];
+            if (threadIdx.x == 0) inlineTotal = 0u;
+            cellNodes = cn;
+            cellTris = ct;
+            cellLeaves = cl;
+        }
         __syncthreads();
         if constexpr (SCENE_LDS == 1) {
             sc.triVerts = tv;
@@ -547,7 +576,14 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
             const uint4 r4 = ps.rng;
             l2 = ps.lsrMisc;
             const float4 bThr = psB.thr, bLi = psB.liLsr;
-            const uint32_t shRaw = pool.shadowHitPrev[q];
+            uint32_t shRaw = 0u;
+            if constexpr (FUSED) {
+                // (the queue is the rare route here: the result is fetched only by a wave one of
+                // whose paths took it, behind the flags -- one ballot, then the dependent load)
+                if (__ballot((asu(l2.z) & kFlagShadowPending) != 0u) != 0ull) shRaw = pool.shadowHitPrev[q];
+            } else {
+                shRaw = pool.shadowHitPrev[q];
+            }
             rng.s0 = r4.x; rng.s1 = r4.y; rng.s2 = r4.z; rng.s3 = r4.w;
             path = asu(l2.w);
             flags = asu(l2.z);
@@ -557,8 +593,9 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
             l4 = first ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : bLi;
             // the last shadow ray's result exists only if the path cast one (a position nothing
             // wrote this batch holds a stale value; its lsr is 0 then, but it is not read)
-            shadowHit = (flags & kFlagShadowPending) != 0u && shRaw != 0u;
-            flags &= ~(kFlagFirst | kFlagShadowPending);
+            // (... or the last pass tested the ray itself: kFlagShadowResolved, set only if occluded)
+            shadowHit = (flags & kFlagShadowResolved) != 0u || ((flags & kFlagShadowPending) != 0u && shRaw != 0u);
+            flags &= ~(kFlagFirst | kFlagShadowPending | kFlagShadowResolved);
         }
         F3 li{l4.x, l4.y, l4.z};
         {
@@ -621,12 +658,24 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
             if (so.debugRng) sample_at(so.debugRng, pix) = make_uint4(rng.s0, rng.s1, rng.s2, rng.s3);
         }
     }
+    // FUSED: the shadow ray's occlusion bit here, after the shading (its temporaries are dead), from
+    // the ray still in registers; `queued`: the rays that take the shadow queue
+    bool inlined = false, occluded = false;
+    if constexpr (FUSED) {
+        const V3 sInv = inv_dir(sD);
+        inlined = active && hasShadow && cells_finite(sInv) && (path & fcv.shadowInlineMask) == 0u;
+        if (inlined)
+            occluded = cells_occluded_cached(si.cells, si.res, mk(sO.x, sO.y, sO.z), sD, sO.w, sInv,
+                                             (fcv.features & DCRT_FEATURE_WATERTIGHT) != 0, cellNodes, cellTris, cellLeaves);
+        inlineRays += (uint32_t)__popcll(__ballot(inlined));
+    }
+    const bool queued = active && hasShadow && !inlined;
     DCRT_MCLK(5);
     uint32_t es, ss;
     // (paths ended with a shadow ray pending: the next CONTROL pass completes them)
     const bool fin = active && terminate && hasShadow;
     uint32_t fb;
-    block_append3(active && !terminate, qctr(cnt, kQExt, shard), active && hasShadow, qctr(cnt, kQShadow, shard),
+    block_append3(active && !terminate, qctr(cnt, kQExt, shard), queued, qctr(cnt, kQShadow, shard),
                   fin, qctr(cnt, kQFinish, fshard), sm + (round & 1u) * 48u, &es, &ss, &fb);
     DCRT_MCLK(6);
     const uint32_t qNext = shard * pool.recCap + es;           // the continuing path's records
@@ -651,14 +700,16 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
         st.rng = sRng;
         stB.thr = make_float4(sT.x, sT.y, sT.z, sThr.w);
         stB.liLsr = make_float4(sL.x, sL.y, sL.z, sLsr.x);
-        st.lsrMisc = make_float4(sLsr.y, sLsr.z, asf(pathFlags | (hasShadow ? kFlagShadowPending : 0u)), asf(path));
+        st.lsrMisc = make_float4(sLsr.y, sLsr.z, asf(pathFlags | (queued ? kFlagShadowPending : 0u) | (occluded ? kFlagShadowResolved : 0u)), asf(path));
     }
     if (fin) {
         FinishRec& fr = pool.finRec[fPos];
         fr.liLsr = make_float4(sL.x, sL.y, sL.z, sLsr.x);
         fr.lsrSlot = make_float4(sLsr.y, sLsr.z, asf(path), 0.0f);
+        // (the result CONTROL reads beside it: the cast writes a queued ray's)
+        if (inlined) pool.finHit[fPos] = occluded ? 1u : 0u;
     }
-    if (active && hasShadow) {
+    if (queued) {
         const uint32_t sq = shard * pool.recCap + ss;
         float4* r = ext_rec(pool.shRec, sq);
         r[0] = sO;
@@ -671,6 +722,12 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
     }
     DCRT_MCLK(2);
     ++round;
+    }
+    if constexpr (FUSED) {
+        // shadow_rays counts every shadow ray: the ones tested here, one add per workgroup
+        if ((threadIdx.x & 63u) == 0u && inlineRays) atomicAdd(&inlineTotal, inlineRays);
+        __syncthreads();
+        if (threadIdx.x == 0 && inlineTotal) atomicAdd(&cnt->w[(kInlineShadowWord + shard) * kShardStride], inlineTotal);
     }
     DCRT_MCLK_FLUSH(itemsDone);
     (void)itemsDone;
@@ -995,7 +1052,8 @@ __device__ __forceinline__ void end_iteration(const Counters* cnt, Counters* nex
             const uint32_t virt = virtual_items(cnt);
             const uint32_t ext = virt ? virt : qtotal(cnt, kQExt);
             if (!virt) g->extRays += ext;
-            g->shadowRays += shadowRays;
+            // (with the rays MATERIAL's FUSED variant tested itself: they are in no queue)
+            g->shadowRays += shadowRays + inline_shadow_rays(cnt);
             g->iterations += 1ull;
             g->staticFill = 0u;   // only a batch's first CONTROL pass claims statically
             // IsImageComplete (WavefrontPathTracer.cpp:508-523), exact and on the device: no
@@ -1006,7 +1064,7 @@ __device__ __forceinline__ void end_iteration(const Counters* cnt, Counters* nex
             g->imageComplete = (idle && !g->stopped) ? 1u : 0u;
             g->prevLive = ext + fin;
         }
-        if (threadIdx.x < kCounterWords + 2) nextCnt->w[threadIdx.x * kShardStride] = 0u;   // (with kVirtual/kDrainedWord)
+        if (threadIdx.x < kCounterLines) nextCnt->w[threadIdx.x * kShardStride] = 0u;   // (with kVirtual/kDrainedWord, kInlineShadowWord)
     }
 }
 
@@ -1517,8 +1575,8 @@ __global__ __launch_bounds__(256) void drain_kernel(PathPool pool, DeviceScene s
             thr = psB.thr;
             l4 = psB.liLsr;
         }
-        bool shadowHit = (flags & kFlagShadowPending) ? pool.shadowHit[q] != 0u : false;
-        flags &= ~(kFlagFirst | kFlagShadowPending);
+        bool shadowHit = (flags & kFlagShadowResolved) != 0u || ((flags & kFlagShadowPending) ? pool.shadowHit[q] != 0u : false);
+        flags &= ~(kFlagFirst | kFlagShadowPending | kFlagShadowResolved);
         F3 li{l4.x, l4.y, l4.z};
         V3 lsr0 = mk(l4.w, ps.lsrMisc.x, ps.lsrMisc.y);
         for (;;) {

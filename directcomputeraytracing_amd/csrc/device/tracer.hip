@@ -288,6 +288,10 @@ struct ShadingKnobs {
     bool materialGeneric = false;      // DCRT_MATERIAL_GENERIC=1: always the generic MATERIAL variant
     uint32_t materialLds = 16384;      // DCRT_MATERIAL_LDS = bytes budget of MATERIAL's LDS scene copy, 0: off
     bool materialLdsPartial = true;    // DCRT_MATERIAL_LDS_PARTIAL=0: no mode 2 (everything but the triangles)
+    // DCRT_FUSED_SHADOW: MATERIAL tests the shadow rays of a scene with direction cells itself
+    // (material_kernel's FUSED); 0: every shadow ray takes the shadow queue. n > 1 (tests): fused, and
+    // the path slots with (slot & (n - 1)) != 0 take the queue all the same, so a wave mixes both routes.
+    uint32_t fusedShadow = 1;
 };
 ShadingKnobs ReadShadingKnobs()
 {
@@ -295,6 +299,7 @@ ShadingKnobs ReadShadingKnobs()
     k.materialGeneric = EnvFlag("DCRT_MATERIAL_GENERIC", false);
     k.materialLds = (uint32_t)std::max(0, EnvInt("DCRT_MATERIAL_LDS", (int)k.materialLds));
     k.materialLdsPartial = EnvFlag("DCRT_MATERIAL_LDS_PARTIAL", true);
+    k.fusedShadow = (uint32_t)std::max(0, EnvInt("DCRT_FUSED_SHADOW", (int)k.fusedShadow));
     return k;
 }
 
@@ -352,10 +357,12 @@ struct CastPlan {
     // The cast of a frame with or without counters and ALLOW_ANYHIT_SHADER. The ring and the flat
     // kernel are non-counting and opaque (the counting and any-hit kernels keep the whole stack
     // and the plain scene); the cells go with the flat kernel while a table stands.
+    // (Cells: that launch is the CELLS cast -- MATERIAL's fused variant goes with exactly these launches)
+    bool Cells(bool instr, bool opacity) const { return flat && !instr && !opacity && sceneFlat.shadowRes != 0u; }
     CastLaunch Launch(bool instr, bool opacity) const
     {
         const bool useFlat = flat && !instr && !opacity, useRing = ringRows != 0 && !instr && !opacity;
-        const CastVariant v{ instr, opacity, allCached, pair, ident, useRing, useFlat, useFlat && sceneFlat.shadowRes != 0u };
+        const CastVariant v{ instr, opacity, allCached, pair, ident, useRing, useFlat, Cells(instr, opacity) };
         return { CastKernel(v), useFlat ? ldsFlat : useRing ? ldsRing : ldsWholeStack, useFlat ? sceneFlat : useRing ? sceneRing : scene,
                  resident[instr][opacity] };
     }
@@ -403,6 +410,16 @@ struct dcrt_tracer {
     uint32_t materialCaps = kCapAll;   // the MATERIAL variant launched for it
     uint32_t materialLds = 0;          // MATERIAL's dynamic LDS: the scene copy's bytes (0: the global-memory variant)
     uint32_t materialLdsMode = 0;      // material_kernel<CAPS, mode>: 0 no copy, 1 whole shading data, 2 all but the triangles
+    // MATERIAL's fused variant (material_kernel's FUSED, DeriveFusedShadow): the bytes its copy of the
+    // cells' data adds behind the shading copy -- 0: the scene, the LDS budget or the occupancy rule it
+    // out, or DCRT_FUSED_SHADOW=0 -- and the knob's path-slot mask (FrameConstants::shadowInlineMask)
+    uint32_t fusedLds = 0;
+    uint32_t fusedMask = 0;
+    // MATERIAL of the next launch tests its shadow rays itself: where the cast is the CELLS kernel
+    bool FusedShadow() const
+    {
+        return fusedLds != 0u && !rowProbe && plan.Cells(instrCounters, (frame.features & DCRT_FEATURE_ALLOW_ANYHIT) != 0);
+    }
     // The arrays the partial updates replace (UpdateMaterials / UpdateLights / UpdateInstanceFlags):
     // their device buffers, and host copies of the two that DeriveShading reads. The lights
     // buffer holds DCRT_MAX_LIGHT_COUNT entries, so a changed count never moves it.
@@ -546,6 +563,7 @@ struct dcrt_tracer {
     int SizeGrids(const UploadKnobs& k);
     int CastOccupancy(CastFn k, size_t lds, int* out);
     void DeriveShading();
+    int DeriveFusedShadow();
     int DeriveDrainGrid();
     int RederiveShading();
     int UpdateMaterials(const dcrt_material* materials, uint32_t count);
@@ -884,6 +902,32 @@ void dcrt_tracer::DeriveShading()
     }
 }
 
+// MATERIAL's fused variant for the flat cast's scene (after DeriveShading and PlanFlatCast): its copy of
+// the entry-free nodes, the rotated triangles and the leaf words goes behind the whole shading copy
+// (mode 1) if it fits the same budget again and costs the kernel no resident workgroup -- by registers
+// or by LDS -- against the unfused variant it replaces. Whether a table stands is the launch's question
+// (FusedShadow): this sizes the variant for any table of the scene.
+int dcrt_tracer::DeriveFusedShadow()
+{
+    const ShadingKnobs k = ReadShadingKnobs();
+    fusedLds = 0;
+    fusedMask = k.fusedShadow > 1u ? k.fusedShadow - 1u : 0u;
+    if (!k.fusedShadow || !plan.flat || !plan.cellsRes || materialLdsMode != 1u) return DCRT_OK;
+    const uint32_t extra = material_cells_lds_bytes(plan.sceneFlat.cachedNodes, plan.scene.triangleCount);
+    if (extra > k.materialLds) return DCRT_OK;
+    const bool od = materialCaps == kCapOpaqueDelta;
+    const void* plain = od ? (const void*)material_kernel<kCapOpaqueDelta, 1> : (const void*)material_kernel<kCapAll, 1>;
+    const void* fused = od ? (const void*)material_kernel<kCapOpaqueDelta, 1, false, true> : (const void*)material_kernel<kCapAll, 1, false, true>;
+    const size_t fusedBytes = material_cells_lds_offset(materialLds) + extra;
+    int plainPerCU = 0, fusedPerCU = 0;
+    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&plainPerCU, plain, (int)kMaterialBlock, materialLds));
+    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&fusedPerCU, fused, (int)kMaterialBlock, fusedBytes));
+    plainPerCU = std::min(plainPerCU, LdsResident(materialLds, plain));
+    fusedPerCU = std::min(fusedPerCU, LdsResident(fusedBytes, fused));
+    if (fusedPerCU >= plainPerCU && fusedPerCU > 0) fusedLds = extra;
+    return DCRT_OK;
+}
+
 // drain_kernel's grid: resident workgroups of the variant materialCaps selects
 int dcrt_tracer::DeriveDrainGrid()
 {
@@ -902,9 +946,12 @@ int dcrt_tracer::RederiveShading()
 {
     const uint32_t caps = materialCaps, mode = materialLdsMode, lds = materialLds, grid = drainResident;
     const uint32_t ldsM = plan.scene.ldsMaterials, ldsL = plan.scene.ldsLights;
+    const uint32_t fused = fusedLds, mask = fusedMask;
     DeriveShading();
+    CHECKED(DeriveFusedShadow());
     if (materialCaps != caps) CHECKED(DeriveDrainGrid());
-    if (materialCaps != caps || materialLdsMode != mode || materialLds != lds || drainResident != grid ||
+    if (fusedMask != mask) newImage = true;   // (the frame constants carry it)
+    if (materialCaps != caps || materialLdsMode != mode || materialLds != lds || drainResident != grid || fusedLds != fused ||
         plan.scene.ldsMaterials != ldsM || plan.scene.ldsLights != ldsL) {
         HIPCHECK(hipStreamSynchronize(stream));
         InvalidateGraph();
@@ -1289,6 +1336,7 @@ int dcrt_tracer::PlanFlatCast(const dcrt_flat_scene& s, const UploadKnobs& k)
     const DeviceScene& d = plan.scene;
     plan.flat = false;
     plan.cellsRes = 0;
+    fusedLds = 0;            // (MATERIAL's fused variant goes with the cells: DeriveFusedShadow below)
     dCells = nullptr;        // (sceneAllocs: freed by UploadArrays)
     dCellLeaves = nullptr;
     cells = ShadowCells{};
@@ -1333,7 +1381,7 @@ int dcrt_tracer::PlanFlatCast(const dcrt_flat_scene& s, const UploadKnobs& k)
         cellTriangles.assign(s.triangles, s.triangles + (size_t)s.triangle_count * 3);
         cellTransforms.assign(s.instance_transforms, s.instance_transforms + (size_t)s.instance_count * 2);
     }
-    return DCRT_OK;
+    return DeriveFusedShadow();
 }
 
 // UploadScene's third job: the persistent grids -- the traversal kernels run exactly one resident
@@ -1635,6 +1683,7 @@ int dcrt_tracer::BeginImage()
     fc.apertureBaseAngle = frame.aperture_base_angle;
     fc.frameSeed = frame.frame_seed;
     fc.seedStride = seedStride;
+    fc.shadowInlineMask = fusedMask;
     fc.maxBounce = frame.max_bounce_count;
     fc.lightCount = frame.light_count;
     fc.envLightIndex = frame.environment_light_index;
@@ -1703,7 +1752,13 @@ int dcrt_tracer::LaunchIteration(uint32_t par, bool timed, bool sequenced)
         hipExtLaunchKernelGGL(control_kernel, dim3(controlGrid), dim3(kControlBlock), 0, stream, c0, c1, 0, pool, claims,
                               (const FrameConstants*)dFrame, cnt, (const Counters*)next, dGlobals, (uint32_t)(film.debugRng != nullptr));
     }
+    // (the fused variant with the CELLS cast, and only with it: FusedShadow)
+    const bool fused = FusedShadow();
+    ShadowInline si{};
+    if (fused) si = ShadowInline{ plan.sceneFlat.nodes, plan.sceneFlat.shadowCells, plan.sceneFlat.shadowLeaves, plan.sceneFlat.cachedNodes, plan.sceneFlat.shadowRes };
+    const uint32_t materialBytes = rowProbe ? 0u : fused ? material_cells_lds_offset(materialLds) + fusedLds : materialLds;
     auto material = rowProbe ? material_kernel<kCapAll, 0, true>
+                  : fused ? (materialCaps == kCapOpaqueDelta ? material_kernel<kCapOpaqueDelta, 1, false, true> : material_kernel<kCapAll, 1, false, true>)
                   : materialCaps == kCapOpaqueDelta
                         ? (materialLdsMode == 1 ? material_kernel<kCapOpaqueDelta, 1>
                                                 : materialLdsMode == 2 ? material_kernel<kCapOpaqueDelta, 2> : material_kernel<kCapOpaqueDelta, 0>)
@@ -1712,8 +1767,8 @@ int dcrt_tracer::LaunchIteration(uint32_t par, bool timed, bool sequenced)
     if (timed) CHECKED(TimedPair(kTimedMaterial, &m0, &m1));
     {
         Annotation a("Material", !capturing);
-        hipExtLaunchKernelGGL(material, dim3(materialGrid), dim3(kMaterialBlock), rowProbe ? 0u : materialLds, stream, m0, m1, 0, pool, plan.scene,
-                              (const FrameConstants*)dFrame, cnt, (const Counters*)next, (const SampleOut*)dSampleOut);
+        hipExtLaunchKernelGGL(material, dim3(materialGrid), dim3(kMaterialBlock), materialBytes, stream, m0, m1, 0, pool, plan.scene,
+                              (const FrameConstants*)dFrame, cnt, (const Counters*)next, (const SampleOut*)dSampleOut, si);
     }
     if (timed) CHECKED(TimedPair(kTimedCast, &e0, &e1));
     Annotation castAnnotation(knobs.mergedCasts ? "Extension + shadow ray cast" : "Extension ray cast, shadow ray cast", !capturing);
@@ -3077,6 +3132,7 @@ DCRT_API int dcrt_tracer_get_info(dcrt_tracer* t, dcrt_tracer_info* out)
     out->shadow_cells = cells ? shipped.scene.shadowRes : 0u;
     out->shadow_cell_max_leaves = cells ? t->cells.maxLeaves : 0u;
     out->shadow_cell_mean_leaves = cells ? t->cells.meanLeaves : 0.0f;
+    out->shadow_inline = t->hasScene && t->FusedShadow() ? 1u : 0u;
     return DCRT_OK;
 }
 

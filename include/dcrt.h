@@ -308,6 +308,10 @@ typedef struct dcrt_tracer_info {
                                      6 * R * R direction cells (dcrt_shadow_cells_build) instead of walking the BVH */
     uint32_t shadow_cell_max_leaves;   /* leaves in the fullest cell, and the mean over the cells */
     float shadow_cell_mean_leaves;
+    uint32_t shadow_inline;       /* 1: MATERIAL tests the shadow rays against those cells itself, as the next launch
+                                     stands (frame features, instrumentation): no shadow-queue record, no result word;
+                                     0: they take the shadow queue to the cast (DCRT_FUSED_SHADOW=0, no table, any-hit,
+                                     counters, the row-cost probe) */
 } dcrt_tracer_info;
 
 typedef struct dcrt_tracer dcrt_tracer;
@@ -316,12 +320,12 @@ typedef struct dcrt_scene dcrt_scene;
 /* ===== version / device ================================================== */
 /* ABI version of this header: bumped whenever a struct changes size or an entry point its
  * meaning (2: dcrt_tracer_info grew cast_waves_per_cu / ring_rows / stack_lds_rows; 3: it grew
- * shadow_cells / shadow_cell_max_leaves / shadow_cell_mean_leaves). A caller
+ * shadow_cells / shadow_cell_max_leaves / shadow_cell_mean_leaves; 4: shadow_inline). A caller
  * compiled against another header checks dcrt_abi_version() == DCRT_ABI_VERSION before it
  * passes any struct (a smaller dcrt_tracer_info would be written past its end). Added entry
  * points with structs of their own (the scene updates, the output views, the film denoiser)
  * leave it as it is: nothing an older caller passes has changed. */
-#define DCRT_ABI_VERSION 3
+#define DCRT_ABI_VERSION 4
 DCRT_API int dcrt_abi_version(void);
 DCRT_API const char* dcrt_version(void);
 DCRT_API const char* dcrt_last_error(void);
