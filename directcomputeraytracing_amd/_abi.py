@@ -15,7 +15,7 @@ LIB_PATH = PKG_DIR / "libdcrt.so"
 
 # ---- status codes / flags (dcrt.h) -----------------------------------------
 DCRT_OK = 0
-ABI_VERSION = 4          # DCRT_ABI_VERSION: load_library refuses a libdcrt.so of another
+ABI_VERSION = 5          # DCRT_ABI_VERSION: load_library refuses a libdcrt.so of another
 ERRORS = {-1: "DCRT_E_INVALID_ARG", -2: "DCRT_E_HIP", -3: "DCRT_E_NO_SCENE", -4: "DCRT_E_IO",
           -5: "DCRT_E_LIMIT", -6: "DCRT_E_NO_DEVICE"}
 LIGHT_INDEX_INVALID = 0xFFFFFFFF
@@ -179,7 +179,8 @@ class TracerInfo(C.Structure):
                 ("material_grid", C.c_uint32), ("cast_grid", C.c_uint32), ("material_lds", C.c_uint32),
                 ("cast_identity", C.c_uint32), ("stack_lds_rows", C.c_uint32), ("ring_rows", C.c_uint32),
                 ("cast_waves_per_cu", C.c_uint32), ("shadow_cells", C.c_uint32), ("shadow_cell_max_leaves", C.c_uint32),
-                ("shadow_cell_mean_leaves", C.c_float), ("shadow_inline", C.c_uint32)]
+                ("shadow_cell_mean_leaves", C.c_float), ("shadow_inline", C.c_uint32), ("shading_tables", C.c_uint32),
+                ("dielectric_row_bytes", C.c_uint32), ("dielectric_row_lds", C.c_uint32), ("frame_table_bytes", C.c_uint32)]
 
 
 class ShadowCellsInfo(C.Structure):
@@ -370,6 +371,8 @@ SIGNATURES = [
     ("dcrt_write_bmp", _I, [C.c_char_p, _U, _U, C.POINTER(C.c_uint8)]),
     ("dcrt_device_math_eval", _I, [_P, _I, _FP, _U, _FP]),
     ("dcrt_device_bsdf_eval", _I, [_P, C.POINTER(BsdfProbeMaterial), _U, _FP, _FP, _U, _FP, _FP]),
+    ("dcrt_device_frame_probe", _I, [_P, C.POINTER(C.c_uint32), _U, _I, _FP]),
+    ("dcrt_flat_scene_triangle_instances", _I, [C.POINTER(FlatScene), C.POINTER(C.c_uint32), _U, C.POINTER(C.c_int)]),
     ("dcrt_device_bsdf_sample", _I, [_P, C.POINTER(BsdfProbeMaterial), _U, _FP, _FP, _U, _FP, _FP, _FP, C.POINTER(C.c_uint32)]),
 ]
 

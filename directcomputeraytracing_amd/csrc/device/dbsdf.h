@@ -248,10 +248,11 @@ DEV V3 specular_bsdf_sample(V3 wo, float sample, float etaO, float etaI, bool th
 }
 
 // ---- BSDFs.inc.hlsl dispatch -----------------------------------------------------
-DEV V3 isf_factor(const DeviceScene& s, float alpha, V3 albedo, float ior, uint32_t mode)
+// (`rows`: the material's rows of the dielectric LUT, whose float 130 is that average, or null)
+DEV V3 isf_factor(const DeviceScene& s, float alpha, V3 albedo, float ior, uint32_t mode, const float* rows = nullptr)
 {
     if (mode == DCRT_INTERNAL_SCATTERING_IGNORE) return mk(1.0f, 1.0f, 1.0f);
-    const float avg = lut_brdf_dielectric_avg(s, alpha, ior, true);
+    const float avg = rows ? rows[130] : lut_brdf_dielectric_avg(s, alpha, ior, true);
     const float f = 1.0f - avg;
     V3 factor = mk(f, f, f);
     if (mode == DCRT_INTERNAL_SCATTERING_MULTIPLE)
@@ -314,8 +315,9 @@ DEV BsdfFrame bsdf_frame(const DeviceScene& s, V3 woW, const Intersection& it)
         f.Eavg = lut_brdf_avg(s, it.alpha);
     }
     if (type == DCRT_MATERIAL_TYPE_PLASTIC && f.any) {
-        f.diel = lut_brdf_dielectric(s, cosO, it.alpha, it.ior.x, false);
-        f.isf = isf_factor(s, it.alpha, it.albedo, it.ior.x, it.internalScatteringMode);
+        // (the material's rows where the scene has them: the same operands, read instead of formed)
+        f.diel = it.dielRows ? lut_brdf_dielectric_rows(it.dielRows, cosO) : lut_brdf_dielectric(s, cosO, it.alpha, it.ior.x, false);
+        f.isf = isf_factor(s, it.alpha, it.albedo, it.ior.x, it.internalScatteringMode, it.dielRows);
     }
     if (type == DCRT_MATERIAL_TYPE_DIELECTRIC && it.multiscattering && !(it.alpha < kAlphaThreshold))
         f.dms = dielectric_ms(s, cosO, it.alpha, it.ior.x, f.inv);

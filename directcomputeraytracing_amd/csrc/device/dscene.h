@@ -102,7 +102,34 @@ struct DeviceScene {
     const uint64_t* shadowCells;
     const uint32_t* shadowLeaves;   // kCellWords words
     uint32_t shadowRes;
+    // Scene-constant shading work done once at upload (DCRT_SHADING_TABLES, kTable* below): the bits
+    // in force, the per-material rows of the plastic dielectric LUT (kDielRowFloats floats per
+    // material, build_diel_rows_kernel; null: every hit samples the LUT itself) and how many
+    // materials' rows MATERIAL's LDS scene copy holds behind the lights (0, or ldsMaterials).
+    const float* dielRows;
+    uint32_t ldsRows;
+    uint32_t shadingTables;
+    // The world-space shading frames per triangle (kTableFrames; build_tri_frames_kernel): 3 float4 --
+    // (normal, flags), (tangent, 0), (geometry normal, 0) -- of a scene whose every BLAS has one
+    // instance, or null; ldsFrames: 1 when MATERIAL's LDS copy holds them (behind the rows).
+    const float4* triFrames;
+    uint32_t ldsFrames;
 };
+
+// DCRT_SHADING_TABLES bits: per-hit work whose inputs are fixed at scene upload
+constexpr uint32_t kTableDeltaPdf = 1u << 0;   // no BSDF pdf for a delta light's sample: its MIS weight is the constant 1
+constexpr uint32_t kTableDielRows = 1u << 1;   // lut_brdf_dielectric from per-material float rows
+constexpr uint32_t kTableFrames = 1u << 2;     // the normal / tangent / geometry normal of a hit from a per-triangle table
+constexpr uint32_t kTableAll = kTableDeltaPdf | kTableDielRows | kTableFrames;
+// flags in triFrames[3 t].w: the triangle's three vertex normals are bitwise equal; its tangents likewise
+constexpr uint32_t kFrameFlatNormal = 1u, kFrameFlatTangent = 2u;
+// A material's rows of the 32 x 16 x 32 dielectric LUT: the two slices x two y rows x 32 texels that
+// sample_array / bilinear_u16 read for alpha = roughness^2 and ior.x, as floats already divided by
+// 65535 ([slice][y][x]), then bilinear_u16's fy, sample_array's fraction, isf_factor's
+// lut_brdf_dielectric_avg, and a pad to 16 B.
+constexpr uint32_t kDielRowFloats = 132;
+constexpr uint32_t kDielRowsMaxMaterials = 64;   // beyond it (33 KiB of rows) the scene keeps the per-hit LUT path
+__host__ __device__ inline uint32_t diel_rows_bytes(uint32_t materials) { return 4u * kDielRowFloats * materials; }
 
 // MATERIAL's LDS scene copy, in 16-B units: triVerts (3 T), triShade (6 T), the forward
 // instance transforms (3 I), then 4-B words: instance light indices (I), overrides (I),
@@ -1023,6 +1050,48 @@ DEV float lut_brdf_dielectric_avg(const DeviceScene& s, float alpha, float eta, 
 {
     return sample_array(s.lutBrdfDielectricAvg, 16, 16, 2, alpha, (eta - 1.0f) / 2.0f, 0.0f, 1, entering ? 1u : 0u);
 }
+// Float `k` (< kDielRowFloats) of the rows of a material with (alpha, eta): what
+// lut_brdf_dielectric(s, cosThetaO, alpha, eta, false) reads and forms that does not depend on
+// cosThetaO, through sample_array's and bilinear_u16's own expressions -- and, at k = 130,
+// lut_brdf_dielectric_avg(s, alpha, eta, true) itself.
+DEV float diel_row_value(const uint16_t* lut, const uint16_t* lutAvg, float alpha, float eta, uint32_t k)
+{
+    const float ww = (eta - 1.0f) / 2.0f;
+    const float slicePos = ww * ((float)16u - 1.0f);
+    const float fraction = slicePos - floorf(slicePos);
+    const float v = remap(16, alpha);
+    const float y = v * (float)16 - 0.5f;
+    const float fy0 = floorf(y);
+    const float fy = y - fy0;
+    if (k < 128u) {
+        const uint32_t sl = (uint32_t)(int32_t)slicePos + (k >> 6);
+        const int i = array_slice((float)sl, 32);
+        const int yy = clampi((int)fy0 + (int)((k >> 5) & 1u), 0, 16 - 1);
+        return u16tex(lut + (size_t)i * 32 * 16, (int)(k & 31u), yy, 32);
+    }
+    if (k == 128u) return fy;
+    if (k == 129u) return fraction;
+    if (k == 130u) return sample_array(lutAvg, 16, 16, 2, alpha, ww, 0.0f, 1, 1u);
+    return 0.0f;
+}
+// lut_brdf_dielectric(s, cosThetaO, alpha, eta, false) from the material's rows `r`: what is left per
+// hit is bilinear_u16's x side and the same lerps over the same operands in the same order.
+DEV float lut_brdf_dielectric_rows(const float* r, float cosThetaO)
+{
+    const float u = remap(32, cosThetaO);
+    const float x = u * (float)32 - 0.5f;
+    const float fx0 = floorf(x);
+    const float fx = x - fx0;
+    const int x0 = clampi((int)fx0, 0, 32 - 1), x1 = clampi((int)fx0 + 1, 0, 32 - 1);
+    const float fy = r[128], fraction = r[129];
+    const float a0 = r[x0] * (1.0f - fx) + r[x1] * fx;
+    const float c0 = r[32 + x0] * (1.0f - fx) + r[32 + x1] * fx;
+    const float a = a0 * (1.0f - fy) + c0 * fy;
+    const float a1 = r[64 + x0] * (1.0f - fx) + r[64 + x1] * fx;
+    const float c1 = r[96 + x0] * (1.0f - fx) + r[96 + x1] * fx;
+    const float b = a1 * (1.0f - fy) + c1 * fy;
+    return lerp(a, b, fraction);
+}
 DEV float lut_bsdf(const DeviceScene& s, float cosThetaO, float alpha, float eta, bool entering)
 {
     return sample_array(s.lutBsdf, 32, 16, 32, cosThetaO, alpha, (eta - 1.0f) / 2.0f, 16, entering ? 16u : 0u);
@@ -1092,6 +1161,7 @@ struct Intersection {
     V3 position, normal, tangent, geometryNormal, ior;
     bool isTwoSided, backface, multiscattering;
     uint32_t internalScatteringMode, materialType, lightIndex, triangleIndex;
+    const float* dielRows;   // the material's rows of the dielectric LUT (kDielRowFloats), or null: sample the LUT
 };
 
 DEV V3 bary3(V3 p0, V3 p1, V3 p2, float u, float v)   // Math.inc.hlsl:35-43
@@ -1102,7 +1172,34 @@ DEV V3 bary3(V3 p0, V3 p1, V3 p2, float u, float v)   // Math.inc.hlsl:35-43
     return r1;
 }
 
-template <uint32_t CAPS = kCapAll>
+// The frame part of HitInfoToIntersection in instance space, for the per-hit path and for
+// build_tri_frames_kernel alike: the interpolated normal, the tangent made orthogonal to it, the
+// geometry normal (each then goes through normalize(mul43(., 0, M)) into world space).
+DEV V3 frame_normal(float4 a0, float4 a1, float4 a2, float u, float v)
+{
+    return normalize(bary3(mk(a0.x, a0.y, a0.z), mk(a1.x, a1.y, a1.z), mk(a2.x, a2.y, a2.z), u, v));
+}
+DEV V3 frame_tangent(float4 a0, float4 b0, float4 a1, float4 b1, float4 a2, float4 b2, float u, float v, V3 normal)
+{
+    V3 tangent = bary3(mk(a0.w, b0.x, b0.y), mk(a1.w, b1.x, b1.y), mk(a2.w, b2.x, b2.y), u, v);
+    float tl = length(tangent);
+    if (tl >= 0.000001f) {
+        tangent = tangent - normal * dot(tangent, normal);
+        tl = length(tangent);
+    }
+    if (tl < 0.000001f) {
+        tangent = cross(normal, mk(0.0f, 1.0f, 0.0f));
+        tl = length(tangent);
+        tangent = tl >= 0.000001f ? tangent : mk(1.0f, 0.0f, 0.0f);
+    }
+    return tangent / tl;
+}
+DEV V3 frame_geometry_normal(V3 p0, V3 p1, V3 p2) { return normalize(cross(p2 - p0, p1 - p0)); }
+
+// FRAMES: the caller may be handed a frame table (s.triFrames) -- MATERIAL's delta-only variant over the
+// whole-scene LDS copy; every other caller compiles the per-hit frame alone (the any-scene variants
+// spill one more register with the table's branch in them, tools/vgprs.sh).
+template <uint32_t CAPS = kCapAll, bool FRAMES = false>
 DEV void hit_to_intersection(const DeviceScene& s, const HitRecord& h, Intersection& it)
 {
     const uint32_t inst = h.inst, tri = h.tri & 0x7FFFFFFFu;
@@ -1118,20 +1215,39 @@ DEV void hit_to_intersection(const DeviceScene& s, const HitRecord& h, Intersect
     const float u = h.u, v = h.v;
     const V3 p0 = mk(q0.x, q0.y, q0.z), p1 = mk(q1.x, q1.y, q1.z), p2 = mk(q2.x, q2.y, q2.z);
     it.position = bary3(p0, p1, p2, u, v);
-    it.normal = normalize(bary3(mk(a0.x, a0.y, a0.z), mk(a1.x, a1.y, a1.z), mk(a2.x, a2.y, a2.z), u, v));
-    V3 tangent = bary3(mk(a0.w, b0.x, b0.y), mk(a1.w, b1.x, b1.y), mk(a2.w, b2.x, b2.y), u, v);
-    float tl = length(tangent);
-    if (tl >= 0.000001f) {
-        tangent = tangent - it.normal * dot(tangent, it.normal);
-        tl = length(tangent);
+    if constexpr (!FRAMES) {
+        it.normal = frame_normal(a0, a1, a2, u, v);
+        it.tangent = frame_tangent(a0, b0, a1, b1, a2, b2, u, v, it.normal);
+        it.geometryNormal = frame_geometry_normal(p0, p1, p2);
+    } else {
+        // The frame: from the triangle's table entry what the entry holds for this hit, the rest per hit.
+        // With bitwise-equal vertex normals bary3 forms (+0) u + n0 + (+0) v, which does not depend on u
+        // and v unless a product is -0 (a watertight edge hit can return u == -0, and then a -0 component
+        // of n0 stays -0): the table's normal (u = v = +0) stands for hits with neither sign bit set,
+        // its tangent where the tangents are equal too, its geometry normal always.
+        {
+            const float4* M = s.transforms + (size_t)inst * 3;
+            const float4* F = s.triFrames;
+            uint32_t flat = 0u;
+            float4 f0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), f1 = f0, f2 = f0;
+            if (F != nullptr) {
+                F += (size_t)tri * 3;
+                f0 = F[0]; f1 = F[1]; f2 = F[2];
+                flat = ((__float_as_uint(u) | __float_as_uint(v)) & 0x80000000u) == 0u ? __float_as_uint(f0.w) : 0u;
+            }
+            if ((flat & (kFrameFlatNormal | kFrameFlatTangent)) == (kFrameFlatNormal | kFrameFlatTangent)) {
+                it.normal = mk(f0.x, f0.y, f0.z);
+                it.tangent = mk(f1.x, f1.y, f1.z);
+            } else {
+                const V3 n = frame_normal(a0, a1, a2, u, v);
+                it.tangent = normalize(mul43(frame_tangent(a0, b0, a1, b1, a2, b2, u, v, n), 0.0f, M));
+                if (flat & kFrameFlatNormal) it.normal = mk(f0.x, f0.y, f0.z);
+                else it.normal = normalize(mul43(n, 0.0f, M));
+            }
+            if (F != nullptr) it.geometryNormal = mk(f2.x, f2.y, f2.z);
+            else it.geometryNormal = normalize(mul43(frame_geometry_normal(p0, p1, p2), 0.0f, M));
+        }
     }
-    if (tl < 0.000001f) {
-        tangent = cross(it.normal, mk(0.0f, 1.0f, 0.0f));
-        tl = length(tangent);
-        tangent = tl >= 0.000001f ? tangent : mk(1.0f, 0.0f, 0.0f);
-    }
-    it.tangent = tangent / tl;
-    it.geometryNormal = normalize(cross(p2 - p0, p1 - p0));
     const uint32_t mid = ov != DCRT_INSTANCE_MATERIAL_OVERRIDE_NONE ? ov : __float_as_uint(q1.w);
     const dcrt_material& m = s.materials[mid];
     if constexpr ((CAPS & kCapTextures) == 0u) {
@@ -1167,11 +1283,15 @@ DEV void hit_to_intersection(const DeviceScene& s, const HitRecord& h, Intersect
     it.multiscattering = (m.flags & DCRT_MATERIAL_FLAG_MULTISCATTERING) != 0;
     it.internalScatteringMode = (m.flags & DCRT_MATERIAL_FLAG_INTERNAL_SCATTERING_MASK) >> DCRT_MATERIAL_FLAG_INTERNAL_SCATTERING_SHIFT;
     it.backface = (h.tri & 0x80000000u) != 0;
+    // (the rows hold alpha = roughness^2 of the material: not under the checkerboard, which varies it per hit)
+    it.dielRows = s.dielRows != nullptr && (m.flags & DCRT_MATERIAL_FLAG_ROUGHNESS_TEXTURE) == 0u ? s.dielRows + (size_t)mid * kDielRowFloats : nullptr;
     const float4* M = s.transforms + (size_t)inst * 3;
     it.position = mul43(it.position, 1.0f, M);
-    it.normal = normalize(mul43(it.normal, 0.0f, M));
-    it.geometryNormal = normalize(mul43(it.geometryNormal, 0.0f, M));
-    it.tangent = normalize(mul43(it.tangent, 0.0f, M));
+    if constexpr (!FRAMES) {
+        it.normal = normalize(mul43(it.normal, 0.0f, M));
+        it.geometryNormal = normalize(mul43(it.geometryNormal, 0.0f, M));
+        it.tangent = normalize(mul43(it.tangent, 0.0f, M));
+    }
 }
 
 // ---- lights (Light.inc.hlsl, RayTracingCommon.inc.hlsl:124-225) -------------------

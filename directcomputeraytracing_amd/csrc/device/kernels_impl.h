@@ -165,6 +165,63 @@ __device__ __forceinline__ void begin_batch_claims(Globals* g)
     g->staticFill = G ? 1u : 0u;
 }
 
+// The per-material rows of the plastic dielectric LUT (DeviceScene::dielRows; a launch per upload of
+// the materials or the LUTs): float k of material m at rows[m * kDielRowFloats + k], with alpha as
+// hit_to_intersection forms it for a material without the roughness checkerboard.
+__global__ void build_diel_rows_kernel(const dcrt_material* materials, uint32_t count, const uint16_t* lut, const uint16_t* lutAvg,
+                                       float* rows)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count * kDielRowFloats) return;
+    const uint32_t m = i / kDielRowFloats, k = i % kDielRowFloats;
+    float roughness = materials[m].roughness;
+    roughness = roughness * 1.0f;
+    const float alpha = roughness * roughness;
+    rows[i] = diel_row_value(lut, lutAvg, alpha, materials[m].ior[0], k);
+}
+// (tests) the rows of the BSDF probe kernels' one material, whose alpha is given as it stands
+__global__ void probe_diel_rows_kernel(const uint16_t* lut, const uint16_t* lutAvg, float* rows, float alpha, float ior)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < kDielRowFloats) rows[k] = diel_row_value(lut, lutAvg, alpha, ior, k);
+}
+
+// The world-space frame of every triangle (DeviceScene::triFrames) of a scene whose triangles each
+// belong to one instance (`triInstance`, UINT32_MAX: a triangle no instance reaches): the per-hit
+// helpers at u = v = +0 with the instance's matrix, and the two flags that say for which hits the
+// normal and the tangent stand (hit_to_intersection).
+__global__ void build_tri_frames_kernel(const float4* triVerts, const float4* triShade, const float4* transforms, const uint32_t* triInstance,
+                                        uint32_t count, float4* frames)
+{
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    const uint32_t inst = triInstance[t];
+    float4 f0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), f1 = f0, f2 = f0;
+    if (inst != 0xFFFFFFFFu) {
+        const float4* P = triVerts + (size_t)t * 3;
+        const float4* Q = triShade + (size_t)t * 6;
+        const float4 q0 = P[0], q1 = P[1], q2 = P[2];
+        const float4 a0 = Q[0], b0 = Q[1], a1 = Q[2], b1 = Q[3], a2 = Q[4], b2 = Q[5];
+        const float4* M = transforms + (size_t)inst * 3;
+        const V3 n = frame_normal(a0, a1, a2, 0.0f, 0.0f);
+        const V3 nw = normalize(mul43(n, 0.0f, M));
+        const V3 tw = normalize(mul43(frame_tangent(a0, b0, a1, b1, a2, b2, 0.0f, 0.0f, n), 0.0f, M));
+        const V3 gw = normalize(mul43(frame_geometry_normal(mk(q0.x, q0.y, q0.z), mk(q1.x, q1.y, q1.z), mk(q2.x, q2.y, q2.z)), 0.0f, M));
+        auto same3 = [](float x0, float y0, float z0, float x1, float y1, float z1) {
+            return asu(x0) == asu(x1) && asu(y0) == asu(y1) && asu(z0) == asu(z1);
+        };
+        uint32_t flags = 0u;
+        if (same3(a0.x, a0.y, a0.z, a1.x, a1.y, a1.z) && same3(a0.x, a0.y, a0.z, a2.x, a2.y, a2.z)) flags |= kFrameFlatNormal;
+        if (same3(a0.w, b0.x, b0.y, a1.w, b1.x, b1.y) && same3(a0.w, b0.x, b0.y, a2.w, b2.x, b2.y)) flags |= kFrameFlatTangent;
+        f0 = make_float4(nw.x, nw.y, nw.z, asf(flags));
+        f1 = make_float4(tw.x, tw.y, tw.z, 0.0f);
+        f2 = make_float4(gw.x, gw.y, gw.z, 0.0f);
+    }
+    frames[(size_t)t * 3] = f0;
+    frames[(size_t)t * 3 + 1] = f1;
+    frames[(size_t)t * 3 + 2] = f2;
+}
+
 // Upload-time gathers of the triangles' vertices (one fetch level less for the traversal
 // and for MATERIAL's HitInfoToIntersection): positions (+ the degenerate flag and the
 // per-triangle material id in the w words) and the shading attributes.
@@ -331,7 +388,7 @@ __global__ __launch_bounds__(kControlBlock) void control_kernel(PathPool pool, F
 // BSDF sample (the next extension ray), the new throughput, bsdfPdf (thr.w) and flags. `li` is
 // the path's Li after CONTROL's `Li += light sampling result`. Shared by material_kernel and
 // the drain kernel (drain_kernel), so both run the same arithmetic in the same order.
-template <uint32_t CAPS>
+template <uint32_t CAPS, bool FRAMES = false>
 __device__ __forceinline__ void shade_path(const DeviceScene& sc, const FrameConstants& fc, const HitRecord& hit, V3 dir, Rng& rng,
                                            uint32_t& flags, float4& thr, const F3& li, V3& T, V3& L, V3& lsr, bool& terminate,
                                            bool& hasShadow, V3& nO, V3& nD, float4& sO, V3& sD, float& extOpacity,
@@ -344,7 +401,7 @@ __device__ __forceinline__ void shade_path(const DeviceScene& sc, const FrameCon
     Intersection it;
     it.lightIndex = DCRT_LIGHT_INDEX_INVALID; it.triangleIndex = 0;
     it.geometryNormal = mk(0.0f, 0.0f, 0.0f);
-    if (hasHit) hit_to_intersection<CAPS>(sc, hit, it);
+    if (hasHit) hit_to_intersection<CAPS, FRAMES>(sc, hit, it);
     DCRT_MCLK(1);
     T = mk(thr.x, thr.y, thr.z);
     L = mk(li.x, li.y, li.z);
@@ -373,7 +430,14 @@ __device__ __forceinline__ void shade_path(const DeviceScene& sc, const FrameCon
             if (any_pos(ls.radiance) && ls.pdf > 0.0f) {
                 const V3 bsdf = evaluate_bsdf(sc, vndf, ls.wi, bf, it);
                 const float NdotWI = fabsf(dot(it.normal, ls.wi));
-                const float bsdfPdf = evaluate_bsdf_pdf(sc, vndf, ls.wi, bf, it);
+                // The pdf enters the weight of an area light's sample alone (kTableDeltaPdf): a variant
+                // without mesh and environment lights samples delta lights only, and one wave-uniform
+                // test of the knob stands in front of the call. The other variants compute it for every
+                // sample as before (a branch per sample diverges where delta and area lights mix).
+                bool wantPdf = true;
+                if constexpr ((CAPS & (kCapLightMesh | kCapLightEnv)) == 0u) wantPdf = (sc.shadingTables & kTableDeltaPdf) == 0u;
+                float bsdfPdf = 0.0f;
+                if (wantPdf) bsdfPdf = evaluate_bsdf_pdf(sc, vndf, ls.wi, bf, it);
                 const float weight = ls.isDelta ? 1.0f : power_heuristic(ls.pdf, bsdfPdf);
                 lsr = T * ls.radiance * bsdf * NdotWI * weight / ls.pdf;
                 const V3 so = offset_ray_origin(it.position, it.geometryNormal, ls.wi);
@@ -485,6 +549,13 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
         uint32_t* ov = li + I;
         uint32_t* mt = ov + I;
         uint32_t* lt = mt + 13u * sc.ldsMaterials;
+        float* rw = (float*)(lt + 7u * sc.ldsLights);   // (the dielectric LUT's rows of sc.ldsRows materials)
+        for (uint32_t i = threadIdx.x; i < kDielRowFloats * sc.ldsRows; i += blockDim.x) rw[i] = sc.dielRows[i];
+        // (the triangles' frames at the next 16-B boundary, in front of the fused variant's cells)
+        const uint32_t frameOff = material_cells_lds_offset(material_lds_bytes(T, I, sc.ldsMaterials, sc.ldsLights) + diel_rows_bytes(sc.ldsRows));
+        const uint32_t FT = sc.ldsFrames ? T : 0u;
+        float4* fr = sceneLds + (frameOff >> 4);
+        for (uint32_t i = threadIdx.x; i < 3u * FT; i += blockDim.x) fr[i] = sc.triFrames[i];
         for (uint32_t i = threadIdx.x; i < 3u * T; i += blockDim.x) tv[i] = sc.triVerts[i];
         for (uint32_t i = threadIdx.x; i < 6u * T; i += blockDim.x) ts[i] = sc.triShade[i];
         for (uint32_t i = threadIdx.x; i < 3u * I; i += blockDim.x) tf[i] = sc.transforms[i];
@@ -494,7 +565,7 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
         if constexpr (FUSED) {
             // behind the shading copy (material_cells_lds_offset): the cast's scene cache of the flat
             // scene, as scene_cache_load<true> fills it, then the leaf words
-            float4* cn = sceneLds + (material_cells_lds_offset(material_lds_bytes(T, I, sc.ldsMaterials, sc.ldsLights)) >> 4);
+            float4* cn = fr + 3u * FT;
             float4* ct = cn + 2u * si.nodeCount;
             uint32_t* cl = (uint32_t*)(ct + kRotTriFloat4 * T);
             for (uint32_t i = threadIdx.x; i < 2u * si.nodeCount; i += blockDim.x) cn[i] = si.nodes[i];
@@ -515,6 +586,8 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
         sc.overrides = ov;
         sc.materials = (const dcrt_material*)mt;
         sc.lights = (const dcrt_light*)lt;
+        if (sc.ldsRows != 0u) sc.dielRows = rw;
+        if (FT != 0u) sc.triFrames = fr;
     }
     DCRT_MCLK_INIT;
     uint32_t itemsDone = 0;
@@ -614,7 +687,7 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
         float extOpacity = 0.0f, shadowOpacity = 0.0f;
         V3 T, L, lsr;
         DCRT_MCLK(0);
-        shade_path<CAPS>(sc, fcv, hit, dir, rng, flags, thr, li, T, L, lsr, terminate, hasShadow, nO, nD, sO, sD,
+        shade_path<CAPS, SCENE_LDS == 1 && CAPS != kCapAll>(sc, fcv, hit, dir, rng, flags, thr, li, T, L, lsr, terminate, hasShadow, nO, nD, sO, sD,
                          extOpacity, shadowOpacity DCRT_MCLK_ARGS);
         DCRT_MCLK(4);
         if (fcv.features & DCRT_FEATURE_ALLOW_ANYHIT) {   // :422-430
@@ -1692,7 +1765,7 @@ __global__ void math_eval_kernel(int function, const float* x, uint32_t n, float
 
 // One material's BSDF at a caller's directions (tests): MATERIAL's bsdf_frame / evaluate_bsdf /
 // evaluate_bsdf_pdf / sample_bsdf in the frame n = (0,0,1), t = (1,0,0). Of `sc` only the LUTs are read.
-__device__ __forceinline__ Intersection bsdf_probe_intersection(const dcrt_bsdf_probe_material& m)
+__device__ __forceinline__ Intersection bsdf_probe_intersection(const dcrt_bsdf_probe_material& m, const float* dielRows)
 {
     Intersection it;
     it.albedo = mk(m.albedo[0], m.albedo[1], m.albedo[2]);
@@ -1709,7 +1782,24 @@ __device__ __forceinline__ Intersection bsdf_probe_intersection(const dcrt_bsdf_
     it.materialType = m.type;
     it.lightIndex = DCRT_LIGHT_INDEX_INVALID;
     it.triangleIndex = 0;
+    it.dielRows = dielRows;   // (the probe material's own rows, or null)
     return it;
+}
+// The frame of caller-supplied hit records (tests): hit_to_intersection in the form that takes the
+// frame table (sc.triFrames, or null), as MATERIAL's delta-only whole-scene variants call it.
+__global__ void frame_probe_kernel(DeviceScene sc, const uint4* records, uint32_t n, float* out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint4 r = records[i];
+    HitRecord h;
+    h.t = 1.0f; h.u = asf(r.x); h.v = asf(r.y); h.tri = r.z; h.inst = r.w;
+    Intersection it;
+    hit_to_intersection<kCapAll, true>(sc, h, it);
+    float* o = out + (size_t)i * 9;
+    o[0] = it.normal.x; o[1] = it.normal.y; o[2] = it.normal.z;
+    o[3] = it.tangent.x; o[4] = it.tangent.y; o[5] = it.tangent.z;
+    o[6] = it.geometryNormal.x; o[7] = it.geometryNormal.y; o[8] = it.geometryNormal.z;
 }
 __global__ void bsdf_eval_kernel(DeviceScene sc, dcrt_bsdf_probe_material m, uint32_t features, const float* wi, const float* wo,
                                  uint32_t n, float* f, float* pdf)
@@ -1717,7 +1807,7 @@ __global__ void bsdf_eval_kernel(DeviceScene sc, dcrt_bsdf_probe_material m, uin
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const bool vndf = (features & DCRT_FEATURE_GGX_SAMPLE_VNDF) != 0;
-    const Intersection it = bsdf_probe_intersection(m);
+    const Intersection it = bsdf_probe_intersection(m, sc.dielRows);
     const V3 a = mk(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]), b = mk(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]);
     const BsdfFrame bf = bsdf_frame(sc, b, it);
     const V3 v = evaluate_bsdf(sc, vndf, a, bf, it);
@@ -1730,7 +1820,7 @@ __global__ void bsdf_sample_kernel(DeviceScene sc, dcrt_bsdf_probe_material m, u
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const bool vndf = (features & DCRT_FEATURE_GGX_SAMPLE_VNDF) != 0;
-    const Intersection it = bsdf_probe_intersection(m);
+    const Intersection it = bsdf_probe_intersection(m, sc.dielRows);
     const V3 b = mk(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]);
     const BsdfFrame bf = bsdf_frame(sc, b, it);
     V3 w, v; float p; bool d;

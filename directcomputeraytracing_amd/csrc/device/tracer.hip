@@ -292,6 +292,9 @@ struct ShadingKnobs {
     // (material_kernel's FUSED); 0: every shadow ray takes the shadow queue. n > 1 (tests): fused, and
     // the path slots with (slot & (n - 1)) != 0 take the queue all the same, so a wave mixes both routes.
     uint32_t fusedShadow = 1;
+    // DCRT_SHADING_TABLES: scene-constant shading work done at upload instead of per hit, one bit
+    // each (kTableDeltaPdf, kTableDielRows of dscene.h); 0: every hit does it itself.
+    uint32_t shadingTables = kTableAll;
 };
 ShadingKnobs ReadShadingKnobs()
 {
@@ -300,6 +303,7 @@ ShadingKnobs ReadShadingKnobs()
     k.materialLds = (uint32_t)std::max(0, EnvInt("DCRT_MATERIAL_LDS", (int)k.materialLds));
     k.materialLdsPartial = EnvFlag("DCRT_MATERIAL_LDS_PARTIAL", true);
     k.fusedShadow = (uint32_t)std::max(0, EnvInt("DCRT_FUSED_SHADOW", (int)k.fusedShadow));
+    k.shadingTables = (uint32_t)std::max(0, EnvInt("DCRT_SHADING_TABLES", (int)k.shadingTables)) & kTableAll;
     return k;
 }
 
@@ -415,6 +419,18 @@ struct dcrt_tracer {
     // out, or DCRT_FUSED_SHADOW=0 -- and the knob's path-slot mask (FrameConstants::shadowInlineMask)
     uint32_t fusedLds = 0;
     uint32_t fusedMask = 0;
+    // DCRT_SHADING_TABLES as it stands for the scene (DeriveShadingTables): the bits in force (the
+    // rows' bit only while the scene has rows), the rows' buffer -- room for the scene's materials, null
+    // beyond kDielRowsMaxMaterials -- and the bytes of rows in MATERIAL's LDS copy (behind materialLds;
+    // 0: the variant reads them from global memory, or no rows)
+    uint32_t shadingTables = 0;
+    float* dDielRows = nullptr;
+    uint32_t dielRowsLds = 0;
+    // ... and the triangles' world-space frames (kTableFrames): built at upload where no BLAS has two
+    // instances (else null), in force -- framesLds bytes behind the rows -- where MATERIAL holds the
+    // whole shading data in LDS (mode 1) and the table costs no resident workgroup
+    float4* dTriFrames = nullptr;
+    uint32_t framesLds = 0;
     // MATERIAL of the next launch tests its shadow rays itself: where the cast is the CELLS kernel
     bool FusedShadow() const
     {
@@ -564,6 +580,8 @@ struct dcrt_tracer {
     int CastOccupancy(CastFn k, size_t lds, int* out);
     void DeriveShading();
     int DeriveFusedShadow();
+    int DeriveShadingTables();
+    int BuildDielRows();
     int DeriveDrainGrid();
     int RederiveShading();
     int UpdateMaterials(const dcrt_material* materials, uint32_t count);
@@ -928,6 +946,95 @@ int dcrt_tracer::DeriveFusedShadow()
     return DCRT_OK;
 }
 
+// The MATERIAL variant of (caps, LDS mode, fused)
+static const void* MaterialKernel(uint32_t caps, uint32_t mode, bool fused)
+{
+    const bool od = caps == kCapOpaqueDelta;
+    if (fused) return od ? (const void*)material_kernel<kCapOpaqueDelta, 1, false, true> : (const void*)material_kernel<kCapAll, 1, false, true>;
+    if (mode == 1u) return od ? (const void*)material_kernel<kCapOpaqueDelta, 1> : (const void*)material_kernel<kCapAll, 1>;
+    if (mode == 2u) return od ? (const void*)material_kernel<kCapOpaqueDelta, 2> : (const void*)material_kernel<kCapAll, 2>;
+    return od ? (const void*)material_kernel<kCapOpaqueDelta, 0> : (const void*)material_kernel<kCapAll, 0>;
+}
+
+// DCRT_SHADING_TABLES for the scene as it stands (after DeriveShading and DeriveFusedShadow; again
+// after every edit of the materials, the lights or the LUTs): the per-material rows of the dielectric
+// LUT rebuilt from the device's materials and LUTs, and copied into MATERIAL's LDS (behind the lights)
+// where that costs neither the plain nor the fused variant a resident workgroup; else the kernels read
+// them from global memory. Written to all the DeviceScene copies in use.
+// The rows of the materials and the LUTs as they stand on the device (a scene with rows)
+int dcrt_tracer::BuildDielRows()
+{
+    const uint32_t materialCount = (uint32_t)hostMaterials.size(), n = materialCount * kDielRowFloats;
+    hipLaunchKernelGGL(build_diel_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const dcrt_material*)dMaterials, materialCount,
+                       (const uint16_t*)dLuts->brdf_dielectric, (const uint16_t*)dLuts->brdf_dielectric_avg, dDielRows);
+    HIPCHECK(hipGetLastError());
+    return DCRT_OK;
+}
+
+int dcrt_tracer::DeriveShadingTables()
+{
+    const ShadingKnobs k = ReadShadingKnobs();
+    const uint32_t materialCount = (uint32_t)hostMaterials.size();
+    shadingTables = k.shadingTables;
+    dielRowsLds = 0;
+    framesLds = 0;
+    // (rows only where a material reads them -- plastic, its roughness not under the checkerboard: a scene
+    // without one keeps the parent's launch, and its LDS to the byte)
+    bool reads = false;
+    for (const dcrt_material& m : hostMaterials)
+        reads = reads || ((m.flags & DCRT_MATERIAL_FLAG_TYPE_MASK) == DCRT_MATERIAL_TYPE_PLASTIC && !(m.flags & DCRT_MATERIAL_FLAG_ROUGHNESS_TEXTURE));
+    if (!dDielRows || !reads) shadingTables &= ~kTableDielRows;
+    if (shadingTables & kTableDielRows) {
+        CHECKED(BuildDielRows());
+        if (materialLdsMode != 0u) {
+            const uint32_t rows = diel_rows_bytes(materialCount);
+            bool fits = true;
+            for (const bool fused : { false, true }) {
+                if (fused && !fusedLds) continue;
+                const void* fn = MaterialKernel(materialCaps, materialLdsMode, fused);
+                const size_t without = fused ? material_cells_lds_offset(materialLds) + fusedLds : materialLds;
+                const size_t with = fused ? material_cells_lds_offset(materialLds + rows) + fusedLds : materialLds + rows;
+                int a = 0, b = 0;
+                HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, fn, (int)kMaterialBlock, without));
+                HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, fn, (int)kMaterialBlock, with));
+                a = std::min(a, LdsResident(without, fn));
+                b = std::min(b, LdsResident(with, fn));
+                fits = fits && b >= a && b > 0 && with <= 65536;
+            }
+            if (fits) dielRowsLds = rows;
+        }
+    }
+    // the frames: with MATERIAL's whole-scene LDS copy (mode 1) only, under the same occupancy rule
+    // (and with the delta-only variant only: the any-scene one takes a register more with the table in it, and spills it)
+    if (!dTriFrames || materialLdsMode != 1u || materialCaps == kCapAll) shadingTables &= ~kTableFrames;
+    if (shadingTables & kTableFrames) {
+        const uint32_t frames = 48u * plan.scene.triangleCount;
+        bool fits = true;
+        for (const bool fused : { false, true }) {
+            if (fused && !fusedLds) continue;
+            const void* fn = MaterialKernel(materialCaps, materialLdsMode, fused);
+            const size_t without = fused ? material_cells_lds_offset(materialLds + dielRowsLds) + fusedLds : materialLds + dielRowsLds;
+            const size_t with = material_cells_lds_offset(materialLds + dielRowsLds) + frames + (fused ? fusedLds : 0u);
+            int a = 0, b = 0;
+            HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, fn, (int)kMaterialBlock, without));
+            HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, fn, (int)kMaterialBlock, with));
+            a = std::min(a, LdsResident(without, fn));
+            b = std::min(b, LdsResident(with, fn));
+            fits = fits && b >= a && b > 0 && with <= 65536;
+        }
+        if (fits) framesLds = frames;
+        else shadingTables &= ~kTableFrames;
+    }
+    for (DeviceScene* d : { &plan.scene, &plan.sceneFlat, &plan.sceneRing }) {
+        d->shadingTables = shadingTables;
+        d->dielRows = (shadingTables & kTableDielRows) ? dDielRows : nullptr;
+        d->ldsRows = dielRowsLds ? materialCount : 0u;
+        d->triFrames = (shadingTables & kTableFrames) ? dTriFrames : nullptr;
+        d->ldsFrames = framesLds ? 1u : 0u;
+    }
+    return DCRT_OK;
+}
+
 // drain_kernel's grid: resident workgroups of the variant materialCaps selects
 int dcrt_tracer::DeriveDrainGrid()
 {
@@ -947,11 +1054,13 @@ int dcrt_tracer::RederiveShading()
     const uint32_t caps = materialCaps, mode = materialLdsMode, lds = materialLds, grid = drainResident;
     const uint32_t ldsM = plan.scene.ldsMaterials, ldsL = plan.scene.ldsLights;
     const uint32_t fused = fusedLds, mask = fusedMask;
+    const uint32_t tables = shadingTables, rowsLds = dielRowsLds + framesLds;
     DeriveShading();
     CHECKED(DeriveFusedShadow());
+    CHECKED(DeriveShadingTables());
     if (materialCaps != caps) CHECKED(DeriveDrainGrid());
     if (fusedMask != mask) newImage = true;   // (the frame constants carry it)
-    if (materialCaps != caps || materialLdsMode != mode || materialLds != lds || drainResident != grid || fusedLds != fused ||
+    if (materialCaps != caps || materialLdsMode != mode || materialLds != lds || drainResident != grid || fusedLds != fused || shadingTables != tables || dielRowsLds + framesLds != rowsLds ||
         plan.scene.ldsMaterials != ldsM || plan.scene.ldsLights != ldsL) {
         HIPCHECK(hipStreamSynchronize(stream));
         InvalidateGraph();
@@ -1059,6 +1168,7 @@ int dcrt_tracer::UploadScene(const dcrt_flat_scene& s)
     CHECKED(UploadArrays(s, &identity));
     CHECKED(PlanCast(s, k, identity));
     CHECKED(SizeGrids(k));
+    CHECKED(DeriveShadingTables());
     CHECKED(RebuildShadowCells());
     HIPCHECK(hipStreamSynchronize(stream));
     hasScene = true;
@@ -1118,6 +1228,9 @@ int dcrt_tracer::UploadArrays(const dcrt_flat_scene& s, std::vector<uint32_t>* i
     CHECKED(Upload(&lights, s.lights, s.light_count, shading, DCRT_MAX_LIGHT_COUNT));
     dMaterials = mats;
     dLights = lights;
+    // (the materials' rows of the dielectric LUT: DeriveShadingTables fills them)
+    dDielRows = nullptr;
+    if (s.material_count <= kDielRowsMaxMaterials) CHECKED(DeviceAlloc(&dDielRows, (size_t)s.material_count * kDielRowFloats, &sceneAllocs));
     dInstanceFlags = iflags;
     hostMaterials.assign(s.materials, s.materials + s.material_count);
     if (s.light_count) hostLights.assign(s.lights, s.lights + s.light_count);
@@ -1130,6 +1243,18 @@ int dcrt_tracer::UploadArrays(const dcrt_flat_scene& s, std::vector<uint32_t>* i
         hipLaunchKernelGGL(build_tri_verts_kernel, dim3((s.triangle_count + 255) / 256), dim3(256), 0, stream, vtx, tris, mids,
                            s.triangle_count, triVerts, triShade);
     HIPCHECK(hipGetLastError());
+    // the triangles' world-space frames, where a triangle index names one (instance, triangle) pair
+    dTriFrames = nullptr;
+    std::vector<uint32_t> triInstance;
+    if (s.triangle_count && dcrt::TriangleInstances(s, &triInstance)) {
+        uint32_t* dTriInstance = nullptr;
+        CHECKED(Upload(&dTriInstance, (const uint32_t*)triInstance.data(), s.triangle_count, geometry));
+        CHECKED(DeviceAlloc(&dTriFrames, (size_t)s.triangle_count * 3, &sceneAllocs));
+        hipLaunchKernelGGL(build_tri_frames_kernel, dim3((s.triangle_count + 255) / 256), dim3(256), 0, stream, (const float4*)triVerts,
+                           (const float4*)triShade, (const float4*)xf, (const uint32_t*)dTriInstance, s.triangle_count, dTriFrames);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipStreamSynchronize(stream));   // (triInstance ends with this function)
+    }
     // textures: one texel blob + descriptors (Scene.cpp:586-608)
     std::vector<TextureDesc> descs(std::max<uint32_t>(s.texture_count, 1));
     std::vector<uint8_t> blob;
@@ -1756,7 +1881,9 @@ int dcrt_tracer::LaunchIteration(uint32_t par, bool timed, bool sequenced)
     const bool fused = FusedShadow();
     ShadowInline si{};
     if (fused) si = ShadowInline{ plan.sceneFlat.nodes, plan.sceneFlat.shadowCells, plan.sceneFlat.shadowLeaves, plan.sceneFlat.cachedNodes, plan.sceneFlat.shadowRes };
-    const uint32_t materialBytes = rowProbe ? 0u : fused ? material_cells_lds_offset(materialLds) + fusedLds : materialLds;
+    // (the LDS scene copy, the dielectric LUT's rows behind it, then the fused variant's cells)
+    const uint32_t shadingBytes = framesLds ? material_cells_lds_offset(materialLds + dielRowsLds) + framesLds : materialLds + dielRowsLds;
+    const uint32_t materialBytes = rowProbe ? 0u : fused ? material_cells_lds_offset(shadingBytes) + fusedLds : shadingBytes;
     auto material = rowProbe ? material_kernel<kCapAll, 0, true>
                   : fused ? (materialCaps == kCapOpaqueDelta ? material_kernel<kCapOpaqueDelta, 1, false, true> : material_kernel<kCapAll, 1, false, true>)
                   : materialCaps == kCapOpaqueDelta
@@ -3133,6 +3260,10 @@ DCRT_API int dcrt_tracer_get_info(dcrt_tracer* t, dcrt_tracer_info* out)
     out->shadow_cell_max_leaves = cells ? t->cells.maxLeaves : 0u;
     out->shadow_cell_mean_leaves = cells ? t->cells.meanLeaves : 0.0f;
     out->shadow_inline = t->hasScene && t->FusedShadow() ? 1u : 0u;
+    out->shading_tables = t->hasScene ? t->shadingTables : 0u;
+    out->dielectric_row_bytes = t->hasScene && (t->shadingTables & kTableDielRows) ? diel_rows_bytes((uint32_t)t->hostMaterials.size()) : 0u;
+    out->dielectric_row_lds = t->hasScene ? t->dielRowsLds : 0u;
+    out->frame_table_bytes = t->hasScene ? t->framesLds : 0u;
     return DCRT_OK;
 }
 
@@ -3214,6 +3345,11 @@ DCRT_API int dcrt_tracer_set_luts(dcrt_tracer* t, const dcrt_bxdf_luts* luts)
     if (!luts) return DCRT_E_INVALID_ARG;
     HIPCHECK(hipMemcpyAsync(t->dLuts, luts, sizeof(dcrt_bxdf_luts), hipMemcpyHostToDevice, t->stream));
     HIPCHECK(hipStreamSynchronize(t->stream));
+    // (the materials' rows of the dielectric LUT hold the old texels: the same buffer refilled, nothing re-derived)
+    if (t->hasScene && (t->shadingTables & kTableDielRows)) {
+        CHECKED(t->BuildDielRows());
+        HIPCHECK(hipStreamSynchronize(t->stream));
+    }
     return DCRT_OK;
 }
 
@@ -3549,6 +3685,21 @@ static DeviceScene LutOnlyScene(const dcrt_tracer* t)
     d.lutBsdfAvg = t->dLuts->bsdf_avg;
     return d;
 }
+// ... and, under DCRT_SHADING_TABLES' rows bit, the probe material's rows of the dielectric LUT (in
+// `tmp`), so the probe kernels run the path MATERIAL takes for a material with that alpha and ior.
+static int ProbeScene(dcrt_tracer* t, const dcrt_bsdf_probe_material& m, std::vector<void*>* tmp, DeviceScene* out)
+{
+    *out = LutOnlyScene(t);
+    if (!(ReadShadingKnobs().shadingTables & kTableDielRows)) return DCRT_OK;
+    float* rows = nullptr;
+    CHECKED(DeviceAlloc(&rows, kDielRowFloats, tmp));
+    hipLaunchKernelGGL(probe_diel_rows_kernel, dim3(1), dim3(256), 0, t->stream, out->lutBrdfDielectric, out->lutBrdfDielectricAvg, rows,
+                       m.alpha, m.ior[0]);
+    HIPCHECK(hipGetLastError());
+    out->dielRows = rows;
+    out->shadingTables = kTableDielRows;
+    return DCRT_OK;
+}
 
 DCRT_API int dcrt_device_bsdf_eval(dcrt_tracer* t, const dcrt_bsdf_probe_material* m, uint32_t features, const float* wi,
                                    const float* wo, uint32_t n, float* f, float* pdf)
@@ -3561,16 +3712,47 @@ DCRT_API int dcrt_device_bsdf_eval(dcrt_tracer* t, const dcrt_bsdf_probe_materia
     CHECKED(DeviceAlloc(&dwo, (size_t)n * 3, &tmp));
     CHECKED(DeviceAlloc(&df, (size_t)n * 3, &tmp));
     CHECKED(DeviceAlloc(&dpdf, n, &tmp));
+    DeviceScene ps;
+    if (const int prc = ProbeScene(t, *m, &tmp, &ps); prc != DCRT_OK) { FreeAll(&tmp); return prc; }
     int rc = DCRT_OK;
     if (hipMemcpyAsync(dwi, wi, (size_t)n * 12, hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
     if (rc == DCRT_OK && hipMemcpyAsync(dwo, wo, (size_t)n * 12, hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
     if (rc == DCRT_OK && n) {
-        hipLaunchKernelGGL(bsdf_eval_kernel, dim3((n + 255) / 256), dim3(256), 0, t->stream, LutOnlyScene(t), *m, features,
+        hipLaunchKernelGGL(bsdf_eval_kernel, dim3((n + 255) / 256), dim3(256), 0, t->stream, ps, *m, features,
                            (const float*)dwi, (const float*)dwo, n, df, dpdf);
         if (hipGetLastError() != hipSuccess) rc = DCRT_E_HIP;
     }
     if (rc == DCRT_OK && hipMemcpyAsync(f, df, (size_t)n * 12, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
     if (rc == DCRT_OK && hipMemcpyAsync(pdf, dpdf, (size_t)n * 4, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    FreeAll(&tmp);
+    return rc;
+}
+
+DCRT_API int dcrt_device_frame_probe(dcrt_tracer* t, const uint32_t* records, uint32_t n, int use_table, float* out)
+{
+    TRACER_GUARD(t);
+    if ((!records || !out) && n) return DCRT_E_INVALID_ARG;
+    if (!t->hasScene || (use_table && !t->dTriFrames)) { SetLastError("no scene uploaded, or no frame table for it"); return DCRT_E_NO_SCENE; }
+    DeviceScene sc = t->plan.scene;   // (the global-memory arrays)
+    for (uint32_t i = 0; i < n; ++i) {
+        if ((records[4 * (size_t)i + 2] & 0x7FFFFFFFu) >= sc.triangleCount || records[4 * (size_t)i + 3] >= sc.instanceCount) {
+            SetLastError("frame probe: triangle or instance index out of range");
+            return DCRT_E_INVALID_ARG;
+        }
+    }
+    sc.triFrames = use_table ? t->dTriFrames : nullptr;
+    std::vector<void*> tmp;
+    uint4* drec = nullptr;
+    float* dout = nullptr;
+    int rc = DeviceAlloc(&drec, n, &tmp);
+    if (rc == DCRT_OK) rc = DeviceAlloc(&dout, (size_t)n * 9, &tmp);
+    if (rc == DCRT_OK && hipMemcpyAsync(drec, records, (size_t)n * 16, hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    if (rc == DCRT_OK && n) {
+        hipLaunchKernelGGL(frame_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, t->stream, sc, (const uint4*)drec, n, dout);
+        if (hipGetLastError() != hipSuccess) rc = DCRT_E_HIP;
+    }
+    if (rc == DCRT_OK && hipMemcpyAsync(out, dout, (size_t)n * 36, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
     if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
     FreeAll(&tmp);
     return rc;
@@ -3590,11 +3772,13 @@ DCRT_API int dcrt_device_bsdf_sample(dcrt_tracer* t, const dcrt_bsdf_probe_mater
     CHECKED(DeviceAlloc(&df, (size_t)n * 3, &tmp));
     CHECKED(DeviceAlloc(&dpdf, n, &tmp));
     CHECKED(DeviceAlloc(&ddelta, n, &tmp));
+    DeviceScene ps;
+    if (const int prc = ProbeScene(t, *m, &tmp, &ps); prc != DCRT_OK) { FreeAll(&tmp); return prc; }
     int rc = DCRT_OK;
     if (hipMemcpyAsync(dwo, wo, (size_t)n * 12, hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
     if (rc == DCRT_OK && hipMemcpyAsync(du, u, (size_t)n * 12, hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
     if (rc == DCRT_OK && n) {
-        hipLaunchKernelGGL(bsdf_sample_kernel, dim3((n + 255) / 256), dim3(256), 0, t->stream, LutOnlyScene(t), *m, features,
+        hipLaunchKernelGGL(bsdf_sample_kernel, dim3((n + 255) / 256), dim3(256), 0, t->stream, ps, *m, features,
                            (const float*)dwo, (const float*)du, n, dwi, df, dpdf, ddelta);
         if (hipGetLastError() != hipSuccess) rc = DCRT_E_HIP;
     }

@@ -264,4 +264,41 @@ bool SingleTriangleLeaves(const dcrt_flat_scene& s)
     return true;
 }
 
+bool TriangleInstances(const dcrt_flat_scene& s, std::vector<uint32_t>* out)
+{
+    const dcrt_bvh_node* nd = s.bvh_nodes;
+    const uint32_t n = s.bvh_node_count;
+    out->assign(s.triangle_count, UINT32_MAX);
+    if (n == 0u) return false;
+    // (node, instance + 1 or 0 in the TLAS)
+    struct Item { uint32_t node, inst1; };
+    std::vector<Item> todo{{0u, 0u}};
+    size_t visits = 0;
+    while (!todo.empty()) {
+        const Item it = todo.back();
+        todo.pop_back();
+        if (it.node >= n || ++visits > (size_t)n * 4u + 64u) return false;
+        const dcrt_bvh_node& v = nd[it.node];
+        if (it.inst1 == 0u && (v.misc & 0x4u)) {
+            const uint32_t inst = (v.misc >> 3) & DCRT_BVHNODE_MISC_MASK_PRIMITIVE_COUNT;
+            if (inst >= s.instance_count) return false;
+            todo.push_back({v.right_child_or_prim_index, inst + 1u});
+        } else if (v.misc >= 4u) {
+            if (it.inst1 == 0u) return false;   // (a TLAS-level triangle leaf cannot exist)
+            const uint32_t count = (v.misc >> 3) & DCRT_BVHNODE_MISC_MASK_PRIMITIVE_COUNT;
+            for (uint32_t k = 0; k < count; ++k) {
+                const uint64_t t = (uint64_t)v.right_child_or_prim_index + k;
+                if (t >= s.triangle_count) return false;
+                uint32_t& owner = (*out)[(size_t)t];
+                if (owner != UINT32_MAX && owner != it.inst1 - 1u) return false;   // a BLAS with two instances
+                owner = it.inst1 - 1u;
+            }
+        } else {
+            todo.push_back({v.right_child_or_prim_index, it.inst1});
+            todo.push_back({it.node + 1u, it.inst1});
+        }
+    }
+    return true;
+}
+
 }  // namespace dcrt

@@ -29,4 +29,9 @@ bool AllInstancesBitwiseIdentity(const dcrt_flat_scene& s);
 // Every BLAS leaf holds one triangle.
 bool SingleTriangleLeaves(const dcrt_flat_scene& s);
 
+// out[t]: the instance whose BLAS holds triangle t (UINT32_MAX: none reaches it). False -- and no
+// per-triangle world-space table -- where a BLAS is entered by two instances, so that a triangle
+// index names more than one (instance, triangle) pair, or where the tree is malformed.
+bool TriangleInstances(const dcrt_flat_scene& s, std::vector<uint32_t>* out);
+
 }  // namespace dcrt

@@ -637,6 +637,15 @@ DCRT_API int dcrt_shadow_cells_build(const dcrt_flat_scene* s, uint32_t resoluti
     return DCRT_OK;
 }
 
+DCRT_API int dcrt_flat_scene_triangle_instances(const dcrt_flat_scene* scene, uint32_t* out_instances, uint32_t capacity, int* out_single_use)
+{
+    if (!scene || !out_single_use || !scene->bvh_nodes || (!out_instances && capacity)) return DCRT_E_INVALID_ARG;
+    std::vector<uint32_t> owner;
+    *out_single_use = dcrt::TriangleInstances(*scene, &owner) ? 1 : 0;
+    for (uint32_t t = 0; t < capacity && t < owner.size(); ++t) out_instances[t] = owner[t];
+    return DCRT_OK;
+}
+
 DCRT_API int dcrt_shadow_cell_indices(uint32_t resolution, const float* w, uint32_t count, uint32_t* out)
 {
     if (resolution == 0u || resolution > dcrt::kCellMaxRes || ((!w || !out) && count)) return DCRT_E_INVALID_ARG;

@@ -235,6 +235,12 @@ class Scene:
         return {"resolution": R, "cells": cells, "leaf_words": words, "nodes": nodes, "leaf_count": info.leaf_count,
                 "mean_leaves": info.mean_leaves, "max_leaves": info.max_leaves, "r0": info.r0}
 
+    def triangle_instances(self):
+        """(single_use, owners): the instance whose BLAS holds each triangle of the flat scene (0xFFFFFFFF:
+        none reaches it), and whether every BLAS has one instance -- the frame table's eligibility rule
+        (dcrt_flat_scene_triangle_instances, host only)."""
+        return flat_triangle_instances(self._lib, self.flat())
+
     def shadow_cell_indices(self, resolution: int, w: np.ndarray) -> np.ndarray:
         """Cells (flat indices into "cells") of directions w [n, 3], from the light to the ray."""
         w = np.ascontiguousarray(w, np.float32).reshape(-1, 3)
@@ -365,3 +371,12 @@ def load_obj_meshes(path, scene_layout: bool = True, material_index_base: int = 
         return {"meshes": meshes, "materials": materials}
     finally:
         lib.dcrt_obj_free(h)
+
+
+def flat_triangle_instances(lib, flat):
+    """dcrt_flat_scene_triangle_instances of a FlatScene: (single_use, owners [triangle_count] uint32)."""
+    owners = np.full(flat.triangle_count, 0xFFFFFFFF, np.uint32)
+    single = C.c_int(0)
+    check(lib.dcrt_flat_scene_triangle_instances(C.byref(flat), owners.ctypes.data_as(C.POINTER(C.c_uint32)), len(owners),
+                                                 C.byref(single)), "TriangleInstances")
+    return bool(single.value), owners

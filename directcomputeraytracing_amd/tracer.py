@@ -536,6 +536,20 @@ class WavefrontPathTracer:
               "BsdfEval")
         return f, pdf
 
+    def frame_probe(self, u, v, triangles, instances, use_table: bool) -> np.ndarray:
+        """The world-space normal, tangent and geometry normal (N, 3, 3) of hit records (u, v, triangle,
+        instance) of the uploaded scene, as MATERIAL reconstructs them with the per-triangle frame table
+        (use_table) or without it (dcrt_device_frame_probe)."""
+        rec = np.empty((len(u), 4), np.uint32)
+        rec[:, 0] = np.asarray(u, np.float32).view(np.uint32)
+        rec[:, 1] = np.asarray(v, np.float32).view(np.uint32)
+        rec[:, 2] = np.asarray(triangles, np.uint32)
+        rec[:, 3] = np.asarray(instances, np.uint32)
+        out = np.zeros((len(rec), 3, 3), np.float32)
+        check(self._lib.dcrt_device_frame_probe(self._h, rec.ctypes.data_as(C.POINTER(C.c_uint32)), len(rec), int(bool(use_table)),
+                                                out.ctypes.data_as(_abi._FP)), "FrameProbe")
+        return out
+
     def bsdf_sample(self, material: _abi.BsdfProbeMaterial, wo: np.ndarray, u: np.ndarray,
                     features: int = _abi.FEATURE_DEFAULT):
         """MATERIAL's sample_bsdf likewise: for (N, 3) wo and (N, 3) numbers (sx, sy, sel), the

@@ -312,6 +312,17 @@ typedef struct dcrt_tracer_info {
                                      stands (frame features, instrumentation): no shadow-queue record, no result word;
                                      0: they take the shadow queue to the cast (DCRT_FUSED_SHADOW=0, no table, any-hit,
                                      counters, the row-cost probe) */
+    uint32_t shading_tables;      /* DCRT_SHADING_TABLES as it stands for the scene, one bit per piece of scene-constant
+                                     shading work taken out of the per-hit path: 1: no BSDF pdf for a delta light's
+                                     sample; 2: the plastic dielectric LUT read from per-material float rows; 4: the hit's frame
+                                     from a per-triangle table */
+    uint32_t dielectric_row_bytes;   /* bytes of those rows (528 per material; 0: none -- bit 2 off, no plastic
+                                        material, or more than 64 materials) and how many of them sit in MATERIAL's LDS behind material_lds */
+    uint32_t dielectric_row_lds;
+    uint32_t frame_table_bytes;   /* 0, or the bytes (48 per triangle) of the per-triangle world-space frames -- normal,
+                                     tangent, geometry normal -- that MATERIAL reads per hit instead of rebuilding them
+                                     (bit 4 of shading_tables): scenes of the opaque, delta-lit MATERIAL variant whose every
+                                     BLAS has one instance and whose whole shading data sits in MATERIAL's LDS */
 } dcrt_tracer_info;
 
 typedef struct dcrt_tracer dcrt_tracer;
@@ -320,12 +331,13 @@ typedef struct dcrt_scene dcrt_scene;
 /* ===== version / device ================================================== */
 /* ABI version of this header: bumped whenever a struct changes size or an entry point its
  * meaning (2: dcrt_tracer_info grew cast_waves_per_cu / ring_rows / stack_lds_rows; 3: it grew
- * shadow_cells / shadow_cell_max_leaves / shadow_cell_mean_leaves; 4: shadow_inline). A caller
+ * shadow_cells / shadow_cell_max_leaves / shadow_cell_mean_leaves; 4: shadow_inline; 5: shading_tables /
+ * dielectric_row_bytes / dielectric_row_lds / frame_table_bytes). A caller
  * compiled against another header checks dcrt_abi_version() == DCRT_ABI_VERSION before it
  * passes any struct (a smaller dcrt_tracer_info would be written past its end). Added entry
  * points with structs of their own (the scene updates, the output views, the film denoiser)
  * leave it as it is: nothing an older caller passes has changed. */
-#define DCRT_ABI_VERSION 4
+#define DCRT_ABI_VERSION 5
 DCRT_API int dcrt_abi_version(void);
 DCRT_API const char* dcrt_version(void);
 DCRT_API const char* dcrt_last_error(void);
@@ -941,7 +953,9 @@ DCRT_API int dcrt_device_math_eval(dcrt_tracer* tracer, int function, const floa
 /* One material's BSDF at chosen directions (tests): MATERIAL's own bsdf_frame / evaluate_bsdf /
    evaluate_bsdf_pdf / sample_bsdf in the frame normal = geometric normal = (0,0,1), tangent =
    (1,0,0), with the tracer's current LUTs (dcrt_tracer_set_luts); no scene is needed. albedo holds
-   a conductor's k. Of `features` only DCRT_FEATURE_GGX_SAMPLE_VNDF is read. */
+   a conductor's k. Of `features` only DCRT_FEATURE_GGX_SAMPLE_VNDF is read. DCRT_SHADING_TABLES' rows bit
+   is read at every call (the tracer reads it at uploads and edits): with it the probe builds the
+   material's rows of the dielectric LUT and takes MATERIAL's path over them. */
 typedef struct dcrt_bsdf_probe_material {
     uint32_t type;                        /* DCRT_MATERIAL_TYPE_* */
     float albedo[3];
@@ -957,6 +971,19 @@ DCRT_API int dcrt_device_bsdf_eval(dcrt_tracer* tracer, const dcrt_bsdf_probe_ma
 DCRT_API int dcrt_device_bsdf_sample(dcrt_tracer* tracer, const dcrt_bsdf_probe_material* material, uint32_t features,
                                      const float* wo, const float* u, uint32_t count, float* out_wi, float* out_f,
                                      float* out_pdf, uint32_t* out_delta);
+
+/* The shading frame of chosen hit records of the uploaded scene (tests): MATERIAL's hit reconstruction in
+   the form that may take the per-triangle frame table, over `count` records of 4 words each -- u, v (floats,
+   any bit pattern: a -0 among them), the triangle index and the instance index (uint32 bits) -- with the
+   scene's table (use_table != 0; DCRT_E_NO_SCENE when the scene has none: a BLAS with two instances) or
+   without it. out_frames: 9 floats per record, the world-space normal, tangent and geometry normal. */
+DCRT_API int dcrt_device_frame_probe(dcrt_tracer* tracer, const uint32_t* records, uint32_t count, int use_table, float* out_frames);
+
+/* The instance whose BLAS holds each triangle of a flat scene (host only; the frame table's eligibility
+   rule): out_instances[t], UINT32_MAX for a triangle no instance reaches. Returns DCRT_OK and *out_single_use
+   = 1 where every reached triangle belongs to one instance, 0 where a BLAS has two instances or the tree is
+   malformed (out_instances is then unspecified). */
+DCRT_API int dcrt_flat_scene_triangle_instances(const dcrt_flat_scene* scene, uint32_t* out_instances, uint32_t capacity, int* out_single_use);
 
 #ifdef __cplusplus
 }
