@@ -129,21 +129,43 @@ constexpr uint32_t kFrameFlatNormal = 1u, kFrameFlatTangent = 2u;
 // lut_brdf_dielectric_avg, and a pad to 16 B.
 constexpr uint32_t kDielRowFloats = 132;
 constexpr uint32_t kDielRowsMaxMaterials = 64;   // beyond it (33 KiB of rows) the scene keeps the per-hit LUT path
-__host__ __device__ inline uint32_t diel_rows_bytes(uint32_t materials) { return 4u * kDielRowFloats * materials; }
+constexpr __host__ __device__ uint32_t diel_rows_bytes(uint32_t materials) { return 4u * kDielRowFloats * materials; }
 
-// MATERIAL's LDS scene copy, in 16-B units: triVerts (3 T), triShade (6 T), the forward
-// instance transforms (3 I), then 4-B words: instance light indices (I), overrides (I),
-// materials (13 M), lights (7 L). Bytes for T triangles, I instances, M materials, L lights.
-__host__ __device__ inline uint32_t material_lds_bytes(uint32_t T, uint32_t I, uint32_t M, uint32_t L)
+// MATERIAL's dynamic LDS, the one layout the host sizes launches by and material_kernel carves up: four
+// sections, each with its bytes (0: not held).
+// * shading, at 0 -- in 16-B units triVerts (3 T), triShade (6 T), the forward instance transforms (3 I), then
+//   4-B words: instance light indices (I), overrides (I), materials (13 M), lights (7 L); T = 0: SCENE_LDS == 2;
+// * rows, straight behind it -- the dielectric LUT's rows of `rowMaterials` materials;
+// * frames, at the next 16-B boundary (framesAt) -- 3 float4 per triangle;
+// * cells, at the next 16-B boundary again (cellsAt; material_kernel's FUSED, for cells_occluded_cached) -- the
+//   entry-free nodes (2 float4 each), the rotated triangle copies (9 float4 each), the cell table's leaf words.
+// A launch without the cells takes Bytes(false): it ends where its last section ends, unpadded.
+struct MaterialLds {
+    uint32_t shading, rows, frames, cells;
+    uint32_t framesAt, cellsAt;
+    constexpr __host__ __device__ uint32_t Bytes(bool fused) const { return fused ? cellsAt + cells : frames ? framesAt + frames : shading + rows; }
+};
+constexpr __host__ __device__ MaterialLds material_lds_layout(uint32_t T, uint32_t I, uint32_t M, uint32_t L, uint32_t rowMaterials, bool frames,
+                                                              uint32_t cellNodes, bool fused)
 {
-    return 16u * (9u * T + 3u * I) + 4u * (2u * I + 13u * M + 7u * L);
+    MaterialLds l{};
+    l.shading = 16u * (9u * T + 3u * I) + 4u * (2u * I + 13u * M + 7u * L);
+    l.rows = diel_rows_bytes(rowMaterials);
+    l.framesAt = (l.shading + l.rows + 15u) & ~15u;
+    l.frames = frames ? 48u * T : 0u;
+    l.cellsAt = (l.Bytes(false) + 15u) & ~15u;
+    l.cells = fused ? 32u * cellNodes + 144u * T + 4u * kCellWords : 0u;
+    return l;
 }
-
-// What MATERIAL's fused variant (material_kernel's FUSED) copies behind the shading copy, at the next
-// 16-B boundary, for cells_occluded_cached: the entry-free nodes (2 float4 each), the rotated triangle
-// copies (9 float4 each), the cell table's leaf words.
-__host__ __device__ inline uint32_t material_cells_lds_bytes(uint32_t nodes, uint32_t T) { return 32u * nodes + 144u * T + 4u * kCellWords; }
-__host__ __device__ inline uint32_t material_cells_lds_offset(uint32_t shadingBytes) { return (shadingBytes + 15u) & ~15u; }
+// (pinned against the formulas this function replaced, for Cornell's 32 triangles, 8 instances, 6 materials, 1 light and 40
+// entry-free nodes: rows, frames and cells on and off; the copy without triangles; 3 lights: shading bytes no multiple of 16)
+static_assert(material_lds_layout(32, 8, 6, 1, 0, false, 0, false).shading == 5396u && material_lds_layout(32, 8, 6, 1, 0, false, 0, false).Bytes(false) == 5396u, "");
+static_assert(material_lds_layout(32, 8, 6, 1, 6, false, 0, false).Bytes(false) == 8564u && material_lds_layout(32, 8, 6, 1, 6, true, 0, false).Bytes(false) == 8576u + 1536u, "");
+static_assert(material_lds_layout(32, 8, 6, 1, 6, true, 40, true).cellsAt == 10112u && material_lds_layout(32, 8, 6, 1, 6, true, 40, true).Bytes(true) == 10112u + 5888u + 4u * kCellWords, "");
+static_assert(material_lds_layout(32, 8, 6, 1, 0, false, 40, true).cellsAt == 5408u && material_lds_layout(32, 8, 6, 1, 6, false, 40, true).cellsAt == 8576u, "");
+static_assert(material_lds_layout(0, 8, 6, 1, 0, false, 0, false).Bytes(false) == 788u && material_lds_layout(0, 8, 6, 1, 6, false, 0, false).Bytes(false) == 3956u, "");
+static_assert(material_lds_layout(32, 8, 6, 3, 0, false, 0, false).shading == 5452u && material_lds_layout(32, 8, 6, 3, 0, true, 0, false).framesAt == 5456u, "");
+static_assert(material_lds_layout(32, 8, 6, 3, 0, true, 40, true).cellsAt == 5456u + 1536u && material_lds_layout(32, 8, 6, 3, 0, false, 40, true).cellsAt == 5456u, "");
 
 // Node orders on the device. kLayoutFlat is PackBVH's depth-first order, as in the flat
 // scene: an interior node's left child is node + 1 and its `right` field the right child.

@@ -498,7 +498,7 @@ static_assert(DCRT_MATERIAL_BLOCK % 64 == 0 && DCRT_MATERIAL_BLOCK <= 960, "MATE
 // SCENE_LDS: the scene arrays MATERIAL's shading reads per item are copied into LDS by each
 // workgroup first, so HitInfoToIntersection's dependent fetches are LDS reads -- 1: all of them
 // (pre-gathered triangles, the forward instance transforms and instance words, materials,
-// lights: small scenes, material_lds_bytes within the host's budget); 2: all but the triangles
+// lights: small scenes, material_lds_layout's shading bytes within the host's budget); 2: all but the triangles
 // (larger scenes: the hit -> triangle fetch stays global, the triangle -> material one and the
 // light sample's reads become LDS reads); 0: none.
 // PROBE: counts the rays per film row (the row-cost probe); launched only while it is on.
@@ -551,8 +551,9 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
         uint32_t* lt = mt + 13u * sc.ldsMaterials;
         float* rw = (float*)(lt + 7u * sc.ldsLights);   // (the dielectric LUT's rows of sc.ldsRows materials)
         for (uint32_t i = threadIdx.x; i < kDielRowFloats * sc.ldsRows; i += blockDim.x) rw[i] = sc.dielRows[i];
-        // (the triangles' frames at the next 16-B boundary, in front of the fused variant's cells)
-        const uint32_t frameOff = material_cells_lds_offset(material_lds_bytes(T, I, sc.ldsMaterials, sc.ldsLights) + diel_rows_bytes(sc.ldsRows));
+        // (the triangles' frames at the next 16-B boundary, in front of the fused variant's cells: material_lds_layout,
+        // dscene.h, is the layout these pointers walk and the host sizes the launch by)
+        const uint32_t frameOff = material_lds_layout(T, I, sc.ldsMaterials, sc.ldsLights, sc.ldsRows, false, 0u, false).framesAt;
         const uint32_t FT = sc.ldsFrames ? T : 0u;
         float4* fr = sceneLds + (frameOff >> 4);
         for (uint32_t i = threadIdx.x; i < 3u * FT; i += blockDim.x) fr[i] = sc.triFrames[i];
@@ -563,7 +564,7 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
         for (uint32_t i = threadIdx.x; i < 13u * sc.ldsMaterials; i += blockDim.x) mt[i] = ((const uint32_t*)sc.materials)[i];
         for (uint32_t i = threadIdx.x; i < 7u * sc.ldsLights; i += blockDim.x) lt[i] = ((const uint32_t*)sc.lights)[i];
         if constexpr (FUSED) {
-            // behind the shading copy (material_cells_lds_offset): the cast's scene cache of the flat
+            // behind the shading copy (material_lds_layout's cellsAt): the cast's scene cache of the flat
             // scene, as scene_cache_load<true> fills it, then the leaf words
             float4* cn = fr + 3u * FT;
             float4* ct = cn + 2u * si.nodeCount;

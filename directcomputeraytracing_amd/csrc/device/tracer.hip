@@ -326,6 +326,15 @@ int LdsResident(size_t lds, const void* kernel = nullptr)
     }
     return lds ? (int)(g_ldsPerCU / ((lds + kLdsGranule - 1) / kLdsGranule * kLdsGranule)) : 1 << 20;
 }
+// Resident workgroups per CU of `kernel` with `block` threads and `lds` bytes of dynamic LDS: what its
+// registers allow (the occupancy API) and what the LDS granules allow
+int ResidentPerCU(const void* kernel, uint32_t block, size_t lds, int* out)
+{
+    int n = 0;
+    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, (int)block, lds));
+    *out = std::min(n, LdsResident(lds, kernel));
+    return DCRT_OK;
+}
 
 // What a launch of the cast needs
 struct CastLaunch {
@@ -372,6 +381,58 @@ struct CastPlan {
     }
 };
 
+using MaterialFn = void (*)(PathPool, DeviceScene, const FrameConstants*, Counters*, const Counters*, const SampleOut*, ShadowInline);
+
+// How MATERIAL (and the drain kernel, which shades with the same variant) is launched for the uploaded
+// scene with its current materials and lights (dcrt_tracer::PlanMaterial): the one place that says which
+// material_kernel runs and with how much LDS.
+struct MaterialPlan {
+    uint32_t caps = kCapAll;           // the compiled variant that covers the scene: kCapOpaqueDelta or kCapAll (dscene.h)
+    uint32_t mode = 0;                 // material_kernel's SCENE_LDS: 0 no copy, 1 whole shading data, 2 all but the triangles
+    uint32_t materials = 0, lights = 0;   // the counts the LDS copy holds (0 without one)
+    // The sections of the dynamic LDS (dscene.h material_lds_layout; 0 bytes: not held). cells != 0: the fused
+    // variant is sized for the scene; a launch takes it with the CELLS cast alone (dcrt_tracer::FusedShadow).
+    MaterialLds lds{};
+    // DCRT_SHADING_TABLES as it stands for the scene: the bits in force, and the buffers of the tables in force
+    uint32_t tables = 0;
+    const float* dielRows = nullptr;
+    const float4* triFrames = nullptr;
+    uint32_t fusedMask = 0;            // DCRT_FUSED_SHADOW's path-slot mask (FrameConstants::shadowInlineMask: not baked into a graph)
+    uint32_t drainGrid = 0;            // drain_kernel's grid: resident workgroups on the whole chip
+
+    // The one table from variant to compiled kernel. probe: the row-cost probe's variant (no LDS copy)
+    MaterialFn Kernel(bool probe, bool fused) const
+    {
+        if (probe) return material_kernel<kCapAll, 0, true>;
+        const bool od = caps == kCapOpaqueDelta;
+        if (fused) return od ? material_kernel<kCapOpaqueDelta, 1, false, true> : material_kernel<kCapAll, 1, false, true>;
+        switch (mode) {
+        case 1: return od ? material_kernel<kCapOpaqueDelta, 1> : material_kernel<kCapAll, 1>;
+        case 2: return od ? material_kernel<kCapOpaqueDelta, 2> : material_kernel<kCapAll, 2>;
+        default: return od ? material_kernel<kCapOpaqueDelta, 0> : material_kernel<kCapAll, 0>;
+        }
+    }
+    auto DrainKernel() const { return caps == kCapOpaqueDelta ? drain_kernel<kCapOpaqueDelta> : drain_kernel<kCapAll>; }
+    size_t LdsBytes(bool probe, bool fused) const { return probe ? 0u : lds.Bytes(fused); }
+    // The shading fields of a DeviceScene (kernels take it by value)
+    void Apply(DeviceScene* d) const
+    {
+        d->ldsMaterials = materials;
+        d->ldsLights = lights;
+        d->shadingTables = tables;
+        d->dielRows = dielRows;
+        d->ldsRows = lds.rows ? materials : 0u;
+        d->triFrames = triFrames;
+        d->ldsFrames = lds.frames ? 1u : 0u;
+    }
+    // What a captured graph bakes in: kernels, LDS bytes, the drain grid, what Apply writes (the pointers follow the bits)
+    bool BakedEquals(const MaterialPlan& o) const
+    {
+        return caps == o.caps && mode == o.mode && materials == o.materials && lights == o.lights && lds.shading == o.lds.shading &&
+               lds.rows == o.lds.rows && lds.frames == o.lds.frames && lds.cells == o.lds.cells && tables == o.tables && drainGrid == o.drainGrid;
+    }
+};
+
 }  // namespace
 
 struct dcrt_tracer {
@@ -410,34 +471,19 @@ struct dcrt_tracer {
     bool hasScene = false;
     CastPlan plan;
     dcrt_upload_stats uploadStats{};
-    uint32_t sceneCaps = kCapAll;      // what the uploaded scene uses (kCap* of dscene.h)
-    uint32_t materialCaps = kCapAll;   // the MATERIAL variant launched for it
-    uint32_t materialLds = 0;          // MATERIAL's dynamic LDS: the scene copy's bytes (0: the global-memory variant)
-    uint32_t materialLdsMode = 0;      // material_kernel<CAPS, mode>: 0 no copy, 1 whole shading data, 2 all but the triangles
-    // MATERIAL's fused variant (material_kernel's FUSED, DeriveFusedShadow): the bytes its copy of the
-    // cells' data adds behind the shading copy -- 0: the scene, the LDS budget or the occupancy rule it
-    // out, or DCRT_FUSED_SHADOW=0 -- and the knob's path-slot mask (FrameConstants::shadowInlineMask)
-    uint32_t fusedLds = 0;
-    uint32_t fusedMask = 0;
-    // DCRT_SHADING_TABLES as it stands for the scene (DeriveShadingTables): the bits in force (the
-    // rows' bit only while the scene has rows), the rows' buffer -- room for the scene's materials, null
-    // beyond kDielRowsMaxMaterials -- and the bytes of rows in MATERIAL's LDS copy (behind materialLds;
-    // 0: the variant reads them from global memory, or no rows)
-    uint32_t shadingTables = 0;
+    MaterialPlan material;
+    // The tables' buffers (DCRT_SHADING_TABLES; material.tables says which are in force): the rows of
+    // the dielectric LUT -- room for the scene's materials, null beyond kDielRowsMaxMaterials -- and
+    // the triangles' world-space frames, built at upload where no BLAS has two instances (else null)
     float* dDielRows = nullptr;
-    uint32_t dielRowsLds = 0;
-    // ... and the triangles' world-space frames (kTableFrames): built at upload where no BLAS has two
-    // instances (else null), in force -- framesLds bytes behind the rows -- where MATERIAL holds the
-    // whole shading data in LDS (mode 1) and the table costs no resident workgroup
     float4* dTriFrames = nullptr;
-    uint32_t framesLds = 0;
     // MATERIAL of the next launch tests its shadow rays itself: where the cast is the CELLS kernel
     bool FusedShadow() const
     {
-        return fusedLds != 0u && !rowProbe && plan.Cells(instrCounters, (frame.features & DCRT_FEATURE_ALLOW_ANYHIT) != 0);
+        return material.lds.cells != 0u && !rowProbe && plan.Cells(instrCounters, (frame.features & DCRT_FEATURE_ALLOW_ANYHIT) != 0);
     }
     // The arrays the partial updates replace (UpdateMaterials / UpdateLights / UpdateInstanceFlags):
-    // their device buffers, and host copies of the two that DeriveShading reads. The lights
+    // their device buffers, and host copies of the two that PlanMaterial reads. The lights
     // buffer holds DCRT_MAX_LIGHT_COUNT entries, so a changed count never moves it.
     dcrt_material* dMaterials = nullptr;
     dcrt_light* dLights = nullptr;
@@ -456,7 +502,6 @@ struct dcrt_tracer {
     uint32_t megaResident = 0;         // persistent megakernel grid
     uint32_t viewResident = 0;         // persistent view_kernel grid
     uint32_t viewResidentOpacity = 0;  // the same for the ALLOW_ANYHIT_SHADER variant
-    uint32_t drainResident = 0;        // drain_kernel grid (resident workgroups)
 
     // ---- film, its rows and the sample textures ----
     std::vector<void*> filmAllocs, sampleAllocs, rowAllocs;
@@ -578,11 +623,9 @@ struct dcrt_tracer {
     int PlanFlatCast(const dcrt_flat_scene& s, const UploadKnobs& k);
     int SizeGrids(const UploadKnobs& k);
     int CastOccupancy(CastFn k, size_t lds, int* out);
-    void DeriveShading();
-    int DeriveFusedShadow();
-    int DeriveShadingTables();
+    int PlanMaterial(const MaterialPlan* before, MaterialPlan* out);
+    int ApplyMaterialPlan(const MaterialPlan& p);
     int BuildDielRows();
-    int DeriveDrainGrid();
     int RederiveShading();
     int UpdateMaterials(const dcrt_material* materials, uint32_t count);
     int UpdateLights(const dcrt_light* lights, uint32_t count);
@@ -779,7 +822,7 @@ int dcrt_tracer::Create(const dcrt_tracer_config& cfg)
         if (prop.maxSharedMemoryPerMultiProcessor > 0) g_ldsPerCU = prop.maxSharedMemoryPerMultiProcessor;
         int cPerCU = 0, mPerCU = 0;
         HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&cPerCU, control_kernel, (int)kControlBlock, 0));
-        HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&mPerCU, material_kernel<kCapAll, 0>, (int)kMaterialBlock, 0));
+        HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&mPerCU, MaterialPlan{}.Kernel(false, false), (int)kMaterialBlock, 0));   // (the any-scene variant without an LDS copy)
         auto resident = [&](int perCU, uint32_t mul) {
             if (mul == 0) return V;
             const uint64_t r = (uint64_t)std::max(1, perCU) * (uint64_t)std::max(1, prop.multiProcessorCount) * mul;
@@ -886,82 +929,112 @@ static int ValidateInstanceFlags(const uint32_t* flags, uint32_t count)
     return DCRT_OK;
 }
 
-// Everything the tracer derives from the materials and the lights (hostMaterials, hostLights;
-// the triangle / instance counts and the cube of `scene`): the MATERIAL / drain variant and
-// MATERIAL's LDS scene copy, written to all the DeviceScene copies in use. UploadScene and the
-// partial updates both come here.
-void dcrt_tracer::DeriveShading()
+// The rule every addition to MATERIAL's LDS is judged by (the fused variant's cells, the rows, the frames):
+// `keeps` is cleared unless the variant keeps its resident workgroups per CU -- by registers and by LDS -- when
+// the addition takes it from `before` (kernel, dynamic LDS bytes) to `after`, within 64 KiB of LDS (`cap`).
+static int KeepsResident(MaterialFn before, size_t a, MaterialFn after, size_t b, bool cap, bool* keeps)
+{
+    int ra = 0, rb = 0;
+    CHECKED(ResidentPerCU((const void*)before, kMaterialBlock, a, &ra));
+    CHECKED(ResidentPerCU((const void*)after, kMaterialBlock, b, &rb));
+    *keeps = *keeps && rb >= ra && rb > 0 && (!cap || b <= 65536);
+    return DCRT_OK;
+}
+
+// The MaterialPlan of the scene as it stands (UploadScene once the grids are sized; every edit of the
+// materials or the lights) from the shading knobs -- read here, once: tests set them between uploads --
+// hostMaterials, hostLights, the scene's counts and cube, the CastPlan and the tables' buffers. Five
+// decisions in this order, each judged against what the earlier ones settled. `before`: the plan in
+// force (its drain grid stands while the variant does: no query), or null.
+int dcrt_tracer::PlanMaterial(const MaterialPlan* before, MaterialPlan* out)
 {
     const ShadingKnobs k = ReadShadingKnobs();
     const DeviceScene& scene = plan.scene;
-    const uint32_t materialCount = (uint32_t)hostMaterials.size(), lightCount = (uint32_t)hostLights.size();
-    // MATERIAL variant: the smallest compiled one whose capabilities cover the scene
-    sceneCaps = scene.envCube ? kCapEnvCube : 0u;
+    const uint32_t T = scene.triangleCount, I = scene.instanceCount;
+    const uint32_t M = (uint32_t)hostMaterials.size(), L = (uint32_t)hostLights.size();
+    MaterialPlan p;
+    // 1. the variant: the smallest compiled one whose capabilities cover the scene
+    uint32_t sceneCaps = scene.envCube ? kCapEnvCube : 0u;   // what the scene uses (kCap* of dscene.h)
+    bool readsRows = false;   // (a plastic material, its roughness not under the checkerboard)
     for (const dcrt_material& m : hostMaterials) {
         const uint32_t type = m.flags & DCRT_MATERIAL_FLAG_TYPE_MASK;
         sceneCaps |= type <= DCRT_MATERIAL_TYPE_THIN_DIELECTRIC ? (1u << type) : kCapAll;
         if (m.flags & DCRT_MATERIAL_FLAG_MULTISCATTERING) sceneCaps |= kCapMultiscatter;
         if (m.albedo_texture_index != -1 || (m.flags & DCRT_MATERIAL_FLAG_ROUGHNESS_TEXTURE)) sceneCaps |= kCapTextures;
+        readsRows = readsRows || (type == DCRT_MATERIAL_TYPE_PLASTIC && !(m.flags & DCRT_MATERIAL_FLAG_ROUGHNESS_TEXTURE));
     }
     for (const dcrt_light& l : hostLights) sceneCaps |= (l.flags & 0xFu) << kCapLightShift;
-    materialCaps = (sceneCaps & ~kCapOpaqueDelta) == 0u ? kCapOpaqueDelta : kCapAll;
-    if (k.materialGeneric) materialCaps = kCapAll;
-    // MATERIAL's LDS scene copy (material_kernel<CAPS, mode>): the whole shading data of a small
-    // scene (mode 1), else everything but the triangles (mode 2)
-    const bool counts = scene.triangleCount > 0 && scene.triangleCount < (1u << 20) && scene.instanceCount < (1u << 20) &&
-                        materialCount < (1u << 20) && lightCount < (1u << 20);
-    const uint64_t whole = material_lds_bytes(scene.triangleCount, scene.instanceCount, materialCount, lightCount);
-    const uint64_t rest = material_lds_bytes(0u, scene.instanceCount, materialCount, lightCount);
-    materialLdsMode = !counts ? 0u : whole <= k.materialLds ? 1u : (k.materialLdsPartial && rest <= k.materialLds ? 2u : 0u);
-    materialLds = materialLdsMode == 1 ? (uint32_t)whole : materialLdsMode == 2 ? (uint32_t)rest : 0u;
-    for (DeviceScene* d : { &plan.scene, &plan.sceneFlat, &plan.sceneRing }) {   // (the two variants' copies: unused ones are rewritten with the next upload)
-        d->ldsMaterials = materialLdsMode ? materialCount : 0u;
-        d->ldsLights = materialLdsMode ? lightCount : 0u;
+    p.caps = (sceneCaps & ~kCapOpaqueDelta) == 0u && !k.materialGeneric ? kCapOpaqueDelta : kCapAll;
+    // 2. the LDS scene copy within the knob's budget: the whole shading data (mode 1), else all but the triangles (mode 2)
+    const bool counts = T > 0 && T < (1u << 20) && I < (1u << 20) && M < (1u << 20) && L < (1u << 20);
+    const uint64_t whole = material_lds_layout(T, I, M, L, 0u, false, 0u, false).shading;
+    const uint64_t rest = material_lds_layout(0u, I, M, L, 0u, false, 0u, false).shading;
+    p.mode = !counts ? 0u : whole <= k.materialLds ? 1u : (k.materialLdsPartial && rest <= k.materialLds ? 2u : 0u);
+    p.materials = p.mode ? M : 0u;
+    p.lights = p.mode ? L : 0u;
+    // (the layout with so many materials' rows, the frames and the cells: the counts are the copy's)
+    auto layout = [&](uint32_t rowMaterials, bool frames, bool cells) {
+        return p.mode ? material_lds_layout(p.mode == 1u ? T : 0u, I, M, L, rowMaterials, frames, plan.sceneFlat.cachedNodes, cells) : MaterialLds{};
+    };
+    // (the layout `bigger` is taken if neither variant the plan launches loses a resident workgroup to it)
+    auto grow = [&](const MaterialLds& bigger, bool* taken) {
+        *taken = true;
+        for (const bool fused : { false, true })
+            if (!fused || p.lds.cells) CHECKED(KeepsResident(p.Kernel(false, fused), p.lds.Bytes(fused), p.Kernel(false, fused), bigger.Bytes(fused), true, taken));
+        if (*taken) p.lds = bigger;
+        return (int)DCRT_OK;
+    };
+    p.lds = layout(0u, false, false);
+    // 3. the fused variant for the flat cast's scene: the cells go behind the whole shading copy (mode 1) if
+    // they fit the same budget again and cost no resident workgroup against the unfused variant they replace
+    // (sized for any table of the scene: whether one stands is the launch's question, FusedShadow). No 64 KiB
+    // cap: copy and cells are each within the budget, so up to a budget of 32 KiB (the default is 16) the sum
+    // cannot pass it; with the knob raised beyond, the occupancy query alone decides, as it always has.
+    p.fusedMask = k.fusedShadow > 1u ? k.fusedShadow - 1u : 0u;
+    if (k.fusedShadow && plan.flat && plan.cellsRes && p.mode == 1u) {
+        const MaterialLds fused = layout(0u, false, true);
+        bool fits = fused.cells <= k.materialLds;
+        if (fits) CHECKED(KeepsResident(p.Kernel(false, false), p.lds.Bytes(false), p.Kernel(false, true), fused.Bytes(true), false, &fits));
+        if (fits) p.lds = fused;
     }
-}
-
-// MATERIAL's fused variant for the flat cast's scene (after DeriveShading and PlanFlatCast): its copy of
-// the entry-free nodes, the rotated triangles and the leaf words goes behind the whole shading copy
-// (mode 1) if it fits the same budget again and costs the kernel no resident workgroup -- by registers
-// or by LDS -- against the unfused variant it replaces. Whether a table stands is the launch's question
-// (FusedShadow): this sizes the variant for any table of the scene.
-int dcrt_tracer::DeriveFusedShadow()
-{
-    const ShadingKnobs k = ReadShadingKnobs();
-    fusedLds = 0;
-    fusedMask = k.fusedShadow > 1u ? k.fusedShadow - 1u : 0u;
-    if (!k.fusedShadow || !plan.flat || !plan.cellsRes || materialLdsMode != 1u) return DCRT_OK;
-    const uint32_t extra = material_cells_lds_bytes(plan.sceneFlat.cachedNodes, plan.scene.triangleCount);
-    if (extra > k.materialLds) return DCRT_OK;
-    const bool od = materialCaps == kCapOpaqueDelta;
-    const void* plain = od ? (const void*)material_kernel<kCapOpaqueDelta, 1> : (const void*)material_kernel<kCapAll, 1>;
-    const void* fused = od ? (const void*)material_kernel<kCapOpaqueDelta, 1, false, true> : (const void*)material_kernel<kCapAll, 1, false, true>;
-    const size_t fusedBytes = material_cells_lds_offset(materialLds) + extra;
-    int plainPerCU = 0, fusedPerCU = 0;
-    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&plainPerCU, plain, (int)kMaterialBlock, materialLds));
-    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&fusedPerCU, fused, (int)kMaterialBlock, fusedBytes));
-    plainPerCU = std::min(plainPerCU, LdsResident(materialLds, plain));
-    fusedPerCU = std::min(fusedPerCU, LdsResident(fusedBytes, fused));
-    if (fusedPerCU >= plainPerCU && fusedPerCU > 0) fusedLds = extra;
+    // 4. the rows: only where a material reads them (a scene without one keeps its LDS to the byte); in the LDS
+    // copy where that costs neither variant a resident workgroup, else the kernels read them from global memory
+    p.tables = k.shadingTables;
+    if (!dDielRows || !readsRows) p.tables &= ~kTableDielRows;
+    bool taken = false;
+    if ((p.tables & kTableDielRows) && p.mode != 0u) CHECKED(grow(layout(M, false, p.lds.cells != 0u), &taken));
+    // 5. the frames: in the whole-scene LDS copy of the delta-only variant under the same rule, or not at all
+    // (the any-scene variant takes a register more with the table in it, and spills it)
+    if (!dTriFrames || p.mode != 1u || p.caps == kCapAll) p.tables &= ~kTableFrames;
+    if (p.tables & kTableFrames) {
+        CHECKED(grow(layout(p.lds.rows ? M : 0u, true, p.lds.cells != 0u), &taken));
+        if (!taken) p.tables &= ~kTableFrames;
+    }
+    p.dielRows = (p.tables & kTableDielRows) ? dDielRows : nullptr;
+    p.triFrames = (p.tables & kTableFrames) ? dTriFrames : nullptr;
+    // drain_kernel's grid: resident workgroups of the variant's drain kernel, launched like the casts
+    if (before && before->caps == p.caps) {
+        p.drainGrid = before->drainGrid;
+    } else {
+        int perCU = 0;
+        CHECKED(ResidentPerCU((const void*)p.DrainKernel(), plan.block, plan.ldsWholeStack, &perCU));
+        p.drainGrid = (uint32_t)std::max(1, perCU) * cuCount;
+    }
+    *out = p;
     return DCRT_OK;
 }
 
-// The MATERIAL variant of (caps, LDS mode, fused)
-static const void* MaterialKernel(uint32_t caps, uint32_t mode, bool fused)
+// `p` in force: written to all the DeviceScene copies (those not in use are rewritten with the next
+// upload), and a scene's rows rebuilt from the materials and the LUTs as they stand on the device
+int dcrt_tracer::ApplyMaterialPlan(const MaterialPlan& p)
 {
-    const bool od = caps == kCapOpaqueDelta;
-    if (fused) return od ? (const void*)material_kernel<kCapOpaqueDelta, 1, false, true> : (const void*)material_kernel<kCapAll, 1, false, true>;
-    if (mode == 1u) return od ? (const void*)material_kernel<kCapOpaqueDelta, 1> : (const void*)material_kernel<kCapAll, 1>;
-    if (mode == 2u) return od ? (const void*)material_kernel<kCapOpaqueDelta, 2> : (const void*)material_kernel<kCapAll, 2>;
-    return od ? (const void*)material_kernel<kCapOpaqueDelta, 0> : (const void*)material_kernel<kCapAll, 0>;
+    material = p;
+    for (DeviceScene* d : { &plan.scene, &plan.sceneFlat, &plan.sceneRing }) material.Apply(d);
+    if (material.tables & kTableDielRows) CHECKED(BuildDielRows());
+    return DCRT_OK;
 }
 
-// DCRT_SHADING_TABLES for the scene as it stands (after DeriveShading and DeriveFusedShadow; again
-// after every edit of the materials, the lights or the LUTs): the per-material rows of the dielectric
-// LUT rebuilt from the device's materials and LUTs, and copied into MATERIAL's LDS (behind the lights)
-// where that costs neither the plain nor the fused variant a resident workgroup; else the kernels read
-// them from global memory. Written to all the DeviceScene copies in use.
-// The rows of the materials and the LUTs as they stand on the device (a scene with rows)
+// The rows of the materials and the LUTs as they stand on the device (a scene with rows; set_luts needs it alone)
 int dcrt_tracer::BuildDielRows()
 {
     const uint32_t materialCount = (uint32_t)hostMaterials.size(), n = materialCount * kDielRowFloats;
@@ -971,97 +1044,16 @@ int dcrt_tracer::BuildDielRows()
     return DCRT_OK;
 }
 
-int dcrt_tracer::DeriveShadingTables()
-{
-    const ShadingKnobs k = ReadShadingKnobs();
-    const uint32_t materialCount = (uint32_t)hostMaterials.size();
-    shadingTables = k.shadingTables;
-    dielRowsLds = 0;
-    framesLds = 0;
-    // (rows only where a material reads them -- plastic, its roughness not under the checkerboard: a scene
-    // without one keeps the parent's launch, and its LDS to the byte)
-    bool reads = false;
-    for (const dcrt_material& m : hostMaterials)
-        reads = reads || ((m.flags & DCRT_MATERIAL_FLAG_TYPE_MASK) == DCRT_MATERIAL_TYPE_PLASTIC && !(m.flags & DCRT_MATERIAL_FLAG_ROUGHNESS_TEXTURE));
-    if (!dDielRows || !reads) shadingTables &= ~kTableDielRows;
-    if (shadingTables & kTableDielRows) {
-        CHECKED(BuildDielRows());
-        if (materialLdsMode != 0u) {
-            const uint32_t rows = diel_rows_bytes(materialCount);
-            bool fits = true;
-            for (const bool fused : { false, true }) {
-                if (fused && !fusedLds) continue;
-                const void* fn = MaterialKernel(materialCaps, materialLdsMode, fused);
-                const size_t without = fused ? material_cells_lds_offset(materialLds) + fusedLds : materialLds;
-                const size_t with = fused ? material_cells_lds_offset(materialLds + rows) + fusedLds : materialLds + rows;
-                int a = 0, b = 0;
-                HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, fn, (int)kMaterialBlock, without));
-                HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, fn, (int)kMaterialBlock, with));
-                a = std::min(a, LdsResident(without, fn));
-                b = std::min(b, LdsResident(with, fn));
-                fits = fits && b >= a && b > 0 && with <= 65536;
-            }
-            if (fits) dielRowsLds = rows;
-        }
-    }
-    // the frames: with MATERIAL's whole-scene LDS copy (mode 1) only, under the same occupancy rule
-    // (and with the delta-only variant only: the any-scene one takes a register more with the table in it, and spills it)
-    if (!dTriFrames || materialLdsMode != 1u || materialCaps == kCapAll) shadingTables &= ~kTableFrames;
-    if (shadingTables & kTableFrames) {
-        const uint32_t frames = 48u * plan.scene.triangleCount;
-        bool fits = true;
-        for (const bool fused : { false, true }) {
-            if (fused && !fusedLds) continue;
-            const void* fn = MaterialKernel(materialCaps, materialLdsMode, fused);
-            const size_t without = fused ? material_cells_lds_offset(materialLds + dielRowsLds) + fusedLds : materialLds + dielRowsLds;
-            const size_t with = material_cells_lds_offset(materialLds + dielRowsLds) + frames + (fused ? fusedLds : 0u);
-            int a = 0, b = 0;
-            HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, fn, (int)kMaterialBlock, without));
-            HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, fn, (int)kMaterialBlock, with));
-            a = std::min(a, LdsResident(without, fn));
-            b = std::min(b, LdsResident(with, fn));
-            fits = fits && b >= a && b > 0 && with <= 65536;
-        }
-        if (fits) framesLds = frames;
-        else shadingTables &= ~kTableFrames;
-    }
-    for (DeviceScene* d : { &plan.scene, &plan.sceneFlat, &plan.sceneRing }) {
-        d->shadingTables = shadingTables;
-        d->dielRows = (shadingTables & kTableDielRows) ? dDielRows : nullptr;
-        d->ldsRows = dielRowsLds ? materialCount : 0u;
-        d->triFrames = (shadingTables & kTableFrames) ? dTriFrames : nullptr;
-        d->ldsFrames = framesLds ? 1u : 0u;
-    }
-    return DCRT_OK;
-}
-
-// drain_kernel's grid: resident workgroups of the variant materialCaps selects
-int dcrt_tracer::DeriveDrainGrid()
-{
-    const void* fn = materialCaps == kCapOpaqueDelta ? (const void*)drain_kernel<kCapOpaqueDelta> : (const void*)drain_kernel<kCapAll>;
-    int drainPerCU = 0;
-    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&drainPerCU, materialCaps == kCapOpaqueDelta ? drain_kernel<kCapOpaqueDelta> : drain_kernel<kCapAll>,
-                                                          (int)plan.block, plan.ldsWholeStack));
-    drainResident = (uint32_t)std::max(1, std::min(drainPerCU, LdsResident(plan.ldsWholeStack, fn))) * cuCount;
-    return DCRT_OK;
-}
-
-// After an update replaced the materials or the lights: the derived state again, and the
-// captured graphs dropped exactly when something they bake in changed -- the MATERIAL / drain
-// variant, MATERIAL's LDS bytes, the drain grid or a DeviceScene field (kernels take it by value).
+// After an update replaced the materials or the lights: the plan again, and the captured graphs
+// dropped exactly when something they bake in changed (MaterialPlan::BakedEquals).
 int dcrt_tracer::RederiveShading()
 {
-    const uint32_t caps = materialCaps, mode = materialLdsMode, lds = materialLds, grid = drainResident;
-    const uint32_t ldsM = plan.scene.ldsMaterials, ldsL = plan.scene.ldsLights;
-    const uint32_t fused = fusedLds, mask = fusedMask;
-    const uint32_t tables = shadingTables, rowsLds = dielRowsLds + framesLds;
-    DeriveShading();
-    CHECKED(DeriveFusedShadow());
-    CHECKED(DeriveShadingTables());
-    if (materialCaps != caps) CHECKED(DeriveDrainGrid());
-    if (fusedMask != mask) newImage = true;   // (the frame constants carry it)
-    if (materialCaps != caps || materialLdsMode != mode || materialLds != lds || drainResident != grid || fusedLds != fused || shadingTables != tables || dielRowsLds + framesLds != rowsLds ||
-        plan.scene.ldsMaterials != ldsM || plan.scene.ldsLights != ldsL) {
+    MaterialPlan next;
+    CHECKED(PlanMaterial(&material, &next));
+    if (next.fusedMask != material.fusedMask) newImage = true;   // (the frame constants carry it)
+    const bool baked = next.BakedEquals(material);
+    CHECKED(ApplyMaterialPlan(next));
+    if (!baked) {
         HIPCHECK(hipStreamSynchronize(stream));
         InvalidateGraph();
     }
@@ -1168,7 +1160,9 @@ int dcrt_tracer::UploadScene(const dcrt_flat_scene& s)
     CHECKED(UploadArrays(s, &identity));
     CHECKED(PlanCast(s, k, identity));
     CHECKED(SizeGrids(k));
-    CHECKED(DeriveShadingTables());
+    MaterialPlan shading;
+    CHECKED(PlanMaterial(nullptr, &shading));
+    CHECKED(ApplyMaterialPlan(shading));
     CHECKED(RebuildShadowCells());
     HIPCHECK(hipStreamSynchronize(stream));
     hasScene = true;
@@ -1228,7 +1222,7 @@ int dcrt_tracer::UploadArrays(const dcrt_flat_scene& s, std::vector<uint32_t>* i
     CHECKED(Upload(&lights, s.lights, s.light_count, shading, DCRT_MAX_LIGHT_COUNT));
     dMaterials = mats;
     dLights = lights;
-    // (the materials' rows of the dielectric LUT: DeriveShadingTables fills them)
+    // (the materials' rows of the dielectric LUT: BuildDielRows fills them)
     dDielRows = nullptr;
     if (s.material_count <= kDielRowsMaxMaterials) CHECKED(DeviceAlloc(&dDielRows, (size_t)s.material_count * kDielRowFloats, &sceneAllocs));
     dInstanceFlags = iflags;
@@ -1307,8 +1301,6 @@ int dcrt_tracer::UploadArrays(const dcrt_flat_scene& s, std::vector<uint32_t>* i
     d.stackSize = std::max<uint32_t>(s.bvh_traversal_stack_size, 1u);
     d.singlePrimLeaves = dcrt::SingleTriangleLeaves(s) ? 1u : 0u;
     plan.scene = d;
-    // the MATERIAL variant and its LDS scene copy (plan.scene carries the two counts on)
-    DeriveShading();
     return DCRT_OK;
 }
 
@@ -1316,11 +1308,7 @@ int dcrt_tracer::UploadArrays(const dcrt_flat_scene& s, std::vector<uint32_t>* i
 // LDS (gfx950's 1280-B allocation granule, LdsResident). Split casts run extension_kernel's.
 int dcrt_tracer::CastOccupancy(CastFn k, size_t lds, int* out)
 {
-    int n = 0;
-    if (knobs.mergedCasts) HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, (int)plan.block, lds));
-    else HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, extension_kernel<false, false>, (int)plan.block, lds));
-    *out = std::min(n, LdsResident(lds, knobs.mergedCasts ? (const void*)k : (const void*)extension_kernel<false, false>));
-    return DCRT_OK;
+    return ResidentPerCU(knobs.mergedCasts ? (const void*)k : (const void*)extension_kernel<false, false>, plan.block, lds, out);
 }
 
 // UploadScene's second job: the cast's workgroup size, its LDS scene cache, which traversal the
@@ -1461,7 +1449,6 @@ int dcrt_tracer::PlanFlatCast(const dcrt_flat_scene& s, const UploadKnobs& k)
     const DeviceScene& d = plan.scene;
     plan.flat = false;
     plan.cellsRes = 0;
-    fusedLds = 0;            // (MATERIAL's fused variant goes with the cells: DeriveFusedShadow below)
     dCells = nullptr;        // (sceneAllocs: freed by UploadArrays)
     dCellLeaves = nullptr;
     cells = ShadowCells{};
@@ -1506,7 +1493,7 @@ int dcrt_tracer::PlanFlatCast(const dcrt_flat_scene& s, const UploadKnobs& k)
         cellTriangles.assign(s.triangles, s.triangles + (size_t)s.triangle_count * 3);
         cellTransforms.assign(s.instance_transforms, s.instance_transforms + (size_t)s.instance_count * 2);
     }
-    return DeriveFusedShadow();
+    return DCRT_OK;
 }
 
 // UploadScene's third job: the persistent grids -- the traversal kernels run exactly one resident
@@ -1540,15 +1527,14 @@ int dcrt_tracer::SizeGrids(const UploadKnobs& k)
     const uint32_t block = plan.block;
     const size_t lds = plan.ldsWholeStack;
     int megaPerCU = 0;
-    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&megaPerCU, megakernel<false>, (int)block, lds));
-    megaResident = (uint32_t)std::max(1, std::min(megaPerCU, LdsResident(lds, (const void*)megakernel<false>))) * cuCount;
+    CHECKED(ResidentPerCU((const void*)megakernel<false>, block, lds, &megaPerCU));
+    megaResident = (uint32_t)std::max(1, megaPerCU) * cuCount;
     // the first-hit view kernel: the megakernel's launch shape, its own register budget
     int viewPerCU = 0, viewOpacityPerCU = 0;
-    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&viewPerCU, view_kernel<false>, (int)block, lds));
-    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&viewOpacityPerCU, view_kernel<true>, (int)block, lds));
-    viewResident = (uint32_t)std::max(1, std::min(viewPerCU, LdsResident(lds, (const void*)view_kernel<false>))) * cuCount;
-    viewResidentOpacity = (uint32_t)std::max(1, std::min(viewOpacityPerCU, LdsResident(lds, (const void*)view_kernel<true>))) * cuCount;
-    CHECKED(DeriveDrainGrid());
+    CHECKED(ResidentPerCU((const void*)view_kernel<false>, block, lds, &viewPerCU));
+    CHECKED(ResidentPerCU((const void*)view_kernel<true>, block, lds, &viewOpacityPerCU));
+    viewResident = (uint32_t)std::max(1, viewPerCU) * cuCount;
+    viewResidentOpacity = (uint32_t)std::max(1, viewOpacityPerCU) * cuCount;
     if (plan.ringRows) {
         // the spill columns: stackSize entries per lane of the persistent ring grid
         const size_t words = (size_t)plan.resident[0][0] * block * plan.scene.stackSize;
@@ -1808,7 +1794,7 @@ int dcrt_tracer::BeginImage()
     fc.apertureBaseAngle = frame.aperture_base_angle;
     fc.frameSeed = frame.frame_seed;
     fc.seedStride = seedStride;
-    fc.shadowInlineMask = fusedMask;
+    fc.shadowInlineMask = material.fusedMask;
     fc.maxBounce = frame.max_bounce_count;
     fc.lightCount = frame.light_count;
     fc.envLightIndex = frame.environment_light_index;
@@ -1881,20 +1867,10 @@ int dcrt_tracer::LaunchIteration(uint32_t par, bool timed, bool sequenced)
     const bool fused = FusedShadow();
     ShadowInline si{};
     if (fused) si = ShadowInline{ plan.sceneFlat.nodes, plan.sceneFlat.shadowCells, plan.sceneFlat.shadowLeaves, plan.sceneFlat.cachedNodes, plan.sceneFlat.shadowRes };
-    // (the LDS scene copy, the dielectric LUT's rows behind it, then the fused variant's cells)
-    const uint32_t shadingBytes = framesLds ? material_cells_lds_offset(materialLds + dielRowsLds) + framesLds : materialLds + dielRowsLds;
-    const uint32_t materialBytes = rowProbe ? 0u : fused ? material_cells_lds_offset(shadingBytes) + fusedLds : shadingBytes;
-    auto material = rowProbe ? material_kernel<kCapAll, 0, true>
-                  : fused ? (materialCaps == kCapOpaqueDelta ? material_kernel<kCapOpaqueDelta, 1, false, true> : material_kernel<kCapAll, 1, false, true>)
-                  : materialCaps == kCapOpaqueDelta
-                        ? (materialLdsMode == 1 ? material_kernel<kCapOpaqueDelta, 1>
-                                                : materialLdsMode == 2 ? material_kernel<kCapOpaqueDelta, 2> : material_kernel<kCapOpaqueDelta, 0>)
-                        : (materialLdsMode == 1 ? material_kernel<kCapAll, 1>
-                                                : materialLdsMode == 2 ? material_kernel<kCapAll, 2> : material_kernel<kCapAll, 0>);
     if (timed) CHECKED(TimedPair(kTimedMaterial, &m0, &m1));
     {
         Annotation a("Material", !capturing);
-        hipExtLaunchKernelGGL(material, dim3(materialGrid), dim3(kMaterialBlock), materialBytes, stream, m0, m1, 0, pool, plan.scene,
+        hipExtLaunchKernelGGL(material.Kernel(rowProbe, fused), dim3(materialGrid), dim3(kMaterialBlock), material.LdsBytes(rowProbe, fused), stream, m0, m1, 0, pool, plan.scene,
                               (const FrameConstants*)dFrame, cnt, (const Counters*)next, (const SampleOut*)dSampleOut, si);
     }
     if (timed) CHECKED(TimedPair(kTimedCast, &e0, &e1));
@@ -1914,8 +1890,7 @@ int dcrt_tracer::LaunchIteration(uint32_t par, bool timed, bool sequenced)
     }
     if (knobs.drainPaths) {
         // (returns at once unless the batch's last paths are few enough: fc.drainPaths)
-        auto drain = materialCaps == kCapOpaqueDelta ? drain_kernel<kCapOpaqueDelta> : drain_kernel<kCapAll>;
-        hipLaunchKernelGGL(drain, dim3(drainResident), dim3(castBlock), plan.ldsWholeStack, stream, pool, plan.scene, (const FrameConstants*)dFrame, cnt,
+        hipLaunchKernelGGL(material.DrainKernel(), dim3(material.drainGrid), dim3(castBlock), plan.ldsWholeStack, stream, pool, plan.scene, (const FrameConstants*)dFrame, cnt,
                            dGlobals, (const SampleOut*)dSampleOut);
     }
     if (sequenced) {
@@ -3245,12 +3220,12 @@ DCRT_API int dcrt_tracer_get_info(dcrt_tracer* t, dcrt_tracer_info* out)
     out->cached_triangles = t->hasScene ? plan.scene.cachedTris : 0u;
     out->cast_block = plan.block;
     out->traversal_stack = t->hasScene ? plan.scene.stackSize : 0u;
-    out->material_generic = t->materialCaps == kCapAll ? 1u : 0u;
+    out->material_generic = t->material.caps == kCapAll ? 1u : 0u;
     out->pair_traversal = t->hasScene && plan.pair ? 1u : 0u;
     out->control_grid = t->controlGrid;
     out->material_grid = t->materialGrid;
     out->cast_grid = shipped.resident;
-    out->material_lds = t->materialLds;
+    out->material_lds = t->material.lds.shading;
     out->cast_identity = plan.ident ? (plan.flat ? 2u : 1u) : 0u;
     out->stack_lds_rows = t->hasScene ? shipped.scene.stackRows : 0u;
     out->ring_rows = t->hasScene ? plan.ringRows : 0u;
@@ -3260,10 +3235,10 @@ DCRT_API int dcrt_tracer_get_info(dcrt_tracer* t, dcrt_tracer_info* out)
     out->shadow_cell_max_leaves = cells ? t->cells.maxLeaves : 0u;
     out->shadow_cell_mean_leaves = cells ? t->cells.meanLeaves : 0.0f;
     out->shadow_inline = t->hasScene && t->FusedShadow() ? 1u : 0u;
-    out->shading_tables = t->hasScene ? t->shadingTables : 0u;
-    out->dielectric_row_bytes = t->hasScene && (t->shadingTables & kTableDielRows) ? diel_rows_bytes((uint32_t)t->hostMaterials.size()) : 0u;
-    out->dielectric_row_lds = t->hasScene ? t->dielRowsLds : 0u;
-    out->frame_table_bytes = t->hasScene ? t->framesLds : 0u;
+    out->shading_tables = t->hasScene ? t->material.tables : 0u;
+    out->dielectric_row_bytes = t->hasScene && (t->material.tables & kTableDielRows) ? diel_rows_bytes((uint32_t)t->hostMaterials.size()) : 0u;
+    out->dielectric_row_lds = t->hasScene ? t->material.lds.rows : 0u;
+    out->frame_table_bytes = t->hasScene ? t->material.lds.frames : 0u;
     return DCRT_OK;
 }
 
@@ -3346,7 +3321,7 @@ DCRT_API int dcrt_tracer_set_luts(dcrt_tracer* t, const dcrt_bxdf_luts* luts)
     HIPCHECK(hipMemcpyAsync(t->dLuts, luts, sizeof(dcrt_bxdf_luts), hipMemcpyHostToDevice, t->stream));
     HIPCHECK(hipStreamSynchronize(t->stream));
     // (the materials' rows of the dielectric LUT hold the old texels: the same buffer refilled, nothing re-derived)
-    if (t->hasScene && (t->shadingTables & kTableDielRows)) {
+    if (t->hasScene && (t->material.tables & kTableDielRows)) {
         CHECKED(t->BuildDielRows());
         HIPCHECK(hipStreamSynchronize(t->stream));
     }
