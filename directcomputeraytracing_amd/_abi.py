@@ -372,6 +372,11 @@ SIGNATURES = [
     ("dcrt_device_math_eval", _I, [_P, _I, _FP, _U, _FP]),
     ("dcrt_device_bsdf_eval", _I, [_P, C.POINTER(BsdfProbeMaterial), _U, _FP, _FP, _U, _FP, _FP]),
     ("dcrt_device_frame_probe", _I, [_P, C.POINTER(C.c_uint32), _U, _I, _FP]),
+    ("dcrt_device_camera_ray", _I, [_P, _FP, _FP, _U, _FP, _FP]),
+    ("dcrt_device_intersection_probe", _I, [_P, C.POINTER(C.c_uint32), _U, _I, _FP, C.POINTER(C.c_uint32)]),
+    ("dcrt_device_light_sample", _I, [_P, _FP, C.POINTER(C.c_uint32), _U, _FP, C.POINTER(C.c_uint32)]),
+    ("dcrt_device_light_eval", _I, [_P, C.POINTER(C.c_uint32), _FP, _U, _FP]),
+    ("dcrt_device_env_lookup", _I, [_P, _FP, _U, _FP]),
     ("dcrt_flat_scene_triangle_instances", _I, [C.POINTER(FlatScene), C.POINTER(C.c_uint32), _U, C.POINTER(C.c_int)]),
     ("dcrt_device_bsdf_sample", _I, [_P, C.POINTER(BsdfProbeMaterial), _U, _FP, _FP, _U, _FP, _FP, _FP, C.POINTER(C.c_uint32)]),
 ]

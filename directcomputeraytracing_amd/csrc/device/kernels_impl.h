@@ -1802,6 +1802,70 @@ __global__ void frame_probe_kernel(DeviceScene sc, const uint4* records, uint32_
     o[3] = it.tangent.x; o[4] = it.tangent.y; o[5] = it.tangent.z;
     o[6] = it.geometryNormal.x; o[7] = it.geometryNormal.y; o[8] = it.geometryNormal.z;
 }
+// The stages between the casts and the BSDF at a caller's inputs (tests; layouts in dcrt.h): generate_ray,
+// hit_to_intersection (TABLE: the form that takes the frame table, else the per-hit form of the any-scene
+// MATERIAL variants), sample_light, evaluate_light and sample_env as the path kernels call them.
+__global__ void camera_ray_probe_kernel(FrameConstants fc, const float* film, const float* aperture, uint32_t n, float* origins, float* directions)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    V3 o, d;
+    generate_ray(fc, film[2 * i], film[2 * i + 1], aperture[3 * i], aperture[3 * i + 1], aperture[3 * i + 2], &o, &d);
+    origins[3 * i] = o.x; origins[3 * i + 1] = o.y; origins[3 * i + 2] = o.z;
+    directions[3 * i] = d.x; directions[3 * i + 1] = d.y; directions[3 * i + 2] = d.z;
+}
+template <bool TABLE>
+__global__ void intersection_probe_kernel(DeviceScene sc, const uint4* records, uint32_t n, float* outFloats, uint32_t* outWords)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint4 r = records[i];
+    HitRecord h;
+    h.t = 1.0f; h.u = asf(r.x); h.v = asf(r.y); h.tri = r.z; h.inst = r.w;
+    Intersection it;
+    hit_to_intersection<kCapAll, TABLE>(sc, h, it);
+    float* o = outFloats + (size_t)i * 16;
+    const V3 v[5] = {it.position, it.normal, it.tangent, it.geometryNormal, it.albedo};
+    for (int k = 0; k < 5; ++k) { o[3 * k] = v[k].x; o[3 * k + 1] = v[k].y; o[3 * k + 2] = v[k].z; }
+    o[15] = it.alpha;
+    uint32_t* w = outWords + (size_t)i * 3;
+    w[0] = it.materialType;
+    w[1] = (it.isTwoSided ? 1u : 0u) | (it.backface ? 2u : 0u) | (it.multiscattering ? 4u : 0u) | (it.internalScatteringMode << 4);
+    w[2] = it.lightIndex;
+}
+__global__ void light_sample_probe_kernel(DeviceScene sc, uint32_t lightCount, const float* points, const uint4* states, uint32_t n,
+                                          float* outFloats, uint32_t* outWords)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint4 s = states[i];
+    Rng rng;
+    rng.s0 = s.x; rng.s1 = s.y; rng.s2 = s.z; rng.s3 = s.w;
+    const LightSample r = sample_light(sc, mk(points[3 * i], points[3 * i + 1], points[3 * i + 2]), lightCount, rng);
+    float* o = outFloats + (size_t)i * 8;
+    o[0] = r.radiance.x; o[1] = r.radiance.y; o[2] = r.radiance.z;
+    o[3] = r.wi.x; o[4] = r.wi.y; o[5] = r.wi.z;
+    o[6] = r.pdf; o[7] = r.distance;
+    uint32_t* w = outWords + (size_t)i * 5;
+    w[0] = r.isDelta ? 1u : 0u;
+    w[1] = rng.s0; w[2] = rng.s1; w[3] = rng.s2; w[4] = rng.s3;
+}
+__global__ void light_eval_probe_kernel(DeviceScene sc, uint32_t lightCount, const uint32_t* lightTriangle, const float* in, uint32_t n, float* out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* a = in + (size_t)i * 7;
+    V3 radiance; float pdf;
+    evaluate_light(sc, lightTriangle[2 * i], lightTriangle[2 * i + 1], mk(a[0], a[1], a[2]), mk(a[3], a[4], a[5]), a[6], lightCount, &radiance, &pdf);
+    out[4 * i] = radiance.x; out[4 * i + 1] = radiance.y; out[4 * i + 2] = radiance.z; out[4 * i + 3] = pdf;
+}
+__global__ void env_lookup_probe_kernel(DeviceScene sc, const float* directions, uint32_t n, float* out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const V3 c = sample_env(sc, mk(directions[3 * i], directions[3 * i + 1], directions[3 * i + 2]));
+    out[3 * i] = c.x; out[3 * i + 1] = c.y; out[3 * i + 2] = c.z;
+}
 __global__ void bsdf_eval_kernel(DeviceScene sc, dcrt_bsdf_probe_material m, uint32_t features, const float* wi, const float* wo,
                                  uint32_t n, float* f, float* pdf)
 {

@@ -1777,12 +1777,11 @@ int dcrt_tracer::SetBands(const uint32_t* b, uint32_t count, uint32_t halo)
     return DCRT_OK;
 }
 
-// ResetImage + SET_IDLE + constant upload for one image (WavefrontPathTracer.cpp:441-468)
-int dcrt_tracer::BeginImage()
+// The camera and film fields of the frame constants, as generate_ray reads them (BeginImage for the path kernels,
+// dcrt_device_camera_ray for the probe: one copy, so both see the same camera)
+static void FillCameraConstants(const dcrt_frame_params& frame, FrameConstants* out)
 {
-    Annotation an("Reset", !capturing);
-    FrameConstants fc;
-    std::memset(&fc, 0, sizeof(fc));
+    FrameConstants& fc = *out;
     std::memcpy(fc.camera, frame.camera_transform, sizeof(fc.camera));
     fc.resolution[0] = frame.resolution[0]; fc.resolution[1] = frame.resolution[1];
     fc.filmSize[0] = frame.film_size[0]; fc.filmSize[1] = frame.film_size[1];
@@ -1792,6 +1791,15 @@ int dcrt_tracer::BeginImage()
     fc.bladeCount = frame.blade_count;
     fc.bladeVertexPos[0] = frame.blade_vertex_pos[0]; fc.bladeVertexPos[1] = frame.blade_vertex_pos[1];
     fc.apertureBaseAngle = frame.aperture_base_angle;
+}
+
+// ResetImage + SET_IDLE + constant upload for one image (WavefrontPathTracer.cpp:441-468)
+int dcrt_tracer::BeginImage()
+{
+    Annotation an("Reset", !capturing);
+    FrameConstants fc;
+    std::memset(&fc, 0, sizeof(fc));
+    FillCameraConstants(frame, &fc);
     fc.frameSeed = frame.frame_seed;
     fc.seedStride = seedStride;
     fc.shadowInlineMask = material.fusedMask;
@@ -3731,6 +3739,172 @@ DCRT_API int dcrt_device_frame_probe(dcrt_tracer* t, const uint32_t* records, ui
     if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
     FreeAll(&tmp);
     return rc;
+}
+
+}  // extern "C"
+
+// The shading probes' common shape: inputs up, one thread per item, outputs down, everything freed.
+struct ProbeBuffer {
+    const void* host;     // input (copied up), or null
+    void* hostOut;        // output (copied down), or null
+    size_t bytesPerItem;
+    void* device;
+};
+template <typename Launch>
+static int RunProbe(dcrt_tracer* t, uint32_t n, ProbeBuffer* buffers, size_t bufferCount, Launch launch)
+{
+    std::vector<void*> tmp;
+    int rc = DCRT_OK;
+    for (size_t b = 0; b < bufferCount && rc == DCRT_OK; ++b) {
+        char* d = nullptr;
+        rc = DeviceAlloc(&d, (size_t)n * buffers[b].bytesPerItem, &tmp);
+        buffers[b].device = d;
+        if (rc == DCRT_OK && buffers[b].host && n &&
+            hipMemcpyAsync(d, buffers[b].host, (size_t)n * buffers[b].bytesPerItem, hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    }
+    if (rc == DCRT_OK && n) {
+        launch(dim3((n + 255) / 256), dim3(256));
+        if (hipGetLastError() != hipSuccess) rc = DCRT_E_HIP;
+    }
+    for (size_t b = 0; b < bufferCount && rc == DCRT_OK; ++b) {
+        if (buffers[b].hostOut && n &&
+            hipMemcpyAsync(buffers[b].hostOut, buffers[b].device, (size_t)n * buffers[b].bytesPerItem, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    }
+    if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    FreeAll(&tmp);
+    return rc;
+}
+
+extern "C" {
+
+// A mesh light's triangle range and instance lie inside the uploaded scene (the probes read them)
+static bool LightInScene(const dcrt_light& L, const DeviceScene& sc)
+{
+    if (!(L.flags & DCRT_LIGHT_FLAGS_MESH_LIGHT) || (L.flags & (DCRT_LIGHT_FLAGS_POINT_LIGHT | DCRT_LIGHT_FLAGS_DIRECTIONAL_LIGHT))) return true;
+    uint32_t w[3];
+    std::memcpy(w, L.position_or_triangle_range, sizeof(w));
+    return w[1] != 0u && w[0] < sc.triangleCount && w[1] <= sc.triangleCount - w[0] && w[2] < sc.instanceCount;
+}
+
+DCRT_API int dcrt_device_camera_ray(dcrt_tracer* t, const float* film, const float* aperture, uint32_t n, float* origins, float* directions)
+{
+    TRACER_GUARD(t);
+    if ((!film || !aperture || !origins || !directions) && n) return DCRT_E_INVALID_ARG;
+    if (!t->hasFrame) { SetLastError("no frame parameters"); return DCRT_E_INVALID_ARG; }
+    FrameConstants fc;
+    std::memset(&fc, 0, sizeof(fc));
+    FillCameraConstants(t->frame, &fc);
+    ProbeBuffer b[4] = {{film, nullptr, 8, nullptr}, {aperture, nullptr, 12, nullptr}, {nullptr, origins, 12, nullptr}, {nullptr, directions, 12, nullptr}};
+    return RunProbe(t, n, b, 4, [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(camera_ray_probe_kernel, grid, block, 0, t->stream, fc, (const float*)b[0].device, (const float*)b[1].device, n,
+                           (float*)b[2].device, (float*)b[3].device);
+    });
+}
+
+DCRT_API int dcrt_device_intersection_probe(dcrt_tracer* t, const uint32_t* records, uint32_t n, int use_table, float* out_floats,
+                                            uint32_t* out_words)
+{
+    TRACER_GUARD(t);
+    if ((!records || !out_floats || !out_words) && n) return DCRT_E_INVALID_ARG;
+    if (!t->hasScene || (use_table && !t->dTriFrames)) { SetLastError("no scene uploaded, or no frame table for it"); return DCRT_E_NO_SCENE; }
+    DeviceScene sc = t->plan.scene;   // (the global-memory arrays)
+    for (uint32_t i = 0; i < n; ++i) {
+        if ((records[4 * (size_t)i + 2] & 0x7FFFFFFFu) >= sc.triangleCount || records[4 * (size_t)i + 3] >= sc.instanceCount) {
+            SetLastError("intersection probe: triangle or instance index out of range");
+            return DCRT_E_INVALID_ARG;
+        }
+    }
+    sc.triFrames = use_table ? t->dTriFrames : nullptr;
+    ProbeBuffer b[3] = {{records, nullptr, 16, nullptr}, {nullptr, out_floats, 64, nullptr}, {nullptr, out_words, 12, nullptr}};
+    return RunProbe(t, n, b, 3, [&](dim3 grid, dim3 block) {
+        if (use_table) hipLaunchKernelGGL(intersection_probe_kernel<true>, grid, block, 0, t->stream, sc, (const uint4*)b[0].device, n, (float*)b[1].device, (uint32_t*)b[2].device);
+        else hipLaunchKernelGGL(intersection_probe_kernel<false>, grid, block, 0, t->stream, sc, (const uint4*)b[0].device, n, (float*)b[1].device, (uint32_t*)b[2].device);
+    });
+}
+
+// The light probes read the frame's light_count lights (CheckFrameLights holds it to the uploaded array)
+static int ProbeLights(dcrt_tracer* t, uint32_t* lightCount)
+{
+    if (!t->hasScene) { SetLastError("no scene uploaded"); return DCRT_E_NO_SCENE; }
+    if (!t->hasFrame) { SetLastError("no frame parameters"); return DCRT_E_INVALID_ARG; }
+    *lightCount = t->frame.light_count;
+    if (*lightCount == 0u || *lightCount > t->hostLights.size()) { SetLastError("light probe: the frame has no lights"); return DCRT_E_INVALID_ARG; }
+    for (uint32_t i = 0; i < *lightCount; ++i) {
+        if (!LightInScene(t->hostLights[i], t->plan.scene)) { SetLastError("light probe: a mesh light's triangles or instance lie outside the scene"); return DCRT_E_INVALID_ARG; }
+    }
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_device_light_sample(dcrt_tracer* t, const float* points, const uint32_t* states, uint32_t n, float* out_floats,
+                                      uint32_t* out_words)
+{
+    TRACER_GUARD(t);
+    if ((!points || !states || !out_floats || !out_words) && n) return DCRT_E_INVALID_ARG;
+    uint32_t lightCount = 0;
+    CHECKED(ProbeLights(t, &lightCount));
+    // the two selections a state leads to stay inside the arrays: float(draw) * count can round up to count
+    // (xoshiro128**'s output and state step, as dmath.h has them)
+    auto rotl = [](uint32_t x, int k) { return (x << k) | (x >> (32 - k)); };
+    for (uint32_t i = 0; i < n; ++i) {
+        uint32_t s[4];
+        std::memcpy(s, states + 4 * (size_t)i, sizeof(s));
+        float draw[2];
+        for (int k = 0; k < 2; ++k) {
+            draw[k] = (float)((rotl(s[0] * 5u, 7) * 9u) >> 8) / 16777216.0f;
+            const uint32_t x = s[1] << 9;
+            s[2] ^= s[0]; s[3] ^= s[1]; s[1] ^= s[2]; s[0] ^= s[3]; s[2] ^= x; s[3] = rotl(s[3], 11);
+        }
+        const float li = floorf(draw[0] * (float)lightCount);
+        bool ok = li < (float)lightCount;
+        if (ok) {
+            const dcrt_light& L = t->hostLights[(uint32_t)li];
+            if ((L.flags & DCRT_LIGHT_FLAGS_MESH_LIGHT) && !(L.flags & (DCRT_LIGHT_FLAGS_POINT_LIGHT | DCRT_LIGHT_FLAGS_DIRECTIONAL_LIGHT))) {
+                uint32_t w[3];
+                std::memcpy(w, L.position_or_triangle_range, sizeof(w));
+                const float tri = (float)w[0] + floorf(draw[1] * (float)w[1]);
+                ok = tri < (float)t->plan.scene.triangleCount && (uint32_t)tri < t->plan.scene.triangleCount;
+            }
+        }
+        if (!ok) { SetLastError("light sample probe: a state selects past the lights or the triangles"); return DCRT_E_INVALID_ARG; }
+    }
+    const DeviceScene sc = t->plan.scene;
+    ProbeBuffer b[4] = {{points, nullptr, 12, nullptr}, {states, nullptr, 16, nullptr}, {nullptr, out_floats, 32, nullptr}, {nullptr, out_words, 20, nullptr}};
+    return RunProbe(t, n, b, 4, [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(light_sample_probe_kernel, grid, block, 0, t->stream, sc, lightCount, (const float*)b[0].device, (const uint4*)b[1].device, n,
+                           (float*)b[2].device, (uint32_t*)b[3].device);
+    });
+}
+
+DCRT_API int dcrt_device_light_eval(dcrt_tracer* t, const uint32_t* light_triangle, const float* normal_wi_distance, uint32_t n, float* out)
+{
+    TRACER_GUARD(t);
+    if ((!light_triangle || !normal_wi_distance || !out) && n) return DCRT_E_INVALID_ARG;
+    uint32_t lightCount = 0;
+    CHECKED(ProbeLights(t, &lightCount));
+    for (uint32_t i = 0; i < n; ++i) {
+        if (light_triangle[2 * (size_t)i] >= lightCount || light_triangle[2 * (size_t)i + 1] >= t->plan.scene.triangleCount) {
+            SetLastError("light eval probe: light or triangle index out of range");
+            return DCRT_E_INVALID_ARG;
+        }
+    }
+    const DeviceScene sc = t->plan.scene;
+    ProbeBuffer b[3] = {{light_triangle, nullptr, 8, nullptr}, {normal_wi_distance, nullptr, 28, nullptr}, {nullptr, out, 16, nullptr}};
+    return RunProbe(t, n, b, 3, [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(light_eval_probe_kernel, grid, block, 0, t->stream, sc, lightCount, (const uint32_t*)b[0].device, (const float*)b[1].device, n,
+                           (float*)b[2].device);
+    });
+}
+
+DCRT_API int dcrt_device_env_lookup(dcrt_tracer* t, const float* directions, uint32_t n, float* out_rgb)
+{
+    TRACER_GUARD(t);
+    if ((!directions || !out_rgb) && n) return DCRT_E_INVALID_ARG;
+    if (!t->hasScene || !t->plan.scene.envCube || t->plan.scene.envCubeSize == 0u) { SetLastError("no scene uploaded, or no environment cube in it"); return DCRT_E_NO_SCENE; }
+    const DeviceScene sc = t->plan.scene;
+    ProbeBuffer b[2] = {{directions, nullptr, 12, nullptr}, {nullptr, out_rgb, 12, nullptr}};
+    return RunProbe(t, n, b, 2, [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(env_lookup_probe_kernel, grid, block, 0, t->stream, sc, (const float*)b[0].device, n, (float*)b[1].device);
+    });
 }
 
 DCRT_API int dcrt_device_bsdf_sample(dcrt_tracer* t, const dcrt_bsdf_probe_material* m, uint32_t features, const float* wo,

@@ -550,6 +550,62 @@ class WavefrontPathTracer:
                                                 out.ctypes.data_as(_abi._FP)), "FrameProbe")
         return out
 
+    # -- the shading probes (tests): the path kernels' own stages on the uploaded scene and the current frame
+    # parameters; layouts in dcrt.h --
+    def camera_ray_at(self, film, aperture):
+        """generate_ray at (N, 2) film samples and (N, 3) aperture numbers: origins, directions (N, 3)."""
+        film = np.ascontiguousarray(film, np.float32).reshape(-1, 2)
+        aperture = np.ascontiguousarray(aperture, np.float32).reshape(-1, 3)
+        if len(film) != len(aperture):
+            raise ValueError("camera_ray_at: film and aperture samples differ in length")
+        o, d = np.zeros((len(film), 3), np.float32), np.zeros((len(film), 3), np.float32)
+        fp = _abi._FP
+        check(self._lib.dcrt_device_camera_ray(self._h, film.ctypes.data_as(fp), aperture.ctypes.data_as(fp), len(film),
+                                               o.ctypes.data_as(fp), d.ctypes.data_as(fp)), "CameraRay")
+        return o, d
+
+    def intersection_probe(self, records, use_table: bool = False):
+        """hit_to_intersection of (N, 4) uint32 hit records (u, v bits, triangle | backface bit 31, instance):
+        (N, 16) floats -- position, normal, tangent, geometry normal, albedo, alpha -- and (N, 3) words --
+        material type, flags, light index."""
+        records = np.ascontiguousarray(records, np.uint32).reshape(-1, 4)
+        f, w = np.zeros((len(records), 16), np.float32), np.zeros((len(records), 3), np.uint32)
+        up = C.POINTER(C.c_uint32)
+        check(self._lib.dcrt_device_intersection_probe(self._h, records.ctypes.data_as(up), len(records), int(bool(use_table)),
+                                                       f.ctypes.data_as(_abi._FP), w.ctypes.data_as(up)), "IntersectionProbe")
+        return f, w
+
+    def light_sample(self, points, states):
+        """sample_light from (N, 3) points and (N, 4) xoshiro states: (N, 8) floats -- radiance, wi, pdf,
+        distance -- and (N, 5) words -- delta flag, advanced state."""
+        points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        states = np.ascontiguousarray(states, np.uint32).reshape(-1, 4)
+        if len(points) != len(states):
+            raise ValueError("light_sample: points and states differ in length")
+        f, w = np.zeros((len(points), 8), np.float32), np.zeros((len(points), 5), np.uint32)
+        up = C.POINTER(C.c_uint32)
+        check(self._lib.dcrt_device_light_sample(self._h, points.ctypes.data_as(_abi._FP), states.ctypes.data_as(up), len(points),
+                                                 f.ctypes.data_as(_abi._FP), w.ctypes.data_as(up)), "LightSample")
+        return f, w
+
+    def light_eval(self, light_triangle, normal_wi_distance):
+        """evaluate_light of (N, 2) (light, triangle) and (N, 7) (normal, wi, distance): (N, 4) radiance, pdf."""
+        lt = np.ascontiguousarray(light_triangle, np.uint32).reshape(-1, 2)
+        a = np.ascontiguousarray(normal_wi_distance, np.float32).reshape(-1, 7)
+        if len(lt) != len(a):
+            raise ValueError("light_eval: index pairs and vectors differ in length")
+        out = np.zeros((len(lt), 4), np.float32)
+        check(self._lib.dcrt_device_light_eval(self._h, lt.ctypes.data_as(C.POINTER(C.c_uint32)), a.ctypes.data_as(_abi._FP), len(lt),
+                                               out.ctypes.data_as(_abi._FP)), "LightEval")
+        return out
+
+    def env_lookup(self, directions):
+        """sample_env at (N, 3) directions: rgb (N, 3)."""
+        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        out = np.zeros_like(d)
+        check(self._lib.dcrt_device_env_lookup(self._h, d.ctypes.data_as(_abi._FP), len(d), out.ctypes.data_as(_abi._FP)), "EnvLookup")
+        return out
+
     def bsdf_sample(self, material: _abi.BsdfProbeMaterial, wo: np.ndarray, u: np.ndarray,
                     features: int = _abi.FEATURE_DEFAULT):
         """MATERIAL's sample_bsdf likewise: for (N, 3) wo and (N, 3) numbers (sx, sy, sel), the

@@ -979,6 +979,34 @@ DCRT_API int dcrt_device_bsdf_sample(dcrt_tracer* tracer, const dcrt_bsdf_probe_
    without it. out_frames: 9 floats per record, the world-space normal, tangent and geometry normal. */
 DCRT_API int dcrt_device_frame_probe(dcrt_tracer* tracer, const uint32_t* records, uint32_t count, int use_table, float* out_frames);
 
+/* The stages between the ray casts and the BSDF at chosen inputs (tests; tests/shading_ref.py is their float64
+   reference): the path kernels' own generate_ray, hit_to_intersection, sample_light, evaluate_light and
+   sample_env, on the uploaded scene and the current frame parameters (dcrt_tracer_set_frame_params). A null
+   pointer with a nonzero count is DCRT_E_INVALID_ARG, as is an index outside the scene.
+   camera_ray: `count` film samples (2 floats each: the film point in [0, 1]^2) and aperture numbers (3 floats
+   each) -> world-space ray origins and directions, 3 floats each. Needs frame parameters only. */
+DCRT_API int dcrt_device_camera_ray(dcrt_tracer* tracer, const float* film_samples, const float* aperture_samples, uint32_t count,
+                                    float* out_origins, float* out_directions);
+/* Hit records as dcrt_device_frame_probe takes them (bit 31 of the triangle word: the backface bit) -> per record
+   16 floats -- world-space position, normal, tangent, geometry normal, albedo (3 each), alpha -- and 3 words --
+   the material type, flags (1 two-sided, 2 backface, 4 multiscattering, internal scattering mode << 4), the
+   instance's light index. use_table != 0: the form of the hit reconstruction that takes the frame table
+   (DCRT_E_NO_SCENE when the scene has none); 0: the per-hit form. */
+DCRT_API int dcrt_device_intersection_probe(dcrt_tracer* tracer, const uint32_t* records, uint32_t count, int use_table,
+                                            float* out_floats, uint32_t* out_words);
+/* Light sampling from `count` points (3 floats) with xoshiro128** states (4 words) over the frame's light_count
+   lights -> per point 8 floats -- radiance, wi (3 each), pdf, distance -- and 5 words -- the delta flag, the
+   state after the draws (1 for a punctual light, 4 for a mesh light, 3 for the environment). A state whose
+   draws select past the lights or the scene's triangles is refused. */
+DCRT_API int dcrt_device_light_sample(dcrt_tracer* tracer, const float* points, const uint32_t* rng_states, uint32_t count,
+                                      float* out_floats, uint32_t* out_words);
+/* Light evaluation of `count` (light index, triangle index) word pairs and 7 floats each -- the light's normal at
+   the hit, wi, distance -> radiance (3 floats) and pdf. */
+DCRT_API int dcrt_device_light_eval(dcrt_tracer* tracer, const uint32_t* light_triangle, const float* normal_wi_distance,
+                                    uint32_t count, float* out_radiance_pdf);
+/* The environment cube at `count` directions (3 floats) -> rgb. DCRT_E_NO_SCENE without a cube. */
+DCRT_API int dcrt_device_env_lookup(dcrt_tracer* tracer, const float* directions, uint32_t count, float* out_rgb);
+
 /* The instance whose BLAS holds each triangle of a flat scene (host only; the frame table's eligibility
    rule): out_instances[t], UINT32_MAX for a triangle no instance reaches. Returns DCRT_OK and *out_single_use
    = 1 where every reached triangle belongs to one instance, 0 where a BLAS has two instances or the tree is

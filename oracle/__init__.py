@@ -96,8 +96,64 @@ def load():
     lib.oracle_bsdf_sample.restype = None
     lib.oracle_bsdf_sample.argtypes = [P(A.BxDFLuts), P(OracleBsdfMaterial), U, P(C.c_float), P(C.c_float), U, P(C.c_float),
                                        P(C.c_float), P(C.c_float), P(C.c_int)]
+    lib.oracle_camera_ray_at.restype = None
+    lib.oracle_camera_ray_at.argtypes = [P(A.FrameParams), P(C.c_float), P(C.c_float), U, P(C.c_float), P(C.c_float)]
+    lib.oracle_intersection_probe.restype = None
+    lib.oracle_intersection_probe.argtypes = [P(A.FlatScene), P(U), U, P(C.c_float), P(U)]
+    lib.oracle_light_sample.restype = None
+    lib.oracle_light_sample.argtypes = [P(A.FlatScene), U, P(C.c_float), P(U), U, P(C.c_float), P(U)]
+    lib.oracle_light_eval.restype = None
+    lib.oracle_light_eval.argtypes = [P(A.FlatScene), U, P(U), P(C.c_float), U, P(C.c_float)]
+    lib.oracle_env_lookup.restype = None
+    lib.oracle_env_lookup.argtypes = [P(A.FlatScene), P(C.c_float), U, P(C.c_float)]
     _lib = lib
     return lib
+
+
+# ---- the shading probes (the device's are WavefrontPathTracer.camera_ray_at and on: same arguments
+# after the scene / frame, same results) ----
+
+def camera_ray_at(frame, film, aperture):
+    """generate_ray at (N, 2) film samples and (N, 3) aperture numbers: origins, directions (N, 3)."""
+    film = np.ascontiguousarray(film, np.float32).reshape(-1, 2)
+    aperture = np.ascontiguousarray(aperture, np.float32).reshape(-1, 3)
+    o, d = np.zeros((len(film), 3), np.float32), np.zeros((len(film), 3), np.float32)
+    load().oracle_camera_ray_at(C.byref(frame), _fp(film), _fp(aperture), len(film), _fp(o), _fp(d))
+    return o, d
+
+
+def intersection_probe(flat, records):
+    """hit_to_intersection of (N, 4) uint32 hit records (u, v bits, triangle | backface bit 31, instance):
+    (N, 16) floats and (N, 3) words (dcrt_oracle.h)."""
+    records = np.ascontiguousarray(records, np.uint32).reshape(-1, 4)
+    f, w = np.zeros((len(records), 16), np.float32), np.zeros((len(records), 3), np.uint32)
+    load().oracle_intersection_probe(C.byref(flat), _up(records), len(records), _fp(f), _up(w))
+    return f, w
+
+
+def light_sample(flat, light_count, points, states):
+    """sample_light from (N, 3) points and (N, 4) xoshiro states: (N, 8) floats, (N, 5) words."""
+    points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    states = np.ascontiguousarray(states, np.uint32).reshape(-1, 4)
+    f, w = np.zeros((len(points), 8), np.float32), np.zeros((len(points), 5), np.uint32)
+    load().oracle_light_sample(C.byref(flat), int(light_count), _fp(points), _up(states), len(points), _fp(f), _up(w))
+    return f, w
+
+
+def light_eval(flat, light_count, light_triangle, normal_wi_distance):
+    """evaluate_light of (N, 2) (light, triangle) and (N, 7) (normal, wi, distance): (N, 4) radiance, pdf."""
+    lt = np.ascontiguousarray(light_triangle, np.uint32).reshape(-1, 2)
+    a = np.ascontiguousarray(normal_wi_distance, np.float32).reshape(-1, 7)
+    out = np.zeros((len(lt), 4), np.float32)
+    load().oracle_light_eval(C.byref(flat), int(light_count), _up(lt), _fp(a), len(lt), _fp(out))
+    return out
+
+
+def env_lookup(flat, directions):
+    d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+    out = np.zeros_like(d)
+    load().oracle_env_lookup(C.byref(flat), _fp(d), len(d), _fp(out))
+    return out
 
 
 class OracleBsdfMaterial(C.Structure):

@@ -1712,6 +1712,74 @@ void oracle_bsdf_sample(const dcrt_bxdf_luts* luts, const oracle_bsdf_material* 
     }
 }
 
+/* Test entries: the stages between the ray casts and the BSDF at a caller's inputs (see dcrt_oracle.h) */
+void oracle_camera_ray_at(const dcrt_frame_params* f, const float* film_samples, const float* aperture_samples, uint32_t count,
+                          float* origins, float* directions)
+{
+    for (uint32_t i = 0; i < count; ++i) {
+        f2 film; film.x = film_samples[2 * i]; film.y = film_samples[2 * i + 1];
+        const v3 ap = V3(aperture_samples[3 * i], aperture_samples[3 * i + 1], aperture_samples[3 * i + 2]);
+        v3 o, d;
+        generate_ray(film, ap, f, &o, &d);
+        origins[3 * i] = o.x; origins[3 * i + 1] = o.y; origins[3 * i + 2] = o.z;
+        directions[3 * i] = d.x; directions[3 * i + 1] = d.y; directions[3 * i + 2] = d.z;
+    }
+}
+void oracle_intersection_probe(const dcrt_flat_scene* sc, const uint32_t* records, uint32_t count, float* out_floats, uint32_t* out_words)
+{
+    init_srgb();
+    for (uint32_t i = 0; i < count; ++i) {
+        const uint32_t* r = records + 4 * (size_t)i;
+        hit_info h;
+        h.t = 1.0f; h.u = asfloat(r[0]); h.v = asfloat(r[1]);
+        h.triangleId = r[2] & 0x7FFFFFFFu; h.backface = (r[2] >> 31) != 0; h.instanceIndex = r[3];
+        isect it;
+        hit_to_intersection(sc, &h, &it);
+        float* o = out_floats + 16 * (size_t)i;
+        const v3 v[5] = { it.position, it.normal, it.tangent, it.geometryNormal, it.albedo };
+        for (int k = 0; k < 5; ++k) { o[3 * k] = v[k].x; o[3 * k + 1] = v[k].y; o[3 * k + 2] = v[k].z; }
+        o[15] = it.alpha;
+        uint32_t* w = out_words + 3 * (size_t)i;
+        w[0] = it.materialType;
+        w[1] = (it.isTwoSided ? 1u : 0u) | (it.backface ? 2u : 0u) | (it.multiscattering ? 4u : 0u) | (it.internalScatteringMode << 4);
+        w[2] = it.lightIndex;
+    }
+}
+void oracle_light_sample(const dcrt_flat_scene* sc, uint32_t light_count, const float* points, const uint32_t* rng_states,
+                         uint32_t count, float* out_floats, uint32_t* out_words)
+{
+    for (uint32_t i = 0; i < count; ++i) {
+        uint32_t s[4];
+        memcpy(s, rng_states + 4 * (size_t)i, 16);
+        const light_sample r = sample_light_direct(sc, V3(points[3 * i], points[3 * i + 1], points[3 * i + 2]), light_count, s);
+        float* o = out_floats + 8 * (size_t)i;
+        o[0] = r.radiance.x; o[1] = r.radiance.y; o[2] = r.radiance.z;
+        o[3] = r.wi.x; o[4] = r.wi.y; o[5] = r.wi.z;
+        o[6] = r.pdf; o[7] = r.distance;
+        uint32_t* w = out_words + 5 * (size_t)i;
+        w[0] = r.isDeltaLight ? 1u : 0u;
+        memcpy(w + 1, s, 16);
+    }
+}
+void oracle_light_eval(const dcrt_flat_scene* sc, uint32_t light_count, const uint32_t* light_triangle, const float* normal_wi_distance,
+                       uint32_t count, float* out)
+{
+    for (uint32_t i = 0; i < count; ++i) {
+        const float* a = normal_wi_distance + 7 * (size_t)i;
+        v3 radiance; float pdf;
+        evaluate_light_direct(sc, light_triangle[2 * i], light_triangle[2 * i + 1], V3(a[0], a[1], a[2]), V3(a[3], a[4], a[5]), a[6],
+                              light_count, &radiance, &pdf);
+        out[4 * i] = radiance.x; out[4 * i + 1] = radiance.y; out[4 * i + 2] = radiance.z; out[4 * i + 3] = pdf;
+    }
+}
+void oracle_env_lookup(const dcrt_flat_scene* sc, const float* directions, uint32_t count, float* out_rgb)
+{
+    for (uint32_t i = 0; i < count; ++i) {
+        const v3 c = sample_env_cube(sc, V3(directions[3 * i], directions[3 * i + 1], directions[3 * i + 2]));
+        out_rgb[3 * i] = c.x; out_rgb[3 * i + 1] = c.y; out_rgb[3 * i + 2] = c.z;
+    }
+}
+
 void oracle_generate_camera_ray(const dcrt_frame_params* f, uint32_t px, uint32_t py, float origin[3], float direction[3], uint32_t rng_out[4])
 {
     uint32_t s[4];

@@ -92,6 +92,29 @@ void oracle_bsdf_eval(const dcrt_bxdf_luts* luts, const oracle_bsdf_material* m,
 void oracle_bsdf_sample(const dcrt_bxdf_luts* luts, const oracle_bsdf_material* m, uint32_t features, const float* wo,
                         const float* u, uint32_t count, float* wi_out, float* f_out, float* pdf_out, int* delta_out);
 
+/* The stages between the ray casts and the BSDF at a caller's inputs (tests/shading_ref.py is their
+   float64 reference; the device has the same entries, dcrt_device_camera_ray and on in dcrt.h, with
+   the same layouts).
+   camera_ray_at: GenerateRay (RayTracingCommon.inc.hlsl:38-86) at `count` film samples (2 floats) and
+   aperture numbers (3 floats): world-space origin and direction, 3 floats each.
+   intersection_probe: HitInfoToIntersection (RayTracingCommon.inc.hlsl:88-116, HitShader.inc.hlsl:14-84)
+   of records of 4 words -- u, v (float bits), triangle | backface bit 31, instance: 16 floats (position,
+   normal, tangent, geometry normal, albedo, alpha) and 3 words (material type; flags: 1 two-sided,
+   2 backface, 4 multiscattering, internal scattering mode << 4; light index) per record.
+   light_sample: SampleLightDirect (Light.inc.hlsl) from points p (3 floats) and xoshiro states (4 words):
+   8 floats (radiance, wi, pdf, distance) and 5 words (delta flag, the advanced state) per point.
+   light_eval: EvaluateLightDirect of (light, triangle) word pairs and 7 floats (normal, wi, distance):
+   radiance and pdf, 4 floats. env_lookup: the environment cube at directions, rgb. */
+void oracle_camera_ray_at(const dcrt_frame_params* frame, const float* film_samples, const float* aperture_samples,
+                          uint32_t count, float* origins, float* directions);
+void oracle_intersection_probe(const dcrt_flat_scene* scene, const uint32_t* records, uint32_t count, float* out_floats,
+                               uint32_t* out_words);
+void oracle_light_sample(const dcrt_flat_scene* scene, uint32_t light_count, const float* points, const uint32_t* rng_states,
+                         uint32_t count, float* out_floats, uint32_t* out_words);
+void oracle_light_eval(const dcrt_flat_scene* scene, uint32_t light_count, const uint32_t* light_triangle,
+                       const float* normal_wi_distance, uint32_t count, float* out);
+void oracle_env_lookup(const dcrt_flat_scene* scene, const float* directions, uint32_t count, float* out_rgb);
+
 /* Post-processing (PostProcessings.hlsl, SumLuminance.hlsl): tone-mapped sRGB8 RGBA. */
 float oracle_sum_log_luminance(const float* film_rgba, uint32_t width, uint32_t height);
 void oracle_resolve_image(const float* film_rgba, uint32_t width, uint32_t height, int enabled, int auto_exposure, float ev100,

@@ -32,7 +32,9 @@ elif mode == "tracer":
     h = _abi._P()
     rc = lib.dcrt_tracer_create(None, C.byref(h))
     assert rc == 0, rc
-    handle, prefix = h, ("dcrt_tracer_", "dcrt_device_math_eval", "dcrt_device_bsdf_eval", "dcrt_device_bsdf_sample")
+    handle, prefix = h, ("dcrt_tracer_", "dcrt_device_math_eval", "dcrt_device_bsdf_eval", "dcrt_device_bsdf_sample",
+                         "dcrt_device_camera_ray", "dcrt_device_intersection_probe", "dcrt_device_light_sample",
+                         "dcrt_device_light_eval", "dcrt_device_env_lookup")
 for name, res, args in _abi.SIGNATURES:
     if res is not _abi._I or not args:
         continue
@@ -50,6 +52,10 @@ for name, res, args in _abi.SIGNATURES:
         if name in ("dcrt_device_bsdf_eval", "dcrt_device_bsdf_sample"):
             vals[1] = C.byref(_abi.BsdfProbeMaterial())   # (a material, so that the null buffers are what is refused)
             vals[5] = 7
+        if name in ("dcrt_device_camera_ray", "dcrt_device_light_sample", "dcrt_device_light_eval"):
+            vals[3] = 7
+        if name in ("dcrt_device_intersection_probe", "dcrt_device_env_lookup"):
+            vals[2] = 7
         if name in ("dcrt_scene_get_material_setting", "dcrt_scene_set_material", "dcrt_scene_set_material_opacity",
                     "dcrt_scene_set_material_multiscattering", "dcrt_scene_get_mesh_light", "dcrt_scene_get_punctual_light",
                     "dcrt_scene_get_instance_material_override", "dcrt_scene_get_loaded_mesh", "dcrt_scene_get_instance"):

@@ -7,6 +7,7 @@ import pytest
 
 import bsdf_ref as R
 from conftest import GOLDEN
+from ref_tolerance import CHI_Z, TOLERANCE_K, TOLERANCE_ULPS, chi_square_quantile, tolerance_ratio  # noqa: F401 (re-exported)
 
 DIFFUSE, PLASTIC, CONDUCTOR, DIELECTRIC, THIN = 0, 1, 2, 3, 4
 VNDF = 1   # DCRT_FEATURE_GGX_SAMPLE_VNDF
@@ -35,8 +36,6 @@ EVAL_MATERIALS = MATERIALS + [
 ]
 EVAL_CASES = [(n, kw, two, feat) for n, kw in EVAL_MATERIALS for two in (False, True) for feat in (VNDF, 0)]
 EVAL_PAIRS = 4000
-TOLERANCE_K = 6      # see test_values_and_pdfs_against_float64_reference
-TOLERANCE_ULPS = 4
 
 
 @pytest.fixture(scope="module")
@@ -114,25 +113,6 @@ def ref_pair(L, kw, wi, wo, features):
     return r64, tuple(x.astype(np.float64) for x in r32)
 
 
-def tolerance_ratio(got, ref64, ref32, ulps=TOLERANCE_ULPS):
-    """Per element, (|got - ref64| - ulps float32 ulps of ref64) / e, at least 0: the K an element
-    needs to pass |got - ref64| <= K e + ulps ulp. e is the float32 run's own error |ref32 - ref64|,
-    but no less than the case's 99th-percentile relative float32 error times |ref64|: one float32
-    run is one draw of the rounding error, and at some elements it lands on the float64 value by
-    luck (or the element's table terms round the same way for every pair), which says nothing
-    about how far another order of the same operations may land."""
-    got = np.asarray(got, np.float64)
-    err32 = np.abs(ref32 - ref64)
-    nz = ref64 != 0
-    floor = np.percentile(err32[nz] / np.abs(ref64[nz]), 99) if nz.any() else 0.0
-    e = np.maximum(err32, floor * np.abs(ref64))
-    slack = ulps * np.spacing(np.abs(ref64).astype(np.float32)).astype(np.float64)
-    excess = np.maximum(np.abs(got - ref64) - slack, 0.0)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        r = excess / e
-    return np.where(excess == 0.0, 0.0, r)
-
-
 def check_values_and_pdfs(bsdf_eval, L, name, kw, two, feat):
     """One case of the value / pdf comparison for an evaluator bsdf_eval(kw, wi, wo, features) ->
     (f, pdf); returns the worst K needed (printed by the callers' -s runs)."""
@@ -169,19 +149,12 @@ def test_values_and_pdfs_against_float64_reference(oracle_mod, golden_luts, ref_
 CHI_DRAWS = 200_000
 CHI_BINS = (32, 64)     # cos(theta) in [-1, 1] x phi in [-pi, pi]: the horizon is a bin edge
 CHI_SUB = (16, 8)       # sub-grid per bin in cos and in phi for the expected counts
-CHI_Z = 4.753424        # standard normal quantile of an upper tail of 1e-6
 CHI_CASES = [(n, kw, z) for n, kw in MATERIALS for z in (0.9, 0.3)]
 
 
 def sampler_numbers(seed, n):
     """(n, 3) float32 numbers in [0, 1) with 24 random bits each (exact in float32, never 1)."""
     return (np.random.default_rng(seed).integers(0, 1 << 24, (n, 3)) / float(1 << 24)).astype(np.float32)
-
-
-def chi_square_quantile(dof, z=CHI_Z):
-    """Wilson-Hilferty: chi^2_dof is close to dof (1 - 2/(9 dof) + z sqrt(2/(9 dof)))^3; at the
-    hundreds of degrees of freedom used here it is good to a fraction of a percent."""
-    return dof * (1.0 - 2.0 / (9.0 * dof) + z * np.sqrt(2.0 / (9.0 * dof))) ** 3
 
 
 def expected_bin_mass(L, kw, wo1, sub=CHI_SUB):
