@@ -368,6 +368,10 @@ SIGNATURES = [
     ("dcrt_tracer_adaptive_timings", _I, [_P, _FP, _FP, _FP]),
     ("dcrt_tracer_render_adaptive", _I, [_P, _U, C.POINTER(ConvergeParams), _U, C.POINTER(FilterParams), C.POINTER(NoiseStats),
                                          C.POINTER(C.c_int), C.POINTER(AdaptiveReport)]),
+    ("dcrt_tracer_set_environment_sampling", _I, [_P, _I]),
+    ("dcrt_tracer_get_environment_sampling", _I, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("dcrt_tracer_read_environment_distribution", _I, [_P, _FP, _FP, _FP]),
+    ("dcrt_tracer_environment_build_timing", _I, [_P, _FP]),
     ("dcrt_write_bmp", _I, [C.c_char_p, _U, _U, C.POINTER(C.c_uint8)]),
     ("dcrt_device_math_eval", _I, [_P, _I, _FP, _U, _FP]),
     ("dcrt_device_bsdf_eval", _I, [_P, C.POINTER(BsdfProbeMaterial), _U, _FP, _FP, _U, _FP, _FP]),

@@ -32,6 +32,13 @@ constexpr uint32_t kCapLightDirectional = 1u << 9;
 constexpr uint32_t kCapLightEnv = 1u << 10;
 constexpr uint32_t kCapEnvCube = 1u << 11;
 constexpr uint32_t kCapAll = (1u << 12) - 1u;
+// Beyond kCapAll: the any-scene variant that also samples the environment cube by importance
+// (DeviceScene::envProb, "environment importance sampling" in dcrt.h). A bit of its own, so that
+// kCapAll and kCapOpaqueDelta keep their values and their code.
+constexpr uint32_t kCapEnvImportance = 1u << 12;
+constexpr uint32_t kCapAllEnvImportance = kCapAll | kCapEnvImportance;
+// CAPS covers any scene (kCapAll, with or without kCapEnvImportance)
+constexpr bool caps_any_scene(uint32_t caps) { return (caps & kCapAll) == kCapAll; }
 constexpr uint32_t kCapMaterialsMask = 0x1Fu;
 constexpr uint32_t kCapLightShift = 7;
 // Opaque delta-lit scenes (the Cornell configs): diffuse / plastic / conductor
@@ -42,7 +49,7 @@ constexpr uint32_t kCapOpaqueDelta = kCapMatDiffuse | kCapMatPlastic | kCapMatCo
 template <uint32_t CAPS>
 DEV void assume_light_caps(uint32_t flags)
 {
-    if constexpr (CAPS != kCapAll) __builtin_assume((flags & ~((CAPS >> kCapLightShift) & 0xFu) & 0xFu) == 0u);
+    if constexpr (!caps_any_scene(CAPS)) __builtin_assume((flags & ~((CAPS >> kCapLightShift) & 0xFu) & 0xFu) == 0u);
 }
 
 struct TextureDesc {
@@ -114,6 +121,12 @@ struct DeviceScene {
     // instance, or null; ldsFrames: 1 when MATERIAL's LDS copy holds them (behind the rows).
     const float4* triFrames;
     uint32_t ldsFrames;
+    // The environment cube's sampling table (DCRT_ENV_SAMPLING_IMPORTANCE, dcrt.h; env_rows_kernel and
+    // its two successors build it), rows r = face * n + y: the texel probabilities [6n][n], the per-row
+    // conditional CDF [6n][n], the marginal CDF over rows [6n]. Null: the light is sampled uniformly.
+    const float* envProb;
+    const float* envRowCdf;
+    const float* envMarginal;
 };
 
 // DCRT_SHADING_TABLES bits: per-hit work whose inputs are fixed at scene upload
@@ -1177,6 +1190,89 @@ DEV V3 sample_env(const DeviceScene& s, V3 d)
     return mk(o[0], o[1], o[2]);
 }
 
+// ---- environment importance sampling (dcrt.h) -------------------------------------
+// The uniform share of the mixture density: keeps the pdf positive everywhere and bounds radiance / pdf.
+constexpr float kEnvUniformShare = 1.0f / 16.0f;
+// A texel's weight in float64: the largest luminance (the film kernels' weighting in float32, a NaN
+// or a negative one counting 0) over its 3 x 3 neighbourhood clamped inside the face -- all that
+// sample_env's clamped bilinear taps read anywhere in the texel -- times the texel's solid angle to
+// first order, (4 / n^2) (1 + sc^2 + tc^2)^(-3/2) at its centre.
+DEV float env_texel_luminance(const float* cube, int n, int face, int y, int x)
+{
+    const float* t = cube + (((size_t)face * n + y) * n + x) * 3;
+    return fmaxf(0.0f, t[0] * 0.299f + t[1] * 0.587f + t[2] * 0.114f);
+}
+DEV double env_texel_weight(const float* cube, int n, int face, int y, int x)
+{
+    float m = 0.0f;
+    for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) m = fmaxf(m, env_texel_luminance(cube, n, face, clampi(y + dy, 0, n - 1), clampi(x + dx, 0, n - 1)));
+    const double sc = (double)(2 * x + 1) / (double)n - 1.0, tc = (double)(2 * y + 1) / (double)n - 1.0;
+    const double q = 1.0 + sc * sc + tc * tc;
+    return (double)m * (4.0 / ((double)n * (double)n)) / (q * sqrt(q));
+}
+// The density of env_sample_direction at wi, per solid angle: the chosen texel's probability over the
+// texel's extent in face coordinates, carried to the sphere, mixed with the uniform share. The texel is
+// that of sample_env's own u and v (its face table and signs, restated here so that sample_env's code
+// stays as it is). Every index is clamped, so any wi -- a NaN included -- reads inside the table.
+DEV float env_pdf(const DeviceScene& s, V3 d)
+{
+    const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
+    int face; float sc, tc, ma;
+    if (ax >= ay && ax >= az) { ma = ax; if (d.x >= 0.0f) { face = 0; sc = -d.z; tc = -d.y; } else { face = 1; sc = d.z; tc = -d.y; } }
+    else if (ay >= az) { ma = ay; if (d.y >= 0.0f) { face = 2; sc = d.x; tc = d.z; } else { face = 3; sc = d.x; tc = -d.z; } }
+    else { ma = az; if (d.z >= 0.0f) { face = 4; sc = d.x; tc = -d.y; } else { face = 5; sc = -d.x; tc = -d.y; } }
+    const float fs = sc / ma, ft = tc / ma;
+    const float u = (fs + 1.0f) * 0.5f, v = (ft + 1.0f) * 0.5f;
+    const int n = (int)s.envCubeSize;
+    const int ix = clampi((int)floorf(u * (float)n), 0, n - 1), iy = clampi((int)floorf(v * (float)n), 0, n - 1);
+    const float p = s.envProb[((size_t)face * n + iy) * n + ix];
+    const float q = 1.0f + fs * fs + ft * ft;
+    const float perTexel = (float)n * (float)n * 0.25f;
+    return (1.0f - kEnvUniformShare) * p * perTexel * (q * sqrtf(q)) + kEnvUniformShare * uniform_sphere_pdf();
+}
+// The first index i of cdf[0, count) with cdf[i] > x, for a non-decreasing cdf whose last entry is 1 > x:
+// the number of entries <= x, gathered bit by bit -- ceil(log2 count) dependent loads, no branch.
+DEV uint32_t env_cdf_search(const float* cdf, uint32_t count, float x)
+{
+    uint32_t lo = 0u;
+    for (uint32_t step = count > 1u ? 1u << (31u - (uint32_t)__builtin_clz(count - 1u)) : 0u; step != 0u; step >>= 1) {
+        const uint32_t probe = lo + step;
+        const float c = cdf[(probe < count ? probe : count) - 1u];
+        lo = (probe <= count && c <= x) ? probe : lo;
+    }
+    return lo < count - 1u ? lo : count - 1u;
+}
+// A direction from the table with the sample_light's two numbers: the uniform share of a, else a row by
+// the marginal CDF, a column by the row's, and the remainders as the position inside the texel.
+DEV V3 env_sample_direction(const DeviceScene& s, float a, float b)
+{
+    if (a < kEnvUniformShare) return uniform_sphere(a / kEnvUniformShare, b);
+    const float a1 = (a - kEnvUniformShare) / (1.0f - kEnvUniformShare);
+    const uint32_t n = s.envCubeSize;
+    const uint32_t r = env_cdf_search(s.envMarginal, 6u * n, a1);
+    const float* rowCdf = s.envRowCdf + (size_t)r * n;
+    const uint32_t c = env_cdf_search(rowCdf, n, b);
+    const float rLo = r ? s.envMarginal[r - 1u] : 0.0f, rHi = s.envMarginal[r];
+    const float cLo = c ? rowCdf[c - 1u] : 0.0f, cHi = rowCdf[c];
+    const float below1 = 0.99999994f;
+    const float fa = fminf(fmaxf((a1 - rLo) / (rHi - rLo), 0.0f), below1);
+    const float fb = fminf(fmaxf((b - cLo) / (cHi - cLo), 0.0f), below1);
+    const uint32_t face = r / n, y = r - face * n;
+    const float sc = 2.0f * ((float)c + fb) / (float)n - 1.0f, tc = 2.0f * ((float)y + fa) / (float)n - 1.0f;
+    // the inverse of sample_env's face map at ma = 1
+    V3 d;
+    switch (face) {
+    case 0: d = mk(1.0f, -tc, -sc); break;
+    case 1: d = mk(-1.0f, -tc, sc); break;
+    case 2: d = mk(sc, 1.0f, tc); break;
+    case 3: d = mk(sc, -1.0f, -tc); break;
+    case 4: d = mk(sc, -tc, 1.0f); break;
+    default: d = mk(-sc, -tc, -1.0f); break;
+    }
+    return normalize(d);
+}
+
 // ---- hit reconstruction --------------------------------------------------------
 struct Intersection {
     V3 albedo; float alpha;
@@ -1338,6 +1434,7 @@ DEV LightSample sample_light(const DeviceScene& s, V3 p, uint32_t lightCount, Rn
     const dcrt_light& L = s.lights[li];
     assume_light_caps<CAPS>(L.flags);
     if constexpr ((CAPS & kCapEnvCube) == 0u) __builtin_assume(s.envCube == nullptr);
+    if constexpr ((CAPS & kCapEnvCube) == 0u || (CAPS & kCapEnvImportance) == 0u) __builtin_assume(s.envProb == nullptr);
     if (L.flags & DCRT_LIGHT_FLAGS_POINT_LIGHT) {
         r.wi = ld3(L.position_or_triangle_range) - p;
         r.distance = length(r.wi);
@@ -1379,8 +1476,16 @@ DEV LightSample sample_light(const DeviceScene& s, V3 p, uint32_t lightCount, Rn
         r.pdf = r.pdf / (float)triCount;
     } else if (L.flags & DCRT_LIGHT_FLAGS_ENVIRONMENT_LIGHT) {
         const float a = next1(rng), b = next1(rng);
-        r.wi = uniform_sphere(a, b);
-        r.pdf = uniform_sphere_pdf();
+        bool table = false;
+        if constexpr ((CAPS & kCapEnvImportance) != 0u) table = s.envProb != nullptr;
+        if (table) {
+            // (the density of the direction produced, not of the texel chosen: evaluate_light's, bit for bit)
+            r.wi = env_sample_direction(s, a, b);
+            r.pdf = env_pdf(s, r.wi);
+        } else {
+            r.wi = uniform_sphere(a, b);
+            r.pdf = uniform_sphere_pdf();
+        }
         r.radiance = s.envCube ? sample_env(s, r.wi) * ld3(L.radiance) : ld3(L.radiance);
         r.distance = inf();
     }
@@ -1398,6 +1503,7 @@ DEV void evaluate_light(const DeviceScene& s, uint32_t li, uint32_t tri, V3 norm
     const dcrt_light& L = s.lights[li];
     assume_light_caps<CAPS>(L.flags);
     if constexpr ((CAPS & kCapEnvCube) == 0u) __builtin_assume(s.envCube == nullptr);
+    if constexpr ((CAPS & kCapEnvCube) == 0u || (CAPS & kCapEnvImportance) == 0u) __builtin_assume(s.envProb == nullptr);
     if (L.flags & DCRT_LIGHT_FLAGS_MESH_LIGHT) {
         const float4* M = s.transforms + (size_t)asu(L.position_or_triangle_range[2]) * 3;
         const V3 v0 = mul43(tri_pos(s, tri, 0), 1.0f, M), v1 = mul43(tri_pos(s, tri, 1), 1.0f, M), v2 = mul43(tri_pos(s, tri, 2), 1.0f, M);
@@ -1410,6 +1516,9 @@ DEV void evaluate_light(const DeviceScene& s, uint32_t li, uint32_t tri, V3 norm
     } else if (L.flags & DCRT_LIGHT_FLAGS_ENVIRONMENT_LIGHT) {
         *radiance = s.envCube ? sample_env(s, wi) * ld3(L.radiance) : ld3(L.radiance);
         *pdf = uniform_sphere_pdf();
+        if constexpr ((CAPS & kCapEnvImportance) != 0u) {
+            if (s.envProb != nullptr) *pdf = env_pdf(s, wi);
+        }
     }
     *pdf = *pdf / (float)lightCount;
 }

@@ -165,6 +165,73 @@ __device__ __forceinline__ void begin_batch_claims(Globals* g)
     g->staticFill = G ? 1u : 0u;
 }
 
+// ---- the environment cube's sampling table (dcrt.h, "environment importance sampling") ----------
+// Three plain 256-thread launches at upload. Sums are float64 throughout; a stored value is one
+// rounding of a float64 quotient.
+// An inclusive scan of one double per lane across the wave (Hillis-Steele over __shfl_up)
+DEV double env_wave_scan(double v)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t d = 1u; d < 64u; d <<= 1) {
+        const double up = __shfl_up(v, d, 64);
+        if (lane >= d) v += up;
+    }
+    return v;
+}
+// One wave per row r = face * n + y: the texel weights (env_texel_weight) scanned in chunks of 64 columns
+// with a carry; the unnormalised row CDF and the row's total.
+__global__ __launch_bounds__(256) void env_rows_kernel(const float* cube, uint32_t n, double* rowSums, double* rowTotals)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (r >= 6u * n) return;   // (whole waves leave: r is wave-uniform)
+    const uint32_t face = r / n, y = r - face * n;
+    double carry = 0.0;
+    for (uint32_t x0 = 0u; x0 < n; x0 += 64u) {
+        const uint32_t x = x0 + lane;
+        const double w = x < n ? env_texel_weight(cube, (int)n, (int)face, (int)y, (int)x) : 0.0;
+        const double inc = carry + env_wave_scan(w);
+        if (x < n) rowSums[(size_t)r * n + x] = inc;
+        carry = __shfl(inc, 63, 64);
+    }
+    if (lane == 0u) rowTotals[r] = carry;
+}
+// One workgroup: the row totals scanned in chunks of its width with a carry; the unnormalised
+// marginal CDF and, behind its last entry, the table's total.
+__global__ __launch_bounds__(256) void env_marginal_kernel(const double* rowTotals, uint32_t rows, double* marginalSums)
+{
+    __shared__ double waveTotals[4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    double carry = 0.0;
+    for (uint32_t r0 = 0u; r0 < rows; r0 += 256u) {
+        const uint32_t r = r0 + threadIdx.x;
+        const double inc = env_wave_scan(r < rows ? rowTotals[r] : 0.0);
+        if (lane == 63u) waveTotals[wave] = inc;
+        __syncthreads();
+        double before = carry;
+        for (uint32_t w = 0u; w < wave; ++w) before += waveTotals[w];
+        if (r < rows) marginalSums[r] = before + inc;
+        carry = carry + waveTotals[0] + waveTotals[1] + waveTotals[2] + waveTotals[3];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0u) marginalSums[rows] = carry;
+}
+// Per texel: P = w / total, the row's CDF over its total (zeros for an empty row); per row: the
+// marginal CDF over the total. The last entry of each stored CDF is exactly 1.
+__global__ __launch_bounds__(256) void env_finish_kernel(const float* cube, uint32_t n, const double* rowSums, const double* rowTotals,
+                                                         const double* marginalSums, float* prob, float* rowCdf, float* marginal)
+{
+    const uint32_t rows = 6u * n;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)rows * n) return;
+    const uint32_t r = (uint32_t)(i / n), x = (uint32_t)(i - (size_t)r * n);
+    const uint32_t face = r / n, y = r - face * n;
+    const double total = marginalSums[rows], rowTotal = rowTotals[r];
+    prob[i] = (float)(env_texel_weight(cube, (int)n, (int)face, (int)y, (int)x) / total);
+    rowCdf[i] = rowTotal > 0.0 ? (x == n - 1u ? 1.0f : (float)(rowSums[i] / rowTotal)) : 0.0f;
+    if (x == 0u) marginal[r] = r == rows - 1u ? 1.0f : (float)(marginalSums[r] / total);
+}
+
 // The per-material rows of the plastic dielectric LUT (DeviceScene::dielRows; a launch per upload of
 // the materials or the LUTs): float k of material m at rows[m * kDielRowFloats + k], with alpha as
 // hit_to_intersection forms it for a material without the roughness checkerboard.
@@ -492,7 +559,7 @@ static_assert(DCRT_MATERIAL_BLOCK % 64 == 0 && DCRT_MATERIAL_BLOCK <= 960, "MATE
 #ifndef DCRT_MATERIAL_OD_WAVES_PER_EU
 #define DCRT_MATERIAL_OD_WAVES_PER_EU 1   // (the opaque / delta-light variants: the compiler's choice)
 #endif
-#define DCRT_MATERIAL_OCCUPANCY __attribute__((amdgpu_waves_per_eu(CAPS == kCapAll || FUSED ? DCRT_MATERIAL_WAVES_PER_EU : DCRT_MATERIAL_OD_WAVES_PER_EU, 8)))
+#define DCRT_MATERIAL_OCCUPANCY __attribute__((amdgpu_waves_per_eu(caps_any_scene(CAPS) || FUSED ? DCRT_MATERIAL_WAVES_PER_EU : DCRT_MATERIAL_OD_WAVES_PER_EU, 8)))
 // CAPS: the scene capabilities this variant is compiled for (kCapAll = any scene; see
 // kCapOpaqueDelta in dscene.h and dcrt_tracer::UploadScene).
 // SCENE_LDS: the scene arrays MATERIAL's shading reads per item are copied into LDS by each
@@ -688,7 +755,7 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
         float extOpacity = 0.0f, shadowOpacity = 0.0f;
         V3 T, L, lsr;
         DCRT_MCLK(0);
-        shade_path<CAPS, SCENE_LDS == 1 && CAPS != kCapAll>(sc, fcv, hit, dir, rng, flags, thr, li, T, L, lsr, terminate, hasShadow, nO, nD, sO, sD,
+        shade_path<CAPS, SCENE_LDS == 1 && !caps_any_scene(CAPS)>(sc, fcv, hit, dir, rng, flags, thr, li, T, L, lsr, terminate, hasShadow, nO, nD, sO, sD,
                          extOpacity, shadowOpacity DCRT_MCLK_ARGS);
         DCRT_MCLK(4);
         if (fcv.features & DCRT_FEATURE_ALLOW_ANYHIT) {   // :422-430
@@ -1353,7 +1420,8 @@ __device__ __forceinline__ bool trace_full(const DeviceScene& sc, V3 o, V3 d, fl
     return s.found;
 }
 
-template <bool OPACITY>
+// CAPS: kCapAll, or kCapAllEnvImportance where the environment cube is sampled by its table
+template <bool OPACITY, uint32_t CAPS = kCapAll>
 __global__ __launch_bounds__(256) void megakernel(DeviceScene sc, const FrameConstants* __restrict__ fcp, Film film, Globals* g, uint32_t debugRng)
 {
     extern __shared__ uint32_t stackMem[];
@@ -1417,7 +1485,7 @@ __global__ __launch_bounds__(256) void megakernel(DeviceScene sc, const FrameCon
                         else L = sc.envCube ? sample_env(sc, rd) * rad : rad;
                     } else {
                         V3 radiance; float lightPdf;
-                        evaluate_light(sc, lightIndex, it.triangleIndex, it.geometryNormal, rd, hitT, fc.lightCount, &radiance, &lightPdf);
+                        evaluate_light<CAPS>(sc, lightIndex, it.triangleIndex, it.geometryNormal, rd, hitT, fc.lightCount, &radiance, &lightPdf);
                         if (lightPdf > 0.0f) {
                             const float weight = !isDeltaPrev ? power_heuristic(bsdfPdfPrev, lightPdf) : 1.0f;
                             L = L + T * radiance * weight;
@@ -1433,7 +1501,7 @@ __global__ __launch_bounds__(256) void megakernel(DeviceScene sc, const FrameCon
             V3 so = mk(0.0f, 0.0f, 0.0f), sd = so;
             float sdist = 0.0f;
             if (fc.lightCount != 0) {
-                const LightSample ls = sample_light(sc, it.position, fc.lightCount, rng);
+                const LightSample ls = sample_light<CAPS>(sc, it.position, fc.lightCount, rng);
                 if (any_pos(ls.radiance) && ls.pdf > 0.0f) {
                     const V3 bsdf = evaluate_bsdf(sc, vndf, ls.wi, bf, it);
                     const float NdotWI = fabsf(dot(it.normal, ls.wi));
@@ -1833,6 +1901,7 @@ __global__ void intersection_probe_kernel(DeviceScene sc, const uint4* records, 
     w[1] = (it.isTwoSided ? 1u : 0u) | (it.backface ? 2u : 0u) | (it.multiscattering ? 4u : 0u) | (it.internalScatteringMode << 4);
     w[2] = it.lightIndex;
 }
+template <uint32_t CAPS>
 __global__ void light_sample_probe_kernel(DeviceScene sc, uint32_t lightCount, const float* points, const uint4* states, uint32_t n,
                                           float* outFloats, uint32_t* outWords)
 {
@@ -1841,7 +1910,7 @@ __global__ void light_sample_probe_kernel(DeviceScene sc, uint32_t lightCount, c
     const uint4 s = states[i];
     Rng rng;
     rng.s0 = s.x; rng.s1 = s.y; rng.s2 = s.z; rng.s3 = s.w;
-    const LightSample r = sample_light(sc, mk(points[3 * i], points[3 * i + 1], points[3 * i + 2]), lightCount, rng);
+    const LightSample r = sample_light<CAPS>(sc, mk(points[3 * i], points[3 * i + 1], points[3 * i + 2]), lightCount, rng);
     float* o = outFloats + (size_t)i * 8;
     o[0] = r.radiance.x; o[1] = r.radiance.y; o[2] = r.radiance.z;
     o[3] = r.wi.x; o[4] = r.wi.y; o[5] = r.wi.z;
@@ -1850,13 +1919,14 @@ __global__ void light_sample_probe_kernel(DeviceScene sc, uint32_t lightCount, c
     w[0] = r.isDelta ? 1u : 0u;
     w[1] = rng.s0; w[2] = rng.s1; w[3] = rng.s2; w[4] = rng.s3;
 }
+template <uint32_t CAPS>
 __global__ void light_eval_probe_kernel(DeviceScene sc, uint32_t lightCount, const uint32_t* lightTriangle, const float* in, uint32_t n, float* out)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float* a = in + (size_t)i * 7;
     V3 radiance; float pdf;
-    evaluate_light(sc, lightTriangle[2 * i], lightTriangle[2 * i + 1], mk(a[0], a[1], a[2]), mk(a[3], a[4], a[5]), a[6], lightCount, &radiance, &pdf);
+    evaluate_light<CAPS>(sc, lightTriangle[2 * i], lightTriangle[2 * i + 1], mk(a[0], a[1], a[2]), mk(a[3], a[4], a[5]), a[6], lightCount, &radiance, &pdf);
     out[4 * i] = radiance.x; out[4 * i + 1] = radiance.y; out[4 * i + 2] = radiance.z; out[4 * i + 3] = pdf;
 }
 __global__ void env_lookup_probe_kernel(DeviceScene sc, const float* directions, uint32_t n, float* out)
@@ -2819,6 +2889,8 @@ DCRT_CAST_VARIANTS(DCRT_INSTANTIATE_CAST)
 #undef DCRT_INSTANTIATE_CAST
 template __global__ void megakernel<false>(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t);
 template __global__ void megakernel<true>(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t);
+template __global__ void megakernel<false, kCapAllEnvImportance>(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t);
+template __global__ void megakernel<true, kCapAllEnvImportance>(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t);
 template __global__ void view_kernel<false>(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t, uint32_t, uint32_t);
 template __global__ void view_kernel<true>(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t, uint32_t, uint32_t);
 template __global__ void batch_trace_kernel<false, false>(DeviceScene, const dcrt_ray*, uint32_t, uint32_t, dcrt_ray_hit*, uint32_t*, unsigned long long*);

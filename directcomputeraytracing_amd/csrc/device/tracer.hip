@@ -387,7 +387,9 @@ using MaterialFn = void (*)(PathPool, DeviceScene, const FrameConstants*, Counte
 // scene with its current materials and lights (dcrt_tracer::PlanMaterial): the one place that says which
 // material_kernel runs and with how much LDS.
 struct MaterialPlan {
-    uint32_t caps = kCapAll;           // the compiled variant that covers the scene: kCapOpaqueDelta or kCapAll (dscene.h)
+    // the compiled variant that covers the scene: kCapOpaqueDelta, kCapAll, or kCapAllEnvImportance -- the any-scene
+    // variant that samples the environment cube by the table `envProb` names (dscene.h)
+    uint32_t caps = kCapAll;
     uint32_t mode = 0;                 // material_kernel's SCENE_LDS: 0 no copy, 1 whole shading data, 2 all but the triangles
     uint32_t materials = 0, lights = 0;   // the counts the LDS copy holds (0 without one)
     // The sections of the dynamic LDS (dscene.h material_lds_layout; 0 bytes: not held). cells != 0: the fused
@@ -397,14 +399,28 @@ struct MaterialPlan {
     uint32_t tables = 0;
     const float* dielRows = nullptr;
     const float4* triFrames = nullptr;
+    // The environment cube's sampling table in force (dcrt_tracer::BuildEnvTable), or null: the uniform sphere
+    const float* envProb = nullptr;
+    const float* envRowCdf = nullptr;
+    const float* envMarginal = nullptr;
     uint32_t fusedMask = 0;            // DCRT_FUSED_SHADOW's path-slot mask (FrameConstants::shadowInlineMask: not baked into a graph)
     uint32_t drainGrid = 0;            // drain_kernel's grid: resident workgroups on the whole chip
 
     // The one table from variant to compiled kernel. probe: the row-cost probe's variant (no LDS copy)
     MaterialFn Kernel(bool probe, bool fused) const
     {
-        if (probe) return material_kernel<kCapAll, 0, true>;
         const bool od = caps == kCapOpaqueDelta;
+        if (caps == kCapAllEnvImportance && !fused) {
+            if (probe) return material_kernel<kCapAllEnvImportance, 0, true>;
+            switch (mode) {
+            case 1: return material_kernel<kCapAllEnvImportance, 1>;
+            case 2: return material_kernel<kCapAllEnvImportance, 2>;
+            default: return material_kernel<kCapAllEnvImportance, 0>;
+            }
+        }
+        if (probe) return material_kernel<kCapAll, 0, true>;
+        // (the fused form never runs beside an environment light -- it goes with one point light's cells -- so a
+        // plan with the table sizes it with the any-scene variant and never launches it)
         if (fused) return od ? material_kernel<kCapOpaqueDelta, 1, false, true> : material_kernel<kCapAll, 1, false, true>;
         switch (mode) {
         case 1: return od ? material_kernel<kCapOpaqueDelta, 1> : material_kernel<kCapAll, 1>;
@@ -412,7 +428,16 @@ struct MaterialPlan {
         default: return od ? material_kernel<kCapOpaqueDelta, 0> : material_kernel<kCapAll, 0>;
         }
     }
-    auto DrainKernel() const { return caps == kCapOpaqueDelta ? drain_kernel<kCapOpaqueDelta> : drain_kernel<kCapAll>; }
+    auto DrainKernel() const
+    {
+        return caps == kCapOpaqueDelta ? drain_kernel<kCapOpaqueDelta> : caps == kCapAllEnvImportance ? drain_kernel<kCapAllEnvImportance> : drain_kernel<kCapAll>;
+    }
+    using MegaFn = void (*)(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t);
+    MegaFn Megakernel(bool opacity) const
+    {
+        if (caps == kCapAllEnvImportance) return opacity ? megakernel<true, kCapAllEnvImportance> : megakernel<false, kCapAllEnvImportance>;
+        return opacity ? megakernel<true> : megakernel<false>;
+    }
     size_t LdsBytes(bool probe, bool fused) const { return probe ? 0u : lds.Bytes(fused); }
     // The shading fields of a DeviceScene (kernels take it by value)
     void Apply(DeviceScene* d) const
@@ -424,12 +449,16 @@ struct MaterialPlan {
         d->ldsRows = lds.rows ? materials : 0u;
         d->triFrames = triFrames;
         d->ldsFrames = lds.frames ? 1u : 0u;
+        d->envProb = envProb;
+        d->envRowCdf = envRowCdf;
+        d->envMarginal = envMarginal;
     }
     // What a captured graph bakes in: kernels, LDS bytes, the drain grid, what Apply writes (the pointers follow the bits)
     bool BakedEquals(const MaterialPlan& o) const
     {
         return caps == o.caps && mode == o.mode && materials == o.materials && lights == o.lights && lds.shading == o.lds.shading &&
-               lds.rows == o.lds.rows && lds.frames == o.lds.frames && lds.cells == o.lds.cells && tables == o.tables && drainGrid == o.drainGrid;
+               lds.rows == o.lds.rows && lds.frames == o.lds.frames && lds.cells == o.lds.cells && tables == o.tables && drainGrid == o.drainGrid &&
+               envProb == o.envProb && envRowCdf == o.envRowCdf && envMarginal == o.envMarginal;
     }
 };
 
@@ -477,6 +506,15 @@ struct dcrt_tracer {
     // the triangles' world-space frames, built at upload where no BLAS has two instances (else null)
     float* dDielRows = nullptr;
     float4* dTriFrames = nullptr;
+    // Environment importance sampling (dcrt.h): the mode asked for, which outlives the scene, and the uploaded
+    // cube's table -- built when the mode is on and the scene has a cube, null when there is none or its
+    // total weight is zero or not finite ("inactive": the uniform sphere) -- with its last build's time.
+    int envSampling = DCRT_ENV_SAMPLING_UNIFORM;
+    float* dEnvProb = nullptr;
+    float* dEnvRowCdf = nullptr;
+    float* dEnvMarginal = nullptr;
+    float envBuildMs = 0.0f;
+    bool EnvTableActive() const { return hasScene && envSampling == DCRT_ENV_SAMPLING_IMPORTANCE && dEnvProb != nullptr; }
     // MATERIAL of the next launch tests its shadow rays itself: where the cast is the CELLS kernel
     bool FusedShadow() const
     {
@@ -625,6 +663,8 @@ struct dcrt_tracer {
     int CastOccupancy(CastFn k, size_t lds, int* out);
     int PlanMaterial(const MaterialPlan* before, MaterialPlan* out);
     int ApplyMaterialPlan(const MaterialPlan& p);
+    int BuildEnvTable();
+    int SetEnvSampling(int mode);
     int BuildDielRows();
     int RederiveShading();
     int UpdateMaterials(const dcrt_material* materials, uint32_t count);
@@ -965,6 +1005,13 @@ int dcrt_tracer::PlanMaterial(const MaterialPlan* before, MaterialPlan* out)
     }
     for (const dcrt_light& l : hostLights) sceneCaps |= (l.flags & 0xFu) << kCapLightShift;
     p.caps = (sceneCaps & ~kCapOpaqueDelta) == 0u && !k.materialGeneric ? kCapOpaqueDelta : kCapAll;
+    // (the cube's table, where the mode is on and one stands, for a scene with an environment light: its own any-scene variant)
+    if (envSampling == DCRT_ENV_SAMPLING_IMPORTANCE && dEnvProb && scene.envCube && (sceneCaps & kCapLightEnv)) {
+        p.caps = kCapAllEnvImportance;
+        p.envProb = dEnvProb;
+        p.envRowCdf = dEnvRowCdf;
+        p.envMarginal = dEnvMarginal;
+    }
     // 2. the LDS scene copy within the knob's budget: the whole shading data (mode 1), else all but the triangles (mode 2)
     const bool counts = T > 0 && T < (1u << 20) && I < (1u << 20) && M < (1u << 20) && L < (1u << 20);
     const uint64_t whole = material_lds_layout(T, I, M, L, 0u, false, 0u, false).shading;
@@ -1005,7 +1052,7 @@ int dcrt_tracer::PlanMaterial(const MaterialPlan* before, MaterialPlan* out)
     if ((p.tables & kTableDielRows) && p.mode != 0u) CHECKED(grow(layout(M, false, p.lds.cells != 0u), &taken));
     // 5. the frames: in the whole-scene LDS copy of the delta-only variant under the same rule, or not at all
     // (the any-scene variant takes a register more with the table in it, and spills it)
-    if (!dTriFrames || p.mode != 1u || p.caps == kCapAll) p.tables &= ~kTableFrames;
+    if (!dTriFrames || p.mode != 1u || caps_any_scene(p.caps)) p.tables &= ~kTableFrames;
     if (p.tables & kTableFrames) {
         CHECKED(grow(layout(p.lds.rows ? M : 0u, true, p.lds.cells != 0u), &taken));
         if (!taken) p.tables &= ~kTableFrames;
@@ -1186,6 +1233,7 @@ int dcrt_tracer::UploadArrays(const dcrt_flat_scene& s, std::vector<uint32_t>* i
     InvalidateGraph();
     FreeAll(&sceneAllocs);
     hasScene = false;
+    dEnvProb = dEnvRowCdf = dEnvMarginal = nullptr;   // (the last scene's table went with sceneAllocs)
     ++uploadStats.scene_uploads;
     DeviceScene d{};
     // (shading_bytes: the three arrays an edit replaces)
@@ -1301,6 +1349,75 @@ int dcrt_tracer::UploadArrays(const dcrt_flat_scene& s, std::vector<uint32_t>* i
     d.stackSize = std::max<uint32_t>(s.bvh_traversal_stack_size, 1u);
     d.singlePrimLeaves = dcrt::SingleTriangleLeaves(s) ? 1u : 0u;
     plan.scene = d;
+    if (envSampling == DCRT_ENV_SAMPLING_IMPORTANCE) CHECKED(BuildEnvTable());
+    return DCRT_OK;
+}
+
+// The sampling table of plan.scene's cube (none: nothing to do), on the tracer's stream: env_rows_kernel,
+// env_marginal_kernel, env_finish_kernel between two events, then the total read back -- zero or not finite:
+// no table, the light stays uniformly sampled. The table depends on the cube alone, so it stands until the
+// next upload whatever the lights' colours become.
+int dcrt_tracer::BuildEnvTable()
+{
+    dEnvProb = dEnvRowCdf = dEnvMarginal = nullptr;
+    envBuildMs = 0.0f;
+    const uint32_t n = plan.scene.envCubeSize;
+    if (!plan.scene.envCube || n == 0u) return DCRT_OK;
+    const uint32_t rows = 6u * n;
+    const size_t texels = (size_t)rows * n;
+    std::vector<void*> tmp;
+    double *rowSums = nullptr, *rowTotals = nullptr, *marginalSums = nullptr;
+    float *prob = nullptr, *rowCdf = nullptr, *marginal = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    double total = 0.0;
+    auto build = [&]() -> int {
+        CHECKED(DeviceAlloc(&rowSums, texels, &tmp));
+        CHECKED(DeviceAlloc(&rowTotals, (size_t)rows, &tmp));
+        CHECKED(DeviceAlloc(&marginalSums, (size_t)rows + 1, &tmp));
+        CHECKED(DeviceAlloc(&prob, texels, &sceneAllocs));
+        CHECKED(DeviceAlloc(&rowCdf, texels, &sceneAllocs));
+        CHECKED(DeviceAlloc(&marginal, (size_t)rows, &sceneAllocs));
+        HIPCHECK(hipEventCreate(&e0));
+        HIPCHECK(hipEventCreate(&e1));
+        HIPCHECK(hipEventRecord(e0, stream));
+        hipLaunchKernelGGL(env_rows_kernel, dim3((rows + 3u) / 4u), dim3(256), 0, stream, plan.scene.envCube, n, rowSums, rowTotals);
+        hipLaunchKernelGGL(env_marginal_kernel, dim3(1), dim3(256), 0, stream, (const double*)rowTotals, rows, marginalSums);
+        hipLaunchKernelGGL(env_finish_kernel, dim3((uint32_t)((texels + 255) / 256)), dim3(256), 0, stream, plan.scene.envCube, n, (const double*)rowSums,
+                           (const double*)rowTotals, (const double*)marginalSums, prob, rowCdf, marginal);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipEventRecord(e1, stream));
+        HIPCHECK(hipMemcpyAsync(&total, marginalSums + rows, sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHECK(hipStreamSynchronize(stream));
+        HIPCHECK(hipEventElapsedTime(&envBuildMs, e0, e1));
+        return DCRT_OK;
+    };
+    const int rc = build();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    FreeAll(&tmp);
+    if (rc != DCRT_OK) return rc;
+    if (total > 0.0 && std::isfinite(total)) {
+        dEnvProb = prob;
+        dEnvRowCdf = rowCdf;
+        dEnvMarginal = marginal;
+    }
+    return DCRT_OK;
+}
+
+// DCRT_ENV_SAMPLING_*: set on an uploaded scene, like the scene edits, and kept for it and every later scene. The
+// table is built when the mode first asks for it, and the plan rederived: the variant and the table's pointers are
+// among what a captured graph bakes in, so a toggle that changes them drops the graphs once. Film and path state
+// stay as they are.
+int dcrt_tracer::SetEnvSampling(int mode)
+{
+    if (mode != DCRT_ENV_SAMPLING_UNIFORM && mode != DCRT_ENV_SAMPLING_IMPORTANCE) { SetLastError("unknown environment sampling mode"); return DCRT_E_INVALID_ARG; }
+    if (!hasScene) { SetLastError("no scene uploaded"); return DCRT_E_NO_SCENE; }
+    if (mode == envSampling) return DCRT_OK;
+    envSampling = mode;
+    HIPCHECK(hipStreamSynchronize(stream));
+    if (mode == DCRT_ENV_SAMPLING_IMPORTANCE && !dEnvProb) CHECKED(BuildEnvTable());
+    CHECKED(RederiveShading());
+    HIPCHECK(hipStreamSynchronize(stream));
     return DCRT_OK;
 }
 
@@ -2286,7 +2403,7 @@ int dcrt_tracer::RenderImages(uint32_t firstSeed, uint32_t count, const dcrt_fil
             } else {
                 hipEvent_t e0 = nullptr, e1 = nullptr;
                 if (extTiming) CHECKED(TimedPair(kTimedCast, &e0, &e1));
-                auto mk = (frame.features & DCRT_FEATURE_ALLOW_ANYHIT) ? megakernel<true> : megakernel<false>;
+                auto mk = material.Megakernel((frame.features & DCRT_FEATURE_ALLOW_ANYHIT) != 0);
                 hipExtLaunchKernelGGL(mk, dim3(megaResident), dim3(plan.block), plan.ldsWholeStack, stream, e0, e1, 0, plan.scene,
                                       (const FrameConstants*)dFrame, claims, dGlobals, (uint32_t)(film.debugRng != nullptr));
             }
@@ -3228,7 +3345,7 @@ DCRT_API int dcrt_tracer_get_info(dcrt_tracer* t, dcrt_tracer_info* out)
     out->cached_triangles = t->hasScene ? plan.scene.cachedTris : 0u;
     out->cast_block = plan.block;
     out->traversal_stack = t->hasScene ? plan.scene.stackSize : 0u;
-    out->material_generic = t->material.caps == kCapAll ? 1u : 0u;
+    out->material_generic = caps_any_scene(t->material.caps) ? 1u : 0u;
     out->pair_traversal = t->hasScene && plan.pair ? 1u : 0u;
     out->control_grid = t->controlGrid;
     out->material_grid = t->materialGrid;
@@ -3870,7 +3987,7 @@ DCRT_API int dcrt_device_light_sample(dcrt_tracer* t, const float* points, const
     const DeviceScene sc = t->plan.scene;
     ProbeBuffer b[4] = {{points, nullptr, 12, nullptr}, {states, nullptr, 16, nullptr}, {nullptr, out_floats, 32, nullptr}, {nullptr, out_words, 20, nullptr}};
     return RunProbe(t, n, b, 4, [&](dim3 grid, dim3 block) {
-        hipLaunchKernelGGL(light_sample_probe_kernel, grid, block, 0, t->stream, sc, lightCount, (const float*)b[0].device, (const uint4*)b[1].device, n,
+        hipLaunchKernelGGL(t->material.caps == kCapAllEnvImportance ? light_sample_probe_kernel<kCapAllEnvImportance> : light_sample_probe_kernel<kCapAll>, grid, block, 0, t->stream, sc, lightCount, (const float*)b[0].device, (const uint4*)b[1].device, n,
                            (float*)b[2].device, (uint32_t*)b[3].device);
     });
 }
@@ -3890,9 +4007,43 @@ DCRT_API int dcrt_device_light_eval(dcrt_tracer* t, const uint32_t* light_triang
     const DeviceScene sc = t->plan.scene;
     ProbeBuffer b[3] = {{light_triangle, nullptr, 8, nullptr}, {normal_wi_distance, nullptr, 28, nullptr}, {nullptr, out, 16, nullptr}};
     return RunProbe(t, n, b, 3, [&](dim3 grid, dim3 block) {
-        hipLaunchKernelGGL(light_eval_probe_kernel, grid, block, 0, t->stream, sc, lightCount, (const uint32_t*)b[0].device, (const float*)b[1].device, n,
+        hipLaunchKernelGGL(t->material.caps == kCapAllEnvImportance ? light_eval_probe_kernel<kCapAllEnvImportance> : light_eval_probe_kernel<kCapAll>, grid, block, 0, t->stream, sc, lightCount, (const uint32_t*)b[0].device, (const float*)b[1].device, n,
                            (float*)b[2].device);
     });
+}
+
+DCRT_API int dcrt_tracer_set_environment_sampling(dcrt_tracer* t, int mode)
+{
+    TRACER_GUARD(t);
+    return t->SetEnvSampling(mode);
+}
+
+DCRT_API int dcrt_tracer_get_environment_sampling(dcrt_tracer* t, int* mode, int* active)
+{
+    if (!t || (!mode && !active)) return DCRT_E_INVALID_ARG;
+    if (mode) *mode = t->envSampling;
+    if (active) *active = t->EnvTableActive() ? 1 : 0;
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_read_environment_distribution(dcrt_tracer* t, float* prob, float* row_cdf, float* marginal_cdf)
+{
+    TRACER_GUARD(t);
+    if (!prob && !row_cdf && !marginal_cdf) return DCRT_E_INVALID_ARG;
+    if (!t->EnvTableActive()) { SetLastError("no environment sampling table: the mode is uniform, or no scene, no cube, or a cube without finite positive weight"); return DCRT_E_NO_SCENE; }
+    const size_t rows = (size_t)6 * t->plan.scene.envCubeSize, texels = rows * t->plan.scene.envCubeSize;
+    if (prob) HIPCHECK(hipMemcpyAsync(prob, t->dEnvProb, texels * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+    if (row_cdf) HIPCHECK(hipMemcpyAsync(row_cdf, t->dEnvRowCdf, texels * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+    if (marginal_cdf) HIPCHECK(hipMemcpyAsync(marginal_cdf, t->dEnvMarginal, rows * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+    HIPCHECK(hipStreamSynchronize(t->stream));
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_environment_build_timing(dcrt_tracer* t, float* out_ms)
+{
+    if (!t || !out_ms) return DCRT_E_INVALID_ARG;
+    *out_ms = t->envBuildMs;
+    return DCRT_OK;
 }
 
 DCRT_API int dcrt_device_env_lookup(dcrt_tracer* t, const float* directions, uint32_t n, float* out_rgb)

@@ -54,6 +54,7 @@ class WavefrontPathTracer:
         check(self._lib.dcrt_tracer_create(C.byref(cfg), C.byref(h)), "Create")
         self._h = h
         self.width = self.height = 0
+        self.env_cube_size = 0
         self.filter = _abi.FilterParams(_abi.FILTER_BOX, 1.0, 1.5, 1 / 3, 1 / 3, 3)
 
     def destroy(self):
@@ -71,6 +72,7 @@ class WavefrontPathTracer:
         """Upload the flattened scene and the camera/film constants (OnSceneLoaded)."""
         flat = scene.flat()
         check(self._lib.dcrt_tracer_upload_scene(self._h, C.byref(flat)), "OnSceneLoaded")
+        self.env_cube_size = int(flat.env_cube_size) if flat.env_cube_rgb else 0
         self.set_frame_params(scene.frame_params(frame_seed))
         self.filter = scene.filter_params()
 
@@ -443,6 +445,37 @@ class WavefrontPathTracer:
                                                     C.byref(done), C.byref(r)), "RenderAdaptive")
         return noise_stats_dict(s), bool(done.value), {k: int(getattr(r, k)) for k, _ in _abi.AdaptiveReport._fields_}
 
+    # ---- environment importance sampling (include/dcrt.h) ----------------------------
+    ENV_SAMPLING = ("uniform", "importance")
+
+    def set_environment_sampling(self, mode: str) -> None:
+        """"uniform" (the default, the reference's sampling) or "importance": light samples follow the
+        environment cube's power. Needs an uploaded scene; kept across later uploads; the caller restarts the image."""
+        if mode not in self.ENV_SAMPLING:
+            raise ValueError(f"environment sampling {mode!r}: one of {self.ENV_SAMPLING}")
+        check(self._lib.dcrt_tracer_set_environment_sampling(self._h, self.ENV_SAMPLING.index(mode)), "SetEnvironmentSampling")
+
+    def environment_sampling(self) -> tuple[str, bool]:
+        """(mode, active): active while the mode is on and a table stands for the uploaded scene's cube."""
+        mode, active = C.c_int(), C.c_int()
+        check(self._lib.dcrt_tracer_get_environment_sampling(self._h, C.byref(mode), C.byref(active)), "GetEnvironmentSampling")
+        return self.ENV_SAMPLING[mode.value], bool(active.value)
+
+    def environment_distribution(self):
+        """The stored table of the uploaded cube (size n): P [6n, n], the per-row CDF [6n, n], the marginal CDF [6n].
+        Raises (no scene) while inactive."""
+        n = max(1, self.env_cube_size)
+        prob, cdf, marginal = np.empty((6 * n, n), np.float32), np.empty((6 * n, n), np.float32), np.empty(6 * n, np.float32)
+        fp = _abi._FP
+        check(self._lib.dcrt_tracer_read_environment_distribution(self._h, prob.ctypes.data_as(fp), cdf.ctypes.data_as(fp),
+                                                                  marginal.ctypes.data_as(fp)), "ReadEnvironmentDistribution")
+        return prob, cdf, marginal
+
+    def environment_build_ms(self) -> float:
+        ms = C.c_float()
+        check(self._lib.dcrt_tracer_environment_build_timing(self._h, C.byref(ms)), "EnvironmentBuildTiming")
+        return float(ms.value)
+
     # ---- statistics ----------------------------------------------------------
     def counters(self) -> dict:
         s = _abi.RayStats()
@@ -668,7 +701,7 @@ def device_count() -> int:
 def make_pipelines(scene, pool: int, streams: int = 2, images: int = 1, iterations: int = 16, world: int = 1,
                    rank: int = 0, stripe: int = 64, mode: str = "wavefront", image_batch: int = 0, device: int = 0,
                    debug_rng: bool = False, row_cost=None, fixed_pool: bool = False, interleave: bool = False,
-                   bands_per_rank: int = 0) -> list:
+                   bands_per_rank: int = 0, env_sampling: str = "uniform") -> list:
     """The concurrent wavefront pipelines bench.py renders with, each a tracer with its share of
     `pool` slots (grown to whole batches of `images` images, partition.pipeline_pool), the
     filter's halo rows, its own stream. With `row_cost` (rays per film row, probe_row_cost) the
@@ -684,7 +717,7 @@ def make_pipelines(scene, pool: int, streams: int = 2, images: int = 1, iteratio
     K = max(1, streams)
     if interleave:
         return _make_interleaved(scene, pool, K, images, iterations, world, rank, stripe, mode, image_batch, device, debug_rng,
-                                 row_cost, fixed_pool, bands_per_rank or K, halo)
+                                 row_cost, fixed_pool, bands_per_rank or K, halo, env_sampling)
     bands = balanced_bands(row_cost, world * K, halo) if row_cost is not None and world * K > 1 else None
     tracers = []
     try:
@@ -697,6 +730,7 @@ def make_pipelines(scene, pool: int, streams: int = 2, images: int = 1, iteratio
             t = WavefrontPathTracer(path_pool_size=p, iterations_per_render=iterations, device=device, debug_rng=debug_rng)
             tracers.append(t)
             t.on_scene_loaded(scene)
+            t.set_environment_sampling(env_sampling)
             t.set_mode(mode)
             t.set_image_batch(image_batch)
             if band is not None:
@@ -711,7 +745,7 @@ def make_pipelines(scene, pool: int, streams: int = 2, images: int = 1, iteratio
 
 
 def _make_interleaved(scene, pool, K, images, iterations, world, rank, stripe, mode, image_batch, device, debug_rng, row_cost,
-                      fixed_pool, bands_per_rank, halo) -> list:
+                      fixed_pool, bands_per_rank, halo, env_sampling="uniform") -> list:
     """make_pipelines(interleave=True): K tracers over the SAME rows -- the whole film on one GPU,
     the rank's share of it on N (`bands_per_rank` cost-balanced bands dealt round-robin, or the
     round-robin stripes without a row cost) -- that split the images instead of the rows
@@ -737,6 +771,7 @@ def _make_interleaved(scene, pool, K, images, iterations, world, rank, stripe, m
             t = WavefrontPathTracer(path_pool_size=p, iterations_per_render=iterations, device=device, debug_rng=debug_rng)
             tracers.append(t)
             t.on_scene_loaded(scene)
+            t.set_environment_sampling(env_sampling)
             t.set_mode(mode)
             t.set_image_batch(image_batch)
             if bands is not None:

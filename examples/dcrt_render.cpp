@@ -9,7 +9,10 @@
 //               [--fixed-seed N] [--iterations N] [--pool N] [--film out.f32] [--samples out.f32]
 //               [--edit N:KIND:ARGS]... [--output NAME [--iteration-threshold N]] [--denoise]
 //               [--converge THRESHOLD[:FRACTION] [--check-points MIN:INTERVAL]] [--noise-map out.bmp]
-//               [--adaptive THRESHOLD:FRACTION[:MARGIN]] [--sample-map out.bmp]
+//               [--adaptive THRESHOLD:FRACTION[:MARGIN]] [--sample-map out.bmp] [--env-importance]
+//
+// --env-importance draws the light samples of an environment cube by its power instead of uniformly
+// (dcrt.h "environment importance sampling"); a scene without a cube renders as without the flag.
 //
 // --adaptive runs like --converge (the same check points, --noise-map, "converged" and "noise"),
 // but through dcrt_tracer_render_adaptive: after every check point only the 8 x 8 pixel blocks
@@ -85,7 +88,7 @@ int Usage(const char* exe)
                  "       [--output path_tracing|normal|tangent|albedo|negative_ndotv|backface|iteration_count]\n"
                  "       [--iteration-threshold N] [--denoise]\n"
                  "       [--converge THRESHOLD[:FRACTION] [--check-points MIN:INTERVAL]] [--noise-map out.bmp]\n"
-                 "       [--adaptive THRESHOLD:FRACTION[:MARGIN]] [--sample-map out.bmp]\n",
+                 "       [--adaptive THRESHOLD:FRACTION[:MARGIN]] [--sample-map out.bmp] [--env-importance]\n",
                  exe);
     return 2;
 }
@@ -204,12 +207,15 @@ int main(int argc, char** argv)
     bool adaptive = false;
     uint32_t adaptiveMargin = 0xFFFFFFFFu;   // (the filter's window rows)
     const char* sampleMapPath = nullptr;
+    bool envImportance = false;
     for (int i = 7; i < argc; ++i) {
         const bool more = i + 1 < argc;
         if (!std::strcmp(argv[i], "--batch")) {
             batch = true;
         } else if (!std::strcmp(argv[i], "--denoise")) {
             denoise = true;
+        } else if (!std::strcmp(argv[i], "--env-importance")) {
+            envImportance = true;
         } else if (!std::strcmp(argv[i], "--point") && i + 6 < argc) {
             pointLight = true;
             for (int k = 0; k < 3; ++k) lightPos[k] = (float)std::atof(argv[i + 1 + k]);
@@ -303,6 +309,7 @@ int main(int argc, char** argv)
     }
     if (!Check(dcrt_scene_set_max_bounce(scene.m_Handle, maxBounce), "SetMaxBounce")) return 1;
     if (!loop.AfterSceneEdited()) return 1;
+    if (envImportance && !tracer.SetEnvironmentSampling(DCRT_ENV_SAMPLING_IMPORTANCE)) return 1;   // (on the uploaded scene; kept across --edit uploads)
     if (seedType == CRendererLoop::EFrameSeedType::Fixed) scene.m_FrameSeed = fixedSeed;   // the UI's seed field (ImGui.cpp:157-160)
 
     const auto t0 = std::chrono::steady_clock::now();

@@ -202,6 +202,11 @@ bool CMI355XPathTracer::SetOutputType(uint32_t type, uint32_t iterationThreshold
     return m_Tracer && Ok(dcrt_tracer_set_output(m_Tracer, &p), "SetOutputType");
 }
 
+bool CMI355XPathTracer::SetEnvironmentSampling(int mode)
+{
+    return m_Tracer && Ok(dcrt_tracer_set_environment_sampling(m_Tracer, mode), "SetEnvironmentSampling");
+}
+
 bool CMI355XPathTracer::GetSampleTextures(void** devicePosition, void** deviceValue)
 {
     return m_Tracer && Ok(dcrt_tracer_sample_device_ptrs(m_Tracer, devicePosition, deviceValue), "SampleTextures");

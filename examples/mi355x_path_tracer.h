@@ -132,6 +132,8 @@ public:
     // 360-372): a DCRT_OUTPUT_* view. A change raises the film-clear trigger, which the frame
     // loop takes through AcquireFilmClearTrigger() as it takes the reference's.
     bool SetOutputType(uint32_t type, uint32_t iterationThreshold);
+    // DCRT_ENV_SAMPLING_*: how light samples of the environment cube are drawn (dcrt.h "environment importance sampling")
+    bool SetEnvironmentSampling(int mode);
     dcrt_tracer* GetTracer() const { return m_Tracer; }
     int LastStatus() const { return m_LastStatus; }
 

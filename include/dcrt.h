@@ -943,6 +943,49 @@ DCRT_API int dcrt_tracer_render_adaptive(dcrt_tracer* tracer, uint32_t first_see
                                          uint32_t margin, const dcrt_filter_params* filter, dcrt_noise_stats* out_stats,
                                          int* out_converged, dcrt_adaptive_report* out_report_or_null);
 
+/* ===== environment importance sampling ==========================================
+ * The environment light is sampled with a uniform direction and pdf 1 / (4 pi), as in the reference
+ * (DCRT_ENV_SAMPLING_UNIFORM, the default: every result is then what it was before this existed). With
+ * DCRT_ENV_SAMPLING_IMPORTANCE and an environment cube in the scene, light samples follow the cube's
+ * power instead. No reference counterpart. tests/env_importance_ref.py restates all of this in float64.
+ *
+ * Texels. n = env_cube_size. Texel (f, y, x) has the face coordinates sc = (2x + 1) / n - 1 and tc =
+ * (2y + 1) / n - 1: the (sc, tc) of the cube lookup, with its face table and axis signs.
+ * Weight. Y = max(0, 0.299 r + 0.587 g + 0.114 b) of the texel in float32, products summed left to
+ * right (the film kernels' luminance; fmaxf semantics: a NaN counts 0). M = the largest Y over the texel's
+ * 3 x 3 neighbourhood clamped inside the face -- the lookup clamps its bilinear taps inside the face, so
+ * anywhere in a texel it reads only that neighbourhood. w = M (4 / n^2) (1 + sc^2 + tc^2)^(-3/2) in float64.
+ * Table. P = w / sum(w); rows r = f n + y. Stored as float32: P [6n][n], the per-row conditional CDF
+ * [6n][n], the marginal CDF over rows [6n]; both CDFs are float64 sums in ascending index order, each
+ * stored CDF's last entry is exactly 1, a row whose total is 0 has a conditional CDF of zeros and the
+ * marginal never selects it. The table depends on the cube alone: dcrt_tracer_update_lights does not
+ * rebuild it. If sum(w) is 0 or not finite there is no table and sampling stays uniform ("inactive").
+ * Density. pdf(wi) = (1 - e) P(texel(wi)) (n^2 / 4) (1 + sc^2 + tc^2)^(3/2) + e / (4 pi), e = 1/16, with
+ * (sc, tc) the face coordinates of wi and texel(wi) the face, ix = clamp(floor(u n)) and iy =
+ * clamp(floor(v n)) of the lookup's own u = (sc + 1) / 2 and v = (tc + 1) / 2. Light sampling returns this
+ * density of the direction it produced, and light evaluation the same function: bitwise equal for one wi.
+ * Sampling. From the same three numbers as uniform sampling -- the light selector, then a, then b: if a < e
+ * the uniform-sphere direction of (a / e, b); else with a' = (a - e) / (1 - e) the row is the first r with
+ * marginal[r] > a', the column the first c with cdf[r][c] > b, the remainders fa = (a' - lo) / (hi - lo) and
+ * fb likewise (each clamped below 1) place the point inside the texel, sc = 2 (c + fb) / n - 1, tc =
+ * 2 (y + fa) / n - 1, and the direction is the inverse of the lookup's face map, normalised. Radiance
+ * (lookup times the light's colour), the infinite distance and the division by the light count are unchanged. */
+#define DCRT_ENV_SAMPLING_UNIFORM 0
+#define DCRT_ENV_SAMPLING_IMPORTANCE 1
+/* The mode: set on an uploaded scene, as the scene edits are (DCRT_E_NO_SCENE without one), and kept across
+ * every later dcrt_tracer_upload_scene; another value is DCRT_E_INVALID_ARG. The table is built at once (and at
+ * every later upload, while the mode is on). A scene without a cube accepts the mode and stays uniform. A change of what the kernels sample by drops the captured graphs;
+ * film and path state are not touched: restart the image, as after a scene edit. */
+DCRT_API int dcrt_tracer_set_environment_sampling(dcrt_tracer* tracer, int mode);
+/* *mode: the mode set; *active: 1 while a table stands for the uploaded scene and the mode is on. Either
+ * pointer may be null. */
+DCRT_API int dcrt_tracer_get_environment_sampling(dcrt_tracer* tracer, int* mode, int* active);
+/* The table as stored: prob and row_cdf 6 n n floats, marginal_cdf 6 n floats (null: not wanted).
+ * DCRT_E_NO_SCENE when inactive. */
+DCRT_API int dcrt_tracer_read_environment_distribution(dcrt_tracer* tracer, float* prob, float* row_cdf, float* marginal_cdf);
+/* The HIP-event time in ms of the last table build's three kernels (0: none built). */
+DCRT_API int dcrt_tracer_environment_build_timing(dcrt_tracer* tracer, float* out_ms);
+
 /* 24-bit BMP writer ("Save Image to File", SaveImageToFile.cpp:92-182). */
 DCRT_API int dcrt_write_bmp(const char* path, uint32_t width, uint32_t height, const uint8_t* rgba8);
 
