@@ -15,7 +15,7 @@ LIB_PATH = PKG_DIR / "libdcrt.so"
 
 # ---- status codes / flags (dcrt.h) -----------------------------------------
 DCRT_OK = 0
-ABI_VERSION = 5          # DCRT_ABI_VERSION: load_library refuses a libdcrt.so of another
+ABI_VERSION = 6         # DCRT_ABI_VERSION: load_library refuses a libdcrt.so of another
 ERRORS = {-1: "DCRT_E_INVALID_ARG", -2: "DCRT_E_HIP", -3: "DCRT_E_NO_SCENE", -4: "DCRT_E_IO",
           -5: "DCRT_E_LIMIT", -6: "DCRT_E_NO_DEVICE"}
 LIGHT_INDEX_INVALID = 0xFFFFFFFF
@@ -155,7 +155,7 @@ class AdaptiveReport(C.Structure):
 
 class RayStats(C.Structure):
     _fields_ = [("extension_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("new_paths", C.c_uint64),
-                ("iterations", C.c_uint64), ("images_completed", C.c_uint64)]
+                ("iterations", C.c_uint64), ("images_completed", C.c_uint64), ("early_finished", C.c_uint64)]
 
 
 class FilmPartition(C.Structure):
@@ -180,7 +180,8 @@ class TracerInfo(C.Structure):
                 ("cast_identity", C.c_uint32), ("stack_lds_rows", C.c_uint32), ("ring_rows", C.c_uint32),
                 ("cast_waves_per_cu", C.c_uint32), ("shadow_cells", C.c_uint32), ("shadow_cell_max_leaves", C.c_uint32),
                 ("shadow_cell_mean_leaves", C.c_float), ("shadow_inline", C.c_uint32), ("shading_tables", C.c_uint32),
-                ("dielectric_row_bytes", C.c_uint32), ("dielectric_row_lds", C.c_uint32), ("frame_table_bytes", C.c_uint32)]
+                ("dielectric_row_bytes", C.c_uint32), ("dielectric_row_lds", C.c_uint32), ("frame_table_bytes", C.c_uint32),
+                ("early_finish", C.c_uint32)]
 
 
 class ShadowCellsInfo(C.Structure):

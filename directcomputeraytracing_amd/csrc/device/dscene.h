@@ -44,6 +44,9 @@ constexpr uint32_t kCapLightShift = 7;
 // Opaque delta-lit scenes (the Cornell configs): diffuse / plastic / conductor
 // materials without multiscattering or textures, point and directional lights.
 constexpr uint32_t kCapOpaqueDelta = kCapMatDiffuse | kCapMatPlastic | kCapMatConductor | kCapLightPoint | kCapLightDirectional;
+// No extension ray of a CAPS scene can find radiance (no instance is a mesh light, a miss meets no
+// environment): a path's last bounce adds nothing to it (material_kernel's early finish)
+constexpr bool caps_early_finish(uint32_t caps) { return (caps & (kCapLightMesh | kCapLightEnv)) == 0u; }
 
 // Light-type flags a variant admits (the reference's light flags are one type bit each).
 template <uint32_t CAPS>
@@ -127,6 +130,9 @@ struct DeviceScene {
     const float* envProb;
     const float* envRowCdf;
     const float* envMarginal;
+    // MATERIAL finishes a path at its last shaded bounce (material_kernel's EARLY; DCRT_EARLY_FINISH): 0 off,
+    // 1 on, 2 on for even path slots only. MaterialPlan sets it where the variant's CAPS admit it.
+    uint32_t earlyFinish;
 };
 
 // DCRT_SHADING_TABLES bits: per-hit work whose inputs are fixed at scene upload

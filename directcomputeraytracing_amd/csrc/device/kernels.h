@@ -21,6 +21,18 @@ constexpr uint32_t kFlagShadowPending = 0x04000000u;   // the path cast a shadow
 // the path's last shadow ray was tested by MATERIAL itself (its FUSED variant) and is occluded: no
 // result to fetch (an unoccluded one sets neither bit)
 constexpr uint32_t kFlagShadowResolved = 0x02000000u;
+// A slot's flags word alone (PathPool::flags): idle for CONTROL's scans from the iteration whose epoch
+// (Counters' kEpochLine) is in the low bits. A path that MATERIAL finishes at its last shaded bounce is
+// completed one or two launches before the MATERIAL pass that would have idled its slot; with this word the
+// scans see the slot idle in the iteration they always did, so pixel blocks are claimed when they always were.
+constexpr uint32_t kFlagIdleFrom = 0x40000000u;
+constexpr uint32_t kEpochMask = 0x3FFFFFFFu;
+DEV uint32_t idle_from(uint32_t epoch) { return kFlagIdleFrom | (epoch & kEpochMask); }
+DEV bool slot_idle(uint32_t flags, uint32_t epoch)
+{
+    // (epoch - from, modulo 2^30: below half the range = reached)
+    return (flags & kFlagIdle) != 0u || ((flags & kFlagIdleFrom) != 0u && ((epoch - flags) & kEpochMask) < (kEpochMask >> 1));
+}
 constexpr uint32_t kBlockW = 8, kBlockH = 8;          // one wave64 = one 8x8 pixel block
 #ifndef DCRT_CONTROL_BLOCK
 #define DCRT_CONTROL_BLOCK 256
@@ -58,19 +70,43 @@ constexpr uint32_t kDrainedWord = kCounterWords + 1;
 // to its shard's word -- the shadow queue then counts only the rays that took the queue, and
 // end_iteration accounts for both
 constexpr uint32_t kInlineShadowWord = kCounterWords + 2;
-constexpr uint32_t kCounterLines = kCounterWords + 2 + kShards;
+// And kShards more: the LAST RAYS. A MATERIAL variant that no ray can bring radiance to (no mesh and no
+// environment light) finishes a path at its last shaded bounce (material_kernel, EARLY): the path is
+// completed there, or goes to the finish queue if its shadow ray's result is still to come, and the
+// extension ray it still casts -- traced and counted like any other, its hit wanted by nobody -- goes to
+// this queue: a 32-B record only, entry e of shard s at position s * recCap + recCap - 1 - e of the
+// extension records, growing down towards the shard's extension-queue entries (both come from the same
+// MATERIAL lanes: together within recCap). The line's second word counts those of the shard's last rays
+// whose paths MATERIAL completed itself (one 64-bit add for both): they are in no list, and live until
+// the pass that would have ended them (end_iteration, drain_kernel).
+constexpr uint32_t kLastRayWord = kInlineShadowWord + kShards;
+constexpr uint32_t kCounterLines = kLastRayWord + kShards;
+// Not cleared with the lines above: the iteration's epoch, one more than the previous iteration's
+// (end_iteration hands it on; BeginImage's set_idle_kernel restarts it with every slot's flags)
+constexpr uint32_t kEpochLine = kCounterLines;
 // Extension-queue entry bit: the path's first MATERIAL pass follows (set by NEW_PATH), whose
 // Li, light sampling result and throughput are the NEW_PATH constants, not stored or loaded
 constexpr uint32_t kEntryFirst = 0x80000000u;
 
 struct Counters {        // one set per iteration parity
-    uint32_t w[kCounterLines * kShardStride];
+    uint32_t w[(kCounterLines + 1) * kShardStride];
 };
+DEV uint32_t epoch_of(const Counters* c) { return c->w[kEpochLine * kShardStride]; }
 DEV uint32_t inline_shadow_rays(const Counters* c)
 {
     uint32_t t = 0;
     for (uint32_t s = 0; s < kShards; ++s) t += c->w[(kInlineShadowWord + s) * kShardStride];
     return t;
+}
+DEV unsigned long long* last_ctr(Counters* c, uint32_t s) { return (unsigned long long*)(c->w + (kLastRayWord + s) * kShardStride); }
+// (all shards: the last rays, and those among them whose paths MATERIAL completed itself)
+DEV void last_totals(const Counters* c, uint32_t* rays, uint32_t* completed)
+{
+    *rays = *completed = 0u;
+    for (uint32_t s = 0; s < kShards; ++s) {
+        *rays += c->w[(kLastRayWord + s) * kShardStride];
+        *completed += c->w[(kLastRayWord + s) * kShardStride + 1u];
+    }
 }
 DEV uint32_t virtual_items(const Counters* c) { return c->w[kVirtualWord * kShardStride]; }
 DEV bool drained(const Counters* c) { return c->w[kDrainedWord * kShardStride] != 0u; }
@@ -94,6 +130,7 @@ struct Globals {
     uint32_t skipFilm;        // RenderImages without the film pass: the caller convolves the images (accumulate_images)
     uint32_t filmImageBase;   // the film's image count when this RenderImages began (film_half_kernel: image parity)
     unsigned long long extRays, shadowRays, iterations;
+    unsigned long long earlyFinished;   // paths finished at their last shaded bounce (= last rays cast)
 };
 
 DEV uint32_t* qctr(Counters* c, uint32_t q, uint32_t s) { return c->w + (q * kShards + s) * kShardStride; }
@@ -141,6 +178,34 @@ DEV uint32_t qpos(uint32_t cap, const QueueMapN<N>& m, uint32_t i)
         base = ge ? m.prefix[k] : base;
     }
     return s * cap + (i - base);
+}
+// Position of last ray j of the concatenated last-ray shards: its shard's records grow down from the shard's
+// end. The counters are read here, per call: the casts look a last ray up in one refill of many (and in one
+// iteration of a batch's maxBounce + 2), and a prefix map held in registers across their traversal loop cost
+// the cache-only cast 22 more spilled SGPRs and every launch 1-3 % of its time.
+DEV uint32_t last_total(const Counters* c)
+{
+    uint32_t t = 0;
+    for (uint32_t s = 0; s < kShards; ++s) t += c->w[(kLastRayWord + s) * kShardStride];
+    return t;
+}
+DEV uint32_t last_pos(const Counters* c, uint32_t cap, uint32_t j)
+{
+    uint32_t s = 0, base = 0, run = 0;
+    const uint32_t* w = c->w;
+#if defined(__HIP_DEVICE_COMPILE__)
+    // (a pointer the compiler takes as new with every call: the loads stay here, not hoisted in front of
+    // the caller's loop as eight more scalar registers)
+    asm volatile("" : "+s"(w));
+#endif
+#pragma unroll
+    for (uint32_t k = 0; k + 1 < kShards; ++k) {
+        run += w[(kLastRayWord + k) * kShardStride];
+        const bool ge = j >= run;
+        s += ge ? 1u : 0u;
+        base = ge ? run : base;
+    }
+    return s * cap + (cap - 1u - (j - base));
 }
 // Extension-ray record `q` (q = shard * recCap + entry) through a 32-bit byte offset (one
 // parity's records stay below 4 GiB: dcrt_tracer::Create checks it)
@@ -286,8 +351,11 @@ struct PathStateB {
 // (Li += lsr when the shadow ray is unoccluded, WriteSample), at its finish-queue position.
 struct FinishRec {
     float4 liLsr;    // Li.xyz, lsr.x
-    float4 lsrSlot;  // lsr.y, lsr.z, asfloat(path slot), -
+    float4 lsrSlot;  // lsr.y, lsr.z, asfloat(path slot), asfloat(kFinishEarly or 0)
 };
+// FinishRec::lsrSlot.w of a path finished at its last shaded bounce: its slot goes idle for the scan of
+// the NEXT iteration (kFlagIdleFrom), the one that follows the MATERIAL pass that would have ended it
+constexpr uint32_t kFinishEarly = 1u;
 // Destination of a shadow ray's result (carried in its record's direction.w): the
 // continuing path's extension-queue position, or its finish-queue position | kDestFinish
 constexpr uint32_t kDestFinish = 0x80000000u;

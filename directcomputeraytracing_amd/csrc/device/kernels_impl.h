@@ -326,6 +326,7 @@ __global__ __launch_bounds__(kControlBlock) void control_kernel(PathPool pool, F
 {
     __shared__ uint32_t sm[64];
     if (g->stopped) return;                    // RenderImages finished: nothing live, nothing to claim
+    const uint32_t epoch = epoch_of(cnt);      // (this iteration's: the previous end_iteration wrote it)
     {
         QueueMapN<kFinShards> fm;
         qmap(prev, kQFinish, &fm);
@@ -348,7 +349,9 @@ __global__ __launch_bounds__(kControlBlock) void control_kernel(PathPool pool, F
             // (debug RNG: MATERIAL stored it when it ended the path)
             // last, after stores that consumed the loads: another workgroup's scan may see the
             // slot idle from here on and start a new path in it
-            slot(pool.flags, path) = kFlagIdle;
+            // (a path finished at its last shaded bounce: idle from the next iteration's scan on,
+            // where MATERIAL's idle flag would have shown -- kFlagIdleFrom)
+            slot(pool.flags, path) = asu(fr.lsrSlot.w) == kFinishEarly ? idle_from(epoch + 1u) : kFlagIdle;
         }
     }
     const uint32_t lane = threadIdx.x & 63u;
@@ -390,7 +393,7 @@ __global__ __launch_bounds__(kControlBlock) void control_kernel(PathPool pool, F
     for (uint32_t base = blockIdx.x * blockDim.x; base < pool.size; base += gridDim.x * blockDim.x) {
     const uint32_t tid = base + threadIdx.x;
     const uint32_t vb = base / kControlBlock;
-    const bool idle = (pool.flags[tid] & kFlagIdle) != 0;
+    const bool idle = slot_idle(pool.flags[tid], epoch);
     // A fully idle wave claims the next 8x8 block (one atomic per workgroup); at a batch
     // start (all slots idle, cursors preset) wave j of the shard takes block j outright.
     const bool waveIdle = __ballot(!idle) == 0ull;
@@ -575,11 +578,17 @@ static_assert(DCRT_MATERIAL_BLOCK % 64 == 0 && DCRT_MATERIAL_BLOCK <= 960, "MATE
 // reads: `si`), instead of travelling through the shadow queue -- no 32-B record, no result word. Its
 // answer goes into the path's flags (kFlagShadowResolved) or, for a path that ends here, straight to
 // finHit at its finish-queue position. A ray with a non-finite 1/d component takes the queue as before.
+// Early finish (variants without mesh and environment lights, not PROBE, sc.earlyFinish != 0, no
+// ALLOW_ANYHIT_SHADER): a path that continues past the last shaded bounce is handed to CONTROL here, as a
+// path that ends with its shadow ray pending is, and its extension ray goes to the last-ray queue
+// (kLastRayWord) -- the pass that would only have completed it has no item.
 template <uint32_t CAPS, int SCENE_LDS, bool PROBE = false, bool FUSED = false>
 __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void material_kernel(PathPool pool, DeviceScene sc, const FrameConstants* __restrict__ fcr, Counters* cnt,
                                                                              const Counters* prev, const SampleOut* __restrict__ sampleOut, ShadowInline si)
 {
     static_assert(!FUSED || (SCENE_LDS == 1 && !PROBE), "FUSED: beside the whole LDS shading copy");
+    // EARLY: this variant may finish a path at its last shaded bounce (sc.earlyFinish says whether it does)
+    constexpr bool EARLY = caps_early_finish(CAPS) && !PROBE;
 #if defined(DCRT_MATERIAL_PRIO) && DCRT_MATERIAL_PRIO > 0
     __builtin_amdgcn_s_setprio(DCRT_MATERIAL_PRIO);   // (A/B: issue priority over a co-resident cast)
 #endif
@@ -660,6 +669,9 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
     DCRT_MCLK_INIT;
     uint32_t itemsDone = 0;
     uint32_t round = 0;   // grid-stride round: alternates block_append2's sm halves
+    // (EARLY) the flags word of a slot whose path this pass completes at its last shaded bounce (one scalar)
+    uint32_t doneFlag = kFlagIdle;
+    if constexpr (EARLY) doneFlag = (uint32_t)__builtin_amdgcn_readfirstlane((int)idle_from(epoch_of(cnt) + 2u));
     for (uint32_t base = blockIdx.x * blockDim.x; base < count; base += gridDim.x * blockDim.x) {
     const uint32_t i = base + threadIdx.x;
     bool active = i < count;
@@ -668,7 +680,7 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
         newPixel = slot(pool.pixel, i);
         active = newPixel != kNoPixel;
     }
-    bool terminate = false, hasShadow = false, ends = false;
+    bool terminate = false, hasShadow = false, ends = false, last = false;
     uint32_t path = 0, pix = 0;
     float4 sample = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float2* outPos = nullptr;
@@ -763,6 +775,16 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
             if (hasShadow) slot(pool.shadowOpacity, out) = shadowOpacity;
         }
         ends = terminate && !hasShadow;
+        // EARLY: the path continues, but its next bounce is past the last one shaded. The pass after
+        // that ray would add no radiance (this variant's scenes have no light a ray can reach) and
+        // only complete the path, which CONTROL does from a finish record; so the path finishes here,
+        // and its ray -- cast all the same -- takes the last-ray queue: no state, no hit record.
+        // (sc.earlyFinish 2, a test value: odd path slots go the long way, so a wave holds both routes.)
+        if constexpr (EARLY) {
+            const uint32_t mode = sc.earlyFinish;
+            last = !terminate && (flags & 0xFFu) > fcv.maxBounce && mode != 0u && (mode != 2u || (path & 1u) == 0u) &&
+                   (fcv.features & DCRT_FEATURE_ALLOW_ANYHIT) == 0u;
+        }
         // the row-cost probe (PROBE: the variant dcrt_tracer_set_row_cost_probe launches): the rays
         // of this pass per film row -- the extension ray this item shades and the shadow ray it
         // casts -- for cost-balanced film bands (partition.balanced_bands)
@@ -779,7 +801,7 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
         sL = L;
         sLsr = lsr;
         sRng = make_uint4(rng.s0, rng.s1, rng.s2, rng.s3);
-        if (ends || terminate) {
+        if (ends || terminate || last) {
             // The path ends here with no shadow ray pending: all CONTROL would still do is
             // Li += light sampling result (0: the same bits as L + 0.0f) and WriteSample
             // (RayTracingCommon.inc.hlsl:118-122), so both happen in this pass and the slot
@@ -788,8 +810,10 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
             // The pixel is loaded here and the sample stored after the queue appends, whose
             // atomic round trip hides the load.
             const SampleOut so = *sampleOut;
-            if (ends || so.debugRng) pix = slot(pool.pixel, out);
-            if (ends) {
+            if (ends || last || so.debugRng) pix = slot(pool.pixel, out);
+            if (ends || last) {
+                // (a path finished at its last shaded bounce: the sample of the pass that would have ended
+                // it, should this pass turn out to know its shadow ray's result -- `done` below)
                 sample = make_float4(L.x + 0.0f, L.y + 0.0f, L.z + 0.0f, 0.0f);
                 // the sample pointers are read here too, not after the appends: read there
                 // (behind the barriers and the atomic) they were one more round trip
@@ -814,11 +838,34 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
     DCRT_MCLK(5);
     uint32_t es, ss;
     // (paths ended with a shadow ray pending: the next CONTROL pass completes them)
-    const bool fin = active && terminate && hasShadow;
+    // A path finished at its last shaded bounce whose shadow ray's result is known here (tested above, or
+    // none cast) is complete: the pass that would have ended it computes (Li + lsr unless occluded) + 0 and
+    // writes that sample, so this pass does, and no list holds the path. One whose shadow ray took the
+    // queue goes to the finish queue, as a path that ends with its shadow ray pending does.
+    const bool done = last && (!hasShadow || inlined);
+    if (done) {
+        sample.x = (sL.x + (!occluded ? sLsr.x : 0.0f)) + 0.0f;
+        sample.y = (sL.y + (!occluded ? sLsr.y : 0.0f)) + 0.0f;
+        sample.z = (sL.z + (!occluded ? sLsr.z : 0.0f)) + 0.0f;
+    }
+    const bool fin = active && ((terminate && hasShadow) || (last && !done));
     uint32_t fb;
-    block_append3(active && !terminate, qctr(cnt, kQExt, shard), queued, qctr(cnt, kQShadow, shard),
+    // The last rays' positions: one atomic per wave that has some (with the count of the paths completed
+    // here in its upper half), issued ahead of the workgroup's three so that all four round trips overlap
+    // (such waves come in one iteration of a batch's maxBounce + 2, and the append's LDS words stay as they are)
+    uint32_t lastBase = 0u, lastRank = 0u;
+    if constexpr (EARLY) {
+        const unsigned long long lm = __ballot(last);
+        if (lm != 0ull) {
+            lastRank = __builtin_amdgcn_mbcnt_hi((uint32_t)(lm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lm, 0u));
+            const unsigned long long both = (unsigned long long)__popcll(lm) | ((unsigned long long)__popcll(__ballot(done)) << 32);
+            if ((threadIdx.x & 63u) == 0u) lastBase = (uint32_t)atomicAdd(last_ctr(cnt, shard), both);
+        }
+    }
+    block_append3(active && !terminate && !last, qctr(cnt, kQExt, shard), queued, qctr(cnt, kQShadow, shard),
                   fin, qctr(cnt, kQFinish, fshard), sm + (round & 1u) * 48u, &es, &ss, &fb);
     DCRT_MCLK(6);
+    if constexpr (EARLY) lastBase = (uint32_t)__builtin_amdgcn_readfirstlane((int)lastBase);
     const uint32_t qNext = shard * pool.recCap + es;           // the continuing path's records
     const uint32_t fPos = fshard * pool.finCap + fb;           // a finishing path's record
     // An ended path's sample (and its slot's idle flag) is stored before the records: its
@@ -827,12 +874,20 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
     // asm takes the pixel in every wave (whether or not one of its paths ended), so that wait
     // is placed here, ahead of every store, and not where the pixel's register is next reused.
     asm volatile("" ::"v"(pix));
-    if (ends) {
+    if (ends || done) {
         store_global(outPos, pix, pixel_sample(fcv, pix));
         store_global(outVal, pix, sample);
-        slot(pool.flags, path) = kFlagIdle;
+        // (done: idle for the scans from the iteration after next on, as after the pass that would have
+        // ended the path -- kFlagIdleFrom)
+        slot(pool.flags, path) = done ? doneFlag : kFlagIdle;
     }
-    if (active && !terminate) {
+    if (last) {
+        // the last ray's record alone, from the end of the shard's records downwards
+        float4* r = ext_rec(pool.extRec, shard * pool.recCap + (pool.recCap - 1u - (lastBase + lastRank)));
+        r[0] = make_float4(nO.x, nO.y, nO.z, 0.0f);
+        r[1] = make_float4(nD.x, nD.y, nD.z, asf(path));
+    }
+    if (active && !terminate && !last) {
         float4* r = ext_rec(pool.extRec, qNext);
         r[0] = make_float4(nO.x, nO.y, nO.z, 0.0f);
         r[1] = make_float4(nD.x, nD.y, nD.z, asf(path));
@@ -846,7 +901,7 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
     if (fin) {
         FinishRec& fr = pool.finRec[fPos];
         fr.liLsr = make_float4(sL.x, sL.y, sL.z, sLsr.x);
-        fr.lsrSlot = make_float4(sLsr.y, sLsr.z, asf(path), 0.0f);
+        fr.lsrSlot = make_float4(sLsr.y, sLsr.z, asf(path), asf(last ? kFinishEarly : 0u));
         // (the result CONTROL reads beside it: the cast writes a queued ray's)
         if (inlined) pool.finHit[fPos] = occluded ? 1u : 0u;
     }
@@ -856,7 +911,7 @@ __global__ __launch_bounds__(DCRT_MATERIAL_BLOCK) DCRT_MATERIAL_OCCUPANCY void m
         r[0] = sO;
         // where the shadow cast writes the result: the continuing path's next state, or its
         // finish record
-        r[1] = make_float4(sD.x, sD.y, sD.z, asf(terminate ? (fPos | kDestFinish) : qNext));
+        r[1] = make_float4(sD.x, sD.y, sD.z, asf(terminate || last ? (fPos | kDestFinish) : qNext));
         // the path slot beside it: only ALLOW_ANYHIT_SHADER's cast reads it (the shadow ray's
         // opacity sample is per slot)
         if (fcv.features & DCRT_FEATURE_ALLOW_ANYHIT) slot(pool.shadowQueue, sq) = path;
@@ -932,6 +987,7 @@ __device__ uint32_t g_waveItems[2][16][8192];
 
 
 constexpr uint32_t kNoItem = 0xFFFFFFFFu;   // a fetch's "no ray for this item"
+constexpr uint32_t kLastItem = 0xFFFFFFFEu;   // a closest-hit fetch's "a last ray: traced, no result wanted" (kLastRayWord)
 #ifndef DCRT_INLINE_ENTRY
 #define DCRT_INLINE_ENTRY 1   // identity-instance BLAS entries in phase A (trav_visit ENTER)
 #endif
@@ -1165,18 +1221,20 @@ __global__ __launch_bounds__(256) DCRT_CAST_OCCUPANCY void extension_kernel(Path
     scene_cache_load(sc, stackMem, block_shift());
     QueueMap qm;
     qmap(cnt, kQExt, &qm);
+    const uint32_t nExt = qm.prefix[kShards];
     TraversalStats st = {};
+    // (the last rays behind the extension queue's: traced alike, nothing written for them)
     persistent_trace<false, INSTR, OPACITY>(
-        sc, qm.prefix[kShards], fc->features, fc->refillLanes, fc->parkLanes, stackMem + threadIdx.x, block_shift(),
-        [&](uint32_t i) __attribute__((always_inline)) { return qpos(pool.recCap, qm, i); },
+        sc, nExt + last_total(cnt), fc->features, fc->refillLanes, fc->parkLanes, stackMem + threadIdx.x, block_shift(),
+        [&](uint32_t i) __attribute__((always_inline)) { return i >= nExt ? last_pos(cnt, pool.recCap, i - nExt) : qpos(pool.recCap, qm, i); },
         [&](uint32_t i, uint32_t q, TravState& s) __attribute__((always_inline)) {
             const float4* r = ext_rec((const float4*)pool.extRec, q);
             const float4 o = r[0], d = r[1];
             trav_init(s, mk(o.x, o.y, o.z), mk(d.x, d.y, d.z), 0.0f, inf());
             if (OPACITY) s.opacitySample = pool.extOpacity[asu(d.w) & ~kEntryFirst];
-            return i;   // the result goes to the ray's queue item
+            return i >= nExt ? kLastItem : i;   // the result goes to the ray's queue item
         },
-        [&](uint32_t item, const TravState& s) __attribute__((always_inline)) { emit_hit(pool, item, s); },
+        [&](uint32_t item, const TravState& s) __attribute__((always_inline)) { if (item != kLastItem) emit_hit(pool, item, s); },
         st, DCRT_WAVE_TAG(g));
     if (INSTR) flush_stats(st, instr);
     (void)g;
@@ -1187,12 +1245,25 @@ __device__ __forceinline__ void end_iteration(const Counters* cnt, Counters* nex
 {
     if (blockIdx.x == 0) {
         if (threadIdx.x == 0) {
+#if defined(__HIP_DEVICE_COMPILE__)
+            // (the counters through a pointer the compiler takes as new here: their scalar loads stay in this
+            // block, not hoisted to the kernel's entry and held -- spilled -- across the whole traversal loop)
+            asm volatile("" : "+s"(cnt));
+#endif
             uint32_t fin = 0;
             for (uint32_t sh = 0; sh < kFinShards; ++sh) fin += qctr_load(cnt, kQFinish, sh);
             // (a virtual batch start's items: its cast counted the rays, holes excluded)
             const uint32_t virt = virtual_items(cnt);
-            const uint32_t ext = virt ? virt : qtotal(cnt, kQExt);
+            // (the last rays are extension rays like the queue's; their paths are in the finish list)
+            // (`completed`: those whose paths MATERIAL completed itself -- in no list, live until the pass that
+            // would have ended them)
+            uint32_t lastRays, completed;
+            last_totals(cnt, &lastRays, &completed);
+            const uint32_t queued = virt ? virt : qtotal(cnt, kQExt);
+            const uint32_t ext = queued + lastRays;
             if (!virt) g->extRays += ext;
+            g->earlyFinished += lastRays;
+            nextCnt->w[kEpochLine * kShardStride] = epoch_of(cnt) + 1u;
             // (with the rays MATERIAL's FUSED variant tested itself: they are in no queue)
             g->shadowRays += shadowRays + inline_shadow_rays(cnt);
             g->iterations += 1ull;
@@ -1203,9 +1274,10 @@ __device__ __forceinline__ void end_iteration(const Counters* cnt, Counters* nex
             const bool idle = g->prevLive == 0u && ext == 0u;
             g->poolIdle = idle ? 1u : 0u;
             g->imageComplete = (idle && !g->stopped) ? 1u : 0u;
-            g->prevLive = ext + fin;
+            g->prevLive = queued + fin + completed;   // (each live path once: the extension queue's, the finish list's, ...)
         }
-        if (threadIdx.x < kCounterLines) nextCnt->w[threadIdx.x * kShardStride] = 0u;   // (with kVirtual/kDrainedWord, kInlineShadowWord)
+        if (threadIdx.x < kCounterLines) nextCnt->w[threadIdx.x * kShardStride] = 0u;   // (with kVirtual/kDrainedWord, kInlineShadowWord, kLastRayWord)
+        if (threadIdx.x < kShards) nextCnt->w[(kLastRayWord + threadIdx.x) * kShardStride + 1u] = 0u;   // (the last-ray lines' second words)
     }
 }
 
@@ -1271,7 +1343,8 @@ __attribute__((amdgpu_waves_per_eu(ALL_CACHED && !OPACITY && !INSTR ? (IDENT ? D
     QueueMap qe, qs;
     qmap(cnt, kQExt, &qe);
     qmap(cnt, kQShadow, &qs);
-    const uint32_t nExt = qe.prefix[kShards], nShadow = qs.prefix[kShards];
+    // (the last rays, kLastRayWord: closest-hit items between the two queues' that emit nothing; nClosest: both)
+    const uint32_t nExt = qe.prefix[kShards], nShadow = qs.prefix[kShards], nClosest = nExt + last_total(cnt);
     const uint32_t* shQueue = sgpr_ptr(pool.shadowQueue);
     const float4* extRec = sgpr_ptr((const float4*)pool.extRec);
     const float4* shRec = sgpr_ptr((const float4*)pool.shRec);
@@ -1330,28 +1403,29 @@ __attribute__((amdgpu_waves_per_eu(ALL_CACHED && !OPACITY && !INSTR ? (IDENT ? D
 #endif
         if (!DCRT_CELLS_LAST) shadowSection();
         persistent_trace<false, INSTR, OPACITY, false, ALL_CACHED, PAIR, kLayout, IDENT, RING, FLAT>(
-            sc, nExt, fc->features, fc->refillLanes, fc->parkLanes, stackMem + threadIdx.x, block_shift(),
-            [&](uint32_t i) __attribute__((always_inline)) { return qpos(pool.recCap, qe, i); },
+            sc, nClosest, fc->features, fc->refillLanes, fc->parkLanes, stackMem + threadIdx.x, block_shift(),
+            [&](uint32_t i) __attribute__((always_inline)) { return i >= nExt ? last_pos(cnt, pool.recCap, i - nExt) : qpos(pool.recCap, qe, i); },
             [&](uint32_t i, uint32_t v, TravState& s) __attribute__((always_inline)) {
                 const float4* r = ext_rec(extRec, v);
                 const float4 o = r[0], d = r[1];
                 trav_init(s, mk(o.x, o.y, o.z), mk(d.x, d.y, d.z), 0.0f, inf());
-                return i;   // the result goes to the ray's queue item
+                return i >= nExt ? kLastItem : i;   // the result goes to the ray's queue item; a last ray's nowhere
             },
-            [&](uint32_t item, const TravState& s) __attribute__((always_inline)) { emit_hit(pool, item, s); },
+            [&](uint32_t item, const TravState& s) __attribute__((always_inline)) { if (item != kLastItem) emit_hit(pool, item, s); },
             st, DCRT_WAVE_TAG(g));
         if (DCRT_CELLS_LAST) shadowSection();
     } else {
     // (node order: the pair kernels run on pair-ordered scenes, the other non-counting ones on
     // PackBVH-ordered ones -- tracer.hip's cast plan takes both from `pair` -- the counting ones on either)
     persistent_trace<false, INSTR, OPACITY, true, ALL_CACHED, PAIR, kLayout, IDENT, RING, FLAT>(
-        sc, nExt + nShadow, fc->features, fc->refillLanes, fc->parkLanes, stackMem + threadIdx.x, block_shift(),
+        sc, nClosest + nShadow, fc->features, fc->refillLanes, fc->parkLanes, stackMem + threadIdx.x, block_shift(),
         [&](uint32_t i) __attribute__((always_inline)) {
-            // either kind: its record's position in its queue (no load)
-            return i >= nExt ? qpos(pool.recCap, qs, i - nExt) : qpos(pool.recCap, qe, i);
+            // any kind: its record's position in its queue (no load)
+            if (i >= nClosest) return qpos(pool.recCap, qs, i - nClosest);
+            return i >= nExt ? last_pos(cnt, pool.recCap, i - nExt) : qpos(pool.recCap, qe, i);
         },
         [&](uint32_t i, uint32_t v, TravState& s) __attribute__((always_inline)) {
-            const bool shadow = i >= nExt;
+            const bool shadow = i >= nClosest;
             // the ray's 32-B record at its queue position v (32-bit byte offsets: the records
             // stay below 4 GiB, dcrt_tracer::Create); a shadow ray's path slot beside it
             const float4* r = ext_rec(shadow ? shRec : extRec, v);
@@ -1364,12 +1438,12 @@ __attribute__((amdgpu_waves_per_eu(ALL_CACHED && !OPACITY && !INSTR ? (IDENT ? D
             }
             if (INSTR) st = TraversalStats{};
             // an extension ray's result goes to its queue item, a shadow ray's to the
-            // destination MATERIAL put in its record
-            return shadow ? asu(d.w) : i;
+            // destination MATERIAL put in its record, a last ray's nowhere
+            return shadow ? asu(d.w) : (i >= nExt ? kLastItem : i);
         },
         [&](uint32_t item, const TravState& s) __attribute__((always_inline)) {
             if (s.anyHit) emit_occlusion(pool, item, s);
-            else emit_hit(pool, item, s);
+            else if (item != kLastItem) emit_hit(pool, item, s);
             if (INSTR) {
                 TraversalStats& dst = s.anyHit ? stShadow : stExt;
                 dst.nodes += st.nodes; dst.tris += st.tris; dst.blas += st.blas;
@@ -1656,7 +1730,11 @@ __global__ __launch_bounds__(256) void drain_kernel(PathPool pool, DeviceScene s
     QueueMapN<kFinShards> fm;
     qmap(cnt, kQFinish, &fm);
     const uint32_t nExt = qe.prefix[kShards], nFin = fm.prefix[kFinShards];
-    if (nExt + nFin == 0u || nExt + nFin > fc.drainPaths) return;
+    // (live all the same: the paths MATERIAL completed at their last shaded bounce, whose last rays this
+    // iteration's cast traced -- nothing is left to do for them)
+    uint32_t lastRays, completed;
+    last_totals(cnt, &lastRays, &completed);
+    if (nExt + nFin + completed == 0u || nExt + nFin + completed > fc.drainPaths) return;
     for (uint32_t sh = 0; sh < kShards; ++sh) {   // a block still to claim: new paths will follow
         const uint32_t blocks = g->totalBlocks > sh ? (g->totalBlocks - sh + kShards - 1) / kShards : 0u;
         if (__hip_atomic_load(&g->nextBlock[sh * kShardStride], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < blocks) return;

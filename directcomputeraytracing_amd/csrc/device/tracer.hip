@@ -295,6 +295,10 @@ struct ShadingKnobs {
     // DCRT_SHADING_TABLES: scene-constant shading work done at upload instead of per hit, one bit
     // each (kTableDeltaPdf, kTableDielRows of dscene.h); 0: every hit does it itself.
     uint32_t shadingTables = kTableAll;
+    // DCRT_EARLY_FINISH: a MATERIAL variant without mesh and environment lights finishes a path at its last
+    // shaded bounce (material_kernel's EARLY); 0: every path takes the pass that only completes it. 2 (tests):
+    // on for the even path slots alone, so a wave mixes both routes.
+    uint32_t earlyFinish = 1;
 };
 ShadingKnobs ReadShadingKnobs()
 {
@@ -304,6 +308,7 @@ ShadingKnobs ReadShadingKnobs()
     k.materialLdsPartial = EnvFlag("DCRT_MATERIAL_LDS_PARTIAL", true);
     k.fusedShadow = (uint32_t)std::max(0, EnvInt("DCRT_FUSED_SHADOW", (int)k.fusedShadow));
     k.shadingTables = (uint32_t)std::max(0, EnvInt("DCRT_SHADING_TABLES", (int)k.shadingTables)) & kTableAll;
+    k.earlyFinish = (uint32_t)std::max(0, std::min(2, EnvInt("DCRT_EARLY_FINISH", (int)k.earlyFinish)));
     return k;
 }
 
@@ -405,6 +410,11 @@ struct MaterialPlan {
     const float* envMarginal = nullptr;
     uint32_t fusedMask = 0;            // DCRT_FUSED_SHADOW's path-slot mask (FrameConstants::shadowInlineMask: not baked into a graph)
     uint32_t drainGrid = 0;            // drain_kernel's grid: resident workgroups on the whole chip
+    // DCRT_EARLY_FINISH as it stands for the variant: 0 unless its CAPS admit it (caps_early_finish). The same
+    // kernel, grid and LDS either way: a scalar the kernel reads (DeviceScene::earlyFinish).
+    uint32_t earlyFinish = 0;
+    // ... and for a launch: not the probe's variant, not with ALLOW_ANYHIT_SHADER (material_kernel tests both itself)
+    uint32_t EarlyFinish(bool probe, bool opacity) const { return probe || opacity ? 0u : earlyFinish; }
 
     // The one table from variant to compiled kernel. probe: the row-cost probe's variant (no LDS copy)
     MaterialFn Kernel(bool probe, bool fused) const
@@ -452,13 +462,14 @@ struct MaterialPlan {
         d->envProb = envProb;
         d->envRowCdf = envRowCdf;
         d->envMarginal = envMarginal;
+        d->earlyFinish = earlyFinish;
     }
     // What a captured graph bakes in: kernels, LDS bytes, the drain grid, what Apply writes (the pointers follow the bits)
     bool BakedEquals(const MaterialPlan& o) const
     {
         return caps == o.caps && mode == o.mode && materials == o.materials && lights == o.lights && lds.shading == o.lds.shading &&
                lds.rows == o.lds.rows && lds.frames == o.lds.frames && lds.cells == o.lds.cells && tables == o.tables && drainGrid == o.drainGrid &&
-               envProb == o.envProb && envRowCdf == o.envRowCdf && envMarginal == o.envMarginal;
+               envProb == o.envProb && envRowCdf == o.envRowCdf && envMarginal == o.envMarginal && earlyFinish == o.earlyFinish;
     }
 };
 
@@ -1057,6 +1068,7 @@ int dcrt_tracer::PlanMaterial(const MaterialPlan* before, MaterialPlan* out)
         CHECKED(grow(layout(p.lds.rows ? M : 0u, true, p.lds.cells != 0u), &taken));
         if (!taken) p.tables &= ~kTableFrames;
     }
+    p.earlyFinish = caps_early_finish(p.caps) ? k.earlyFinish : 0u;
     p.dielRows = (p.tables & kTableDielRows) ? dDielRows : nullptr;
     p.triFrames = (p.tables & kTableFrames) ? dTriFrames : nullptr;
     // drain_kernel's grid: resident workgroups of the variant's drain kernel, launched like the casts
@@ -3321,6 +3333,7 @@ DCRT_API int dcrt_tracer_counters(dcrt_tracer* t, dcrt_ray_stats* out)
     out->new_paths = t->imagesCompleted * (uint64_t)t->rowCount * t->filmW - t->pathsSkipped;
     out->iterations = g.iterations;
     out->images_completed = t->imagesCompleted;
+    out->early_finished = g.earlyFinished;
     return DCRT_OK;
 }
 
@@ -3364,6 +3377,7 @@ DCRT_API int dcrt_tracer_get_info(dcrt_tracer* t, dcrt_tracer_info* out)
     out->dielectric_row_bytes = t->hasScene && (t->material.tables & kTableDielRows) ? diel_rows_bytes((uint32_t)t->hostMaterials.size()) : 0u;
     out->dielectric_row_lds = t->hasScene ? t->material.lds.rows : 0u;
     out->frame_table_bytes = t->hasScene ? t->material.lds.frames : 0u;
+    out->early_finish = t->hasScene ? t->material.EarlyFinish(t->rowProbe, (t->frame.features & DCRT_FEATURE_ALLOW_ANYHIT) != 0) : 0u;
     return DCRT_OK;
 }
 
@@ -3410,7 +3424,7 @@ DCRT_API int dcrt_tracer_reset_stats(dcrt_tracer* t)
     Globals g;
     HIPCHECK(hipMemcpyAsync(&g, t->dGlobals, sizeof(Globals), hipMemcpyDeviceToHost, t->stream));
     HIPCHECK(hipStreamSynchronize(t->stream));
-    g.extRays = g.shadowRays = g.iterations = 0;
+    g.extRays = g.shadowRays = g.iterations = g.earlyFinished = 0;
     t->imagesCompleted = 0;
     t->pathsSkipped = 0;
     HIPCHECK(hipMemcpyAsync(t->dGlobals, &g, sizeof(Globals), hipMemcpyHostToDevice, t->stream));

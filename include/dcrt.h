@@ -252,6 +252,8 @@ typedef struct dcrt_ray_stats {
                                      rendered pixel, halo rows included, per image)   */
     uint64_t iterations;          /* RenderOneIteration equivalents launched          */
     uint64_t images_completed;    /* images finished by render / render_images        */
+    uint64_t early_finished;      /* paths finished at their last shaded bounce (dcrt_tracer_info.early_finish):
+                                     each cast one more extension ray, counted above, that no pass shaded */
 } dcrt_ray_stats;
 
 /* Rows of the film a tracer renders and convolves (multi-GPU film tiling).
@@ -323,6 +325,10 @@ typedef struct dcrt_tracer_info {
                                      tangent, geometry normal -- that MATERIAL reads per hit instead of rebuilding them
                                      (bit 4 of shading_tables): scenes of the opaque, delta-lit MATERIAL variant whose every
                                      BLAS has one instance and whose whole shading data sits in MATERIAL's LDS */
+    uint32_t early_finish;        /* DCRT_EARLY_FINISH as the next launch stands: 1 (2: even path slots only, a test
+                                     value): MATERIAL finishes a path at its last shaded bounce -- its last ray is
+                                     cast and counted, no pass shades its hit, its sample is the same bits; 0: off
+                                     (the knob, a mesh or environment light, any-hit, the row-cost probe) */
 } dcrt_tracer_info;
 
 typedef struct dcrt_tracer dcrt_tracer;
@@ -332,12 +338,13 @@ typedef struct dcrt_scene dcrt_scene;
 /* ABI version of this header: bumped whenever a struct changes size or an entry point its
  * meaning (2: dcrt_tracer_info grew cast_waves_per_cu / ring_rows / stack_lds_rows; 3: it grew
  * shadow_cells / shadow_cell_max_leaves / shadow_cell_mean_leaves; 4: shadow_inline; 5: shading_tables /
- * dielectric_row_bytes / dielectric_row_lds / frame_table_bytes). A caller
+ * dielectric_row_bytes / dielectric_row_lds / frame_table_bytes; 6: early_finish, and dcrt_ray_stats grew
+ * early_finished). A caller
  * compiled against another header checks dcrt_abi_version() == DCRT_ABI_VERSION before it
  * passes any struct (a smaller dcrt_tracer_info would be written past its end). Added entry
  * points with structs of their own (the scene updates, the output views, the film denoiser)
  * leave it as it is: nothing an older caller passes has changed. */
-#define DCRT_ABI_VERSION 5
+#define DCRT_ABI_VERSION 6
 DCRT_API int dcrt_abi_version(void);
 DCRT_API const char* dcrt_version(void);
 DCRT_API const char* dcrt_last_error(void);
