@@ -25,6 +25,8 @@ FEATURE_LIGHT_VISIBLE = 0x04
 FEATURE_WATERTIGHT = 0x08
 FEATURE_ALLOW_ANYHIT = 0x10
 FEATURE_DEFAULT = FEATURE_GGX_SAMPLE_VNDF | FEATURE_LIGHT_VISIBLE | FEATURE_WATERTIGHT
+# dcrt_tracer_cast_rays' out_variant (DCRT_CAST_VARIANT_*)
+CAST_VARIANT = {"opacity": 0x01, "all_cached": 0x02, "pair": 0x04, "ident": 0x08, "ring": 0x10, "flat": 0x20}
 FILTER_BOX, FILTER_TRIANGLE, FILTER_GAUSSIAN, FILTER_MITCHELL, FILTER_LANCZOS = range(5)
 MATERIAL_DIFFUSE, MATERIAL_PLASTIC, MATERIAL_CONDUCTOR, MATERIAL_DIELECTRIC, MATERIAL_THIN_DIELECTRIC = range(5)
 MAX_LIGHT_COUNT = 5000
@@ -330,6 +332,8 @@ SIGNATURES = [
     ("dcrt_tracer_set_luts", _I, [_P, C.POINTER(BxDFLuts)]),
     ("dcrt_tracer_trace_rays", _I, [_P, C.POINTER(Ray), _U, C.POINTER(RayHit), _U]),
     ("dcrt_tracer_occluded", _I, [_P, C.POINTER(Ray), _U, C.POINTER(C.c_uint32), _U]),
+    ("dcrt_tracer_cast_rays", _I, [_P, C.POINTER(Ray), C.POINTER(C.c_uint32), _FP, _U, _U, C.POINTER(RayHit), C.POINTER(C.c_uint32),
+                                   C.POINTER(C.c_uint32)]),
     ("dcrt_tracer_trace_rays_device", _I, [_P, _P, _U, _P, _U]),
     ("dcrt_tracer_trace_occlusion_cells", _I, [_P, C.POINTER(Ray), _U, C.POINTER(C.c_uint32), _U]),
     ("dcrt_shadow_cells_build", _I, [C.POINTER(FlatScene), _U, C.POINTER(ShadowCellsInfo), C.POINTER(C.c_uint64),

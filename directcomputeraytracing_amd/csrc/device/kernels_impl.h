@@ -1876,6 +1876,43 @@ __global__ __launch_bounds__(256) void batch_trace_kernel(DeviceScene sc, const 
     if (INSTR) flush_stats(st, instr);
 }
 
+// cast_kernel's merged section over a caller's ray batch (tests: dcrt_tracer_cast_rays): the same persistent_trace
+// instantiation (LANE_ANY, the variant's template arguments, its kLayout, its occupancy target), launched on the
+// scene copy, LDS bytes and block of the cast plan's launch. kinds[i] != 0: a shadow ray (first hit below its
+// t_max); else an extension ray (closest hit, infinite t_max). OPACITY: ray i carries opacity[i].
+template <bool OPACITY, bool ALL_CACHED, bool PAIR, bool IDENT, bool RING, bool FLAT>
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(ALL_CACHED && !OPACITY ? (IDENT ? DCRT_IDENT_CAST_WAVES_PER_EU : DCRT_CACHED_CAST_WAVES_PER_EU)
+                                   : (!ALL_CACHED && !PAIR && !OPACITY ? DCRT_GLOBAL_CAST_WAVES_PER_EU : DCRT_CAST_WAVES_PER_EU), 8)))
+void cast_rays_kernel(DeviceScene sc, const dcrt_ray* rays, const uint32_t* kinds, const float* opacity, uint32_t n, uint32_t features,
+                      uint32_t refillLanes, uint32_t parkLanes, dcrt_ray_hit* hits, uint32_t* occluded)
+{
+    extern __shared__ uint32_t stackMem[];
+    scene_cache_load<ALL_CACHED>(sc, stackMem, block_shift());
+    constexpr int kLayout = PAIR ? kLayoutPairs : kLayoutFlat;   // (cast_kernel's rule for its non-counting variants)
+    TraversalStats st = {};
+    persistent_trace<false, false, OPACITY, true, ALL_CACHED, PAIR, kLayout, IDENT, RING, FLAT>(
+        sc, n, features, refillLanes, parkLanes, stackMem + threadIdx.x, block_shift(),
+        [&](uint32_t i) __attribute__((always_inline)) { return i; },
+        [&](uint32_t i, uint32_t, TravState& s) __attribute__((always_inline)) {
+            const dcrt_ray r = rays[i];
+            const bool shadow = kinds[i] != 0u;
+            trav_init(s, ld3(r.origin), ld3(r.direction), 0.0f, shadow ? r.t_max : inf());
+            s.anyHit = shadow;
+            if (OPACITY) s.opacitySample = opacity[i];
+            return i;
+        },
+        [&](uint32_t i, const TravState& s) __attribute__((always_inline)) {
+            const bool rec = s.found && !s.anyHit;
+            dcrt_ray_hit o;
+            o.t = rec ? s.hit.t : inf(); o.u = rec ? s.hit.u : 0.0f; o.v = rec ? s.hit.v : 0.0f;
+            o.triangle_id = rec ? s.hit.tri : 0u; o.instance_index = rec ? s.hit.inst : 0u;
+            hits[i] = o;
+            occluded[i] = s.anyHit && s.found ? 1u : 0u;
+        },
+        st);
+}
+
 // The merged cast's streaming shadow section over a caller's ray batch (tests): cast_kernel<..., CELLS>'s
 // LDS layout and device function, one ray per lane
 __global__ __launch_bounds__(256) void cells_occlusion_kernel(DeviceScene sc, const dcrt_ray* rays, uint32_t n, uint32_t features,

@@ -167,7 +167,22 @@ using CastFn = void (*)(PathPool, DeviceScene, const FrameConstants*, Counters*,
 // combination is compiled; the fall-back drops, in this order, what the others rule out: FLAT is
 // the cache-only IDENT kernel, CELLS goes with FLAT; RING, the counting and the any-hit kernels
 // keep PackBVH's or the pair order; IDENT has no any-hit kernel and no pair kernel but the ring's.
-CastFn CastKernel(const CastVariant& want)
+// ... and that variant's traversal over a caller's ray batch (cast_rays_kernel: dcrt_tracer_cast_rays); the
+// counting and the CELLS rows have none.
+using CastRaysFn = void (*)(DeviceScene, const dcrt_ray*, const uint32_t*, const float*, uint32_t, uint32_t, uint32_t, uint32_t, dcrt_ray_hit*,
+                            uint32_t*);
+template <bool INSTR, bool OPACITY, bool ALL_CACHED, bool PAIR, bool IDENT, bool RING, bool FLAT, bool CELLS>
+constexpr CastRaysFn CastRaysOf()
+{
+    if constexpr (INSTR || CELLS) return nullptr;
+    else return cast_rays_kernel<OPACITY, ALL_CACHED, PAIR, IDENT, RING, FLAT>;
+}
+struct CastRow {
+    CastVariant v;
+    CastFn fn;
+    CastRaysFn rays;
+};
+const CastRow* CastTableRow(const CastVariant& want)
 {
     CastVariant v = want;
     v.flat = v.flat && v.ident && v.allCached && !v.opacity && !v.instr && !v.ring;
@@ -181,16 +196,20 @@ CastFn CastKernel(const CastVariant& want)
         v.ident = v.ident && !v.opacity && (v.allCached || v.instr || !v.pair);
         v.pair = v.pair && !v.ident && !v.instr && !v.allCached;
     }
-    struct Row { CastVariant v; CastFn fn; };
-#define DCRT_CAST_ROW(...) { { __VA_ARGS__ }, cast_kernel<__VA_ARGS__> },
-    static const Row table[] = { DCRT_CAST_VARIANTS(DCRT_CAST_ROW) };
+#define DCRT_CAST_ROW(...) { { __VA_ARGS__ }, cast_kernel<__VA_ARGS__>, CastRaysOf<__VA_ARGS__>() },
+    static const CastRow table[] = { DCRT_CAST_VARIANTS(DCRT_CAST_ROW) };
 #undef DCRT_CAST_ROW
-    for (const Row& r : table) {
+    for (const CastRow& r : table) {
         if (r.v.instr == v.instr && r.v.opacity == v.opacity && r.v.allCached == v.allCached && r.v.pair == v.pair &&
             r.v.ident == v.ident && r.v.ring == v.ring && r.v.flat == v.flat && r.v.cells == v.cells)
-            return r.fn;
+            return &r;
     }
     return nullptr;   // (no input gets here: the fall-back above ends on a compiled variant)
+}
+CastFn CastKernel(const CastVariant& want)
+{
+    const CastRow* r = CastTableRow(want);
+    return r ? r->fn : nullptr;
 }
 
 // ---- DCRT_* knobs: one reader per moment they are read at, one struct each -- the list of knobs,
@@ -347,6 +366,7 @@ struct CastLaunch {
     size_t lds;                        // dynamic LDS bytes
     const DeviceScene& scene;
     uint32_t resident;                 // persistent grid: resident workgroups on the whole chip
+    CastVariant asked;                 // what the plan asks CastKernel for (dcrt_tracer_cast_rays picks the ray-batch twin by it)
 };
 
 // How the uploaded scene is cast (PlanCast, SizeGrids): the one place that says which cast_kernel
@@ -382,7 +402,7 @@ struct CastPlan {
         const bool useFlat = flat && !instr && !opacity, useRing = ringRows != 0 && !instr && !opacity;
         const CastVariant v{ instr, opacity, allCached, pair, ident, useRing, useFlat, Cells(instr, opacity) };
         return { CastKernel(v), useFlat ? ldsFlat : useRing ? ldsRing : ldsWholeStack, useFlat ? sceneFlat : useRing ? sceneRing : scene,
-                 resident[instr][opacity] };
+                 resident[instr][opacity], v };
     }
 };
 
@@ -3511,6 +3531,51 @@ DCRT_API int dcrt_tracer_occluded(dcrt_tracer* t, const dcrt_ray* rays, uint32_t
     if (hipMemcpyAsync(dr, rays, (size_t)n * sizeof(dcrt_ray), hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
     if (rc == DCRT_OK) rc = TraceBatch(t, dr, n, nullptr, dOcc, true, features);
     if (rc == DCRT_OK && hipMemcpyAsync(out, dOcc, (size_t)n * 4, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    FreeAll(&tmp);
+    return rc;
+}
+
+DCRT_API int dcrt_tracer_cast_rays(dcrt_tracer* t, const dcrt_ray* rays, const uint32_t* kinds, const float* opacity_samples, uint32_t n,
+                                   uint32_t features, dcrt_ray_hit* out_hits, uint32_t* out_occluded, uint32_t* out_variant)
+{
+    TRACER_GUARD(t);
+    const bool opacity = (features & DCRT_FEATURE_ALLOW_ANYHIT) != 0;
+    if (!out_variant || ((!rays || !kinds || !out_hits || !out_occluded || (opacity && !opacity_samples)) && n)) return DCRT_E_INVALID_ARG;
+    if (!t->hasScene) { SetLastError("no scene uploaded"); return DCRT_E_NO_SCENE; }
+    // the launch a render of this scene with these features would make, and the ray-batch twin of its kernel
+    // (the CELLS cast's shadow section has its own entry: its twin is the plain FLAT kernel's)
+    const CastLaunch cast = t->plan.Launch(false, opacity);
+    CastVariant want = cast.asked;
+    want.cells = false;
+    const CastRow* row = CastTableRow(want);
+    if (!row || !row->rays) { SetLastError("no ray-batch kernel for the scene's cast variant"); return DCRT_E_INVALID_ARG; }
+    const CastVariant& v = row->v;
+    *out_variant = (v.opacity ? DCRT_CAST_VARIANT_OPACITY : 0u) | (v.allCached ? DCRT_CAST_VARIANT_ALL_CACHED : 0u) |
+                   (v.pair ? DCRT_CAST_VARIANT_PAIR : 0u) | (v.ident ? DCRT_CAST_VARIANT_IDENT : 0u) |
+                   (v.ring ? DCRT_CAST_VARIANT_RING : 0u) | (v.flat ? DCRT_CAST_VARIANT_FLAT : 0u);
+    if (n == 0) return DCRT_OK;
+    std::vector<void*> tmp;
+    dcrt_ray* dr = nullptr; uint32_t* dKinds = nullptr; float* dOpacity = nullptr; dcrt_ray_hit* dh = nullptr; uint32_t* dOcc = nullptr;
+    CHECKED(DeviceAlloc(&dr, n, &tmp));
+    int rc = DeviceAlloc(&dKinds, n, &tmp);
+    if (rc == DCRT_OK && opacity) rc = DeviceAlloc(&dOpacity, n, &tmp);
+    if (rc == DCRT_OK) rc = DeviceAlloc(&dh, n, &tmp);
+    if (rc == DCRT_OK) rc = DeviceAlloc(&dOcc, n, &tmp);
+    if (rc == DCRT_OK && hipMemcpyAsync(dr, rays, (size_t)n * sizeof(dcrt_ray), hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    if (rc == DCRT_OK && hipMemcpyAsync(dKinds, kinds, (size_t)n * 4, hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    if (rc == DCRT_OK && opacity && hipMemcpyAsync(dOpacity, opacity_samples, (size_t)n * 4, hipMemcpyHostToDevice, t->stream) != hipSuccess)
+        rc = DCRT_E_HIP;
+    if (rc == DCRT_OK) {
+        // (the refill / park thresholds of a frame: BeginImage)
+        const uint32_t refill = t->knobs.tuneOverride || t->plan.allCached ? t->knobs.refillLanes : DCRT_REFILL_GLOBAL;
+        const uint32_t block = t->plan.block, grid = std::min<uint32_t>((n + block - 1) / block, cast.resident);
+        hipLaunchKernelGGL(row->rays, dim3(grid), dim3(block), cast.lds, t->stream, cast.scene, (const dcrt_ray*)dr, (const uint32_t*)dKinds,
+                           (const float*)dOpacity, n, features, refill, t->knobs.parkLanes, dh, dOcc);
+        if (hipGetLastError() != hipSuccess) rc = DCRT_E_HIP;
+    }
+    if (rc == DCRT_OK && hipMemcpyAsync(out_hits, dh, (size_t)n * sizeof(dcrt_ray_hit), hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    if (rc == DCRT_OK && hipMemcpyAsync(out_occluded, dOcc, (size_t)n * 4, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
     if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
     FreeAll(&tmp);
     return rc;

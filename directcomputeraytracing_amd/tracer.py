@@ -531,6 +531,27 @@ class WavefrontPathTracer:
                                              out.ctypes.data_as(C.POINTER(C.c_uint32)), int(features)), "Occluded")
         return out
 
+    def cast_rays(self, rays: np.ndarray, kinds, opacity_samples=None, features: int = _abi.FEATURE_DEFAULT):
+        """A ray batch through the cast a render of the uploaded scene with `features` launches
+        (dcrt_tracer_cast_rays): kinds[i] == 0 a closest-hit ray, else an any-hit ray below its t_max, each
+        with opacity_samples[i] under FEATURE_ALLOW_ANYHIT. Returns (hits, occluded, variant): `variant`
+        names the flags of the kernel that ran ({"opacity", "all_cached", "pair", "ident", "ring", "flat"})."""
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        kinds = np.ascontiguousarray(kinds, np.uint32)
+        if len(kinds) != len(rays):
+            raise ValueError("one kind per ray")
+        samples = None
+        if opacity_samples is not None:
+            samples = np.ascontiguousarray(opacity_samples, np.float32)
+            if len(samples) != len(rays):
+                raise ValueError("one opacity sample per ray")
+        hits, occ, variant = np.zeros(len(rays), HIT_DTYPE), np.zeros(len(rays), np.uint32), C.c_uint32(0)
+        check(self._lib.dcrt_tracer_cast_rays(self._h, rays.ctypes.data_as(C.POINTER(_abi.Ray)), kinds.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                              None if samples is None else samples.ctypes.data_as(_abi._FP), len(rays), int(features),
+                                              hits.ctypes.data_as(C.POINTER(_abi.RayHit)), occ.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                              C.byref(variant)), "CastRays")
+        return hits, occ, {k for k, bit in _abi.CAST_VARIANT.items() if variant.value & bit}
+
     def occluded_cells(self, rays: np.ndarray, features: int = _abi.FEATURE_DEFAULT) -> np.ndarray:
         """Occlusion bits of shadow rays towards the scene's point light through the merged cast's
         direction-cell section (dcrt_tracer_trace_occlusion_cells); `occluded` is its comparison

@@ -674,6 +674,22 @@ DCRT_API int dcrt_tracer_trace_rays(dcrt_tracer* tracer, const dcrt_ray* rays, u
                                     uint32_t features);
 DCRT_API int dcrt_tracer_occluded(dcrt_tracer* tracer, const dcrt_ray* rays, uint32_t count, uint32_t* out_occluded,
                                   uint32_t features);
+/* A host ray batch through the cast a render of the uploaded scene with `features` launches (the merged
+ * EXTENSION + SHADOW cast's traversal: the same kernel variant, scene copy, LDS bytes and workgroup size).
+ * kinds[i] == 0: an extension ray (closest hit, t_max infinite; out_hits[i] as dcrt_tracer_trace_rays writes
+ * it, out_occluded[i] = 0); otherwise a shadow ray (first accepted hit below the ray's t_max: out_occluded[i],
+ * out_hits[i] the miss record). `features` are taken as given: with DCRT_FEATURE_ALLOW_ANYHIT ray i carries
+ * opacity_samples[i] into the any-hit shader (opacity_samples may be NULL only without the bit).
+ * out_variant: the DCRT_CAST_VARIANT_* flags of the kernel that ran. */
+#define DCRT_CAST_VARIANT_OPACITY    0x01u
+#define DCRT_CAST_VARIANT_ALL_CACHED 0x02u
+#define DCRT_CAST_VARIANT_PAIR       0x04u
+#define DCRT_CAST_VARIANT_IDENT      0x08u
+#define DCRT_CAST_VARIANT_RING       0x10u
+#define DCRT_CAST_VARIANT_FLAT       0x20u
+DCRT_API int dcrt_tracer_cast_rays(dcrt_tracer* tracer, const dcrt_ray* rays, const uint32_t* kinds, const float* opacity_samples,
+                                   uint32_t count, uint32_t features, dcrt_ray_hit* out_hits, uint32_t* out_occluded,
+                                   uint32_t* out_variant);
 /* Device-resident variant for timing: rays/hits already in HBM, launched on the tracer stream. */
 DCRT_API int dcrt_tracer_trace_rays_device(dcrt_tracer* tracer, const void* d_rays, uint32_t count, void* d_hits,
                                            uint32_t features);

@@ -53,6 +53,8 @@ def load():
     lib.oracle_trace_rays.argtypes = [P(A.FlatScene), P(A.Ray), U, P(A.RayHit), U, P(OracleCounters)]
     lib.oracle_occluded.restype = None
     lib.oracle_occluded.argtypes = [P(A.FlatScene), P(A.Ray), U, P(U), U, P(OracleCounters)]
+    lib.oracle_cast_rays.restype = None
+    lib.oracle_cast_rays.argtypes = [P(A.FlatScene), P(A.Ray), P(U), P(C.c_float), U, U, P(A.RayHit), P(U), P(OracleCounters)]
     lib.oracle_lut_integrate.restype = None
     lib.oracle_lut_integrate.argtypes = [C.c_int, U, U, P(C.c_float)]
     lib.oracle_lut_finalize.restype = None
@@ -350,6 +352,23 @@ def occluded(flat, rays, features):
     lib.oracle_occluded(C.byref(flat), rays.ctypes.data_as(C.POINTER(A.Ray)), len(rays), _up(out), features,
                         C.byref(cnt))
     return out, cnt.as_dict()
+
+
+def cast_rays(flat, rays, kinds, opacity_samples, features):
+    """oracle_cast_rays: (hits, occluded, counters). kinds: 0 closest hit, else any hit; `opacity_samples`
+    may be None without the any-hit feature bit."""
+    from directcomputeraytracing_amd import _abi as A
+    from directcomputeraytracing_amd.tracer import HIT_DTYPE
+    lib = load()
+    kinds = np.ascontiguousarray(kinds, np.uint32)
+    assert len(kinds) == len(rays) and (opacity_samples is not None or not features & A.FEATURE_ALLOW_ANYHIT)
+    samples = None if opacity_samples is None else np.ascontiguousarray(opacity_samples, np.float32)
+    assert samples is None or len(samples) == len(rays)
+    hits, occ = np.zeros(len(rays), HIT_DTYPE), np.zeros(len(rays), np.uint32)
+    cnt = OracleCounters()
+    lib.oracle_cast_rays(C.byref(flat), rays.ctypes.data_as(C.POINTER(A.Ray)), _up(kinds), None if samples is None else _fp(samples),
+                         len(rays), features, hits.ctypes.data_as(C.POINTER(A.RayHit)), _up(occ), C.byref(cnt))
+    return hits, occ, cnt.as_dict()
 
 
 def build_luts(threads=None):

@@ -1890,6 +1890,36 @@ void oracle_occluded(const dcrt_flat_scene* sc, const dcrt_ray* rays, uint32_t c
     }
 }
 
+void oracle_cast_rays(const dcrt_flat_scene* sc, const dcrt_ray* rays, const uint32_t* kinds, const float* opacitySamples, uint32_t count,
+                      uint32_t features, dcrt_ray_hit* hits, uint32_t* occ, oracle_counters* cnt)
+{
+    const int allowAnyHit = (features & DCRT_FEATURE_ALLOW_ANYHIT) != 0;
+    init_srgb();   /* (an RGBA opacity texture is decoded per texel) */
+    for (uint32_t i = 0; i < count; ++i) {
+        const int shadow = kinds[i] != 0;
+        const float sample = allowAnyHit ? opacitySamples[i] : 0.0f;
+        hit_info h; memset(&h, 0, sizeof(h));
+        int hasHit;
+        if (shadow) {
+            hasHit = bvh_intersect(sc, vload(rays[i].origin), vload(rays[i].direction), 0.0f, rays[i].t_max, 1, features, sample, &h,
+                                   cnt ? &cnt->shadow_node_visits : NULL, cnt ? &cnt->shadow_triangle_tests : NULL,
+                                   cnt ? &cnt->shadow_blas_entries : NULL);
+            if (cnt) cnt->shadow_rays++;
+        } else {
+            hasHit = bvh_intersect(sc, vload(rays[i].origin), vload(rays[i].direction), 0.0f, o_inf(), 0, features, sample, &h,
+                                   cnt ? &cnt->node_visits : NULL, cnt ? &cnt->triangle_tests : NULL, cnt ? &cnt->blas_entries : NULL);
+            if (cnt) cnt->extension_rays++;
+        }
+        const int rec = hasHit && !shadow;
+        hits[i].t = rec ? h.t : o_inf();
+        hits[i].u = rec ? h.u : 0.0f;
+        hits[i].v = rec ? h.v : 0.0f;
+        hits[i].triangle_id = rec ? ((h.triangleId & 0x7FFFFFFFu) | (h.backface ? 0x80000000u : 0u)) : 0u;
+        hits[i].instance_index = rec ? h.instanceIndex : 0u;
+        occ[i] = shadow && hasHit ? 1u : 0u;
+    }
+}
+
 /* ------------------------------------------------------------------ */
 /* SampleConvolution.hlsl:24-106                                       */
 /* ------------------------------------------------------------------ */

@@ -53,6 +53,13 @@ void oracle_trace_rays(const dcrt_flat_scene* scene, const dcrt_ray* rays, uint3
                        uint32_t features, oracle_counters* counters);
 void oracle_occluded(const dcrt_flat_scene* scene, const dcrt_ray* rays, uint32_t count, uint32_t* occluded,
                      uint32_t features, oracle_counters* counters);
+/* A caller's rays cast as a render casts its own: kinds[i] == 0 is an extension ray (closest hit, t_max
+ * infinite: hits[i] as oracle_trace_rays writes it, occluded[i] = 0), anything else a shadow ray (first
+ * accepted hit below the ray's t_max: occluded[i], hits[i] the miss record). `features` are taken as
+ * given: with DCRT_FEATURE_ALLOW_ANYHIT ray i carries opacity_samples[i] into AnyHitShader
+ * (opacity_samples may be NULL only without the bit). */
+void oracle_cast_rays(const dcrt_flat_scene* scene, const dcrt_ray* rays, const uint32_t* kinds, const float* opacity_samples,
+                      uint32_t count, uint32_t features, dcrt_ray_hit* hits, uint32_t* occluded, oracle_counters* counters);
 
 /* BxDFTexturesBuilding.hlsl restated. which: 0 = BRDF, 1 = BRDF dielectric, 2 = BSDF.
  * Integrates texels [texel_begin, texel_end) of that table's R32 accumulation

@@ -21,6 +21,14 @@ Every ray is classified as clear or ambiguous (`Analysis.reason`, the R_* bits).
 float32 cast is only asserted on clear rays; an ambiguous ray must still miss or report a t near
 one of the reference's candidates (`compare_hits`).
 
+With the any-hit feature a ray carries an opacity sample and a hit counts only if the sample is below
+the hit's opacity (`Opacity`: float64, from the definition, the texel addressing imported from
+tests/shading_ref.py). `Truth.analyse(rays, samples)` then keeps every candidate, takes the nearest
+accepted one, and derives a tolerance on each candidate's opacity the same way (u, v moved by the
+candidate's own tolerance, every float32 input by one ulp, times 8, plus 4 ulps); a candidate whose
+sample lies within it of its opacity is undecided, and a ray with an undecided candidate -- or one
+ambiguous by the reasons above -- at or before its result is ambiguous (R_OPACITY).
+
 The generators below write the scenes (Mitsuba XML + OBJ, as tests/random_scenes.py does) and the
 ray families the ray-truth tests use."""
 from pathlib import Path
@@ -36,9 +44,11 @@ PREFILTER_MARGIN = 0.05   # near misses are looked for this far outside a triang
 COUNT_MASK = 0x1FFFFFFF
 
 # why a ray is ambiguous for the closest hit (`Analysis.occluded` decides separately, for a given t_max)
-R_MARGIN, R_GRAZING, R_GAP, R_NEAR_MISS, R_T_ZERO, R_SLIVER, R_CONDITION = 1, 2, 4, 8, 16, 32, 64
+R_MARGIN, R_GRAZING, R_GAP, R_NEAR_MISS, R_T_ZERO, R_SLIVER, R_CONDITION, R_OPACITY = 1, 2, 4, 8, 16, 32, 64, 128
 REASONS = {R_MARGIN: "margin", R_GRAZING: "grazing", R_GAP: "gap", R_NEAR_MISS: "near-miss", R_T_ZERO: "t~0",
-           R_SLIVER: "sliver", R_CONDITION: "ill-conditioned"}
+           R_SLIVER: "sliver", R_CONDITION: "ill-conditioned", R_OPACITY: "opacity"}
+NO_OVERRIDE = 0xFFFFFFFF
+FLAG_OPAQUE = 1
 
 
 def _cross(a, b):
@@ -103,12 +113,86 @@ def _ulp(x32):
     return np.spacing(np.abs(x32)).astype(np.float64)
 
 
+class Opacity:
+    """The any-hit opacity test of a flat scene (a dcrt_flat_scene), in float64 and from its definition: the
+    material of a candidate is its instance's override if it has one, else its triangle's; the value is the
+    material's opacity, times the red channel of its opacity texture -- bilinear, wrapped, at tex_tiling x the
+    texcoord interpolated at (u, v) -- if it has one; a candidate counts iff sample < value, and always on an
+    instance flagged OPAQUE. The texture addressing (texel centres, wrap, R8 / sRGB decode) is
+    tests/shading_ref.py's."""
+
+    def __init__(self, flat):
+        import ctypes as C
+        import shading_ref as S
+        s = S.from_flat(flat)
+        self.S = S
+        self.tc32 = s["vertices"][:, 9:11].astype(np.float32)[s["triangles"]]              # (T, 3, 2)
+        self.material_ids = s["material_ids"].astype(np.int64)
+        self.overrides = s["overrides"].astype(np.int64)
+        self.opaque = (S._array(flat.instance_flags, C.c_uint32, (flat.instance_count,)) & FLAG_OPAQUE) != 0
+        m = s["materials"]
+        self.tiling32 = m[:, 8:10].copy().view(np.float32)
+        self.opacity32 = m[:, 10].copy().view(np.float32)
+        self.texture = m[:, 12].copy().view(np.int32).astype(np.int64)
+        self.textures = s["textures"]
+
+    def material(self, inst, prim):
+        ov = self.overrides[inst]
+        return np.where(ov != NO_OVERRIDE, ov, self.material_ids[prim])
+
+    def value(self, mat, u, v, tc, tiling, opacity):
+        """The opacity of candidates with material `mat` at (u, v): float64 from the given texcoords (n, 3, 2),
+        tilings (n, 2) and material opacities (n)."""
+        out = np.asarray(opacity, np.float64).copy()
+        w = np.stack([1.0 - u - v, u, v], -1)
+        at = np.einsum("nk,nkc->nc", w, tc) * tiling
+        for k in np.unique(self.texture[mat]):
+            if k < 0:
+                continue
+            rows = np.flatnonzero(self.texture[mat] == k)
+            with np.errstate(invalid="ignore"):
+                ok = np.isfinite(at[rows]).all(1)
+                red = np.full(len(rows), np.nan)
+                red[ok] = self.S.sample_texture(self.textures[k], at[rows][ok], np.float64)[:, 0]
+            out[rows] = out[rows] * red
+        return out
+
+    def decide(self, rng, inst, prim, u, v, tol_uv, sample):
+        """Per candidate: (value, tolerance, accepted, undecided). The tolerance is the largest change of the
+        value when u and v move by the candidate's tol_uv and the float32 texcoords, tiling and material opacity
+        by one ulp each (PERTURBATIONS sign patterns), times 8, plus 4 float32 ulps of the value."""
+        mat = self.material(inst, prim)
+        tc, tiling, op = self.tc32[prim], self.tiling32[mat], self.opacity32[mat]
+        val = self.value(mat, u, v, tc.astype(np.float64), tiling.astype(np.float64), op.astype(np.float64))
+        dv = np.zeros(len(val))
+        for _ in range(PERTURBATIONS):
+            def move(x32):
+                return x32.astype(np.float64) + rng.choice([-1.0, 1.0], x32.shape) * _ulp(x32)
+            with np.errstate(invalid="ignore"):
+                moved = self.value(mat, u + rng.choice([-1.0, 1.0], u.shape) * tol_uv, v + rng.choice([-1.0, 1.0], v.shape) * tol_uv,
+                                   move(tc), move(tiling), move(op))
+                dv = np.fmax(dv, np.abs(moved - val))
+        with np.errstate(invalid="ignore"):
+            tol = 8.0 * dv + 4.0 * _ulp(val.astype(np.float32))
+        tol[~np.isfinite(tol) | ~np.isfinite(val)] = np.inf
+        s = np.asarray(sample, np.float64)
+        opaque = self.opaque[inst]
+        with np.errstate(invalid="ignore"):
+            accepted = opaque | (s < val)
+            undecided = ~opaque & ~(np.abs(s - val) > tol)
+        return val, tol, accepted, undecided
+
+
 class Analysis:
     """What `Truth.analyse` found for a batch of rays. Per ray: hit, t, u, v, inst, prim (the
     nearest hit, object-space intersection), facing (sign of d_obj . (p1 - p0) x (p2 - p0)), cos,
     tol_t, tol_uv and reason (0: clear). Per candidate (a hit, a near miss within BARY_MARGIN, or a
     sliver / zero-area triangle the ray passes close to): c_ray, c_inst, c_prim, c_t, c_u, c_v,
-    c_tol_t, c_tol_uv, c_true (a hit in float64)."""
+    c_tol_t, c_tol_uv, c_true (a hit in float64). With opacity samples (`Truth.analyse(rays, samples)`:
+    every ray carries one into the any-hit test, `Opacity`) also c_opacity, c_tol_opacity, c_accept
+    (sample < opacity, or an OPAQUE instance) and c_undecided (|sample - opacity| within the tolerance);
+    the nearest hit is then the nearest accepted one, and crossed[ray] says that the ray passes a clearly
+    rejected hit before it. Without samples every candidate is accepted and none undecided."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -120,31 +204,41 @@ class Analysis:
     def tie_keys(self):
         """Sorted keys ray * n_pairs + pair of the candidates that tie with the nearest hit."""
         best = self.t[self.c_ray]
-        tie = self.c_true & (self.c_t - best <= 2.0 * np.maximum(self.c_tol_t, self.tol_t[self.c_ray]))
+        tie = self.c_true & (self.c_accept | self.c_undecided) & (self.c_t - best <= 2.0 * np.maximum(self.c_tol_t, self.tol_t[self.c_ray]))
         return np.sort(self.c_ray[tie] * self.n_keys + self.c_inst[tie] * self.n_prims + self.c_prim[tie])
 
     def occluded(self, t_max):
-        """(occluded, ambiguous) for the rays' t_max: any hit with 0 <= t < t_max. Clear when one
-        hit is robust (inside its triangle by BARY_MARGIN, not grazing, not a sliver, and further
-        than its tolerance from 0 and from t_max), or when no candidate at all lies in range."""
+        """(occluded, ambiguous) for the rays' t_max: any accepted hit with 0 <= t < t_max. Clear when
+        one hit is robust (inside its triangle by BARY_MARGIN, not grazing, not a sliver, further
+        than its tolerance from 0 and from t_max, and clearly accepted), or when no candidate that is
+        accepted or undecided lies in range."""
         n = len(self.t)
         tm = np.asarray(t_max, np.float64)[self.c_ray]
         occ = np.zeros(n, bool)
-        occ[self.c_ray[self.c_true & (self.c_t >= 0) & (self.c_t < tm)]] = True
-        robust = self.c_robust & (self.c_t > self.c_tol_t) & (self.c_t < tm - self.c_tol_t)
+        occ[self.c_ray[self.c_true & self.c_accept & (self.c_t >= 0) & (self.c_t < tm)]] = True
+        robust = self.c_robust & self.c_accept & ~self.c_undecided & (self.c_t > self.c_tol_t) & (self.c_t < tm - self.c_tol_t)
         sure = np.zeros(n, bool)
         sure[self.c_ray[robust]] = True
-        near = (self.c_t > -self.c_tol_t) & (self.c_t - self.c_tol_t < tm)
+        near = (self.c_t > -self.c_tol_t) & (self.c_t - self.c_tol_t < tm) & (self.c_accept | self.c_undecided)
         maybe = np.zeros(n, bool)
         maybe[self.c_ray[near]] = True
         return occ, maybe & ~sure
+
+    def crossed_before(self, t_max):
+        """Per ray: a clearly rejected float64 hit lies below t_max (an any-hit ray passes through it)."""
+        tm = np.asarray(t_max, np.float64)[self.c_ray]
+        out = np.zeros(len(self.t), bool)
+        out[self.c_ray[self.c_true & ~self.c_accept & ~self.c_undecided & (self.c_t >= 0) & (self.c_t < tm)]] = True
+        return out
 
 
 class Truth:
     """The float64 reference over one flat scene (`test_scene_pin._flat_arrays`)."""
 
-    def __init__(self, fa, seed=0):
+    def __init__(self, fa, seed=0, opacity=None):
         self.rng = np.random.default_rng(seed)
+        self.opacity = opacity                     # an `Opacity` over the same flat scene: `analyse` takes samples
+        self.opacity_rng = np.random.default_rng(seed + 1)     # (its own draws: the tolerances on t, u, v are the same with and without samples)
         pos = np.ascontiguousarray(fa["vertices"][:, :3]).view(np.float32)
         tri = fa["triangles"].astype(np.int64)
         xf = np.ascontiguousarray(fa["instance_transforms"]).view(np.float32)
@@ -220,7 +314,9 @@ class Truth:
             q = np.clip(np.nan_to_num(q), 0.0, 1.0)
         return np.linalg.norm(w + s[..., None] * u - q[..., None] * v, axis=-1), s
 
-    def analyse(self, rays):
+    def analyse(self, rays, samples=None):
+        """`samples`: one opacity sample per ray (needs `self.opacity`): the any-hit test decides which
+        candidates count; None: every one does."""
         o32 = np.ascontiguousarray(rays["origin"], np.float32)
         d32 = np.ascontiguousarray(rays["direction"], np.float32)
         n, M = len(rays), len(self.prim)
@@ -296,9 +392,19 @@ class Truth:
         need = np.maximum(BARY_MARGIN, tol_uv)
         c_robust = c_true & (margin >= need) & (cos >= GRAZING_COS) & ~self.thin[cm] & (need <= PREFILTER_MARGIN)
 
-        # the nearest hit of every ray
+        # the any-hit test: which candidates count (every one without samples)
+        c_accept, c_undecided = np.ones(len(cr), bool), np.zeros(len(cr), bool)
+        c_opacity, c_tol_opacity = np.ones(len(cr)), np.zeros(len(cr))
+        if samples is not None:
+            s32 = np.ascontiguousarray(samples, np.float32)
+            assert self.opacity is not None and len(s32) == n
+            c_opacity, c_tol_opacity, c_accept, c_undecided = self.opacity.decide(
+                self.opacity_rng, self.inst[cm], self.prim[cm], cu, cv, np.where(np.isfinite(tol_uv), tol_uv, 0.0), s32[cr])
+            c_undecided |= ~self.opacity.opaque[self.inst[cm]] & (cthin | ~np.isfinite(tol_uv))
+
+        # the nearest (accepted) hit of every ray
         order = np.lexsort((ct, cr))
-        order = order[c_true[order]]
+        order = order[(c_true & c_accept)[order]]
         first = order[np.unique(cr[order], return_index=True)[1]]
         hit = np.zeros(n, bool)
         hit[cr[first]] = True
@@ -327,16 +433,25 @@ class Truth:
         flag(np.abs(ct) <= tol_t, R_T_ZERO)
         flag(in_range & (cthin | self.thin[cm]), R_SLIVER)
         flag(in_range & ~cthin & ((need > PREFILTER_MARGIN) | (tol_t > 1e-2 * (1.0 + np.abs(ct)))), R_CONDITION)
+        if samples is not None:
+            # every candidate at or before the nearest accepted hit decides the result: an undecided any-hit
+            # test, or a hit on an edge (a float32 cast may take its neighbour, with another material)
+            flag(in_range & c_undecided, R_OPACITY)
+            flag(in_range & c_true & (margin < need), R_MARGIN)
+        crossed = np.zeros(n, bool)
+        crossed[cr[c_true & ~c_accept & ~c_undecided & (ct < best)]] = True
 
         # world space against object space: the uploaded inverse matrices belong to the forward ones
-        ok = reason == 0
+        # (the world-space pass knows no opacity: checked on the analyses without samples)
+        ok = (reason == 0) & (samples is None)
         assert np.array_equal(np.isfinite(best_w[ok]), hit[ok]), "world- and object-space hit / miss differ on clear rays"
         both = ok & hit
         worst = np.abs(best_w[both] - res["t"][both]) / res["tol_t"][both]
         assert worst.size == 0 or worst.max() <= 1.0, f"world- and object-space t differ by {worst.max():.2f} tolerances"
         return Analysis(n_prims=self.n_prims, n_keys=self.n_inst * self.n_prims, hit=hit, inst=inst, prim=prim, reason=reason,
                         c_ray=cr, c_inst=self.inst[cm], c_prim=self.prim[cm], c_pair=cm, c_t=ct, c_u=cu, c_v=cv, c_tol_t=tol_t,
-                        c_tol_uv=tol_uv, c_true=c_true, c_robust=c_robust, world_t=best_w, **res)
+                        c_tol_uv=tol_uv, c_true=c_true, c_robust=c_robust, world_t=best_w, c_accept=c_accept, c_undecided=c_undecided,
+                        c_opacity=c_opacity, c_tol_opacity=c_tol_opacity, crossed=crossed, **res)
 
     def closest(self, rays):
         return self.analyse(rays)
@@ -358,7 +473,8 @@ def compare_hits(truth, an, rays, hits, exact_aim=False):
     Clear rays: hit / miss equal, (instance, triangle) in the tie set, t, u, v within the derived
     tolerances, the hit point rebuilt from u, v within tolerance of o + t d, the backface bit the
     reference's facing. Ambiguous rays: a miss, or a hit that names one of the ray's candidates (a
-    hit, a near miss, a sliver or a triangle the ray runs along) at that candidate's distance.
+    hit, a near miss, a sliver or a triangle the ray runs along; with opacity samples: one that is
+    accepted or undecided) at that candidate's distance.
     `exact_aim`: the family is aimed at vertices and edges, where ambiguity is the point: every
     ray is held to the ambiguous rays' rule only (no hit / miss equality, the candidates at the
     nearest distance stand in for the id)."""
@@ -400,7 +516,8 @@ def compare_hits(truth, an, rays, hits, exact_aim=False):
     bad["backface"] = np.flatnonzero(c & (back != ((dn < 0) == BACKFACE_IS_NEGATIVE_FACING)))
     # ambiguous rays: a miss, or a hit that names one of the ray's candidates, at that candidate's distance
     with np.errstate(invalid="ignore"):
-        ok = (mine[an.c_ray] == keys) & (np.abs(t[an.c_ray] - an.c_t) <= 2.0 * np.maximum(an.c_tol_t, an.tol_t[an.c_ray]))
+        ok = ((mine[an.c_ray] == keys) & (an.c_accept | an.c_undecided)
+              & (np.abs(t[an.c_ray] - an.c_t) <= 2.0 * np.maximum(an.c_tol_t, an.tol_t[an.c_ray])))
     on_candidate = np.zeros(len(t), bool)
     on_candidate[an.c_ray[ok]] = True
     bad["ambiguous hit not on a candidate"] = np.flatnonzero(~clear & got & ~on_candidate)
@@ -540,6 +657,156 @@ def write_closed_scene(directory, seed):
     return _write_xml(d, meshes)
 
 
+# ---- any-hit opacity: the veil scene and the edit that gives a flat scene its materials -----------------
+VEIL_LAYERS, VEIL_SPACING = 4, 0.25
+VEIL_GRID, WALL_GRID = 2, 1           # quads along a side: 62 triangles in all, so that the scene fits the cast's LDS cache whole
+CARD_STEP, CARD_GAP = 0.5, 1.0       # the cards' pitch along x and the distance from a front card to its back card
+CARD_ORIGIN = (6.0, -2.0, 0.8)       # (away from the veils and the wall; no card's plane through the world's origin)
+
+
+def _grid(n, size, z, rng, jitter=0.0):
+    """An n x n grid of quads over [-size, size]^2 at height z: vertices (jittered in the plane) and triangles."""
+    g = np.linspace(-size, size, n + 1)
+    V = np.stack([*np.meshgrid(g, g, indexing="ij"), np.full((n + 1, n + 1), z)], -1).reshape(-1, 3)
+    V[:, :2] += rng.uniform(-jitter, jitter, (len(V), 2)) * (2.0 * size / n)
+    i, j = (a.reshape(-1) for a in np.meshgrid(np.arange(n), np.arange(n), indexing="ij"))
+    a, b, c, d = i * (n + 1) + j, (i + 1) * (n + 1) + j, (i + 1) * (n + 1) + j + 1, i * (n + 1) + j + 1
+    return V, np.concatenate([np.stack([a, b, c], 1), np.stack([a, c, d], 1)])
+
+
+def card_count():
+    return len(CARDS)
+
+
+def write_veil_scene(directory, seed):
+    """VEIL_LAYERS translucent layers (VEIL_GRID x VEIL_GRID quads each, VEIL_SPACING apart) as one mesh under three adjacent
+    instances -- mirrored, sheared and uniformly scaled (`transform_set`) --, an opaque back wall behind them, and
+    the exact families' cards: per card a front quad and, CARD_GAP behind it, a back quad (`exact_cards`)."""
+    from directcomputeraytracing_amd.scenes import write_obj
+    rng = np.random.default_rng(seed)
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    up = np.array([0.0, 0.0, -1.0])
+
+    def put(name, parts):
+        V = np.concatenate([p[0] for p in parts])
+        F = np.concatenate([p[1] + off for p, off in zip(parts, np.cumsum([0] + [len(p[0]) for p in parts[:-1]]))])
+        write_obj(d / name, V, np.repeat(up[None], len(V), 0), rng.uniform(0.0, 1.0, (len(V), 2)), F)
+    put("veil.obj", [_grid(VEIL_GRID, 1.0, k * VEIL_SPACING, rng, 0.2) for k in range(VEIL_LAYERS)])
+    put("wall.obj", [_grid(WALL_GRID, 4.0, 0.0, rng, 0.2)])
+    cards = []
+    for k in range(card_count()):
+        for z in (0.0, CARD_GAP):
+            V, F = _grid(1, 0.2, z, rng)
+            cards.append((V + [k * CARD_STEP, 0.0, 0.0], F))
+    put("cards.obj", cards)
+    ms = transform_set(rng)
+    wall, card = np.eye(4), np.eye(4)
+    wall[:3, 3] = (0.0, 0.0, 2.5)
+    card[:3, 3] = CARD_ORIGIN
+    return _write_xml(d, [("veil.obj", [ms[3], ms[4], ms[1]]), ("wall.obj", [wall]), ("cards.obj", [card])])
+
+
+# The materials every opacity case gets (`opacity_edit`): (opacity, opacity texture or -1, tex_tiling)
+M_OPAQUE, M_ZERO, M_CONST, M_R8, M_RGBA, M_DYADIC, M_HALF = range(7)
+CONST_OPACITY = np.float32(0.37)
+MATERIALS = [(1.0, -1, (1.0, 1.0)), (0.0, -1, (1.0, 1.0)), (CONST_OPACITY, -1, (1.0, 1.0)), (0.8, 0, (2.5, -1.5)),
+             (1.0, 1, (-0.75, 3.0)), (1.0, 2, (1.0, 1.0)), (0.5, 2, (2.0, -1.0))]
+ONE_BELOW = np.float32(1.0 - 2.0 ** -24)
+
+
+# The exact families' cards: (front quad's material, the texel (x, y) of the dyadic texture its constant texcoord names)
+CARDS = [(M_CONST, None), (M_ZERO, None), (M_OPAQUE, None), (M_DYADIC, (1, 2)), (M_DYADIC, (2, 2)), (M_HALF, (3, 0)), (M_HALF, (0, 1))]
+
+
+def exact_cards():
+    """The aimed families float32 decides exactly: (card, opacity sample, accepted). `<` is strict: a sample
+    equal to the opacity passes through, the float just below it is accepted."""
+    c, zero = CONST_OPACITY, np.float32(0.0)
+    return [(0, c, False), (0, np.nextafter(c, zero), True),          # a constant opacity
+            (1, zero, False),                                          # opacity 0, sample 0
+            (2, ONE_BELOW, True),                                      # opacity 1, sample 1 - 2^-24
+            (3, ONE_BELOW, True), (3, zero, True),                     # a texel of 1
+            (4, zero, False),                                          # a texel of 0
+            (5, np.float32(0.5), False), (5, np.nextafter(np.float32(0.5), zero), True),   # opacity 1/2 x a texel of 1, a negative tiling
+            (6, zero, False)]
+
+
+def opacity_textures(rng):
+    """[(format, pixels)]: an R8 texture, an RGBA one whose red and alpha differ, and an R8 one of 0 and 255
+    alone (texel values 0 and 1: the dyadic texture of the exact families)."""
+    r8 = rng.integers(0, 256, (8, 8, 1)).astype(np.uint8)
+    rgba = rng.integers(0, 256, (4, 8, 4)).astype(np.uint8)
+    rgba[..., 3] = 255 - rgba[..., 0]
+    dyadic = (((np.add.outer(np.arange(4), np.arange(4)) % 3) == 0) * 255).astype(np.uint8)[..., None]   # [y][x]
+    return [(1, r8), (0, rgba), (1, dyadic)]
+
+
+def opacity_edit(flat, frame, seed, instances, cards=False, keep=()):
+    """A copy of `flat` (a dcrt_flat_scene; `frame` its frame parameters, `keep` what owns it) with MATERIALS,
+    the three textures, a random material per triangle, texcoords stretched to [-1, 2) and, per instance,
+    `instances[i]` = (OPAQUE flag, override or NO_OVERRIDE). `cards`: the last 4 * card_count() triangles are
+    the veil scene's cards and get the exact families' materials and constant texel-centre texcoords
+    (`.cards`: {triangle: (card, is front)}). The fields no loader sets (tex_tiling, the textures) are edited
+    in the flat scene, as tests/test_shading_ref.py does. The copy keeps its arrays alive."""
+    import ctypes as C
+    import shading_ref as S
+    from test_shading_ref import Case as FlatCase
+    rng = np.random.default_rng(seed)
+    s = S.from_flat(flat)
+    n_tri, n_inst = len(s["triangles"]), flat.instance_count
+    assert len(instances) == n_inst, (len(instances), n_inst)
+    base = s["materials"][0].copy()
+    mats = np.repeat(base[None], len(MATERIALS), 0)
+    for k, (op, tex, tiling) in enumerate(MATERIALS):
+        mats[k, 8:10] = np.asarray(tiling, np.float32).view(np.uint32)
+        mats[k, 10] = np.asarray([op], np.float32).view(np.uint32)[0]
+        mats[k, 12] = np.asarray([tex], np.int32).view(np.uint32)[0]
+    ids = rng.choice([M_OPAQUE, M_ZERO, M_ZERO, M_CONST, M_R8, M_R8, M_RGBA, M_RGBA], n_tri).astype(np.uint32)
+    V = s["vertices"].copy()
+    V[:, 9:11] = V[:, 9:11] * np.float32(3.0) - np.float32(1.0)
+    textures = opacity_textures(rng)
+    where = {}
+    if cards:
+        # (a BVH build orders a mesh's triangles its own way: a card's are found by where they lie)
+        table = CARDS
+        first = n_tri - 4 * len(table)
+        centre = np.abs(s["vertices"][s["triangles"][first:]][..., :3].astype(np.float64).mean(1))
+        card, front = np.rint(centre[:, 0] / CARD_STEP).astype(int), centre[:, 2] < 0.5 * CARD_GAP
+        assert all(((card == k) & (front == f)).sum() == 2 for k in range(len(table)) for f in (False, True))
+        for tri, k, f in zip(range(first, n_tri), card, front):
+            mat, texel = table[k]
+            where[tri] = (int(k), bool(f))
+            ids[tri] = mat if f else M_OPAQUE
+            if f and texel is not None:                           # tiling x texcoord = the texel's centre, some periods away
+                tc = ((np.asarray(texel, np.float64) + 0.5) / 4.0 + (3.0, -2.0)) / np.asarray(MATERIALS[mat][2], np.float64)
+                V[s["triangles"][tri], 9:11] = tc.astype(np.float32)
+    case = FlatCase(flat, frame, list(keep)).edit(vertices=V, materials=mats, material_ids=ids, textures=textures,
+                                                  overrides=np.asarray([o for _, o in instances], np.uint32))
+    flags = np.asarray([FLAG_OPAQUE if f else 0 for f, _ in instances], np.uint32)
+    case.flat.instance_flags = flags.ctypes.data_as(C.POINTER(C.c_uint32))
+    case._keep.append(flags)
+    case.flat.owner = case           # (the struct keeps the arrays it points into alive)
+    case.flat.cards = where
+    return case.flat
+
+
+CLOSED_SMALL_SEED = 2
+
+
+def write_closed_small_scene(directory, seed=CLOSED_SMALL_SEED):
+    """One jittered closed polyhedron of 32 triangles under `transform_set`, laid out apart: closed meshes
+    small enough for the cast's LDS cache to hold the scene whole."""
+    from directcomputeraytracing_amd.scenes import write_obj
+    rng = np.random.default_rng(seed)
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    V, F = closed_polyhedron(rng, levels=1)
+    assert is_closed(F) and len(F) == 32
+    write_obj(d / "poly.obj", V, V / np.linalg.norm(V, axis=1, keepdims=True), rng.uniform(0, 1, (len(V), 2)), F)
+    return _write_xml(d, [("poly.obj", transform_set(rng, spacing=3.0))])
+
+
 def point_triangle_distance(p, a, b, c):
     """Distance from points p (N, 3) to triangles (M, 3) each: (N, M). Ericson, Real-Time
     Collision Detection 5.1.5, vectorised."""
@@ -668,21 +935,57 @@ SCENES = {
     "closed": dict(seed=1, per_family=700),                                   # 12 closed meshes
     "large": dict(seed=1003, per_family=600, reach=(0.05, 0.3), outside=0.1),  # 3 x 5.2 k triangles: deeper than the LDS node cache
     "obj": dict(seed=2, per_family=700),                                      # identity-only OBJ scene, 44 triangles
+    "veil": dict(seed=4, per_family=1200),                                    # 3 x 32 veil triangles, a wall, the cards
+    "small": dict(seed=5, per_family=700),                                    # a soup small enough for the cast's LDS cache, every transform
 }
-CAPPED = ("soup", "large", "obj")
+CAPPED = ("soup", "large", "obj", "veil", "small")
+# the any-hit cases: scene -> per instance (OPAQUE flag, material override). Adjacent instances differ in both, so
+# a flag or an override carried over from the previous TLAS leaf shows.
+OPACITY_INSTANCES = {
+    # by mesh (the flat scene's instances come in the TLAS builder's order): the veil's three instances in that order,
+    # the wall (its triangles' random materials overridden by the opaque one, without the flag), the cards
+    "veil": {"veil": [(True, M_OPAQUE), (False, M_R8), (False, NO_OVERRIDE)], "wall": [(False, M_OPAQUE)], "cards": [(False, NO_OVERRIDE)]},
+    # (an OPAQUE instance whose override says opacity 0: the flag wins)
+    "soup": {"soup": [(True, M_ZERO), (False, M_R8), (False, NO_OVERRIDE), (False, M_RGBA), (True, NO_OVERRIDE), (False, NO_OVERRIDE)]},
+}
+OPACITY_INSTANCES["small"] = OPACITY_INSTANCES["soup"]
+
+
+def opacity_instances(name, flat):
+    """Per instance of the flat scene (OPAQUE flag, material override): OPACITY_INSTANCES[name], its meshes told
+    apart by their triangle counts."""
+    import ctypes as C
+    import shading_ref as S
+    roles = {k: list(v) for k, v in OPACITY_INSTANCES[name].items()}
+    if len(roles) == 1:
+        return next(iter(roles.values()))
+    size = {VEIL_LAYERS * 2 * VEIL_GRID ** 2: "veil", 2 * WALL_GRID ** 2: "wall", 4 * card_count(): "cards"}
+    nodes = S._array(flat.bvh_nodes, C.c_uint32, (flat.bvh_node_count, 8))
+    return [roles[size[len(p)]].pop(0) for _, p in instance_triangles(nodes)]
+# the seed of a case's materials per triangle, texture bytes and opacity samples: chosen, like SCENES', so that the
+# reference alone meets CAPS with the samples in
+OPACITY_SEEDS = {"veil": 1, "soup": 7, "small": 1}
+CROSSING_SHARE = 0.30      # interior rays that pass a clearly rejected hit before their result, at least
 
 
 def load_scene(name, directory):
     import random_scenes as R
     from directcomputeraytracing_amd import Scene
-    seed = SCENES[name]["seed"]
     s = Scene((48, 36))
+    if name == "closed_small":
+        s.load_from_file(write_closed_small_scene(directory))
+        return s
+    seed = SCENES[name]["seed"]
     if name == "soup":
         s.load_from_file(write_soup_scene(directory, seed))
     elif name == "closed":
         s.load_from_file(write_closed_scene(directory, seed))
     elif name == "large":
         s.load_from_file(write_soup_scene(directory, seed, n_grid=48, n_loose=600, n_instances=3))
+    elif name == "veil":
+        s.load_from_file(write_veil_scene(directory, seed))
+    elif name == "small":
+        s.load_from_file(write_soup_scene(directory, seed, n_grid=3, n_loose=5))
     else:
         R.setup_obj_scene(s, R.write_obj_scene(directory, seed), seed)
     return s
@@ -691,12 +994,18 @@ def load_scene(name, directory):
 class Case:
     """One scene's reference: the families' rays and their analyses, computed once."""
 
-    def __init__(self, name, flat_arrays):
+    def __init__(self, name, flat_arrays, opacity=None):
+        """`opacity`: an `Opacity` over the same flat scene: every ray carries a uniform opacity sample
+        (`samples`), and the analyses are those of the any-hit test."""
         cfg = dict(SCENES[name])
         self.name = name
-        self.truth = Truth(flat_arrays, cfg["seed"])
+        self.truth = Truth(flat_arrays, cfg["seed"], opacity)
         self.families = ray_families(self.truth, cfg.pop("seed"), **cfg)
-        self.analyses = {k: self.truth.analyse(r) for k, r in self.families.items()}
+        self.samples = None
+        if opacity is not None:
+            rng = np.random.default_rng(OPACITY_SEEDS[name])
+            self.samples = {k: rng.random(len(r), np.float32) for k, r in self.families.items()}
+        self.analyses = {k: self.truth.analyse(r, None if self.samples is None else self.samples[k]) for k, r in self.families.items()}
 
     def shares(self):
         return {k: float((~a.clear).mean()) for k, a in self.analyses.items()}
@@ -711,13 +1020,15 @@ class Case:
         return out
 
     def check(self, trace, occluded, families=None):
-        """Every family through `trace(rays)` and `occluded(rays)`; a list of failure messages."""
+        """Every family through `trace(rays)` and `occluded(rays)` -- with opacity samples:
+        `trace(rays, samples)` and `occluded(rays, samples)` --; a list of failure messages."""
         msgs = []
         for fam in families or self.families:
             rays, an = self.families[fam], self.analyses[fam]
-            for what, idx in compare_hits(self.truth, an, rays, trace(rays), exact_aim=(fam == "exact")).items():
+            args = (rays,) if self.samples is None else (rays, self.samples[fam])
+            for what, idx in compare_hits(self.truth, an, rays, trace(*args), exact_aim=(fam == "exact")).items():
                 msgs.append(f"{self.name}/{fam}: {what}: {len(idx)} of {len(rays)} rays, first {describe(an, idx)}")
-            idx, _ = compare_occluded(an, rays, occluded(rays))
+            idx, _ = compare_occluded(an, rays, occluded(*args))
             if len(idx):
                 msgs.append(f"{self.name}/{fam}: occluded: {len(idx)} of {len(rays)} rays differ, first {describe(an, idx)}")
         return msgs
@@ -727,6 +1038,61 @@ class Case:
         rays = np.concatenate(list(self.families.values()))
         order = np.random.default_rng(7).permutation(len(rays))[:n]
         return rays[order], order
+
+
+def mixed_kinds(n):
+    """0 (closest hit) / 1 (any hit) per ray: alternating over the first half of the batch, in runs of 64
+    over the second, so that a cast's waves are both mixed and pure."""
+    i = np.arange(n)
+    return np.where(i < n // 2, i & 1, (i >> 6) & 1).astype(np.uint32)
+
+
+def cast_both(cast, rays, samples=None):
+    """(closest hits, occlusion words) of every ray through `cast(rays, kinds, samples) -> (hits, occluded)`:
+    two batches with complementary `mixed_kinds`, so each ray is cast as both kinds and every batch mixes them.
+    A ray's unused output must be the miss record / 0."""
+    kinds = mixed_kinds(len(rays))
+    h0, o0 = cast(rays, kinds, samples)
+    h1, o1 = cast(rays, 1 - kinds, samples)
+    for h, o, k in ((h0, o0, kinds), (h1, o1, 1 - kinds)):
+        assert np.isinf(h["t"][k == 1]).all() and not h["triangle_id"][k == 1].any() and not o[k == 0].any()
+    closest = kinds == 0
+    hits = h1.copy()
+    hits[closest] = h0[closest]
+    return hits, np.where(closest, o1, o0)
+
+
+def largest_opacity_tolerance(case):
+    """The largest tolerance on the opacity among the decided candidates of the clear rays of every family."""
+    out = 0.0
+    for a in case.analyses.values():
+        m = a.clear[a.c_ray] & ~a.c_undecided & np.isfinite(a.c_tol_opacity) & ~case.truth.opacity.opaque[a.c_inst]
+        out = max(out, float(a.c_tol_opacity[m].max()) if m.any() else 0.0)
+    return out
+
+
+def exact_opacity_rays(truth, cards):
+    """The aimed families of `exact_cards`, one ray per sample and front triangle of its card: straight through an
+    interior point of the front triangle (0.7 in front of it) towards the back card CARD_GAP behind. Returns
+    (rays, samples, accepted, front triangle, card): a closest-hit ray must name the front triangle when
+    accepted and a triangle of the card's back quad otherwise; with t_max between the two quads (the rays'
+    t_max) an any-hit ray is occluded iff accepted."""
+    from directcomputeraytracing_amd import make_rays
+    O, D, S, A, F, K = [], [], [], [], [], []
+    pair_of = {int(p): m for m, p in enumerate(truth.prim) if int(p) in cards}      # (the cards' instance is the only one of its mesh)
+    centre = {kf: np.mean([truth.p_world[pair_of[t]].mean(0) for t, v in cards.items() if v == kf], 0) for kf in set(cards.values())}
+    for tri, (k, front) in sorted(cards.items()):
+        if not front:
+            continue
+        p = truth.p_world[pair_of[tri]]
+        d = centre[(k, False)] - centre[(k, True)]
+        d /= np.linalg.norm(d)
+        target = 0.5 * p[0] + 0.3 * p[1] + 0.2 * p[2]
+        for card, sample, accepted in exact_cards():
+            if card == k:
+                O.append(target - 0.7 * d), D.append(d), S.append(sample), A.append(accepted), F.append(tri), K.append(k)
+    rays = make_rays(np.asarray(O, np.float32), np.asarray(D, np.float32), 0.0, np.float32(0.7 + 0.5 * CARD_GAP))
+    return rays, np.asarray(S, np.float32), np.asarray(A, bool), np.asarray(F), np.asarray(K)
 
 
 def hand_scene(triangles, matrices=(np.eye(4),)):

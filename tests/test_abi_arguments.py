@@ -47,6 +47,8 @@ for name, res, args in _abi.SIGNATURES:
         # a nonzero count with null buffers (the case a zero count would let through)
         if name in ("dcrt_tracer_trace_rays", "dcrt_tracer_occluded", "dcrt_tracer_trace_rays_device"):
             vals[2] = 7
+        if name == "dcrt_tracer_cast_rays":
+            vals[4] = 7
         if name == "dcrt_device_math_eval":
             vals[3] = 7
         if name in ("dcrt_device_bsdf_eval", "dcrt_device_bsdf_sample"):

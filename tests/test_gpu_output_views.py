@@ -14,10 +14,13 @@ material override, the albedo texture) and RayTracingCommon.inc.hlsl:88-116 (the
 transform): the library is built without FMA contraction and with correctly rounded division,
 square root and reciprocal, so the restatement matches to the bit, and must.
 
-The oracle's ray entry points strip the any-hit bit (oracle_trace_rays), so with
-ALLOW_ANYHIT_SHADER on, the values of pixels whose first hit is masked have no oracle: that case
-asserts the RNG state (one more draw than the opaque build: IntersectScene's opacity sample) and
-the sample positions only.
+oracle_trace_rays strips the any-hit bit, and these expectations are built from it: with
+ALLOW_ANYHIT_SHADER on, the values of pixels whose first hit is masked are not rebuilt here, and that
+case asserts the RNG state (one more draw than the opaque build: IntersectScene's opacity sample) and
+the sample positions only. The any-hit test itself -- oracle_cast_rays and the cast kernels' OPACITY
+variants, each ray with its opacity sample -- is held to a float64 reference by tests/test_ray_truth.py
+and tests/test_gpu_ray_truth.py; the view kernel's trace_full<..., OPACITY> has no ray-level entry and
+rests on its renders' bit equality with the oracle.
 """
 import ctypes as C
 import math
