@@ -78,22 +78,34 @@ bool BatchPoolLimit()
     return v;
 }
 
-template <typename T>
-int DeviceAlloc(T** p, size_t count, std::vector<void*>* owner)
-{
-    *p = nullptr;
-    if (count == 0) count = 1;
-    void* q = nullptr;
-    HIPCHECK(hipMalloc(&q, count * sizeof(T)));
-    *p = (T*)q;
-    if (owner) owner->push_back(q);
-    return DCRT_OK;
-}
-void FreeAll(std::vector<void*>* v)
-{
-    for (void* p : *v) (void)hipFree(p);
-    v->clear();
-}
+// The owner of a set of device allocations: a tracer's buffers that live and die together, or a
+// function's temporaries (a local group frees them on every return path; hipFree waits for the device).
+class DeviceGroup {
+public:
+    DeviceGroup() = default;
+    DeviceGroup(const DeviceGroup&) = delete;
+    DeviceGroup& operator=(const DeviceGroup&) = delete;
+    ~DeviceGroup() { Free(); }
+    template <typename T>
+    int Alloc(T** p, size_t count)
+    {
+        *p = nullptr;
+        if (count == 0) count = 1;
+        void* q = nullptr;
+        HIPCHECK(hipMalloc(&q, count * sizeof(T)));
+        *p = (T*)q;
+        ptrs.push_back(q);
+        return DCRT_OK;
+    }
+    void Free()
+    {
+        for (void* p : ptrs) (void)hipFree(p);
+        ptrs.clear();
+    }
+
+private:
+    std::vector<void*> ptrs;
+};
 
 FilterConsts MakeFilter(const dcrt_filter_params& p)   // SampleConvolution.cpp:100-130
 {
@@ -512,7 +524,7 @@ struct dcrt_tracer {
     // CONTROL / MATERIAL grids (ResidentGrid): workgroups that loop over the pool's 256-slot
     // "virtual workgroups" vb = blockIdx.x + round * gridDim.x
     uint32_t controlGrid = 0, materialGrid = 0;
-    std::vector<void*> poolAllocs;
+    DeviceGroup poolAllocs;
     PathPool pool{};                   // (queue pointers set per launch: LaunchIteration)
     float4* extRecs = nullptr;         // 2 parities x kShards x recCap extension-ray records (2 float4)
     PathStateA* stateRecsA = nullptr;  // 2 parities x kShards x recCap path state halves
@@ -527,7 +539,7 @@ struct dcrt_tracer {
     dcrt_bxdf_luts* dLuts = nullptr;
 
     // ---- scene and cast plan ----
-    std::vector<void*> sceneAllocs;
+    DeviceGroup sceneAllocs;
     bool hasScene = false;
     CastPlan plan;
     dcrt_upload_stats uploadStats{};
@@ -573,7 +585,7 @@ struct dcrt_tracer {
     uint32_t viewResidentOpacity = 0;  // the same for the ALLOW_ANYHIT_SHADER variant
 
     // ---- film, its rows and the sample textures ----
-    std::vector<void*> filmAllocs, sampleAllocs, rowAllocs;
+    DeviceGroup filmAllocs, sampleAllocs, rowAllocs;
     Film film{};
     uint32_t filmW = 0, filmH = 0;
     uint32_t rowCount = 0;             // rows this tracer path-traces (film.rowY)
@@ -589,6 +601,7 @@ struct dcrt_tracer {
     SampleOut* dSampleOut = nullptr;   // MATERIAL's copy of the sample pointers (EnsureSamples)
     SampleOut hSampleOut = {};
     void** dSourceLists = nullptr;     // accumulate_images: device copies of the caller's pointer lists
+    DeviceGroup sourceAllocs;
     uint32_t sourceCap = 0;
     FilterConsts* dFilter = nullptr;
     FilterConsts* hFilter = nullptr;   // pinned staging
@@ -633,7 +646,7 @@ struct dcrt_tracer {
     float4* guideAlbedo = nullptr;
     float4* denoised = nullptr;
     bool guidesRendered = false, hasDenoised = false;
-    std::vector<void*> denoiseAllocs;
+    DeviceGroup denoiseAllocs;
     float4* dnWork[2] = { nullptr, nullptr };   // (c.rgb, var), ping-pong
     float4* dnNormal = nullptr;        // decoded guides (n.xyz, 0), (a.xyz, 0)
     float4* dnAlbedo = nullptr;
@@ -646,7 +659,7 @@ struct dcrt_tracer {
     // with the tile count; the maps of the last dcrt_tracer_noise follow the film ----
     bool convergence = false;
     float4* halfFilm = nullptr;
-    std::vector<void*> halfAllocs, noiseAllocs, noiseMapAllocs;
+    DeviceGroup halfAllocs, noiseAllocs, noiseMapAllocs;
     uint32_t noiseTileCap = 0;
     float *nzSum = nullptr, *nzScratch[2] = { nullptr, nullptr }, *nzMax = nullptr, *nzErr = nullptr;
     uint32_t* nzCounts = nullptr;
@@ -660,7 +673,7 @@ struct dcrt_tracer {
     // blocksPerImage, every other launch the plain film. maskAllocs: sample_blocks_device's
     // scratch (the count words, flags when the caller passes none) ----
     bool adaptive = false;
-    std::vector<void*> adaptiveAllocs, maskAllocs;
+    DeviceGroup adaptiveAllocs, maskAllocs;
     uint32_t* dBlockFlags = nullptr;
     uint32_t* dBlockList = nullptr;
     uint32_t* dMaskCount = nullptr;    // [2]: compact_blocks_kernel's count and in-film pixels
@@ -762,7 +775,7 @@ struct dcrt_tracer {
     int Upload(T** dst, const T* src, size_t count, uint64_t* counted, size_t capacity = 0)
     {
         T* p = nullptr;
-        CHECKED(DeviceAlloc(&p, std::max(count, capacity), &sceneAllocs));
+        CHECKED(sceneAllocs.Alloc(&p, std::max(count, capacity)));
         if (count && src) {
             HIPCHECK(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, stream));
             *counted += count * sizeof(T);
@@ -821,20 +834,20 @@ dcrt_tracer::~dcrt_tracer()
     for (hipEvent_t e : stopEvents) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : dnEvents) (void)hipEventDestroy(e);
     for (hipEvent_t e : adEvents) if (e) (void)hipEventDestroy(e);
-    FreeAll(&denoiseAllocs);
-    FreeAll(&halfAllocs);
-    FreeAll(&noiseAllocs);
-    FreeAll(&noiseMapAllocs);
-    FreeAll(&adaptiveAllocs);
-    FreeAll(&maskAllocs);
+    denoiseAllocs.Free();
+    halfAllocs.Free();
+    noiseAllocs.Free();
+    noiseMapAllocs.Free();
+    adaptiveAllocs.Free();
+    maskAllocs.Free();
     if (hFilter) (void)hipHostFree(hFilter);
-    if (dSourceLists) (void)hipFree(dSourceLists);
+    sourceAllocs.Free();
     if (hStop) (void)hipHostFree(hStop);
-    FreeAll(&poolAllocs);
-    FreeAll(&sceneAllocs);
-    FreeAll(&filmAllocs);
-    FreeAll(&sampleAllocs);
-    FreeAll(&rowAllocs);
+    poolAllocs.Free();
+    sceneAllocs.Free();
+    filmAllocs.Free();
+    sampleAllocs.Free();
+    rowAllocs.Free();
     if (hCounters) (void)hipHostFree(hCounters);
     if (ownsStream && stream) (void)hipStreamDestroy(stream);
 }
@@ -873,11 +886,11 @@ int dcrt_tracer::Create(const dcrt_tracer_config& cfg)
     }
     // WavefrontPathTracer.cpp:120-264 (SoA instead of AoS)
     const size_t P = poolSize;
-    CHECKED(DeviceAlloc(&pool.hit, 2 * P, &poolAllocs));   // 2 float4 per extension-queue item
-    CHECKED(DeviceAlloc(&pool.pixel, P, &poolAllocs));
-    CHECKED(DeviceAlloc(&pool.flags, P, &poolAllocs));
-    CHECKED(DeviceAlloc(&pool.extOpacity, P, &poolAllocs));
-    CHECKED(DeviceAlloc(&pool.shadowOpacity, P, &poolAllocs));
+    CHECKED(poolAllocs.Alloc(&pool.hit, 2 * P));   // 2 float4 per extension-queue item
+    CHECKED(poolAllocs.Alloc(&pool.pixel, P));
+    CHECKED(poolAllocs.Alloc(&pool.flags, P));
+    CHECKED(poolAllocs.Alloc(&pool.extOpacity, P));
+    CHECKED(poolAllocs.Alloc(&pool.shadowOpacity, P));
     // the extension and finish queues: one per iteration parity (extRecs / finRecs)
     static_assert(kControlBlock == 256u && kMaterialBlock == 256u, "queue capacities assume 256-slot workgroups");
     const uint32_t V = poolSize / 256u;   // virtual workgroups (256 slots / items each)
@@ -910,32 +923,32 @@ int dcrt_tracer::Create(const dcrt_tracer_config& cfg)
     pool.recCap = std::min<uint32_t>(poolSize, 2u * ((V + kShards - 1) / kShards) * 256u);
     // (32-bit byte offsets address one parity's records: at most 2^32 bytes, e.g. 2^26 slots)
     if ((uint64_t)pool.recCap * kShards * 32u > (1ull << 32)) { SetLastError("path pool too large for the extension-queue records"); return DCRT_E_LIMIT; }
-    CHECKED(DeviceAlloc(&extRecs, (size_t)pool.recCap * kShards * 2 * 2, &poolAllocs));
+    CHECKED(poolAllocs.Alloc(&extRecs, (size_t)pool.recCap * kShards * 2 * 2));
     // the paths' state records and their shadow rays' results, at the same positions
-    CHECKED(DeviceAlloc(&stateRecsA, (size_t)pool.recCap * kShards * 2, &poolAllocs));
-    CHECKED(DeviceAlloc(&stateRecsB, (size_t)pool.recCap * kShards * 2, &poolAllocs));
-    CHECKED(DeviceAlloc(&shadowHits, (size_t)pool.recCap * kShards * 2, &poolAllocs));
+    CHECKED(poolAllocs.Alloc(&stateRecsA, (size_t)pool.recCap * kShards * 2));
+    CHECKED(poolAllocs.Alloc(&stateRecsB, (size_t)pool.recCap * kShards * 2));
+    CHECKED(poolAllocs.Alloc(&shadowHits, (size_t)pool.recCap * kShards * 2));
     // the shadow queue (filled and cast within one iteration): records + path slots
-    CHECKED(DeviceAlloc(&pool.shRec, (size_t)pool.recCap * kShards * 2, &poolAllocs));
-    CHECKED(DeviceAlloc(&pool.shadowQueue, (size_t)pool.recCap * kShards, &poolAllocs));
+    CHECKED(poolAllocs.Alloc(&pool.shRec, (size_t)pool.recCap * kShards * 2));
+    CHECKED(poolAllocs.Alloc(&pool.shadowQueue, (size_t)pool.recCap * kShards));
 
     // MATERIAL's virtual workgroup vb appends the paths it ends with a shadow ray pending to
     // finish shard vb mod kFinShards
     pool.finCap = ((V + kFinShards - 1) / kFinShards) * kMaterialBlock;
-    CHECKED(DeviceAlloc(&finRecs, (size_t)pool.finCap * kFinShards * 2, &poolAllocs));
-    CHECKED(DeviceAlloc(&finHits, (size_t)pool.finCap * kFinShards * 2, &poolAllocs));
+    CHECKED(poolAllocs.Alloc(&finRecs, (size_t)pool.finCap * kFinShards * 2));
+    CHECKED(poolAllocs.Alloc(&finHits, (size_t)pool.finCap * kFinShards * 2));
     pool.size = poolSize;
-    CHECKED(DeviceAlloc(&dFrame, 1, &poolAllocs));
-    CHECKED(DeviceAlloc(&dSampleOut, 1, &poolAllocs));
-    CHECKED(DeviceAlloc(&dCounters, 2, &poolAllocs));
-    CHECKED(DeviceAlloc(&dGlobals, 1, &poolAllocs));
-    CHECKED(DeviceAlloc(&dInstr, 8, &poolAllocs));
-    CHECKED(DeviceAlloc(&dLuts, 1, &poolAllocs));
+    CHECKED(poolAllocs.Alloc(&dFrame, 1));
+    CHECKED(poolAllocs.Alloc(&dSampleOut, 1));
+    CHECKED(poolAllocs.Alloc(&dCounters, 2));
+    CHECKED(poolAllocs.Alloc(&dGlobals, 1));
+    CHECKED(poolAllocs.Alloc(&dInstr, 8));
+    CHECKED(poolAllocs.Alloc(&dLuts, 1));
     HIPCHECK(hipMemsetAsync(dCounters, 0, 2 * sizeof(Counters), stream));
     HIPCHECK(hipMemsetAsync(dGlobals, 0, sizeof(Globals), stream));
     HIPCHECK(hipMemsetAsync(dInstr, 0, 8 * sizeof(unsigned long long), stream));
     HIPCHECK(hipHostMalloc((void**)&hCounters, 2 * sizeof(Counters), hipHostMallocDefault));
-    CHECKED(DeviceAlloc(&dFilter, 1, &poolAllocs));
+    CHECKED(poolAllocs.Alloc(&dFilter, 1));
     HIPCHECK(hipHostMalloc((void**)&hFilter, sizeof(FilterConsts), hipHostMallocDefault));
     HIPCHECK(hipHostMalloc((void**)&hStop, 8 * sizeof(uint32_t), hipHostMallocDefault));
     for (hipEvent_t& e : stopEvents) HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -961,11 +974,11 @@ int dcrt_tracer::BuildLuts()
         HIPCHECK(hipStreamSynchronize(stream));
         return DCRT_OK;
     }
-    std::vector<void*> tmp;
+    DeviceGroup scratch;
     float *brdf = nullptr, *brdfd = nullptr, *bsdf = nullptr;
-    CHECKED(DeviceAlloc(&brdf, DCRT_LUT_BRDF_COUNT, &tmp));
-    CHECKED(DeviceAlloc(&brdfd, DCRT_LUT_BRDF_DIELECTRIC_COUNT, &tmp));
-    CHECKED(DeviceAlloc(&bsdf, DCRT_LUT_BSDF_COUNT, &tmp));
+    CHECKED(scratch.Alloc(&brdf, DCRT_LUT_BRDF_COUNT));
+    CHECKED(scratch.Alloc(&brdfd, DCRT_LUT_BRDF_DIELECTRIC_COUNT));
+    CHECKED(scratch.Alloc(&bsdf, DCRT_LUT_BSDF_COUNT));
     hipLaunchKernelGGL(lut_integrate_kernel, dim3((DCRT_LUT_BRDF_COUNT + 63) / 64), dim3(64), 0, stream, 0, (uint32_t)DCRT_LUT_BRDF_COUNT, brdf);
     hipLaunchKernelGGL(lut_integrate_kernel, dim3((DCRT_LUT_BRDF_DIELECTRIC_COUNT + 63) / 64), dim3(64), 0, stream, 1,
                        (uint32_t)DCRT_LUT_BRDF_DIELECTRIC_COUNT, brdfd);
@@ -973,7 +986,7 @@ int dcrt_tracer::BuildLuts()
     hipLaunchKernelGGL(lut_finalize_kernel, dim3((DCRT_LUT_BRDF_DIELECTRIC_COUNT + 255) / 256), dim3(256), 0, stream, brdf, brdfd, bsdf, dLuts);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(stream));
-    FreeAll(&tmp);
+    scratch.Free();
     dcrt_bxdf_luts* cached = nullptr;
     if (hipMalloc((void**)&cached, sizeof(dcrt_bxdf_luts)) == hipSuccess) {
         if (hipMemcpy(cached, dLuts, sizeof(dcrt_bxdf_luts), hipMemcpyDeviceToDevice) == hipSuccess) g_lutCache[device] = cached;
@@ -1263,7 +1276,7 @@ int dcrt_tracer::UploadArrays(const dcrt_flat_scene& s, std::vector<uint32_t>* i
     CHECKED(ValidateLights(s.lights, s.light_count));
     HIPCHECK(hipStreamSynchronize(stream));
     InvalidateGraph();
-    FreeAll(&sceneAllocs);
+    sceneAllocs.Free();
     hasScene = false;
     dEnvProb = dEnvRowCdf = dEnvMarginal = nullptr;   // (the last scene's table went with sceneAllocs)
     ++uploadStats.scene_uploads;
@@ -1304,15 +1317,15 @@ int dcrt_tracer::UploadArrays(const dcrt_flat_scene& s, std::vector<uint32_t>* i
     dLights = lights;
     // (the materials' rows of the dielectric LUT: BuildDielRows fills them)
     dDielRows = nullptr;
-    if (s.material_count <= kDielRowsMaxMaterials) CHECKED(DeviceAlloc(&dDielRows, (size_t)s.material_count * kDielRowFloats, &sceneAllocs));
+    if (s.material_count <= kDielRowsMaxMaterials) CHECKED(sceneAllocs.Alloc(&dDielRows, (size_t)s.material_count * kDielRowFloats));
     dInstanceFlags = iflags;
     hostMaterials.assign(s.materials, s.materials + s.material_count);
     if (s.light_count) hostLights.assign(s.lights, s.lights + s.light_count);
     else hostLights.clear();
     float4* triVerts = nullptr;
     float4* triShade = nullptr;
-    CHECKED(DeviceAlloc(&triVerts, (size_t)s.triangle_count * 3, &sceneAllocs));
-    CHECKED(DeviceAlloc(&triShade, (size_t)s.triangle_count * 6, &sceneAllocs));
+    CHECKED(sceneAllocs.Alloc(&triVerts, (size_t)s.triangle_count * 3));
+    CHECKED(sceneAllocs.Alloc(&triShade, (size_t)s.triangle_count * 6));
     if (s.triangle_count)
         hipLaunchKernelGGL(build_tri_verts_kernel, dim3((s.triangle_count + 255) / 256), dim3(256), 0, stream, vtx, tris, mids,
                            s.triangle_count, triVerts, triShade);
@@ -1323,7 +1336,7 @@ int dcrt_tracer::UploadArrays(const dcrt_flat_scene& s, std::vector<uint32_t>* i
     if (s.triangle_count && dcrt::TriangleInstances(s, &triInstance)) {
         uint32_t* dTriInstance = nullptr;
         CHECKED(Upload(&dTriInstance, (const uint32_t*)triInstance.data(), s.triangle_count, geometry));
-        CHECKED(DeviceAlloc(&dTriFrames, (size_t)s.triangle_count * 3, &sceneAllocs));
+        CHECKED(sceneAllocs.Alloc(&dTriFrames, (size_t)s.triangle_count * 3));
         hipLaunchKernelGGL(build_tri_frames_kernel, dim3((s.triangle_count + 255) / 256), dim3(256), 0, stream, (const float4*)triVerts,
                            (const float4*)triShade, (const float4*)xf, (const uint32_t*)dTriInstance, s.triangle_count, dTriFrames);
         HIPCHECK(hipGetLastError());
@@ -1397,18 +1410,18 @@ int dcrt_tracer::BuildEnvTable()
     if (!plan.scene.envCube || n == 0u) return DCRT_OK;
     const uint32_t rows = 6u * n;
     const size_t texels = (size_t)rows * n;
-    std::vector<void*> tmp;
+    DeviceGroup scratch;
     double *rowSums = nullptr, *rowTotals = nullptr, *marginalSums = nullptr;
     float *prob = nullptr, *rowCdf = nullptr, *marginal = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     double total = 0.0;
     auto build = [&]() -> int {
-        CHECKED(DeviceAlloc(&rowSums, texels, &tmp));
-        CHECKED(DeviceAlloc(&rowTotals, (size_t)rows, &tmp));
-        CHECKED(DeviceAlloc(&marginalSums, (size_t)rows + 1, &tmp));
-        CHECKED(DeviceAlloc(&prob, texels, &sceneAllocs));
-        CHECKED(DeviceAlloc(&rowCdf, texels, &sceneAllocs));
-        CHECKED(DeviceAlloc(&marginal, (size_t)rows, &sceneAllocs));
+        CHECKED(scratch.Alloc(&rowSums, texels));
+        CHECKED(scratch.Alloc(&rowTotals, (size_t)rows));
+        CHECKED(scratch.Alloc(&marginalSums, (size_t)rows + 1));
+        CHECKED(sceneAllocs.Alloc(&prob, texels));
+        CHECKED(sceneAllocs.Alloc(&rowCdf, texels));
+        CHECKED(sceneAllocs.Alloc(&marginal, (size_t)rows));
         HIPCHECK(hipEventCreate(&e0));
         HIPCHECK(hipEventCreate(&e1));
         HIPCHECK(hipEventRecord(e0, stream));
@@ -1426,7 +1439,6 @@ int dcrt_tracer::BuildEnvTable()
     const int rc = build();
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    FreeAll(&tmp);
     if (rc != DCRT_OK) return rc;
     if (total > 0.0 && std::isfinite(total)) {
         dEnvProb = prob;
@@ -1635,8 +1647,8 @@ int dcrt_tracer::PlanFlatCast(const dcrt_flat_scene& s, const UploadKnobs& k)
     if (wanted && std::min(plainPerCU, cellsPerCU) >= flatPerCU && cellsLds <= 65536) {
         plan.cellsRes = wanted;
         plan.ldsFlat = cellsLds;
-        CHECKED(DeviceAlloc(&dCells, (size_t)6 * plan.cellsRes * plan.cellsRes, &sceneAllocs));
-        CHECKED(DeviceAlloc(&dCellLeaves, dcrt::kCellWords, &sceneAllocs));
+        CHECKED(sceneAllocs.Alloc(&dCells, (size_t)6 * plan.cellsRes * plan.cellsRes));
+        CHECKED(sceneAllocs.Alloc(&dCellLeaves, dcrt::kCellWords));
         cellNodes = flat;
         cellVertices.assign(s.vertices, s.vertices + s.vertex_count);
         cellTriangles.assign(s.triangles, s.triangles + (size_t)s.triangle_count * 3);
@@ -1688,7 +1700,7 @@ int dcrt_tracer::SizeGrids(const UploadKnobs& k)
         // the spill columns: stackSize entries per lane of the persistent ring grid
         const size_t words = (size_t)plan.resident[0][0] * block * plan.scene.stackSize;
         uint32_t* spill = nullptr;
-        CHECKED(DeviceAlloc(&spill, words, &sceneAllocs));
+        CHECKED(sceneAllocs.Alloc(&spill, words));
         HIPCHECK(hipMemsetAsync(spill, 0, words * 4, stream));
         plan.sceneRing = plan.scene;
         plan.sceneRing.stackRows = plan.ringRows;
@@ -1704,22 +1716,22 @@ int dcrt_tracer::EnsureFilm(uint32_t w, uint32_t h)
     if (w == 0 || h == 0 || w > 65535 || h > 65535) { SetLastError("invalid film resolution"); return DCRT_E_INVALID_ARG; }
     HIPCHECK(hipStreamSynchronize(stream));
     InvalidateGraph();
-    FreeAll(&filmAllocs);
-    FreeAll(&sampleAllocs);
+    filmAllocs.Free();
+    sampleAllocs.Free();
     sampleImages = 0;
     guideNormal = guideAlbedo = denoised = nullptr;   // (they follow the film: EnsureGuides)
     guidesRendered = hasDenoised = false;
-    FreeAll(&halfAllocs);                             // (the half film and the noise maps too)
-    FreeAll(&noiseMapAllocs);
+    halfAllocs.Free();                                // (the half film and the noise maps too)
+    noiseMapAllocs.Free();
     halfFilm = nullptr;
     noisePixelMap = noiseTileMap = nullptr;
     hasNoiseMaps = false;
     filmImages = 0;
     const size_t n = (size_t)w * h;
-    CHECKED(DeviceAlloc(&film.accum, n, &filmAllocs));
+    CHECKED(filmAllocs.Alloc(&film.accum, n));
     HIPCHECK(hipMemsetAsync(film.accum, 0, n * sizeof(float4), stream));
     if (convergence) {
-        CHECKED(DeviceAlloc(&halfFilm, n, &halfAllocs));
+        CHECKED(halfAllocs.Alloc(&halfFilm, n));
         HIPCHECK(hipMemsetAsync(halfFilm, 0, n * sizeof(float4), stream));
     }
     filmW = w; filmH = h;
@@ -1735,12 +1747,12 @@ int dcrt_tracer::EnsureSamples(uint32_t images)
     if (images <= sampleImages) return DCRT_OK;
     HIPCHECK(hipStreamSynchronize(stream));
     InvalidateGraph();
-    FreeAll(&sampleAllocs);
+    sampleAllocs.Free();
     const size_t n = (size_t)filmW * filmH * images;
-    CHECKED(DeviceAlloc(&film.samplePosition, n, &sampleAllocs));
-    CHECKED(DeviceAlloc(&film.sampleValue, n, &sampleAllocs));
+    CHECKED(sampleAllocs.Alloc(&film.samplePosition, n));
+    CHECKED(sampleAllocs.Alloc(&film.sampleValue, n));
     film.debugRng = nullptr;
-    if (debugRng) CHECKED(DeviceAlloc(&film.debugRng, n, &sampleAllocs));
+    if (debugRng) CHECKED(sampleAllocs.Alloc(&film.debugRng, n));
     HIPCHECK(hipMemsetAsync(film.samplePosition, 0, n * sizeof(float2), stream));
     HIPCHECK(hipMemsetAsync(film.sampleValue, 0, n * sizeof(float4), stream));
     if (film.debugRng) HIPCHECK(hipMemsetAsync(film.debugRng, 0, n * sizeof(uint4), stream));
@@ -1822,15 +1834,15 @@ int dcrt_tracer::BuildRows()
     }
     if (rows.empty()) rows.push_back(0);
     HIPCHECK(hipStreamSynchronize(stream));
-    FreeAll(&rowAllocs);
+    rowAllocs.Free();
     rowCount = (uint32_t)rows.size();
     bandCount = (rowCount + kBlockH - 1) / kBlockH;
     uint32_t* dRows = nullptr;
-    CHECKED(DeviceAlloc(&dRows, rows.size(), &rowAllocs));
+    CHECKED(rowAllocs.Alloc(&dRows, rows.size()));
     HIPCHECK(hipMemcpyAsync(dRows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, stream));
     uint32_t* dOwned = nullptr;
     if (!owned.empty()) {
-        CHECKED(DeviceAlloc(&dOwned, owned.size(), &rowAllocs));
+        CHECKED(rowAllocs.Alloc(&dOwned, owned.size()));
         HIPCHECK(hipMemcpyAsync(dOwned, owned.data(), owned.size() * 4, hipMemcpyHostToDevice, stream));
     }
     HIPCHECK(hipStreamSynchronize(stream));
@@ -1839,7 +1851,7 @@ int dcrt_tracer::BuildRows()
     film.rowCount = rowCount;
     dRowRays = nullptr;
     if (rowProbe) {   // (the probe's counters follow the film's height)
-        CHECKED(DeviceAlloc(&dRowRays, filmH, &rowAllocs));
+        CHECKED(rowAllocs.Alloc(&dRowRays, filmH));
         HIPCHECK(hipMemsetAsync(dRowRays, 0, (size_t)filmH * 4, stream));
         CHECKED(UploadSampleOut());
     }
@@ -2216,9 +2228,9 @@ int dcrt_tracer::EnsureGuides()
     if (guideNormal) return DCRT_OK;
     if (!film.accum) { SetLastError("no film"); return DCRT_E_INVALID_ARG; }
     const size_t n = (size_t)filmW * filmH;
-    CHECKED(DeviceAlloc(&guideNormal, n, &filmAllocs));
-    CHECKED(DeviceAlloc(&guideAlbedo, n, &filmAllocs));
-    CHECKED(DeviceAlloc(&denoised, n, &filmAllocs));
+    CHECKED(filmAllocs.Alloc(&guideNormal, n));
+    CHECKED(filmAllocs.Alloc(&guideAlbedo, n));
+    CHECKED(filmAllocs.Alloc(&denoised, n));
     return DCRT_OK;
 }
 
@@ -2275,14 +2287,14 @@ int dcrt_tracer::EnsureDenoiseWork(uint32_t w, uint32_t h)
 {
     if (w == dnW && h == dnH && dnWork[0]) return DCRT_OK;
     HIPCHECK(hipStreamSynchronize(stream));
-    FreeAll(&denoiseAllocs);
+    denoiseAllocs.Free();
     dnW = dnH = 0;
     dnWork[0] = dnWork[1] = dnNormal = dnAlbedo = nullptr;
     const size_t n = (size_t)w * h;
-    CHECKED(DeviceAlloc(&dnWork[0], n, &denoiseAllocs));
-    CHECKED(DeviceAlloc(&dnWork[1], n, &denoiseAllocs));
-    CHECKED(DeviceAlloc(&dnNormal, n, &denoiseAllocs));
-    CHECKED(DeviceAlloc(&dnAlbedo, n, &denoiseAllocs));
+    CHECKED(denoiseAllocs.Alloc(&dnWork[0], n));
+    CHECKED(denoiseAllocs.Alloc(&dnWork[1], n));
+    CHECKED(denoiseAllocs.Alloc(&dnNormal, n));
+    CHECKED(denoiseAllocs.Alloc(&dnAlbedo, n));
     dnW = w; dnH = h;
     return DCRT_OK;
 }
@@ -2540,10 +2552,9 @@ int dcrt_tracer::AccumulateImages(const void* const* pos, const void* const* val
     if (count == 0) return DCRT_OK;
     if (count > sourceCap) {
         HIPCHECK(hipStreamSynchronize(stream));
-        if (dSourceLists) (void)hipFree(dSourceLists);
-        dSourceLists = nullptr;
+        sourceAllocs.Free();
         sourceCap = 0;
-        HIPCHECK(hipMalloc(&dSourceLists, (size_t)count * 2 * sizeof(void*)));
+        CHECKED(sourceAllocs.Alloc(&dSourceLists, (size_t)count * 2));
         sourceCap = count;
     }
     std::vector<const void*> lists((size_t)count * 2);
@@ -2605,9 +2616,9 @@ int dcrt_tracer::SetConvergence(bool on)
     if (!film.accum) { SetLastError("set_convergence: no film (set the frame parameters first)"); return DCRT_E_INVALID_ARG; }
     HIPCHECK(hipStreamSynchronize(stream));
     if (on != convergence) InvalidateGraph();   // (the in-graph film pass is another kernel)
-    if (on && !halfFilm) CHECKED(DeviceAlloc(&halfFilm, (size_t)filmW * filmH, &halfAllocs));
+    if (on && !halfFilm) CHECKED(halfAllocs.Alloc(&halfFilm, (size_t)filmW * filmH));
     if (!on) {
-        FreeAll(&halfAllocs);
+        halfAllocs.Free();
         halfFilm = nullptr;
     }
     convergence = on;
@@ -2625,15 +2636,15 @@ int dcrt_tracer::Noise(uint32_t w, uint32_t h, const float4* f, const float4* hf
     const uint32_t T = (uint32_t)kNoiseTile, tilesX = (w + T - 1) / T, tilesY = (h + T - 1) / T, tiles = tilesX * tilesY;
     if (tiles > noiseTileCap) {
         HIPCHECK(hipStreamSynchronize(stream));
-        FreeAll(&noiseAllocs);
+        noiseAllocs.Free();
         noiseTileCap = 0;
-        CHECKED(DeviceAlloc(&nzSum, tiles, &noiseAllocs));
-        CHECKED(DeviceAlloc(&nzScratch[0], (tiles + 127) / 128, &noiseAllocs));
-        CHECKED(DeviceAlloc(&nzScratch[1], (tiles + 127) / 128, &noiseAllocs));
-        CHECKED(DeviceAlloc(&nzMax, tiles, &noiseAllocs));
-        CHECKED(DeviceAlloc(&nzErr, tiles, &noiseAllocs));
-        CHECKED(DeviceAlloc(&nzCounts, (size_t)tiles * 2, &noiseAllocs));
-        CHECKED(DeviceAlloc(&nzTotals, 1, &noiseAllocs));
+        CHECKED(noiseAllocs.Alloc(&nzSum, tiles));
+        CHECKED(noiseAllocs.Alloc(&nzScratch[0], (tiles + 127) / 128));
+        CHECKED(noiseAllocs.Alloc(&nzScratch[1], (tiles + 127) / 128));
+        CHECKED(noiseAllocs.Alloc(&nzMax, tiles));
+        CHECKED(noiseAllocs.Alloc(&nzErr, tiles));
+        CHECKED(noiseAllocs.Alloc(&nzCounts, (size_t)tiles * 2));
+        CHECKED(noiseAllocs.Alloc(&nzTotals, 1));
         noiseTileCap = tiles;
     }
     hipLaunchKernelGGL(noise_tile_kernel, dim3(tilesX, tilesY), dim3(T * T), 0, stream, f, hf, w, h, threshold, pixelMap, tileMap, nzSum,
@@ -2671,8 +2682,8 @@ int dcrt_tracer::NoiseOwn(float threshold, dcrt_noise_stats* out)
     if (!(threshold >= 0.0f)) { SetLastError("noise: the threshold is negative or NaN"); return DCRT_E_INVALID_ARG; }
     if (!noisePixelMap) {
         const uint32_t T = (uint32_t)kNoiseTile;
-        CHECKED(DeviceAlloc(&noisePixelMap, (size_t)filmW * filmH, &noiseMapAllocs));
-        CHECKED(DeviceAlloc(&noiseTileMap, (size_t)((filmW + T - 1) / T) * ((filmH + T - 1) / T), &noiseMapAllocs));
+        CHECKED(noiseMapAllocs.Alloc(&noisePixelMap, (size_t)filmW * filmH));
+        CHECKED(noiseMapAllocs.Alloc(&noiseTileMap, (size_t)((filmW + T - 1) / T) * ((filmH + T - 1) / T)));
     }
     hasNoiseMaps = false;
     CHECKED(Noise(filmW, filmH, film.accum, halfFilm, threshold, noisePixelMap, noiseTileMap, out));
@@ -2715,11 +2726,11 @@ int dcrt_tracer::AllocBlockList()
 {
     HIPCHECK(hipStreamSynchronize(stream));
     InvalidateGraph();   // (captured CONTROL launches hold the old list pointer)
-    FreeAll(&adaptiveAllocs);
+    adaptiveAllocs.Free();
     dBlockFlags = dBlockList = nullptr;
     blockTotal = ((filmW + kBlockW - 1) / kBlockW) * ((filmH + kBlockH - 1) / kBlockH);
-    CHECKED(DeviceAlloc(&dBlockFlags, blockTotal, &adaptiveAllocs));
-    CHECKED(DeviceAlloc(&dBlockList, blockTotal, &adaptiveAllocs));
+    CHECKED(adaptiveAllocs.Alloc(&dBlockFlags, blockTotal));
+    CHECKED(adaptiveAllocs.Alloc(&dBlockList, blockTotal));
     return ResetBlockList();
 }
 
@@ -2746,7 +2757,7 @@ int dcrt_tracer::SetAdaptive(bool on)
     InvalidateGraph();   // (the in-graph CONTROL launches take another Film)
     adaptive = on;
     if (on) return AllocBlockList();
-    FreeAll(&adaptiveAllocs);
+    adaptiveAllocs.Free();
     dBlockFlags = dBlockList = nullptr;
     blockTotal = listCount = listPixels = 0;
     return DCRT_OK;
@@ -2801,12 +2812,12 @@ int dcrt_tracer::SampleBlocks(uint32_t w, uint32_t h, const float4* f, const flo
     const uint32_t blocksX = (w + kBlockW - 1) / kBlockW, blocks = blocksX * ((h + kBlockH - 1) / kBlockH);
     if (!dMaskCount || (!flags && blocks > maskFlagCap)) {
         HIPCHECK(hipStreamSynchronize(stream));
-        FreeAll(&maskAllocs);
+        maskAllocs.Free();
         dMaskCount = dMaskFlags = nullptr;
         maskFlagCap = 0;
-        CHECKED(DeviceAlloc(&dMaskCount, 2, &maskAllocs));
+        CHECKED(maskAllocs.Alloc(&dMaskCount, 2));
         if (!flags) {
-            CHECKED(DeviceAlloc(&dMaskFlags, blocks, &maskAllocs));
+            CHECKED(maskAllocs.Alloc(&dMaskFlags, blocks));
             maskFlagCap = blocks;
         }
     }
@@ -2928,6 +2939,40 @@ int dcrt_tracer::RenderAdaptive(uint32_t firstSeed, const dcrt_converge_params& 
         SetLastError("hipSetDevice failed");                    \
         return DCRT_E_HIP;                                      \
     }
+
+// The one round trip of caller arrays, n items each: inputs up, one launch, outputs down, the stream synchronised.
+// The device copies come from the caller's group, which may hold more (ProbeScene's rows) and frees them all when
+// it goes. n == 0 copies and launches nothing; an array with neither side is left out (its device pointer stays null).
+struct HostArray {
+    const void* in;       // copied up, or null
+    void* out;            // copied down, or null
+    size_t bytesPerItem;
+    void* device = nullptr;
+};
+// `launch` takes no arguments: the caller picks the geometry (ItemGrid: one thread per item). A status it returns is kept.
+template <size_t N, typename Launch>
+static int RoundTrip(dcrt_tracer* t, DeviceGroup& group, uint32_t n, HostArray (&arrays)[N], Launch launch)
+{
+    int rc = DCRT_OK;
+    for (HostArray& a : arrays) {
+        if (rc != DCRT_OK || (!a.in && !a.out)) continue;
+        char* d = nullptr;
+        rc = group.Alloc(&d, (size_t)n * a.bytesPerItem);
+        a.device = d;
+        if (rc == DCRT_OK && a.in && n && hipMemcpyAsync(d, a.in, (size_t)n * a.bytesPerItem, hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    }
+    if (rc == DCRT_OK && n) {
+        if constexpr (std::is_void_v<decltype(launch())>) launch();
+        else rc = launch();
+        if (rc == DCRT_OK && hipGetLastError() != hipSuccess) rc = DCRT_E_HIP;
+    }
+    for (HostArray& a : arrays) {
+        if (rc == DCRT_OK && a.out && n && hipMemcpyAsync(a.out, a.device, (size_t)n * a.bytesPerItem, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    }
+    if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
+    return rc;
+}
+static dim3 ItemGrid(uint32_t n) { return dim3((n + 255) / 256); }   // (with dim3(256) threads)
 
 extern "C" {
 
@@ -3502,38 +3547,27 @@ static int TraceBatch(dcrt_tracer* t, const dcrt_ray* d_rays, uint32_t n, dcrt_r
     return DCRT_OK;
 }
 
-DCRT_API int dcrt_tracer_trace_rays(dcrt_tracer* t, const dcrt_ray* rays, uint32_t n, dcrt_ray_hit* out, uint32_t features)
+// trace_rays / occluded: the caller's rays through TraceBatch, to its hit records or its occlusion words
+static int TraceHostRays(dcrt_tracer* t, const dcrt_ray* rays, uint32_t n, void* out, bool any, uint32_t features)
 {
     TRACER_GUARD(t);
     if ((!rays || !out) && n) return DCRT_E_INVALID_ARG;
-    std::vector<void*> tmp;
-    dcrt_ray* dr = nullptr; dcrt_ray_hit* dh = nullptr;
-    CHECKED(DeviceAlloc(&dr, n, &tmp));
-    CHECKED(DeviceAlloc(&dh, n, &tmp));
-    int rc = DCRT_OK;
-    if (hipMemcpyAsync(dr, rays, (size_t)n * sizeof(dcrt_ray), hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (rc == DCRT_OK) rc = TraceBatch(t, dr, n, dh, nullptr, false, features);
-    if (rc == DCRT_OK && hipMemcpyAsync(out, dh, (size_t)n * sizeof(dcrt_ray_hit), hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    FreeAll(&tmp);
-    return rc;
+    if (!t->hasScene) { SetLastError("no scene uploaded"); return DCRT_E_NO_SCENE; }
+    DeviceGroup scratch;
+    HostArray a[2] = {{rays, nullptr, sizeof(dcrt_ray)}, {nullptr, out, any ? sizeof(uint32_t) : sizeof(dcrt_ray_hit)}};
+    return RoundTrip(t, scratch, n, a, [&] {
+        return TraceBatch(t, (const dcrt_ray*)a[0].device, n, any ? nullptr : (dcrt_ray_hit*)a[1].device, any ? (uint32_t*)a[1].device : nullptr, any, features);
+    });
+}
+
+DCRT_API int dcrt_tracer_trace_rays(dcrt_tracer* t, const dcrt_ray* rays, uint32_t n, dcrt_ray_hit* out, uint32_t features)
+{
+    return TraceHostRays(t, rays, n, out, false, features);
 }
 
 DCRT_API int dcrt_tracer_occluded(dcrt_tracer* t, const dcrt_ray* rays, uint32_t n, uint32_t* out, uint32_t features)
 {
-    TRACER_GUARD(t);
-    if ((!rays || !out) && n) return DCRT_E_INVALID_ARG;
-    std::vector<void*> tmp;
-    dcrt_ray* dr = nullptr; uint32_t* dOcc = nullptr;
-    CHECKED(DeviceAlloc(&dr, n, &tmp));
-    CHECKED(DeviceAlloc(&dOcc, n, &tmp));
-    int rc = DCRT_OK;
-    if (hipMemcpyAsync(dr, rays, (size_t)n * sizeof(dcrt_ray), hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (rc == DCRT_OK) rc = TraceBatch(t, dr, n, nullptr, dOcc, true, features);
-    if (rc == DCRT_OK && hipMemcpyAsync(out, dOcc, (size_t)n * 4, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    FreeAll(&tmp);
-    return rc;
+    return TraceHostRays(t, rays, n, out, true, features);
 }
 
 DCRT_API int dcrt_tracer_cast_rays(dcrt_tracer* t, const dcrt_ray* rays, const uint32_t* kinds, const float* opacity_samples, uint32_t n,
@@ -3554,31 +3588,16 @@ DCRT_API int dcrt_tracer_cast_rays(dcrt_tracer* t, const dcrt_ray* rays, const u
     *out_variant = (v.opacity ? DCRT_CAST_VARIANT_OPACITY : 0u) | (v.allCached ? DCRT_CAST_VARIANT_ALL_CACHED : 0u) |
                    (v.pair ? DCRT_CAST_VARIANT_PAIR : 0u) | (v.ident ? DCRT_CAST_VARIANT_IDENT : 0u) |
                    (v.ring ? DCRT_CAST_VARIANT_RING : 0u) | (v.flat ? DCRT_CAST_VARIANT_FLAT : 0u);
-    if (n == 0) return DCRT_OK;
-    std::vector<void*> tmp;
-    dcrt_ray* dr = nullptr; uint32_t* dKinds = nullptr; float* dOpacity = nullptr; dcrt_ray_hit* dh = nullptr; uint32_t* dOcc = nullptr;
-    CHECKED(DeviceAlloc(&dr, n, &tmp));
-    int rc = DeviceAlloc(&dKinds, n, &tmp);
-    if (rc == DCRT_OK && opacity) rc = DeviceAlloc(&dOpacity, n, &tmp);
-    if (rc == DCRT_OK) rc = DeviceAlloc(&dh, n, &tmp);
-    if (rc == DCRT_OK) rc = DeviceAlloc(&dOcc, n, &tmp);
-    if (rc == DCRT_OK && hipMemcpyAsync(dr, rays, (size_t)n * sizeof(dcrt_ray), hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (rc == DCRT_OK && hipMemcpyAsync(dKinds, kinds, (size_t)n * 4, hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (rc == DCRT_OK && opacity && hipMemcpyAsync(dOpacity, opacity_samples, (size_t)n * 4, hipMemcpyHostToDevice, t->stream) != hipSuccess)
-        rc = DCRT_E_HIP;
-    if (rc == DCRT_OK) {
+    DeviceGroup scratch;
+    HostArray a[5] = {{rays, nullptr, sizeof(dcrt_ray)}, {kinds, nullptr, 4}, {opacity ? opacity_samples : nullptr, nullptr, 4},
+                      {nullptr, out_hits, sizeof(dcrt_ray_hit)}, {nullptr, out_occluded, 4}};
+    return RoundTrip(t, scratch, n, a, [&] {
         // (the refill / park thresholds of a frame: BeginImage)
         const uint32_t refill = t->knobs.tuneOverride || t->plan.allCached ? t->knobs.refillLanes : DCRT_REFILL_GLOBAL;
         const uint32_t block = t->plan.block, grid = std::min<uint32_t>((n + block - 1) / block, cast.resident);
-        hipLaunchKernelGGL(row->rays, dim3(grid), dim3(block), cast.lds, t->stream, cast.scene, (const dcrt_ray*)dr, (const uint32_t*)dKinds,
-                           (const float*)dOpacity, n, features, refill, t->knobs.parkLanes, dh, dOcc);
-        if (hipGetLastError() != hipSuccess) rc = DCRT_E_HIP;
-    }
-    if (rc == DCRT_OK && hipMemcpyAsync(out_hits, dh, (size_t)n * sizeof(dcrt_ray_hit), hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (rc == DCRT_OK && hipMemcpyAsync(out_occluded, dOcc, (size_t)n * 4, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    FreeAll(&tmp);
-    return rc;
+        hipLaunchKernelGGL(row->rays, dim3(grid), dim3(block), cast.lds, t->stream, cast.scene, (const dcrt_ray*)a[0].device, (const uint32_t*)a[1].device,
+                           (const float*)a[2].device, n, features, refill, t->knobs.parkLanes, (dcrt_ray_hit*)a[3].device, (uint32_t*)a[4].device);
+    });
 }
 
 DCRT_API int dcrt_tracer_trace_occlusion_cells(dcrt_tracer* t, const dcrt_ray* rays, uint32_t n, uint32_t* out, uint32_t features)
@@ -3590,23 +3609,13 @@ DCRT_API int dcrt_tracer_trace_occlusion_cells(dcrt_tracer* t, const dcrt_ray* r
         SetLastError("the uploaded scene has no direction-cell table" + (t->cells.reason.empty() ? std::string() : ": " + t->cells.reason));
         return DCRT_E_NO_SCENE;
     }
-    if (n == 0) return DCRT_OK;
-    std::vector<void*> tmp;
-    dcrt_ray* dr = nullptr; uint32_t* dOcc = nullptr;
-    CHECKED(DeviceAlloc(&dr, n, &tmp));
-    CHECKED(DeviceAlloc(&dOcc, n, &tmp));
-    int rc = DCRT_OK;
-    if (hipMemcpyAsync(dr, rays, (size_t)n * sizeof(dcrt_ray), hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (rc == DCRT_OK) {
+    DeviceGroup scratch;
+    HostArray a[2] = {{rays, nullptr, sizeof(dcrt_ray)}, {nullptr, out, 4}};
+    return RoundTrip(t, scratch, n, a, [&] {
         const uint32_t block = t->plan.block, grid = std::min<uint32_t>((n + block - 1) / block, shipped.resident);
-        hipLaunchKernelGGL(cells_occlusion_kernel, dim3(grid), dim3(block), shipped.lds, t->stream, shipped.scene, (const dcrt_ray*)dr, n,
-                           features, dOcc);
-        if (hipGetLastError() != hipSuccess) rc = DCRT_E_HIP;
-    }
-    if (rc == DCRT_OK && hipMemcpyAsync(out, dOcc, (size_t)n * 4, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    FreeAll(&tmp);
-    return rc;
+        hipLaunchKernelGGL(cells_occlusion_kernel, dim3(grid), dim3(block), shipped.lds, t->stream, shipped.scene, (const dcrt_ray*)a[0].device, n,
+                           features, (uint32_t*)a[1].device);
+    });
 }
 
 DCRT_API int dcrt_tracer_trace_rays_device(dcrt_tracer* t, const void* d_rays, uint32_t n, void* d_hits, uint32_t features)
@@ -3670,16 +3679,15 @@ static int ResolveFrom(dcrt_tracer* t, const float4* image, const dcrt_postfx_pa
     const uint32_t W = t->filmW, H = t->filmH;
     float hth[255];
     dcrt_srgb_encode_thresholds(hth);
-    std::vector<void*> tmp;
-    struct Free { std::vector<void*>* v; ~Free() { FreeAll(v); } } guard{ &tmp };
+    DeviceGroup scratch;
     float* dth = nullptr;
-    CHECKED(DeviceAlloc(&dth, 255, &tmp));
+    CHECKED(scratch.Alloc(&dth, 255));
     HIPCHECK(hipMemcpyAsync(dth, hth, sizeof(hth), hipMemcpyHostToDevice, t->stream));
     // SumLuminance: REDUCE_TO_1D then REDUCE_TO_SINGLE until one value (SceneLuminance.cpp:110-190)
     const uint32_t bx = (((W + 7) / 8) + 1) / 2, by = (((H + 7) / 8) + 1) / 2;
     float *la = nullptr, *lb = nullptr;
-    CHECKED(DeviceAlloc(&la, (size_t)bx * by + 1, &tmp));
-    CHECKED(DeviceAlloc(&lb, (size_t)bx * by + 1, &tmp));
+    CHECKED(scratch.Alloc(&la, (size_t)bx * by + 1));
+    CHECKED(scratch.Alloc(&lb, (size_t)bx * by + 1));
     hipLaunchKernelGGL(luminance_1d_kernel, dim3(bx, by), dim3(64), 0, t->stream, image, W, H, bx, by, la);
     uint32_t count = bx * by;
     while (count != 1) {
@@ -3689,7 +3697,7 @@ static int ResolveFrom(dcrt_tracer* t, const float4* image, const dcrt_postfx_pa
         count = groups;
     }
     uchar4* dout = nullptr;
-    CHECKED(DeviceAlloc(&dout, (size_t)W * H, &tmp));
+    CHECKED(scratch.Alloc(&dout, (size_t)W * H));
     const uint32_t grid = std::max<uint32_t>(1u, std::min<uint32_t>((W * H + 255) / 256, kMaxPersistentBlocks));
     hipLaunchKernelGGL(postfx_kernel, dim3(grid), dim3(256), 0, t->stream, image, W, H, prm->enabled,
                        prm->auto_exposure, prm->ev100, prm->luminance_white * prm->luminance_white, (const float*)la,
@@ -3782,10 +3790,9 @@ DCRT_API int dcrt_tracer_denoise_images(dcrt_tracer* t, const dcrt_denoise_param
         return DCRT_E_INVALID_ARG;
     CHECKED(CheckDenoiseParams(*p));
     const size_t n = (size_t)width * height, bytes = n * sizeof(float4);
-    std::vector<void*> tmp;
-    struct Free { std::vector<void*>* v; ~Free() { FreeAll(v); } } guard{ &tmp };
+    DeviceGroup scratch;
     float4* d[4] = {};
-    for (float4*& q : d) CHECKED(DeviceAlloc(&q, n, &tmp));
+    for (float4*& q : d) CHECKED(scratch.Alloc(&q, n));
     const float* src[3] = { color, normal, albedo };
     for (int i = 0; i < 3; ++i) HIPCHECK(hipMemcpyAsync(d[i], src[i], bytes, hipMemcpyHostToDevice, t->stream));
     CHECKED(t->Denoise(*p, width, height, d[0], d[1], d[2], d[3]));
@@ -3836,20 +3843,11 @@ DCRT_API int dcrt_device_math_eval(dcrt_tracer* t, int function, const float* x,
 {
     TRACER_GUARD(t);
     if ((!x || !y) && n) return DCRT_E_INVALID_ARG;
-    std::vector<void*> tmp;
-    float *dx = nullptr, *dy = nullptr;
-    CHECKED(DeviceAlloc(&dx, n, &tmp));
-    CHECKED(DeviceAlloc(&dy, n, &tmp));
-    int rc = DCRT_OK;
-    if (hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (rc == DCRT_OK && n) {
-        hipLaunchKernelGGL(math_eval_kernel, dim3((n + 255) / 256), dim3(256), 0, t->stream, function, dx, n, dy);
-        if (hipGetLastError() != hipSuccess) rc = DCRT_E_HIP;
-    }
-    if (rc == DCRT_OK && hipMemcpyAsync(y, dy, (size_t)n * 4, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    FreeAll(&tmp);
-    return rc;
+    DeviceGroup scratch;
+    HostArray a[2] = {{x, nullptr, 4}, {nullptr, y, 4}};
+    return RoundTrip(t, scratch, n, a, [&] {
+        hipLaunchKernelGGL(math_eval_kernel, ItemGrid(n), dim3(256), 0, t->stream, function, (float*)a[0].device, n, (float*)a[1].device);
+    });
 }
 
 // A DeviceScene with nothing but the tracer's current LUTs (the BSDF probe kernels read no more).
@@ -3865,13 +3863,13 @@ static DeviceScene LutOnlyScene(const dcrt_tracer* t)
     return d;
 }
 // ... and, under DCRT_SHADING_TABLES' rows bit, the probe material's rows of the dielectric LUT (in
-// `tmp`), so the probe kernels run the path MATERIAL takes for a material with that alpha and ior.
-static int ProbeScene(dcrt_tracer* t, const dcrt_bsdf_probe_material& m, std::vector<void*>* tmp, DeviceScene* out)
+// `scratch`), so the probe kernels run the path MATERIAL takes for a material with that alpha and ior.
+static int ProbeScene(dcrt_tracer* t, const dcrt_bsdf_probe_material& m, DeviceGroup& scratch, DeviceScene* out)
 {
     *out = LutOnlyScene(t);
     if (!(ReadShadingKnobs().shadingTables & kTableDielRows)) return DCRT_OK;
     float* rows = nullptr;
-    CHECKED(DeviceAlloc(&rows, kDielRowFloats, tmp));
+    CHECKED(scratch.Alloc(&rows, kDielRowFloats));
     hipLaunchKernelGGL(probe_diel_rows_kernel, dim3(1), dim3(256), 0, t->stream, out->lutBrdfDielectric, out->lutBrdfDielectricAvg, rows,
                        m.alpha, m.ior[0]);
     HIPCHECK(hipGetLastError());
@@ -3885,101 +3883,67 @@ DCRT_API int dcrt_device_bsdf_eval(dcrt_tracer* t, const dcrt_bsdf_probe_materia
 {
     TRACER_GUARD(t);
     if (!m || ((!wi || !wo || !f || !pdf) && n)) return DCRT_E_INVALID_ARG;
-    std::vector<void*> tmp;
-    float *dwi = nullptr, *dwo = nullptr, *df = nullptr, *dpdf = nullptr;
-    CHECKED(DeviceAlloc(&dwi, (size_t)n * 3, &tmp));
-    CHECKED(DeviceAlloc(&dwo, (size_t)n * 3, &tmp));
-    CHECKED(DeviceAlloc(&df, (size_t)n * 3, &tmp));
-    CHECKED(DeviceAlloc(&dpdf, n, &tmp));
+    DeviceGroup scratch;
     DeviceScene ps;
-    if (const int prc = ProbeScene(t, *m, &tmp, &ps); prc != DCRT_OK) { FreeAll(&tmp); return prc; }
-    int rc = DCRT_OK;
-    if (hipMemcpyAsync(dwi, wi, (size_t)n * 12, hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (rc == DCRT_OK && hipMemcpyAsync(dwo, wo, (size_t)n * 12, hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (rc == DCRT_OK && n) {
-        hipLaunchKernelGGL(bsdf_eval_kernel, dim3((n + 255) / 256), dim3(256), 0, t->stream, ps, *m, features,
-                           (const float*)dwi, (const float*)dwo, n, df, dpdf);
-        if (hipGetLastError() != hipSuccess) rc = DCRT_E_HIP;
+    CHECKED(ProbeScene(t, *m, scratch, &ps));
+    HostArray a[4] = {{wi, nullptr, 12}, {wo, nullptr, 12}, {nullptr, f, 12}, {nullptr, pdf, 4}};
+    return RoundTrip(t, scratch, n, a, [&] {
+        hipLaunchKernelGGL(bsdf_eval_kernel, ItemGrid(n), dim3(256), 0, t->stream, ps, *m, features, (const float*)a[0].device,
+                           (const float*)a[1].device, n, (float*)a[2].device, (float*)a[3].device);
+    });
+}
+
+// The frame and intersection probes' scene: plan.scene's global-memory arrays with the frame table or without,
+// once the hit records' triangle and instance indices lie inside it
+static int HitProbeScene(dcrt_tracer* t, const uint32_t* records, uint32_t n, int use_table, const char* probe, DeviceScene* out)
+{
+    if (!t->hasScene || (use_table && !t->dTriFrames)) { SetLastError("no scene uploaded, or no frame table for it"); return DCRT_E_NO_SCENE; }
+    *out = t->plan.scene;
+    for (uint32_t i = 0; i < n; ++i) {
+        if ((records[4 * (size_t)i + 2] & 0x7FFFFFFFu) >= out->triangleCount || records[4 * (size_t)i + 3] >= out->instanceCount) {
+            SetLastError(std::string(probe) + ": triangle or instance index out of range");
+            return DCRT_E_INVALID_ARG;
+        }
     }
-    if (rc == DCRT_OK && hipMemcpyAsync(f, df, (size_t)n * 12, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (rc == DCRT_OK && hipMemcpyAsync(pdf, dpdf, (size_t)n * 4, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    FreeAll(&tmp);
-    return rc;
+    out->triFrames = use_table ? t->dTriFrames : nullptr;
+    return DCRT_OK;
 }
 
 DCRT_API int dcrt_device_frame_probe(dcrt_tracer* t, const uint32_t* records, uint32_t n, int use_table, float* out)
 {
     TRACER_GUARD(t);
     if ((!records || !out) && n) return DCRT_E_INVALID_ARG;
-    if (!t->hasScene || (use_table && !t->dTriFrames)) { SetLastError("no scene uploaded, or no frame table for it"); return DCRT_E_NO_SCENE; }
-    DeviceScene sc = t->plan.scene;   // (the global-memory arrays)
-    for (uint32_t i = 0; i < n; ++i) {
-        if ((records[4 * (size_t)i + 2] & 0x7FFFFFFFu) >= sc.triangleCount || records[4 * (size_t)i + 3] >= sc.instanceCount) {
-            SetLastError("frame probe: triangle or instance index out of range");
-            return DCRT_E_INVALID_ARG;
-        }
-    }
-    sc.triFrames = use_table ? t->dTriFrames : nullptr;
-    std::vector<void*> tmp;
-    uint4* drec = nullptr;
-    float* dout = nullptr;
-    int rc = DeviceAlloc(&drec, n, &tmp);
-    if (rc == DCRT_OK) rc = DeviceAlloc(&dout, (size_t)n * 9, &tmp);
-    if (rc == DCRT_OK && hipMemcpyAsync(drec, records, (size_t)n * 16, hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (rc == DCRT_OK && n) {
-        hipLaunchKernelGGL(frame_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, t->stream, sc, (const uint4*)drec, n, dout);
-        if (hipGetLastError() != hipSuccess) rc = DCRT_E_HIP;
-    }
-    if (rc == DCRT_OK && hipMemcpyAsync(out, dout, (size_t)n * 36, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    FreeAll(&tmp);
-    return rc;
+    DeviceScene sc;
+    CHECKED(HitProbeScene(t, records, n, use_table, "frame probe", &sc));
+    DeviceGroup scratch;
+    HostArray a[2] = {{records, nullptr, 16}, {nullptr, out, 36}};
+    return RoundTrip(t, scratch, n, a, [&] {
+        hipLaunchKernelGGL(frame_probe_kernel, ItemGrid(n), dim3(256), 0, t->stream, sc, (const uint4*)a[0].device, n, (float*)a[1].device);
+    });
 }
 
-}  // extern "C"
-
-// The shading probes' common shape: inputs up, one thread per item, outputs down, everything freed.
-struct ProbeBuffer {
-    const void* host;     // input (copied up), or null
-    void* hostOut;        // output (copied down), or null
-    size_t bytesPerItem;
-    void* device;
-};
-template <typename Launch>
-static int RunProbe(dcrt_tracer* t, uint32_t n, ProbeBuffer* buffers, size_t bufferCount, Launch launch)
+// A mesh light (MESH_LIGHT without POINT or DIRECTIONAL) and its range: first triangle, triangle count, instance
+static bool MeshLightRange(const dcrt_light& L, uint32_t w[3])
 {
-    std::vector<void*> tmp;
-    int rc = DCRT_OK;
-    for (size_t b = 0; b < bufferCount && rc == DCRT_OK; ++b) {
-        char* d = nullptr;
-        rc = DeviceAlloc(&d, (size_t)n * buffers[b].bytesPerItem, &tmp);
-        buffers[b].device = d;
-        if (rc == DCRT_OK && buffers[b].host && n &&
-            hipMemcpyAsync(d, buffers[b].host, (size_t)n * buffers[b].bytesPerItem, hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    }
-    if (rc == DCRT_OK && n) {
-        launch(dim3((n + 255) / 256), dim3(256));
-        if (hipGetLastError() != hipSuccess) rc = DCRT_E_HIP;
-    }
-    for (size_t b = 0; b < bufferCount && rc == DCRT_OK; ++b) {
-        if (buffers[b].hostOut && n &&
-            hipMemcpyAsync(buffers[b].hostOut, buffers[b].device, (size_t)n * buffers[b].bytesPerItem, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    }
-    if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    FreeAll(&tmp);
-    return rc;
+    if (!(L.flags & DCRT_LIGHT_FLAGS_MESH_LIGHT) || (L.flags & (DCRT_LIGHT_FLAGS_POINT_LIGHT | DCRT_LIGHT_FLAGS_DIRECTIONAL_LIGHT))) return false;
+    std::memcpy(w, L.position_or_triangle_range, 3 * sizeof(uint32_t));
+    return true;
 }
-
-extern "C" {
-
 // A mesh light's triangle range and instance lie inside the uploaded scene (the probes read them)
 static bool LightInScene(const dcrt_light& L, const DeviceScene& sc)
 {
-    if (!(L.flags & DCRT_LIGHT_FLAGS_MESH_LIGHT) || (L.flags & (DCRT_LIGHT_FLAGS_POINT_LIGHT | DCRT_LIGHT_FLAGS_DIRECTIONAL_LIGHT))) return true;
     uint32_t w[3];
-    std::memcpy(w, L.position_or_triangle_range, sizeof(w));
+    if (!MeshLightRange(L, w)) return true;
     return w[1] != 0u && w[0] < sc.triangleCount && w[1] <= sc.triangleCount - w[0] && w[2] < sc.instanceCount;
+}
+// The light probes' kernels for the scene's MATERIAL variant: the cube sampled by its table, or the any-scene stack
+static auto LightSampleProbe(const dcrt_tracer* t)
+{
+    return t->material.caps == kCapAllEnvImportance ? light_sample_probe_kernel<kCapAllEnvImportance> : light_sample_probe_kernel<kCapAll>;
+}
+static auto LightEvalProbe(const dcrt_tracer* t)
+{
+    return t->material.caps == kCapAllEnvImportance ? light_eval_probe_kernel<kCapAllEnvImportance> : light_eval_probe_kernel<kCapAll>;
 }
 
 DCRT_API int dcrt_device_camera_ray(dcrt_tracer* t, const float* film, const float* aperture, uint32_t n, float* origins, float* directions)
@@ -3990,9 +3954,10 @@ DCRT_API int dcrt_device_camera_ray(dcrt_tracer* t, const float* film, const flo
     FrameConstants fc;
     std::memset(&fc, 0, sizeof(fc));
     FillCameraConstants(t->frame, &fc);
-    ProbeBuffer b[4] = {{film, nullptr, 8, nullptr}, {aperture, nullptr, 12, nullptr}, {nullptr, origins, 12, nullptr}, {nullptr, directions, 12, nullptr}};
-    return RunProbe(t, n, b, 4, [&](dim3 grid, dim3 block) {
-        hipLaunchKernelGGL(camera_ray_probe_kernel, grid, block, 0, t->stream, fc, (const float*)b[0].device, (const float*)b[1].device, n,
+    DeviceGroup scratch;
+    HostArray b[4] = {{film, nullptr, 8}, {aperture, nullptr, 12}, {nullptr, origins, 12}, {nullptr, directions, 12}};
+    return RoundTrip(t, scratch, n, b, [&] {
+        hipLaunchKernelGGL(camera_ray_probe_kernel, ItemGrid(n), dim3(256), 0, t->stream, fc, (const float*)b[0].device, (const float*)b[1].device, n,
                            (float*)b[2].device, (float*)b[3].device);
     });
 }
@@ -4002,19 +3967,13 @@ DCRT_API int dcrt_device_intersection_probe(dcrt_tracer* t, const uint32_t* reco
 {
     TRACER_GUARD(t);
     if ((!records || !out_floats || !out_words) && n) return DCRT_E_INVALID_ARG;
-    if (!t->hasScene || (use_table && !t->dTriFrames)) { SetLastError("no scene uploaded, or no frame table for it"); return DCRT_E_NO_SCENE; }
-    DeviceScene sc = t->plan.scene;   // (the global-memory arrays)
-    for (uint32_t i = 0; i < n; ++i) {
-        if ((records[4 * (size_t)i + 2] & 0x7FFFFFFFu) >= sc.triangleCount || records[4 * (size_t)i + 3] >= sc.instanceCount) {
-            SetLastError("intersection probe: triangle or instance index out of range");
-            return DCRT_E_INVALID_ARG;
-        }
-    }
-    sc.triFrames = use_table ? t->dTriFrames : nullptr;
-    ProbeBuffer b[3] = {{records, nullptr, 16, nullptr}, {nullptr, out_floats, 64, nullptr}, {nullptr, out_words, 12, nullptr}};
-    return RunProbe(t, n, b, 3, [&](dim3 grid, dim3 block) {
-        if (use_table) hipLaunchKernelGGL(intersection_probe_kernel<true>, grid, block, 0, t->stream, sc, (const uint4*)b[0].device, n, (float*)b[1].device, (uint32_t*)b[2].device);
-        else hipLaunchKernelGGL(intersection_probe_kernel<false>, grid, block, 0, t->stream, sc, (const uint4*)b[0].device, n, (float*)b[1].device, (uint32_t*)b[2].device);
+    DeviceScene sc;
+    CHECKED(HitProbeScene(t, records, n, use_table, "intersection probe", &sc));
+    DeviceGroup scratch;
+    HostArray b[3] = {{records, nullptr, 16}, {nullptr, out_floats, 64}, {nullptr, out_words, 12}};
+    return RoundTrip(t, scratch, n, b, [&] {
+        if (use_table) hipLaunchKernelGGL(intersection_probe_kernel<true>, ItemGrid(n), dim3(256), 0, t->stream, sc, (const uint4*)b[0].device, n, (float*)b[1].device, (uint32_t*)b[2].device);
+        else hipLaunchKernelGGL(intersection_probe_kernel<false>, ItemGrid(n), dim3(256), 0, t->stream, sc, (const uint4*)b[0].device, n, (float*)b[1].device, (uint32_t*)b[2].device);
     });
 }
 
@@ -4053,10 +4012,8 @@ DCRT_API int dcrt_device_light_sample(dcrt_tracer* t, const float* points, const
         const float li = floorf(draw[0] * (float)lightCount);
         bool ok = li < (float)lightCount;
         if (ok) {
-            const dcrt_light& L = t->hostLights[(uint32_t)li];
-            if ((L.flags & DCRT_LIGHT_FLAGS_MESH_LIGHT) && !(L.flags & (DCRT_LIGHT_FLAGS_POINT_LIGHT | DCRT_LIGHT_FLAGS_DIRECTIONAL_LIGHT))) {
-                uint32_t w[3];
-                std::memcpy(w, L.position_or_triangle_range, sizeof(w));
+            uint32_t w[3];
+            if (MeshLightRange(t->hostLights[(uint32_t)li], w)) {
                 const float tri = (float)w[0] + floorf(draw[1] * (float)w[1]);
                 ok = tri < (float)t->plan.scene.triangleCount && (uint32_t)tri < t->plan.scene.triangleCount;
             }
@@ -4064,9 +4021,10 @@ DCRT_API int dcrt_device_light_sample(dcrt_tracer* t, const float* points, const
         if (!ok) { SetLastError("light sample probe: a state selects past the lights or the triangles"); return DCRT_E_INVALID_ARG; }
     }
     const DeviceScene sc = t->plan.scene;
-    ProbeBuffer b[4] = {{points, nullptr, 12, nullptr}, {states, nullptr, 16, nullptr}, {nullptr, out_floats, 32, nullptr}, {nullptr, out_words, 20, nullptr}};
-    return RunProbe(t, n, b, 4, [&](dim3 grid, dim3 block) {
-        hipLaunchKernelGGL(t->material.caps == kCapAllEnvImportance ? light_sample_probe_kernel<kCapAllEnvImportance> : light_sample_probe_kernel<kCapAll>, grid, block, 0, t->stream, sc, lightCount, (const float*)b[0].device, (const uint4*)b[1].device, n,
+    DeviceGroup scratch;
+    HostArray b[4] = {{points, nullptr, 12}, {states, nullptr, 16}, {nullptr, out_floats, 32}, {nullptr, out_words, 20}};
+    return RoundTrip(t, scratch, n, b, [&] {
+        hipLaunchKernelGGL(LightSampleProbe(t), ItemGrid(n), dim3(256), 0, t->stream, sc, lightCount, (const float*)b[0].device, (const uint4*)b[1].device, n,
                            (float*)b[2].device, (uint32_t*)b[3].device);
     });
 }
@@ -4084,9 +4042,10 @@ DCRT_API int dcrt_device_light_eval(dcrt_tracer* t, const uint32_t* light_triang
         }
     }
     const DeviceScene sc = t->plan.scene;
-    ProbeBuffer b[3] = {{light_triangle, nullptr, 8, nullptr}, {normal_wi_distance, nullptr, 28, nullptr}, {nullptr, out, 16, nullptr}};
-    return RunProbe(t, n, b, 3, [&](dim3 grid, dim3 block) {
-        hipLaunchKernelGGL(t->material.caps == kCapAllEnvImportance ? light_eval_probe_kernel<kCapAllEnvImportance> : light_eval_probe_kernel<kCapAll>, grid, block, 0, t->stream, sc, lightCount, (const uint32_t*)b[0].device, (const float*)b[1].device, n,
+    DeviceGroup scratch;
+    HostArray b[3] = {{light_triangle, nullptr, 8}, {normal_wi_distance, nullptr, 28}, {nullptr, out, 16}};
+    return RoundTrip(t, scratch, n, b, [&] {
+        hipLaunchKernelGGL(LightEvalProbe(t), ItemGrid(n), dim3(256), 0, t->stream, sc, lightCount, (const uint32_t*)b[0].device, (const float*)b[1].device, n,
                            (float*)b[2].device);
     });
 }
@@ -4131,9 +4090,10 @@ DCRT_API int dcrt_device_env_lookup(dcrt_tracer* t, const float* directions, uin
     if ((!directions || !out_rgb) && n) return DCRT_E_INVALID_ARG;
     if (!t->hasScene || !t->plan.scene.envCube || t->plan.scene.envCubeSize == 0u) { SetLastError("no scene uploaded, or no environment cube in it"); return DCRT_E_NO_SCENE; }
     const DeviceScene sc = t->plan.scene;
-    ProbeBuffer b[2] = {{directions, nullptr, 12, nullptr}, {nullptr, out_rgb, 12, nullptr}};
-    return RunProbe(t, n, b, 2, [&](dim3 grid, dim3 block) {
-        hipLaunchKernelGGL(env_lookup_probe_kernel, grid, block, 0, t->stream, sc, (const float*)b[0].device, n, (float*)b[1].device);
+    DeviceGroup scratch;
+    HostArray b[2] = {{directions, nullptr, 12}, {nullptr, out_rgb, 12}};
+    return RoundTrip(t, scratch, n, b, [&] {
+        hipLaunchKernelGGL(env_lookup_probe_kernel, ItemGrid(n), dim3(256), 0, t->stream, sc, (const float*)b[0].device, n, (float*)b[1].device);
     });
 }
 
@@ -4142,32 +4102,14 @@ DCRT_API int dcrt_device_bsdf_sample(dcrt_tracer* t, const dcrt_bsdf_probe_mater
 {
     TRACER_GUARD(t);
     if (!m || ((!wo || !u || !wi || !f || !pdf || !delta) && n)) return DCRT_E_INVALID_ARG;
-    std::vector<void*> tmp;
-    float *dwo = nullptr, *du = nullptr, *dwi = nullptr, *df = nullptr, *dpdf = nullptr;
-    uint32_t* ddelta = nullptr;
-    CHECKED(DeviceAlloc(&dwo, (size_t)n * 3, &tmp));
-    CHECKED(DeviceAlloc(&du, (size_t)n * 3, &tmp));
-    CHECKED(DeviceAlloc(&dwi, (size_t)n * 3, &tmp));
-    CHECKED(DeviceAlloc(&df, (size_t)n * 3, &tmp));
-    CHECKED(DeviceAlloc(&dpdf, n, &tmp));
-    CHECKED(DeviceAlloc(&ddelta, n, &tmp));
+    DeviceGroup scratch;
     DeviceScene ps;
-    if (const int prc = ProbeScene(t, *m, &tmp, &ps); prc != DCRT_OK) { FreeAll(&tmp); return prc; }
-    int rc = DCRT_OK;
-    if (hipMemcpyAsync(dwo, wo, (size_t)n * 12, hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (rc == DCRT_OK && hipMemcpyAsync(du, u, (size_t)n * 12, hipMemcpyHostToDevice, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (rc == DCRT_OK && n) {
-        hipLaunchKernelGGL(bsdf_sample_kernel, dim3((n + 255) / 256), dim3(256), 0, t->stream, ps, *m, features,
-                           (const float*)dwo, (const float*)du, n, dwi, df, dpdf, ddelta);
-        if (hipGetLastError() != hipSuccess) rc = DCRT_E_HIP;
-    }
-    if (rc == DCRT_OK && hipMemcpyAsync(wi, dwi, (size_t)n * 12, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (rc == DCRT_OK && hipMemcpyAsync(f, df, (size_t)n * 12, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (rc == DCRT_OK && hipMemcpyAsync(pdf, dpdf, (size_t)n * 4, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (rc == DCRT_OK && hipMemcpyAsync(delta, ddelta, (size_t)n * 4, hipMemcpyDeviceToHost, t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    if (hipStreamSynchronize(t->stream) != hipSuccess) rc = DCRT_E_HIP;
-    FreeAll(&tmp);
-    return rc;
+    CHECKED(ProbeScene(t, *m, scratch, &ps));
+    HostArray a[6] = {{wo, nullptr, 12}, {u, nullptr, 12}, {nullptr, wi, 12}, {nullptr, f, 12}, {nullptr, pdf, 4}, {nullptr, delta, 4}};
+    return RoundTrip(t, scratch, n, a, [&] {
+        hipLaunchKernelGGL(bsdf_sample_kernel, ItemGrid(n), dim3(256), 0, t->stream, ps, *m, features, (const float*)a[0].device,
+                           (const float*)a[1].device, n, (float*)a[2].device, (float*)a[3].device, (float*)a[4].device, (uint32_t*)a[5].device);
+    });
 }
 
 }  // extern "C"
