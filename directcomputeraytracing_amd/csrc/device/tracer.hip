@@ -107,6 +107,64 @@ private:
     std::vector<void*> ptrs;
 };
 
+// Pinned host staging for one T or T[N]: what a device-to-host copy of a few words lands in before the
+// stream is synchronised. Allocated once (Alloc: again is free), freed with its owner.
+template <typename T, size_t N = 1>
+class Pinned {
+public:
+    Pinned() = default;
+    Pinned(const Pinned&) = delete;
+    Pinned& operator=(const Pinned&) = delete;
+    ~Pinned()
+    {
+        if (p) (void)hipHostFree(p);
+    }
+    int Alloc()
+    {
+        if (!p) HIPCHECK(hipHostMalloc((void**)&p, N * sizeof(T), hipHostMallocDefault));
+        return DCRT_OK;
+    }
+    T* get() const { return p; }
+    T& operator[](size_t i) const { return p[i]; }
+
+private:
+    T* p = nullptr;
+};
+
+// Events recorded between the kernels of one stage (ext_timing): mark i stands in front of kernel i, so
+// kernel i took ElapsedBetween(i, i + 1). The events are created on first use and kept.
+class EventMarks {
+public:
+    EventMarks() = default;
+    EventMarks(const EventMarks&) = delete;
+    EventMarks& operator=(const EventMarks&) = delete;
+    ~EventMarks()
+    {
+        for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    }
+    void Reset() { used = 0; }
+    uint32_t Count() const { return used; }
+    int Mark(hipStream_t stream)
+    {
+        if (events.size() <= used) {
+            hipEvent_t e;
+            HIPCHECK(hipEventCreate(&e));
+            events.push_back(e);
+        }
+        HIPCHECK(hipEventRecord(events[used++], stream));
+        return DCRT_OK;
+    }
+    int ElapsedBetween(uint32_t i, uint32_t j, float* ms) const
+    {
+        HIPCHECK(hipEventElapsedTime(ms, events[i], events[j]));
+        return DCRT_OK;
+    }
+
+private:
+    std::vector<hipEvent_t> events;
+    uint32_t used = 0;
+};
+
 FilterConsts MakeFilter(const dcrt_filter_params& p)   // SampleConvolution.cpp:100-130
 {
     FilterConsts c;
@@ -164,6 +222,281 @@ struct Annotation {
         if (on) roctx().pop();
     }
 };
+
+// ---- The three stages that work on any W x H device images once the samples exist. Each owns its device
+// scratch, its pinned staging and its event marks, takes the stream (and whether ext_timing is on) per call,
+// and knows nothing of the tracer that holds it.
+// The filter of dcrt.h "film denoiser"
+class FilmDenoiser {
+public:
+    int Run(hipStream_t stream, bool timing, const dcrt_denoise_params& p, uint32_t w, uint32_t h, const float4* color, const float4* normal,
+            const float4* albedo, float4* out);
+    // ms per kernel of the last Run that was timed (prologue, variance, passes): at most `capacity` of *outCount
+    int Timings(float* outMs, uint32_t capacity, uint32_t* outCount) const;
+
+private:
+    int EnsureWork(hipStream_t stream, uint32_t w, uint32_t h);
+    DeviceGroup allocs;
+    float4* work[2] = { nullptr, nullptr };   // (c.rgb, var), ping-pong
+    float4* guideN = nullptr;                 // decoded guides (n.xyz, 0), (a.xyz, 0)
+    float4* guideA = nullptr;
+    uint32_t width = 0, height = 0;           // of the working images
+    EventMarks marks;                         // one per kernel boundary of the last Run
+};
+// The noise kernels over a film and its half film (dcrt.h "film noise estimate")
+class NoiseEstimator {
+public:
+    int Run(hipStream_t stream, uint32_t w, uint32_t h, const float4* f, const float4* hf, float threshold, float* pixelMap, float* tileMap,
+            dcrt_noise_stats* out);
+
+private:
+    DeviceGroup allocs;                       // grows with the tile count
+    uint32_t tileCap = 0;
+    float *sum = nullptr, *scratch[2] = { nullptr, nullptr }, *tileMax = nullptr, *tileErr = nullptr;
+    uint32_t* counts = nullptr;
+    NoiseTotals* totals = nullptr;
+    Pinned<NoiseTotals> hostTotals;
+};
+// The block lists of dcrt.h "adaptive sampling": the mask and compaction kernels, and the sentinel fill
+class BlockSampler {
+public:
+    int Run(hipStream_t stream, bool timing, uint32_t w, uint32_t h, const float4* f, const float4* hf, float threshold, uint32_t margin,
+            uint32_t* flags, uint32_t* list, uint32_t* outCount, uint32_t* outPixels);
+    // The sentinel sample into the inactive pixels of `slots` sample images
+    int Fill(hipStream_t stream, bool timing, float2* pos, float4* val, const uint32_t* flags, uint32_t w, uint32_t h, uint32_t slots);
+    // ms of the last Run's two kernels and the last Fill's, 0 where that one was not timed
+    int Timings(float* maskMs, float* compactMs, float* fillMs) const;
+
+private:
+    DeviceGroup allocs;
+    uint32_t* count = nullptr;                // [2]: compact_blocks_kernel's count and in-film pixels
+    uint32_t* ownFlags = nullptr;             // when the caller passes none
+    uint32_t flagCap = 0;
+    Pinned<uint32_t, 2> hostCount;
+    EventMarks maskMarks, fillMarks;          // 3 and 2 marks when timed, else none
+};
+
+int FilmDenoiser::EnsureWork(hipStream_t stream, uint32_t w, uint32_t h)
+{
+    if (w == width && h == height && work[0]) return DCRT_OK;
+    HIPCHECK(hipStreamSynchronize(stream));
+    allocs.Free();
+    width = height = 0;
+    work[0] = work[1] = guideN = guideA = nullptr;
+    const size_t n = (size_t)w * h;
+    CHECKED(allocs.Alloc(&work[0], n));
+    CHECKED(allocs.Alloc(&work[1], n));
+    CHECKED(allocs.Alloc(&guideN, n));
+    CHECKED(allocs.Alloc(&guideA, n));
+    width = w; height = h;
+    return DCRT_OK;
+}
+
+static int CheckDenoiseParams(const dcrt_denoise_params& p)
+{
+    if (p.iterations < 1u || p.iterations > 8u) { SetLastError("denoise: iterations 1..8"); return DCRT_E_INVALID_ARG; }
+    for (const float s : { p.sigma_luminance, p.sigma_normal, p.sigma_albedo }) {
+        if (!(s >= 0.0f) || !std::isfinite(s)) { SetLastError("denoise: sigmas are finite and >= 0 (0 switches a term off)"); return DCRT_E_INVALID_ARG; }
+    }
+    return DCRT_OK;
+}
+
+// The lattice stride L of the pass at `step` (DESIGN "Film denoiser", profiles/denoise_ab_pass.txt):
+// 0 every tap from memory; 1 the LDS-staged pixel tile (halo 2 * step); L > 1 the LDS-staged
+// lattice of every L-th pixel, its taps step / L points apart. DCRT_DENOISE_PASS=global | tile |
+// lattice (L = step) | latticeN (L = min(N, step)) forces one for an A/B, where its span fits.
+// All compute the same bits. The default is what measured fastest per step at 1920x1080
+// (profiles/denoise_ab_pass.txt): the tile up to step 4; from memory at step 8 (the lattice's
+// staging loads lie 128 B apart there and take twice as long); the lattice at 16 and 32; from
+// memory again at 64 and 128, where most taps fall outside the image and most lattice
+// workgroups hold a handful of points.
+static uint32_t DenoisePassLattice(uint32_t step)
+{
+    uint32_t L = step <= 4u ? 1u : (step == 16u || step == 32u) ? step : 0u;
+    if (const char* e = std::getenv("DCRT_DENOISE_PASS")) {
+        uint32_t want = L;
+        if (!std::strcmp(e, "global")) want = 0u;
+        else if (!std::strcmp(e, "tile")) want = 1u;
+        else if (!std::strcmp(e, "lattice")) want = step;
+        else if (!std::strncmp(e, "lattice", 7)) want = std::min<uint32_t>(step, std::max(1, std::atoi(e + 7)));
+        // (a stride that divides the step and leaves taps at most 4 lattice points apart: 48 KiB of LDS)
+        if (want == 0u || (step % want == 0u && step / want <= 4u)) L = want;
+    }
+    return L;
+}
+
+// The filter of dcrt.h "film denoiser" over W x H device images in film convention, into `out`
+// (c_N * d, 1): prologue (resolve + pack), variance estimate, `iterations` a-trous passes that
+// ping-pong between the two working images, the last one remodulating into `out`. Synchronous.
+// timing: a mark in front of every kernel and one behind the last.
+int FilmDenoiser::Run(hipStream_t stream, bool timing, const dcrt_denoise_params& p, uint32_t w, uint32_t h, const float4* color,
+                      const float4* normal, const float4* albedo, float4* out)
+{
+    Annotation an("Denoise");
+    CHECKED(CheckDenoiseParams(p));
+    if (w == 0 || h == 0 || w > 65535u || h > 65535u) { SetLastError("denoise: invalid image size"); return DCRT_E_INVALID_ARG; }
+    if (!color || !normal || !albedo || !out) { SetLastError("denoise: null image"); return DCRT_E_INVALID_ARG; }
+    const size_t n = (size_t)w * h, bytes = n * sizeof(float4);
+    for (const float4* in : { color, normal, albedo }) {
+        const char *a = (const char*)in, *b = (const char*)out;
+        if (a < b + bytes && b < a + bytes) { SetLastError("denoise: the output image overlaps an input"); return DCRT_E_INVALID_ARG; }
+    }
+    CHECKED(EnsureWork(stream, w, h));
+    DenoiseConsts k;
+    k.sigmaL = p.sigma_luminance;
+    k.kn = p.sigma_normal > 0.0f ? 1.0f / (p.sigma_normal * p.sigma_normal) : 0.0f;
+    k.ka = p.sigma_albedo > 0.0f ? 1.0f / (p.sigma_albedo * p.sigma_albedo) : 0.0f;
+    k.demodulate = p.demodulate ? 1u : 0u;
+    marks.Reset();
+    auto mark = [&] { return timing ? marks.Mark(stream) : (int)DCRT_OK; };
+    const int W = (int)w, H = (int)h;
+    const uint32_t tiles = ((w + kDnTile - 1) / kDnTile) * ((h + kDnTile - 1) / kDnTile);
+    CHECKED(mark());
+    hipLaunchKernelGGL(denoise_prologue_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)((n + 255) / 256), kMaxPersistentBlocks * 4u))),
+                       dim3(256), 0, stream, color, normal, albedo, (uint32_t)n, k.demodulate, work[0], guideN, guideA);
+    CHECKED(mark());
+    hipLaunchKernelGGL(denoise_variance_kernel, dim3(tiles), dim3(kDnThreads), 0, stream, k, (const float4*)work[0],
+                       (const float4*)guideN, (const float4*)guideA, W, H, work[1]);
+    CHECKED(mark());
+    uint32_t src = 1;
+    for (uint32_t i = 0; i < p.iterations; ++i) {
+        const uint32_t step = 1u << i;
+        float4* finalOut = i + 1 == p.iterations ? out : nullptr;
+        uint32_t L = DenoisePassLattice(step);
+        const uint32_t Ls = std::max(1u, L), t = step / Ls, span = (uint32_t)kDnTile + 4u * t;
+        const uint64_t blocks = (uint64_t)Ls * Ls * (((w + Ls - 1) / Ls + kDnTile - 1) / kDnTile) * (((h + Ls - 1) / Ls + kDnTile - 1) / kDnTile);
+        if (blocks > 0x7FFFFFFFull) L = 0u;   // (a lattice of a huge image at a large step: more classes than a grid holds)
+        if (L == 0u) {
+            hipLaunchKernelGGL(denoise_pass_global_kernel, dim3(tiles), dim3(kDnThreads), 0, stream, k, (const float4*)work[src],
+                               (const float4*)guideN, (const float4*)guideA, W, H, (int)step, work[src ^ 1u], finalOut);
+        } else {
+            hipLaunchKernelGGL(denoise_pass_staged_kernel, dim3((uint32_t)blocks), dim3(kDnThreads), (size_t)3 * span * span * sizeof(float4),
+                               stream, k, (const float4*)work[src], (const float4*)guideN, (const float4*)guideA, W, H, (int)step,
+                               (int)L, work[src ^ 1u], finalOut);
+        }
+        CHECKED(mark());
+        src ^= 1u;
+    }
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(stream));
+    return DCRT_OK;
+}
+
+int FilmDenoiser::Timings(float* outMs, uint32_t capacity, uint32_t* outCount) const
+{
+    const uint32_t kernels = marks.Count() ? marks.Count() - 1u : 0u;
+    *outCount = kernels;
+    for (uint32_t i = 0; i < kernels && i < capacity; ++i) CHECKED(marks.ElapsedBetween(i, i + 1, &outMs[i]));
+    return DCRT_OK;
+}
+
+// The noise kernels over a film and its half film (dcrt.h): tiles, the 128-group reduction of
+// the tile sums with luminance_single_kernel, counts and maxima; one copy of the totals back.
+int NoiseEstimator::Run(hipStream_t stream, uint32_t w, uint32_t h, const float4* f, const float4* hf, float threshold, float* pixelMap,
+                        float* tileMap, dcrt_noise_stats* out)
+{
+    Annotation an("Noise estimate");
+    if (!f || !hf || !out || w == 0 || h == 0 || w > 65535u || h > 65535u) return DCRT_E_INVALID_ARG;
+    if (!(threshold >= 0.0f)) { SetLastError("noise: the threshold is negative or NaN"); return DCRT_E_INVALID_ARG; }
+    const uint32_t T = (uint32_t)kNoiseTile, tilesX = (w + T - 1) / T, tilesY = (h + T - 1) / T, tiles = tilesX * tilesY;
+    if (tiles > tileCap) {
+        HIPCHECK(hipStreamSynchronize(stream));
+        allocs.Free();
+        tileCap = 0;
+        CHECKED(allocs.Alloc(&sum, tiles));
+        CHECKED(allocs.Alloc(&scratch[0], (tiles + 127) / 128));
+        CHECKED(allocs.Alloc(&scratch[1], (tiles + 127) / 128));
+        CHECKED(allocs.Alloc(&tileMax, tiles));
+        CHECKED(allocs.Alloc(&tileErr, tiles));
+        CHECKED(allocs.Alloc(&counts, (size_t)tiles * 2));
+        CHECKED(allocs.Alloc(&totals, 1));
+        tileCap = tiles;
+    }
+    hipLaunchKernelGGL(noise_tile_kernel, dim3(tilesX, tilesY), dim3(T * T), 0, stream, f, hf, w, h, threshold, pixelMap, tileMap, sum,
+                       tileMax, tileErr, counts);
+    const float* in = sum;
+    uint32_t count = tiles, side = 0;
+    while (count != 1) {
+        const uint32_t groups = (count + 127) / 128;
+        hipLaunchKernelGGL(luminance_single_kernel, dim3(groups), dim3(128), 0, stream, in, count, scratch[side]);
+        in = scratch[side];
+        side ^= 1u;
+        count = groups;
+    }
+    hipLaunchKernelGGL(noise_finish_kernel, dim3(1), dim3(256), 0, stream, (const float*)tileMax, (const float*)tileErr,
+                       (const uint32_t*)counts, tiles, in, totals);
+    HIPCHECK(hipGetLastError());
+    CHECKED(hostTotals.Alloc());
+    const NoiseTotals* host = hostTotals.get();
+    HIPCHECK(hipMemcpyAsync(hostTotals.get(), totals, sizeof(NoiseTotals), hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+    out->images = 0;
+    out->valid_pixels = host->valid;
+    out->converged_pixels = host->converged;
+    out->mean_error = host->valid ? host->total / (float)host->valid : 0.0f;
+    out->max_error = host->maxError;
+    out->max_tile_error = host->maxTileError;
+    return DCRT_OK;
+}
+
+// sample_mask_kernel + compact_blocks_kernel over a film and its half film; the copy of the count
+// (and the listed blocks' pixels) is the one synchronisation.
+int BlockSampler::Run(hipStream_t stream, bool timing, uint32_t w, uint32_t h, const float4* f, const float4* hf, float threshold, uint32_t margin,
+                      uint32_t* flags, uint32_t* list, uint32_t* outCount, uint32_t* outPixels)
+{
+    Annotation an("Sample blocks");
+    if (!f || !hf || !list || !outCount || w == 0 || h == 0 || w > 65535u || h > 65535u) return DCRT_E_INVALID_ARG;
+    if (!(threshold >= 0.0f)) { SetLastError("sample blocks: the threshold is negative or NaN"); return DCRT_E_INVALID_ARG; }
+    const uint32_t blocksX = (w + kBlockW - 1) / kBlockW, blocks = blocksX * ((h + kBlockH - 1) / kBlockH);
+    if (!count || (!flags && blocks > flagCap)) {
+        HIPCHECK(hipStreamSynchronize(stream));
+        allocs.Free();
+        count = ownFlags = nullptr;
+        flagCap = 0;
+        CHECKED(allocs.Alloc(&count, 2));
+        if (!flags) {
+            CHECKED(allocs.Alloc(&ownFlags, blocks));
+            flagCap = blocks;
+        }
+    }
+    if (!flags) flags = ownFlags;
+    CHECKED(hostCount.Alloc());
+    maskMarks.Reset();
+    if (timing) CHECKED(maskMarks.Mark(stream));
+    hipLaunchKernelGGL(sample_mask_kernel, dim3((blocks + 3) / 4), dim3(256), 0, stream, f, hf, w, h, threshold, margin, blocksX, blocks, flags);
+    if (timing) CHECKED(maskMarks.Mark(stream));
+    hipLaunchKernelGGL(compact_blocks_kernel, dim3(1), dim3(256), 0, stream, (const uint32_t*)flags, blocks, blocksX, w, h, list, count);
+    if (timing) CHECKED(maskMarks.Mark(stream));
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(hostCount.get(), count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+    *outCount = hostCount[0];
+    if (outPixels) *outPixels = hostCount[1];
+    return DCRT_OK;
+}
+
+int BlockSampler::Fill(hipStream_t stream, bool timing, float2* pos, float4* val, const uint32_t* flags, uint32_t w, uint32_t h, uint32_t slots)
+{
+    const uint32_t n = w * h;
+    fillMarks.Reset();
+    if (timing) CHECKED(fillMarks.Mark(stream));
+    hipLaunchKernelGGL(fill_inactive_samples_kernel, dim3(std::min<uint32_t>((n + 255) / 256, 8u * kMaxPersistentBlocks)), dim3(256), 0, stream,
+                       pos, val, flags, w, h, (w + kBlockW - 1) / kBlockW, slots);
+    HIPCHECK(hipGetLastError());
+    if (timing) CHECKED(fillMarks.Mark(stream));
+    return DCRT_OK;
+}
+
+int BlockSampler::Timings(float* maskMs, float* compactMs, float* fillMs) const
+{
+    *maskMs = *compactMs = *fillMs = 0.0f;
+    if (maskMarks.Count() == 3u) {
+        CHECKED(maskMarks.ElapsedBetween(0, 1, maskMs));
+        CHECKED(maskMarks.ElapsedBetween(1, 2, compactMs));
+    }
+    if (fillMarks.Count() == 2u) CHECKED(fillMarks.ElapsedBetween(0, 1, fillMs));
+    return DCRT_OK;
+}
 
 // A cast_kernel variant, by its template parameters: instrumented counts x ALLOW_ANYHIT_SHADER x
 // whole scene in the LDS cache x pair-expanding traversal (the non-counting kernels of scenes not
@@ -511,6 +844,15 @@ struct dcrt_tracer {
     int device = 0;
     hipStream_t stream = nullptr;
     bool ownsStream = false;
+    // The first member, so the last to go: every member below frees what it owns (device groups, pinned staging,
+    // the stages' scratch and marks) before the stream is destroyed, as ~dcrt_tracer always had it.
+    struct StreamEnd {
+        dcrt_tracer* t;
+        ~StreamEnd()
+        {
+            if (t->ownsStream && t->stream) (void)hipStreamDestroy(t->stream);
+        }
+    } streamEnd{ this };
     uint32_t cuCount = 1;              // compute units (the persistent grids' factor)
     CreateKnobs knobs;
     uint32_t iterationsPerRender = kDefaultIterations;
@@ -535,7 +877,7 @@ struct dcrt_tracer {
     FrameConstants* dFrame = nullptr;
     Counters* dCounters = nullptr;     // [2]
     Globals* dGlobals = nullptr;
-    Counters* hCounters = nullptr;     // pinned [2]
+    Pinned<uint32_t> hPoolIdle;        // ReadCompletion's copy of Globals::poolIdle
     dcrt_bxdf_luts* dLuts = nullptr;
 
     // ---- scene and cast plan ----
@@ -604,7 +946,7 @@ struct dcrt_tracer {
     DeviceGroup sourceAllocs;
     uint32_t sourceCap = 0;
     FilterConsts* dFilter = nullptr;
-    FilterConsts* hFilter = nullptr;   // pinned staging
+    Pinned<FilterConsts> hFilter;      // its staging
     dcrt_filter_params lastFilter{};   // the reconstruction filter on the device (UploadFilter)
     bool hasFilter = false;
     uint32_t filmImages = 0;           // images convolved into the film since the last clear
@@ -623,7 +965,7 @@ struct dcrt_tracer {
         hipGraphExec_t exec = nullptr;
         uint32_t iters = 0;
     } graphs[3];   // unsequenced (Render), sequenced (RenderImages), sequenced tail chunks
-    uint32_t* hStop = nullptr;         // pinned [4][2]: Globals::stopped, imagesDone per poll
+    Pinned<uint32_t, 8> hStop;         // [4][2]: Globals::stopped, imagesDone per poll
     hipEvent_t stopEvents[4] = {};
 
     // ---- instrumentation ----
@@ -641,59 +983,39 @@ struct dcrt_tracer {
     uint64_t kindLaunches[kTimedKinds] = {};
 
     // ---- the film denoiser (dcrt_tracer_render_guides / dcrt_tracer_denoise*): two guide films and the
-    // denoised image follow the film (filmAllocs); the working images follow the denoised size ----
+    // denoised image follow the film (filmAllocs); the filter and its working images are `denoiser` ----
     float4* guideNormal = nullptr;
     float4* guideAlbedo = nullptr;
     float4* denoised = nullptr;
     bool guidesRendered = false, hasDenoised = false;
-    DeviceGroup denoiseAllocs;
-    float4* dnWork[2] = { nullptr, nullptr };   // (c.rgb, var), ping-pong
-    float4* dnNormal = nullptr;        // decoded guides (n.xyz, 0), (a.xyz, 0)
-    float4* dnAlbedo = nullptr;
-    uint32_t dnW = 0, dnH = 0;
-    std::vector<hipEvent_t> dnEvents;  // ext_timing: one event per kernel boundary of the last denoise
-    uint32_t dnEventsUsed = 0;
+    FilmDenoiser denoiser;
 
     // ---- the film noise estimate (dcrt_tracer_set_convergence / dcrt_tracer_noise*): the half film takes
-    // every other image of the film's (even film image counts); the kernels' working buffers grow
-    // with the tile count; the maps of the last dcrt_tracer_noise follow the film ----
+    // every other image of the film's (even film image counts); the maps of the last dcrt_tracer_noise
+    // follow the film; the kernels and their working buffers are `noiseEstimator` ----
     bool convergence = false;
     float4* halfFilm = nullptr;
-    DeviceGroup halfAllocs, noiseAllocs, noiseMapAllocs;
-    uint32_t noiseTileCap = 0;
-    float *nzSum = nullptr, *nzScratch[2] = { nullptr, nullptr }, *nzMax = nullptr, *nzErr = nullptr;
-    uint32_t* nzCounts = nullptr;
-    NoiseTotals* nzTotals = nullptr;
+    DeviceGroup halfAllocs, noiseMapAllocs;
     float *noisePixelMap = nullptr, *noiseTileMap = nullptr;
     bool hasNoiseMaps = false;
+    NoiseEstimator noiseEstimator;
 
     // ---- adaptive sampling (dcrt_tracer_set_adaptive): one flag per 8x8 block of the film and the
     // ascending list of the active ones, both with room for every block (adaptiveAllocs: they
     // follow the film's size); RenderImages' kernels get `dBlockList` and the list's length as
-    // blocksPerImage, every other launch the plain film. maskAllocs: sample_blocks_device's
-    // scratch (the count words, flags when the caller passes none) ----
+    // blocksPerImage, every other launch the plain film. The mask, compaction and fill kernels
+    // are `blockSampler` ----
     bool adaptive = false;
-    DeviceGroup adaptiveAllocs, maskAllocs;
+    DeviceGroup adaptiveAllocs;
     uint32_t* dBlockFlags = nullptr;
     uint32_t* dBlockList = nullptr;
-    uint32_t* dMaskCount = nullptr;    // [2]: compact_blocks_kernel's count and in-film pixels
-    uint32_t* dMaskFlags = nullptr;
-    uint32_t maskFlagCap = 0;
+    BlockSampler blockSampler;
     uint32_t blockTotal = 0;           // blocks of the film: blocksX * ceil(H / 8)
     uint32_t listCount = 0;            // active blocks
     uint32_t listPixels = 0;           // their pixels inside the film: the paths an image starts
     bool inactiveFilled = false;       // every slot's inactive pixels hold the sentinel sample
     bool listFrame = false;            // BeginImage: the frame constants' blocksPerImage is the list's length
     uint64_t pathsSkipped = 0;         // pixels the lists left out since the last ResetStats (counters())
-    // ext_timing: events around the last mask, compaction and fill kernels (dcrt_tracer_adaptive_timings)
-    hipEvent_t adEvents[5] = {};
-    bool adMaskTimed = false, adFillTimed = false;
-    int AdaptiveEvents()
-    {
-        for (hipEvent_t& e : adEvents)
-            if (!e) HIPCHECK(hipEventCreate(&e));
-        return DCRT_OK;
-    }
 
     ~dcrt_tracer();
     int Create(const dcrt_tracer_config& cfg);
@@ -725,10 +1047,26 @@ struct dcrt_tracer {
     int UploadSampleOut();
     int SetRowProbe(bool on);
     int EnsureSamples(uint32_t images);
+    int CheckHalo(float radius) const;
+    // The sample textures' slot 0 holds another image now (a view or guide image): no kept slots, no sentinel fill
+    void SlotZeroOverwritten()
+    {
+        keptSlots = false;
+        inactiveFilled = false;
+        lastSlot = 0;
+    }
     int UploadFilter(const dcrt_filter_params& f);
     int ClearFilm();
+    int LaunchFilm(const Film& target, float4* half, bool timed, uint32_t images, const Globals* guard, const float2* const* posList,
+                   const float4* const* valList, uint32_t firstIndex);
     int LaunchFilm(uint32_t images, const Globals* guard, const float2* const* posList, const float4* const* valList,
-                   uint32_t firstIndex);
+                   uint32_t firstIndex)
+    {
+        return LaunchFilm(film, convergence ? halfFilm : nullptr, extTiming && !capturing, images, guard, posList, valList, firstIndex);
+    }
+    int AddFilm(float4* dst, const void* src);
+    int ReadImage(const float4* image, float* out);
+    int NeedHalfFilm() const;
     int AccumulateImages(const void* const* pos, const void* const* val, uint32_t count, const dcrt_filter_params& filter);
     int Accumulate(const dcrt_filter_params& filter);
     // rendering
@@ -748,27 +1086,23 @@ struct dcrt_tracer {
     // denoiser, noise estimate
     int EnsureGuides();
     int RenderGuides(uint32_t firstSeed, uint32_t count);
-    int EnsureDenoiseWork(uint32_t w, uint32_t h);
-    int Denoise(const dcrt_denoise_params& p, uint32_t w, uint32_t h, const float4* color, const float4* normal,
-                const float4* albedo, float4* out);
     int SetConvergence(bool on);
-    int Noise(uint32_t w, uint32_t h, const float4* f, const float4* hf, float threshold, float* pixelMap, float* tileMap,
-              dcrt_noise_stats* out);
     int NoiseOwn(float threshold, dcrt_noise_stats* out);
+    // render_converged, and with `adaptiveCall` render_adaptive
+    struct AdaptiveCall {
+        uint32_t margin;                 // 0xFFFFFFFF: the filter's window rows
+        dcrt_adaptive_report* report;    // filled in once the call has started on every block, or null
+    };
     int RenderConverged(uint32_t firstSeed, const dcrt_converge_params& p, const dcrt_filter_params& filter, dcrt_noise_stats* outStats,
-                        int* outConverged);
+                        int* outConverged, const AdaptiveCall* adaptiveCall = nullptr);
     // adaptive sampling
     int SetAdaptive(bool on);
     int AllocBlockList();
     int ResetBlockList();
     int SetSampleBlocks(const uint32_t* blocks, uint32_t count);
     int GetSampleBlocks(uint32_t* out, uint32_t capacity, uint32_t* outCount);
-    int SampleBlocks(uint32_t w, uint32_t h, const float4* f, const float4* hf, float threshold, uint32_t margin, uint32_t* flags,
-                     uint32_t* list, uint32_t* outCount, uint32_t* outPixels);
     int UpdateSampleBlocks(float threshold, uint32_t margin, uint32_t* outActive);
     int FillInactive();
-    int RenderAdaptive(uint32_t firstSeed, const dcrt_converge_params& p, uint32_t margin, const dcrt_filter_params& filter,
-                       dcrt_noise_stats* outStats, int* outConverged, dcrt_adaptive_report* report);
 
     // One device array of the scene: allocated (sceneAllocs), filled from `src` and counted in `*counted`
     template <typename T>
@@ -825,6 +1159,8 @@ struct dcrt_tracer {
     }
 };
 
+// (the members free what they own once this has made the device current, waited for the stream and dropped the
+// graphs; `streamEnd` then destroys the stream)
 dcrt_tracer::~dcrt_tracer()
 {
     (void)hipSetDevice(device);
@@ -832,24 +1168,6 @@ dcrt_tracer::~dcrt_tracer()
     InvalidateGraph();
     for (hipEvent_t e : events) (void)hipEventDestroy(e);
     for (hipEvent_t e : stopEvents) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : dnEvents) (void)hipEventDestroy(e);
-    for (hipEvent_t e : adEvents) if (e) (void)hipEventDestroy(e);
-    denoiseAllocs.Free();
-    halfAllocs.Free();
-    noiseAllocs.Free();
-    noiseMapAllocs.Free();
-    adaptiveAllocs.Free();
-    maskAllocs.Free();
-    if (hFilter) (void)hipHostFree(hFilter);
-    sourceAllocs.Free();
-    if (hStop) (void)hipHostFree(hStop);
-    poolAllocs.Free();
-    sceneAllocs.Free();
-    filmAllocs.Free();
-    sampleAllocs.Free();
-    rowAllocs.Free();
-    if (hCounters) (void)hipHostFree(hCounters);
-    if (ownsStream && stream) (void)hipStreamDestroy(stream);
 }
 
 int dcrt_tracer::Create(const dcrt_tracer_config& cfg)
@@ -947,10 +1265,10 @@ int dcrt_tracer::Create(const dcrt_tracer_config& cfg)
     HIPCHECK(hipMemsetAsync(dCounters, 0, 2 * sizeof(Counters), stream));
     HIPCHECK(hipMemsetAsync(dGlobals, 0, sizeof(Globals), stream));
     HIPCHECK(hipMemsetAsync(dInstr, 0, 8 * sizeof(unsigned long long), stream));
-    HIPCHECK(hipHostMalloc((void**)&hCounters, 2 * sizeof(Counters), hipHostMallocDefault));
+    CHECKED(hPoolIdle.Alloc());
     CHECKED(poolAllocs.Alloc(&dFilter, 1));
-    HIPCHECK(hipHostMalloc((void**)&hFilter, sizeof(FilterConsts), hipHostMallocDefault));
-    HIPCHECK(hipHostMalloc((void**)&hStop, 8 * sizeof(uint32_t), hipHostMallocDefault));
+    CHECKED(hFilter.Alloc());
+    CHECKED(hStop.Alloc());
     for (hipEvent_t& e : stopEvents) HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     CHECKED(BuildLuts());
     HIPCHECK(hipStreamSynchronize(stream));
@@ -1879,6 +2197,19 @@ int dcrt_tracer::SetRowProbe(bool on)
     return UploadSampleOut();
 }
 
+// A partitioned or banded film's convolution reads the filter's window rows beyond its stripes: refuse a
+// radius that needs more of them than the halo the tracer renders
+int dcrt_tracer::CheckHalo(float radius) const
+{
+    if (partition.world_size <= 1 && bands.empty()) return DCRT_OK;
+    const uint32_t halo = partition.halo_rows ? partition.halo_rows : 2u;
+    if (!(radius >= 0.0f) || FilterSupportRows(radius, filmH) > halo) {
+        SetLastError("filter radius needs more halo rows than the film partition renders");
+        return DCRT_E_INVALID_ARG;
+    }
+    return DCRT_OK;
+}
+
 int dcrt_tracer::SetFrame(const dcrt_frame_params& p)
 {
     if (p.resolution[0] == 0 || p.resolution[1] == 0 || p.max_bounce_count > DCRT_MAX_RAY_BOUNCE) {
@@ -2145,10 +2476,9 @@ int dcrt_tracer::RunIterations(uint32_t n)
 // iteration and none was started (Globals::poolIdle). Here exact, not 2 frames late.
 int dcrt_tracer::ReadCompletion(bool* complete)
 {
-    uint32_t* h = (uint32_t*)hCounters;   // (pinned staging)
-    HIPCHECK(hipMemcpyAsync(h, &dGlobals->poolIdle, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipMemcpyAsync(hPoolIdle.get(), &dGlobals->poolIdle, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     HIPCHECK(hipStreamSynchronize(stream));
-    *complete = *h != 0;
+    *complete = hPoolIdle[0] != 0;
     return DCRT_OK;
 }
 
@@ -2176,11 +2506,9 @@ int dcrt_tracer::Render(uint32_t maxIterations)
     if (!hasScene) { SetLastError("no scene uploaded"); return DCRT_E_NO_SCENE; }
     if (!hasFrame) { SetLastError("no frame parameters"); return DCRT_E_INVALID_ARG; }
     CHECKED(CheckFrameLights());
-    inactiveFilled = false;   // (a progressive or view image fills slot 0 in every block)
     if (output.output_type != DCRT_OUTPUT_PATH_TRACING) {
         // a view image is one launch: the whole image of the current frame seed, complete on return
-        keptSlots = false;   // (slot 0 is this image's now)
-        lastSlot = 0;
+        SlotZeroOverwritten();
         CHECKED(BeginImage());
         CHECKED(LaunchView());
         HIPCHECK(hipStreamSynchronize(stream));
@@ -2189,8 +2517,10 @@ int dcrt_tracer::Render(uint32_t maxIterations)
         newImage = true;
         return DCRT_OK;
     }
-    if (newImage) CHECKED(BeginImage());
+    // (a progressive image fills slot 0 in every block; what an earlier render_images kept stays on offer)
+    inactiveFilled = false;
     lastSlot = 0;
+    if (newImage) CHECKED(BeginImage());
     CHECKED(RunIterations(maxIterations ? maxIterations : iterationsPerRender));
     bool complete = false;
     CHECKED(ReadCompletion(&complete));
@@ -2204,10 +2534,10 @@ int dcrt_tracer::UploadFilter(const dcrt_filter_params& f)
 {
     CHECKED(dcrt::CheckFilterParams(f));        // (refused before anything is enqueued or changed)
     HIPCHECK(hipStreamSynchronize(stream));     // the pinned staging buffer is reused
-    *hFilter = MakeFilter(f);
+    *hFilter.get() = MakeFilter(f);
     lastFilter = f;
     hasFilter = true;
-    HIPCHECK(hipMemcpyAsync(dFilter, hFilter, sizeof(FilterConsts), hipMemcpyHostToDevice, stream));
+    HIPCHECK(hipMemcpyAsync(dFilter, hFilter.get(), sizeof(FilterConsts), hipMemcpyHostToDevice, stream));
     return DCRT_OK;
 }
 
@@ -2245,21 +2575,13 @@ int dcrt_tracer::RenderGuides(uint32_t firstSeed, uint32_t count)
     if (!hasFrame) { SetLastError("no frame parameters"); return DCRT_E_INVALID_ARG; }
     if (!hasFilter) { SetLastError("render_guides convolves with the film's filter: render or accumulate the film first"); return DCRT_E_INVALID_ARG; }
     CHECKED(CheckFrameLights());
-    if (partition.world_size > 1 || !bands.empty()) {
-        const uint32_t halo = partition.halo_rows ? partition.halo_rows : 2u;
-        if (!(lastFilter.radius >= 0.0f) || FilterSupportRows(lastFilter.radius, filmH) > halo) {
-            SetLastError("filter radius needs more halo rows than the film partition renders");
-            return DCRT_E_INVALID_ARG;
-        }
-    }
+    CHECKED(CheckHalo(lastFilter.radius));
     CHECKED(EnsureGuides());
     const size_t n = (size_t)filmW * filmH;
     HIPCHECK(hipMemsetAsync(guideNormal, 0, n * sizeof(float4), stream));
     HIPCHECK(hipMemsetAsync(guideAlbedo, 0, n * sizeof(float4), stream));
     guidesRendered = false;
-    keptSlots = false;   // (slot 0 holds the last guide image now)
-    inactiveFilled = false;
-    lastSlot = 0;
+    SlotZeroOverwritten();   // (slot 0 holds the last guide image now)
     const uint32_t seed = frame.frame_seed;
     int rc = DCRT_OK;
     for (uint32_t img = 0; img < count && rc == DCRT_OK; ++img) {
@@ -2270,8 +2592,7 @@ int dcrt_tracer::RenderGuides(uint32_t firstSeed, uint32_t count)
             rc = BeginImage();
             if (rc == DCRT_OK) rc = LaunchView(which == 0 ? DCRT_OUTPUT_SHADING_NORMAL : DCRT_OUTPUT_ALBEDO, target);
             if (rc != DCRT_OK) break;
-            hipLaunchKernelGGL(film_kernel, dim3(FilmGrid()), dim3(kFilmThreads), 0, stream, target, (const FilterConsts*)dFilter, 1u,
-                               (const Globals*)nullptr, (const float2* const*)nullptr, (const float4* const*)nullptr);
+            (void)LaunchFilm(target, nullptr, false, 1u, nullptr, nullptr, nullptr, 0u);   // (a guide film: never timed, no half)
             if (hipGetLastError() != hipSuccess) { SetLastError("guide film pass failed to launch"); rc = DCRT_E_HIP; }
         }
     }
@@ -2280,120 +2601,6 @@ int dcrt_tracer::RenderGuides(uint32_t firstSeed, uint32_t count)
     if (rc != DCRT_OK) return rc;
     HIPCHECK(hipStreamSynchronize(stream));
     guidesRendered = true;
-    return DCRT_OK;
-}
-
-int dcrt_tracer::EnsureDenoiseWork(uint32_t w, uint32_t h)
-{
-    if (w == dnW && h == dnH && dnWork[0]) return DCRT_OK;
-    HIPCHECK(hipStreamSynchronize(stream));
-    denoiseAllocs.Free();
-    dnW = dnH = 0;
-    dnWork[0] = dnWork[1] = dnNormal = dnAlbedo = nullptr;
-    const size_t n = (size_t)w * h;
-    CHECKED(denoiseAllocs.Alloc(&dnWork[0], n));
-    CHECKED(denoiseAllocs.Alloc(&dnWork[1], n));
-    CHECKED(denoiseAllocs.Alloc(&dnNormal, n));
-    CHECKED(denoiseAllocs.Alloc(&dnAlbedo, n));
-    dnW = w; dnH = h;
-    return DCRT_OK;
-}
-
-static int CheckDenoiseParams(const dcrt_denoise_params& p)
-{
-    if (p.iterations < 1u || p.iterations > 8u) { SetLastError("denoise: iterations 1..8"); return DCRT_E_INVALID_ARG; }
-    for (const float s : { p.sigma_luminance, p.sigma_normal, p.sigma_albedo }) {
-        if (!(s >= 0.0f) || !std::isfinite(s)) { SetLastError("denoise: sigmas are finite and >= 0 (0 switches a term off)"); return DCRT_E_INVALID_ARG; }
-    }
-    return DCRT_OK;
-}
-
-// The lattice stride L of the pass at `step` (DESIGN "Film denoiser", profiles/denoise_ab_pass.txt):
-// 0 every tap from memory; 1 the LDS-staged pixel tile (halo 2 * step); L > 1 the LDS-staged
-// lattice of every L-th pixel, its taps step / L points apart. DCRT_DENOISE_PASS=global | tile |
-// lattice (L = step) | latticeN (L = min(N, step)) forces one for an A/B, where its span fits.
-// All compute the same bits. The default is what measured fastest per step at 1920x1080
-// (profiles/denoise_ab_pass.txt): the tile up to step 4; from memory at step 8 (the lattice's
-// staging loads lie 128 B apart there and take twice as long); the lattice at 16 and 32; from
-// memory again at 64 and 128, where most taps fall outside the image and most lattice
-// workgroups hold a handful of points.
-static uint32_t DenoisePassLattice(uint32_t step)
-{
-    uint32_t L = step <= 4u ? 1u : (step == 16u || step == 32u) ? step : 0u;
-    if (const char* e = std::getenv("DCRT_DENOISE_PASS")) {
-        uint32_t want = L;
-        if (!std::strcmp(e, "global")) want = 0u;
-        else if (!std::strcmp(e, "tile")) want = 1u;
-        else if (!std::strcmp(e, "lattice")) want = step;
-        else if (!std::strncmp(e, "lattice", 7)) want = std::min<uint32_t>(step, std::max(1, std::atoi(e + 7)));
-        // (a stride that divides the step and leaves taps at most 4 lattice points apart: 48 KiB of LDS)
-        if (want == 0u || (step % want == 0u && step / want <= 4u)) L = want;
-    }
-    return L;
-}
-
-// The filter of dcrt.h "film denoiser" over W x H device images in film convention, into `out`
-// (c_N * d, 1): prologue (resolve + pack), variance estimate, `iterations` a-trous passes that
-// ping-pong between the two working images, the last one remodulating into `out`. Synchronous.
-int dcrt_tracer::Denoise(const dcrt_denoise_params& p, uint32_t w, uint32_t h, const float4* color, const float4* normal,
-                         const float4* albedo, float4* out)
-{
-    Annotation an("Denoise");
-    CHECKED(CheckDenoiseParams(p));
-    if (w == 0 || h == 0 || w > 65535u || h > 65535u) { SetLastError("denoise: invalid image size"); return DCRT_E_INVALID_ARG; }
-    if (!color || !normal || !albedo || !out) { SetLastError("denoise: null image"); return DCRT_E_INVALID_ARG; }
-    const size_t n = (size_t)w * h, bytes = n * sizeof(float4);
-    for (const float4* in : { color, normal, albedo }) {
-        const char *a = (const char*)in, *b = (const char*)out;
-        if (a < b + bytes && b < a + bytes) { SetLastError("denoise: the output image overlaps an input"); return DCRT_E_INVALID_ARG; }
-    }
-    CHECKED(EnsureDenoiseWork(w, h));
-    DenoiseConsts k;
-    k.sigmaL = p.sigma_luminance;
-    k.kn = p.sigma_normal > 0.0f ? 1.0f / (p.sigma_normal * p.sigma_normal) : 0.0f;
-    k.ka = p.sigma_albedo > 0.0f ? 1.0f / (p.sigma_albedo * p.sigma_albedo) : 0.0f;
-    k.demodulate = p.demodulate ? 1u : 0u;
-    dnEventsUsed = 0;
-    auto mark = [&]() -> int {
-        if (!extTiming) return DCRT_OK;
-        if (dnEvents.size() <= dnEventsUsed) {
-            hipEvent_t e;
-            HIPCHECK(hipEventCreate(&e));
-            dnEvents.push_back(e);
-        }
-        HIPCHECK(hipEventRecord(dnEvents[dnEventsUsed++], stream));
-        return DCRT_OK;
-    };
-    const int W = (int)w, H = (int)h;
-    const uint32_t tiles = ((w + kDnTile - 1) / kDnTile) * ((h + kDnTile - 1) / kDnTile);
-    CHECKED(mark());
-    hipLaunchKernelGGL(denoise_prologue_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)((n + 255) / 256), kMaxPersistentBlocks * 4u))),
-                       dim3(256), 0, stream, color, normal, albedo, (uint32_t)n, k.demodulate, dnWork[0], dnNormal, dnAlbedo);
-    CHECKED(mark());
-    hipLaunchKernelGGL(denoise_variance_kernel, dim3(tiles), dim3(kDnThreads), 0, stream, k, (const float4*)dnWork[0],
-                       (const float4*)dnNormal, (const float4*)dnAlbedo, W, H, dnWork[1]);
-    CHECKED(mark());
-    uint32_t src = 1;
-    for (uint32_t i = 0; i < p.iterations; ++i) {
-        const uint32_t step = 1u << i;
-        float4* finalOut = i + 1 == p.iterations ? out : nullptr;
-        uint32_t L = DenoisePassLattice(step);
-        const uint32_t Ls = std::max(1u, L), t = step / Ls, span = (uint32_t)kDnTile + 4u * t;
-        const uint64_t blocks = (uint64_t)Ls * Ls * (((w + Ls - 1) / Ls + kDnTile - 1) / kDnTile) * (((h + Ls - 1) / Ls + kDnTile - 1) / kDnTile);
-        if (blocks > 0x7FFFFFFFull) L = 0u;   // (a lattice of a huge image at a large step: more classes than a grid holds)
-        if (L == 0u) {
-            hipLaunchKernelGGL(denoise_pass_global_kernel, dim3(tiles), dim3(kDnThreads), 0, stream, k, (const float4*)dnWork[src],
-                               (const float4*)dnNormal, (const float4*)dnAlbedo, W, H, (int)step, dnWork[src ^ 1u], finalOut);
-        } else {
-            hipLaunchKernelGGL(denoise_pass_staged_kernel, dim3((uint32_t)blocks), dim3(kDnThreads), (size_t)3 * span * span * sizeof(float4),
-                               stream, k, (const float4*)dnWork[src], (const float4*)dnNormal, (const float4*)dnAlbedo, W, H, (int)step,
-                               (int)L, dnWork[src ^ 1u], finalOut);
-        }
-        CHECKED(mark());
-        src ^= 1u;
-    }
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(stream));
     return DCRT_OK;
 }
 
@@ -2410,14 +2617,7 @@ int dcrt_tracer::RenderImages(uint32_t firstSeed, uint32_t count, const dcrt_fil
     if (!hasFrame) { SetLastError("no frame parameters"); return DCRT_E_INVALID_ARG; }
     CHECKED(CheckFrameLights());
     if (count == 0) return DCRT_OK;
-    if (partition.world_size > 1 || !bands.empty()) {
-        // a partitioned film's convolution reads the filter's window rows beyond its stripes
-        const uint32_t halo = partition.halo_rows ? partition.halo_rows : 2u;
-        if (!(filter.radius >= 0.0f) || FilterSupportRows(filter.radius, filmH) > halo) {
-            SetLastError("filter radius needs more halo rows than the film partition renders");
-            return DCRT_E_INVALID_ARG;
-        }
-    }
+    CHECKED(CheckHalo(filter.radius));
     lastSlot = 0;
     // MegakernelPathTracer::Render: one persistent launch + SampleConvolution per image -- the
     // path-tracing megakernel, or the first-hit kernel of the selected output view
@@ -2433,7 +2633,7 @@ int dcrt_tracer::RenderImages(uint32_t firstSeed, uint32_t count, const dcrt_fil
         }
         CHECKED(UploadFilter(filter));
         if (listed) CHECKED(FillInactive());
-        if (view) inactiveFilled = false;   // (slot 0 gets a whole view image)
+        if (view) SlotZeroOverwritten();   // (slot 0 gets a whole view image)
         Film claims = film;
         claims.blockList = listed ? dBlockList : nullptr;
         for (uint32_t img = 0; img < count; ++img) {
@@ -2526,7 +2726,7 @@ int dcrt_tracer::RenderImages(uint32_t firstSeed, uint32_t count, const dcrt_fil
     }
     HIPCHECK(hipStreamSynchronize(stream));
     if (!stopped) {
-        HIPCHECK(hipMemcpy(hStop, &dGlobals->stopped, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(hStop.get(), &dGlobals->stopped, sizeof(uint32_t), hipMemcpyDeviceToHost));
         if (!hStop[0]) { SetLastError("images did not complete"); return DCRT_E_LIMIT; }
     }
     imageComplete = true;
@@ -2572,31 +2772,56 @@ int dcrt_tracer::AccumulateImages(const void* const* pos, const void* const* val
     return DCRT_OK;
 }
 
-// ---- film noise estimate --------------------------------------------------------------------
-// A film pass into the film: film_kernel, or with convergence on the kernel that also feeds the
-// half film (firstIndex: the film image count of the pass's first image; under `guard` the kernel
-// takes it from Globals instead).
-int dcrt_tracer::LaunchFilm(uint32_t images, const Globals* guard, const float2* const* posList, const float4* const* valList,
-                            uint32_t firstIndex)
+// ---- the film pass, the films and the film noise estimate -------------------------------------
+// A film pass into `target` (of the film's size): film_kernel, or with `half` the kernel that also feeds that
+// half film (firstIndex: the film image count of the pass's first image; under `guard` the kernel takes it from
+// Globals instead). The tracer's own film takes the overload in the struct.
+int dcrt_tracer::LaunchFilm(const Film& target, float4* half, bool timed, uint32_t images, const Globals* guard, const float2* const* posList,
+                            const float4* const* valList, uint32_t firstIndex)
 {
-    if (extTiming && !capturing) {
+    if (timed) {
         // timed (ext_timing): the dispatch's own timestamps, as the cast / MATERIAL / CONTROL launches'
         hipEvent_t e0 = nullptr, e1 = nullptr;
         CHECKED(TimedPair(kTimedFilm, &e0, &e1));
-        if (convergence && halfFilm) {
-            hipExtLaunchKernelGGL(film_half_kernel, dim3(FilmGrid()), dim3(kFilmThreads), 0, stream, e0, e1, 0, film,
-                                  (const FilterConsts*)dFilter, images, guard, posList, valList, halfFilm, firstIndex);
+        if (half) {
+            hipExtLaunchKernelGGL(film_half_kernel, dim3(FilmGrid()), dim3(kFilmThreads), 0, stream, e0, e1, 0, target,
+                                  (const FilterConsts*)dFilter, images, guard, posList, valList, half, firstIndex);
         } else {
-            hipExtLaunchKernelGGL(film_kernel, dim3(FilmGrid()), dim3(kFilmThreads), 0, stream, e0, e1, 0, film,
+            hipExtLaunchKernelGGL(film_kernel, dim3(FilmGrid()), dim3(kFilmThreads), 0, stream, e0, e1, 0, target,
                                   (const FilterConsts*)dFilter, images, guard, posList, valList);
         }
-    } else if (convergence && halfFilm) {
-        hipLaunchKernelGGL(film_half_kernel, dim3(FilmGrid()), dim3(kFilmThreads), 0, stream, film, (const FilterConsts*)dFilter, images,
-                           guard, posList, valList, halfFilm, firstIndex);
+    } else if (half) {
+        hipLaunchKernelGGL(film_half_kernel, dim3(FilmGrid()), dim3(kFilmThreads), 0, stream, target, (const FilterConsts*)dFilter, images,
+                           guard, posList, valList, half, firstIndex);
     } else {
-        hipLaunchKernelGGL(film_kernel, dim3(FilmGrid()), dim3(kFilmThreads), 0, stream, film, (const FilterConsts*)dFilter, images,
+        hipLaunchKernelGGL(film_kernel, dim3(FilmGrid()), dim3(kFilmThreads), 0, stream, target, (const FilterConsts*)dFilter, images,
                            guard, posList, valList);
     }
+    return DCRT_OK;
+}
+
+// dst += src, two W x H films on the device (the films of disjoint film partitions). Synchronous.
+int dcrt_tracer::AddFilm(float4* dst, const void* src)
+{
+    const uint32_t n = filmW * filmH;
+    hipLaunchKernelGGL(add_film_kernel, dim3(std::min<uint32_t>((n + 255) / 256, kMaxPersistentBlocks)), dim3(256), 0, stream, dst,
+                       (const float4*)src, n);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(stream));
+    return DCRT_OK;
+}
+
+// A W x H float4 image of the film's size to the host. Synchronous.
+int dcrt_tracer::ReadImage(const float4* image, float* out)
+{
+    HIPCHECK(hipMemcpyAsync(out, image, (size_t)filmW * filmH * sizeof(float4), hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+    return DCRT_OK;
+}
+
+int dcrt_tracer::NeedHalfFilm() const
+{
+    if (!halfFilm) { SetLastError("no half film: convergence is off (dcrt_tracer_set_convergence)"); return DCRT_E_INVALID_ARG; }
     return DCRT_OK;
 }
 
@@ -2625,54 +2850,6 @@ int dcrt_tracer::SetConvergence(bool on)
     return ClearFilm();
 }
 
-// The noise kernels over a film and its half film (dcrt.h): tiles, the 128-group reduction of
-// the tile sums with luminance_single_kernel, counts and maxima; one copy of the totals back.
-int dcrt_tracer::Noise(uint32_t w, uint32_t h, const float4* f, const float4* hf, float threshold, float* pixelMap, float* tileMap,
-                       dcrt_noise_stats* out)
-{
-    Annotation an("Noise estimate");
-    if (!f || !hf || !out || w == 0 || h == 0 || w > 65535u || h > 65535u) return DCRT_E_INVALID_ARG;
-    if (!(threshold >= 0.0f)) { SetLastError("noise: the threshold is negative or NaN"); return DCRT_E_INVALID_ARG; }
-    const uint32_t T = (uint32_t)kNoiseTile, tilesX = (w + T - 1) / T, tilesY = (h + T - 1) / T, tiles = tilesX * tilesY;
-    if (tiles > noiseTileCap) {
-        HIPCHECK(hipStreamSynchronize(stream));
-        noiseAllocs.Free();
-        noiseTileCap = 0;
-        CHECKED(noiseAllocs.Alloc(&nzSum, tiles));
-        CHECKED(noiseAllocs.Alloc(&nzScratch[0], (tiles + 127) / 128));
-        CHECKED(noiseAllocs.Alloc(&nzScratch[1], (tiles + 127) / 128));
-        CHECKED(noiseAllocs.Alloc(&nzMax, tiles));
-        CHECKED(noiseAllocs.Alloc(&nzErr, tiles));
-        CHECKED(noiseAllocs.Alloc(&nzCounts, (size_t)tiles * 2));
-        CHECKED(noiseAllocs.Alloc(&nzTotals, 1));
-        noiseTileCap = tiles;
-    }
-    hipLaunchKernelGGL(noise_tile_kernel, dim3(tilesX, tilesY), dim3(T * T), 0, stream, f, hf, w, h, threshold, pixelMap, tileMap, nzSum,
-                       nzMax, nzErr, nzCounts);
-    const float* in = nzSum;
-    uint32_t count = tiles, side = 0;
-    while (count != 1) {
-        const uint32_t groups = (count + 127) / 128;
-        hipLaunchKernelGGL(luminance_single_kernel, dim3(groups), dim3(128), 0, stream, in, count, nzScratch[side]);
-        in = nzScratch[side];
-        side ^= 1u;
-        count = groups;
-    }
-    hipLaunchKernelGGL(noise_finish_kernel, dim3(1), dim3(256), 0, stream, (const float*)nzMax, (const float*)nzErr,
-                       (const uint32_t*)nzCounts, tiles, in, nzTotals);
-    HIPCHECK(hipGetLastError());
-    NoiseTotals* host = (NoiseTotals*)hCounters;   // (pinned staging)
-    HIPCHECK(hipMemcpyAsync(host, nzTotals, sizeof(NoiseTotals), hipMemcpyDeviceToHost, stream));
-    HIPCHECK(hipStreamSynchronize(stream));
-    out->images = 0;
-    out->valid_pixels = host->valid;
-    out->converged_pixels = host->converged;
-    out->mean_error = host->valid ? host->total / (float)host->valid : 0.0f;
-    out->max_error = host->maxError;
-    out->max_tile_error = host->maxTileError;
-    return DCRT_OK;
-}
-
 // ... of the tracer's own film, into its own maps
 int dcrt_tracer::NoiseOwn(float threshold, dcrt_noise_stats* out)
 {
@@ -2686,7 +2863,7 @@ int dcrt_tracer::NoiseOwn(float threshold, dcrt_noise_stats* out)
         CHECKED(noiseMapAllocs.Alloc(&noiseTileMap, (size_t)((filmW + T - 1) / T) * ((filmH + T - 1) / T)));
     }
     hasNoiseMaps = false;
-    CHECKED(Noise(filmW, filmH, film.accum, halfFilm, threshold, noisePixelMap, noiseTileMap, out));
+    CHECKED(noiseEstimator.Run(stream, filmW, filmH, film.accum, halfFilm, threshold, noisePixelMap, noiseTileMap, out));
     out->images = filmImages;
     hasNoiseMaps = true;
     return DCRT_OK;
@@ -2695,28 +2872,52 @@ int dcrt_tracer::NoiseOwn(float threshold, dcrt_noise_stats* out)
 // Render until the estimate meets the target: RenderImages between the check points (film image
 // counts min, min + interval, ..., capped at max), the image with film image count i of seed
 // firstSeed + i, so the film at count n is RenderImages(firstSeed, n)'s.
-int dcrt_tracer::RenderConverged(uint32_t firstSeed, const dcrt_converge_params& p, const dcrt_filter_params& filter,
-                                 dcrt_noise_stats* outStats, int* outConverged)
+// adaptiveCall (render_adaptive): the same loop with the block list rebuilt at every check point that
+// goes on -- the list is a function of the film, the half film, the threshold and the margin alone, so a
+// block whose neighbourhood turns noisy again wakes up. The call starts on every block, and fills in
+// `report` once it has.
+int dcrt_tracer::RenderConverged(uint32_t firstSeed, const dcrt_converge_params& p, const dcrt_filter_params& filter, dcrt_noise_stats* outStats,
+                                 int* outConverged, const AdaptiveCall* adaptiveCall)
 {
-    if (!convergence || !halfFilm) { SetLastError("render_converged: convergence is off (dcrt_tracer_set_convergence)"); return DCRT_E_INVALID_ARG; }
+    const char* const prefix = adaptiveCall ? "render_adaptive" : "render_converged";
+    auto refuse = [&](const char* what, int code) { SetLastError(std::string(prefix) + what); return code; };
+    if (adaptiveCall && !adaptive) return refuse(": adaptive sampling is off (dcrt_tracer_set_adaptive)", DCRT_E_INVALID_ARG);
+    if (!convergence || !halfFilm) return refuse(": convergence is off (dcrt_tracer_set_convergence)", DCRT_E_INVALID_ARG);
     if (!(p.threshold >= 0.0f) || !(p.target_fraction > 0.0f && p.target_fraction <= 1.0f) || p.min_images < 2u ||
-        p.max_images < p.min_images || p.check_interval < 1u) {
-        SetLastError("render_converged: threshold >= 0, 0 < target_fraction <= 1, 2 <= min_images <= max_images, check_interval >= 1");
-        return DCRT_E_INVALID_ARG;
-    }
+        p.max_images < p.min_images || p.check_interval < 1u)
+        return refuse(": threshold >= 0, 0 < target_fraction <= 1, 2 <= min_images <= max_images, check_interval >= 1", DCRT_E_INVALID_ARG);
     CHECKED(dcrt::CheckFilterParams(filter));
-    *outConverged = 0;
-    for (uint64_t point = p.min_images;; point += p.check_interval) {
-        const uint32_t target = (uint32_t)std::min<uint64_t>(point, p.max_images);
-        if (filmImages < target) CHECKED(RenderImages(firstSeed + filmImages, target - filmImages, filter));
-        if (filmImages < target) { SetLastError("render_converged: the images did not reach the film"); return DCRT_E_LIMIT; }
-        CHECKED(NoiseOwn(p.threshold, outStats));
-        if ((double)outStats->converged_pixels >= (double)p.target_fraction * (double)outStats->valid_pixels) {
-            *outConverged = 1;
-            return DCRT_OK;
-        }
-        if (filmImages >= p.max_images) return DCRT_OK;
+    dcrt_adaptive_report rep{};
+    uint32_t margin = 0;
+    if (adaptiveCall) {
+        margin = adaptiveCall->margin == 0xFFFFFFFFu ? FilterSupportRows(filter.radius, filmH) : adaptiveCall->margin;
+        CHECKED(ResetBlockList());
+        rep.total_blocks = blockTotal;
+        rep.active_blocks = listCount;
     }
+    *outConverged = 0;
+    int rc = DCRT_OK;
+    for (uint64_t point = p.min_images; rc == DCRT_OK; point += p.check_interval) {
+        const uint32_t target = (uint32_t)std::min<uint64_t>(point, p.max_images);
+        if (filmImages < target) {
+            const uint32_t n = target - filmImages;
+            rc = RenderImages(firstSeed + filmImages, n, filter);
+            if (rc != DCRT_OK) break;
+            rep.images += n;
+            rep.pixel_samples += (uint64_t)n * listPixels;
+        }
+        if (filmImages < target) { rc = refuse(": the images did not reach the film", DCRT_E_LIMIT); break; }
+        rc = NoiseOwn(p.threshold, outStats);
+        if (rc != DCRT_OK) break;
+        ++rep.check_points;
+        if ((double)outStats->converged_pixels >= (double)p.target_fraction * (double)outStats->valid_pixels) { *outConverged = 1; break; }
+        if (filmImages >= p.max_images) break;
+        if (!adaptiveCall) continue;
+        rc = UpdateSampleBlocks(p.threshold, margin, &rep.active_blocks);
+        if (rc == DCRT_OK && rep.active_blocks == 0u) { *outConverged = 1; break; }
+    }
+    if (adaptiveCall && adaptiveCall->report) *adaptiveCall->report = rep;
+    return rc;
 }
 
 // ---- adaptive sampling (dcrt.h "adaptive sampling") -----------------------------------------
@@ -2801,48 +3002,6 @@ int dcrt_tracer::GetSampleBlocks(uint32_t* out, uint32_t capacity, uint32_t* out
     return DCRT_OK;
 }
 
-// sample_mask_kernel + compact_blocks_kernel over a film and its half film; the copy of the count
-// (and the listed blocks' pixels) is the one synchronisation.
-int dcrt_tracer::SampleBlocks(uint32_t w, uint32_t h, const float4* f, const float4* hf, float threshold, uint32_t margin, uint32_t* flags,
-                              uint32_t* list, uint32_t* outCount, uint32_t* outPixels)
-{
-    Annotation an("Sample blocks");
-    if (!f || !hf || !list || !outCount || w == 0 || h == 0 || w > 65535u || h > 65535u) return DCRT_E_INVALID_ARG;
-    if (!(threshold >= 0.0f)) { SetLastError("sample blocks: the threshold is negative or NaN"); return DCRT_E_INVALID_ARG; }
-    const uint32_t blocksX = (w + kBlockW - 1) / kBlockW, blocks = blocksX * ((h + kBlockH - 1) / kBlockH);
-    if (!dMaskCount || (!flags && blocks > maskFlagCap)) {
-        HIPCHECK(hipStreamSynchronize(stream));
-        maskAllocs.Free();
-        dMaskCount = dMaskFlags = nullptr;
-        maskFlagCap = 0;
-        CHECKED(maskAllocs.Alloc(&dMaskCount, 2));
-        if (!flags) {
-            CHECKED(maskAllocs.Alloc(&dMaskFlags, blocks));
-            maskFlagCap = blocks;
-        }
-    }
-    if (!flags) flags = dMaskFlags;
-    adMaskTimed = false;
-    if (extTiming) {
-        CHECKED(AdaptiveEvents());
-        HIPCHECK(hipEventRecord(adEvents[0], stream));
-    }
-    hipLaunchKernelGGL(sample_mask_kernel, dim3((blocks + 3) / 4), dim3(256), 0, stream, f, hf, w, h, threshold, margin, blocksX, blocks, flags);
-    if (extTiming) HIPCHECK(hipEventRecord(adEvents[1], stream));
-    hipLaunchKernelGGL(compact_blocks_kernel, dim3(1), dim3(256), 0, stream, (const uint32_t*)flags, blocks, blocksX, w, h, list, dMaskCount);
-    if (extTiming) {
-        HIPCHECK(hipEventRecord(adEvents[2], stream));
-        adMaskTimed = true;
-    }
-    HIPCHECK(hipGetLastError());
-    uint32_t* host = (uint32_t*)hCounters;   // (pinned staging)
-    HIPCHECK(hipMemcpyAsync(host, dMaskCount, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    HIPCHECK(hipStreamSynchronize(stream));
-    *outCount = host[0];
-    if (outPixels) *outPixels = host[1];
-    return DCRT_OK;
-}
-
 // ... of the tracer's own film and half film into its own list
 int dcrt_tracer::UpdateSampleBlocks(float threshold, uint32_t margin, uint32_t* outActive)
 {
@@ -2855,7 +3014,7 @@ int dcrt_tracer::UpdateSampleBlocks(float threshold, uint32_t margin, uint32_t* 
         margin = FilterSupportRows(lastFilter.radius, filmH);
     }
     uint32_t count = 0, pixels = 0;
-    CHECKED(SampleBlocks(filmW, filmH, film.accum, halfFilm, threshold, margin, dBlockFlags, dBlockList, &count, &pixels));
+    CHECKED(blockSampler.Run(stream, extTiming, filmW, filmH, film.accum, halfFilm, threshold, margin, dBlockFlags, dBlockList, &count, &pixels));
     listCount = count;
     listPixels = pixels;
     inactiveFilled = false;
@@ -2869,67 +3028,10 @@ int dcrt_tracer::UpdateSampleBlocks(float threshold, uint32_t margin, uint32_t* 
 int dcrt_tracer::FillInactive()
 {
     if (inactiveFilled) return DCRT_OK;
-    if (listCount < blockTotal) {
-        const uint32_t n = filmW * filmH;
-        adFillTimed = false;
-        if (extTiming) {
-            CHECKED(AdaptiveEvents());
-            HIPCHECK(hipEventRecord(adEvents[3], stream));
-        }
-        hipLaunchKernelGGL(fill_inactive_samples_kernel, dim3(std::min<uint32_t>((n + 255) / 256, 8u * kMaxPersistentBlocks)), dim3(256), 0, stream,
-                           film.samplePosition, film.sampleValue, (const uint32_t*)dBlockFlags, filmW, filmH, (filmW + kBlockW - 1) / kBlockW,
-                           sampleImages);
-        HIPCHECK(hipGetLastError());
-        if (extTiming) {
-            HIPCHECK(hipEventRecord(adEvents[4], stream));
-            adFillTimed = true;
-        }
-    }
+    if (listCount < blockTotal)
+        CHECKED(blockSampler.Fill(stream, extTiming, film.samplePosition, film.sampleValue, dBlockFlags, filmW, filmH, sampleImages));
     inactiveFilled = true;
     return DCRT_OK;
-}
-
-// RenderConverged's loop with the block list rebuilt at every check point that goes on: the list
-// is a function of the film, the half film, the threshold and the margin alone, so a block whose
-// neighbourhood turns noisy again wakes up. The call starts on every block.
-int dcrt_tracer::RenderAdaptive(uint32_t firstSeed, const dcrt_converge_params& p, uint32_t margin, const dcrt_filter_params& filter,
-                                dcrt_noise_stats* outStats, int* outConverged, dcrt_adaptive_report* report)
-{
-    if (!adaptive) { SetLastError("render_adaptive: adaptive sampling is off (dcrt_tracer_set_adaptive)"); return DCRT_E_INVALID_ARG; }
-    if (!convergence || !halfFilm) { SetLastError("render_adaptive: convergence is off (dcrt_tracer_set_convergence)"); return DCRT_E_INVALID_ARG; }
-    if (!(p.threshold >= 0.0f) || !(p.target_fraction > 0.0f && p.target_fraction <= 1.0f) || p.min_images < 2u ||
-        p.max_images < p.min_images || p.check_interval < 1u) {
-        SetLastError("render_adaptive: threshold >= 0, 0 < target_fraction <= 1, 2 <= min_images <= max_images, check_interval >= 1");
-        return DCRT_E_INVALID_ARG;
-    }
-    CHECKED(dcrt::CheckFilterParams(filter));
-    if (margin == 0xFFFFFFFFu) margin = FilterSupportRows(filter.radius, filmH);
-    CHECKED(ResetBlockList());
-    *outConverged = 0;
-    dcrt_adaptive_report rep{};
-    rep.total_blocks = blockTotal;
-    rep.active_blocks = listCount;
-    int rc = DCRT_OK;
-    for (uint64_t point = p.min_images; rc == DCRT_OK; point += p.check_interval) {
-        const uint32_t target = (uint32_t)std::min<uint64_t>(point, p.max_images);
-        if (filmImages < target) {
-            const uint32_t n = target - filmImages;
-            rc = RenderImages(firstSeed + filmImages, n, filter);
-            if (rc != DCRT_OK) break;
-            rep.images += n;
-            rep.pixel_samples += (uint64_t)n * listPixels;
-        }
-        if (filmImages < target) { SetLastError("render_adaptive: the images did not reach the film"); rc = DCRT_E_LIMIT; break; }
-        rc = NoiseOwn(p.threshold, outStats);
-        if (rc != DCRT_OK) break;
-        ++rep.check_points;
-        if ((double)outStats->converged_pixels >= (double)p.target_fraction * (double)outStats->valid_pixels) { *outConverged = 1; break; }
-        if (filmImages >= p.max_images) break;
-        rc = UpdateSampleBlocks(p.threshold, margin, &rep.active_blocks);
-        if (rc == DCRT_OK && rep.active_blocks == 0u) { *outConverged = 1; break; }
-    }
-    if (report) *report = rep;
-    return rc;
 }
 
 // ============================ C ABI ========================================
@@ -3141,9 +3243,7 @@ DCRT_API int dcrt_tracer_read_film(dcrt_tracer* t, float* out)
 {
     TRACER_GUARD(t);
     if (!out || !t->film.accum) return DCRT_E_INVALID_ARG;
-    HIPCHECK(hipMemcpyAsync(out, t->film.accum, (size_t)t->filmW * t->filmH * sizeof(float4), hipMemcpyDeviceToHost, t->stream));
-    HIPCHECK(hipStreamSynchronize(t->stream));
-    return DCRT_OK;
+    return t->ReadImage(t->film.accum, out);
 }
 
 DCRT_API int dcrt_tracer_read_samples(dcrt_tracer* t, float* pos, float* val)
@@ -3217,12 +3317,7 @@ DCRT_API int dcrt_tracer_add_film_device(dcrt_tracer* t, const void* d_src)
 {
     TRACER_GUARD(t);
     if (!d_src || !t->film.accum) return DCRT_E_INVALID_ARG;
-    const uint32_t n = t->filmW * t->filmH;
-    hipLaunchKernelGGL(add_film_kernel, dim3(std::min<uint32_t>((n + 255) / 256, kMaxPersistentBlocks)), dim3(256), 0, t->stream,
-                       t->film.accum, (const float4*)d_src, n);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(t->stream));
-    return DCRT_OK;
+    return t->AddFilm(t->film.accum, d_src);
 }
 
 // ---- film noise estimate ----------------------------------------------------------------------
@@ -3236,7 +3331,7 @@ DCRT_API int dcrt_tracer_half_film_device_ptr(dcrt_tracer* t, void** out)
 {
     TRACER_GUARD(t);
     if (!out) return DCRT_E_INVALID_ARG;
-    if (!t->halfFilm) { SetLastError("no half film: convergence is off (dcrt_tracer_set_convergence)"); return DCRT_E_INVALID_ARG; }
+    CHECKED(t->NeedHalfFilm());
     *out = t->halfFilm;
     return DCRT_OK;
 }
@@ -3245,23 +3340,16 @@ DCRT_API int dcrt_tracer_read_half_film(dcrt_tracer* t, float* out)
 {
     TRACER_GUARD(t);
     if (!out) return DCRT_E_INVALID_ARG;
-    if (!t->halfFilm) { SetLastError("no half film: convergence is off (dcrt_tracer_set_convergence)"); return DCRT_E_INVALID_ARG; }
-    HIPCHECK(hipMemcpyAsync(out, t->halfFilm, (size_t)t->filmW * t->filmH * sizeof(float4), hipMemcpyDeviceToHost, t->stream));
-    HIPCHECK(hipStreamSynchronize(t->stream));
-    return DCRT_OK;
+    CHECKED(t->NeedHalfFilm());
+    return t->ReadImage(t->halfFilm, out);
 }
 
 DCRT_API int dcrt_tracer_add_half_film_device(dcrt_tracer* t, const void* d_src)
 {
     TRACER_GUARD(t);
     if (!d_src) return DCRT_E_INVALID_ARG;
-    if (!t->halfFilm) { SetLastError("no half film: convergence is off (dcrt_tracer_set_convergence)"); return DCRT_E_INVALID_ARG; }
-    const uint32_t n = t->filmW * t->filmH;
-    hipLaunchKernelGGL(add_film_kernel, dim3(std::min<uint32_t>((n + 255) / 256, kMaxPersistentBlocks)), dim3(256), 0, t->stream,
-                       t->halfFilm, (const float4*)d_src, n);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(t->stream));
-    return DCRT_OK;
+    CHECKED(t->NeedHalfFilm());
+    return t->AddFilm(t->halfFilm, d_src);
 }
 
 DCRT_API int dcrt_tracer_film_image_count(dcrt_tracer* t, uint32_t* out)
@@ -3293,7 +3381,7 @@ DCRT_API int dcrt_tracer_noise_device(dcrt_tracer* t, uint32_t width, uint32_t h
                                       float threshold, void* d_pixel_map, void* d_tile_map, dcrt_noise_stats* out)
 {
     TRACER_GUARD(t);
-    return t->Noise(width, height, (const float4*)d_film, (const float4*)d_half, threshold, (float*)d_pixel_map, (float*)d_tile_map, out);
+    return t->noiseEstimator.Run(t->stream, width, height, (const float4*)d_film, (const float4*)d_half, threshold, (float*)d_pixel_map, (float*)d_tile_map, out);
 }
 
 DCRT_API int dcrt_tracer_noise_map_device_ptrs(dcrt_tracer* t, void** out_pixel, void** out_tile)
@@ -3357,7 +3445,7 @@ DCRT_API int dcrt_tracer_sample_blocks_device(dcrt_tracer* t, uint32_t width, ui
                                               float threshold, uint32_t margin, void* d_flags, void* d_list, uint32_t* out_count)
 {
     TRACER_GUARD(t);
-    return t->SampleBlocks(width, height, (const float4*)d_film, (const float4*)d_half, threshold, margin, (uint32_t*)d_flags,
+    return t->blockSampler.Run(t->stream, t->extTiming, width, height, (const float4*)d_film, (const float4*)d_half, threshold, margin, (uint32_t*)d_flags,
                            (uint32_t*)d_list, out_count, nullptr);
 }
 
@@ -3365,14 +3453,8 @@ DCRT_API int dcrt_tracer_adaptive_timings(dcrt_tracer* t, float* out_mask_ms, fl
 {
     TRACER_GUARD(t);
     if (!out_mask_ms || !out_compact_ms || !out_fill_ms) return DCRT_E_INVALID_ARG;
-    *out_mask_ms = *out_compact_ms = *out_fill_ms = 0.0f;
     HIPCHECK(hipStreamSynchronize(t->stream));
-    if (t->adMaskTimed) {
-        HIPCHECK(hipEventElapsedTime(out_mask_ms, t->adEvents[0], t->adEvents[1]));
-        HIPCHECK(hipEventElapsedTime(out_compact_ms, t->adEvents[1], t->adEvents[2]));
-    }
-    if (t->adFillTimed) HIPCHECK(hipEventElapsedTime(out_fill_ms, t->adEvents[3], t->adEvents[4]));
-    return DCRT_OK;
+    return t->blockSampler.Timings(out_mask_ms, out_compact_ms, out_fill_ms);
 }
 
 DCRT_API int dcrt_tracer_render_adaptive(dcrt_tracer* t, uint32_t first_seed, const dcrt_converge_params* p, uint32_t margin,
@@ -3381,7 +3463,8 @@ DCRT_API int dcrt_tracer_render_adaptive(dcrt_tracer* t, uint32_t first_seed, co
 {
     TRACER_GUARD(t);
     if (!p || !f || !out_stats || !out_converged) return DCRT_E_INVALID_ARG;
-    return t->RenderAdaptive(first_seed, *p, margin, *f, out_stats, out_converged, out_report);
+    const dcrt_tracer::AdaptiveCall call{ margin, out_report };
+    return t->RenderConverged(first_seed, *p, *f, out_stats, out_converged, &call);
 }
 
 DCRT_API int dcrt_tracer_counters(dcrt_tracer* t, dcrt_ray_stats* out)
@@ -3769,7 +3852,7 @@ DCRT_API int dcrt_tracer_denoise(dcrt_tracer* t, const dcrt_denoise_params* p)
         SetLastError("denoise: no guides rendered at this resolution (dcrt_tracer_render_guides)");
         return DCRT_E_INVALID_ARG;
     }
-    CHECKED(t->Denoise(*p, t->filmW, t->filmH, t->film.accum, t->guideNormal, t->guideAlbedo, t->denoised));
+    CHECKED(t->denoiser.Run(t->stream, t->extTiming, *p, t->filmW, t->filmH, t->film.accum, t->guideNormal, t->guideAlbedo, t->denoised));
     t->hasDenoised = true;
     return DCRT_OK;
 }
@@ -3779,7 +3862,7 @@ DCRT_API int dcrt_tracer_denoise_device(dcrt_tracer* t, const dcrt_denoise_param
 {
     TRACER_GUARD(t);
     if (!p) return DCRT_E_INVALID_ARG;
-    return t->Denoise(*p, width, height, (const float4*)d_color, (const float4*)d_normal, (const float4*)d_albedo, (float4*)d_out);
+    return t->denoiser.Run(t->stream, t->extTiming, *p, width, height, (const float4*)d_color, (const float4*)d_normal, (const float4*)d_albedo, (float4*)d_out);
 }
 
 DCRT_API int dcrt_tracer_denoise_images(dcrt_tracer* t, const dcrt_denoise_params* p, uint32_t width, uint32_t height,
@@ -3795,7 +3878,7 @@ DCRT_API int dcrt_tracer_denoise_images(dcrt_tracer* t, const dcrt_denoise_param
     for (float4*& q : d) CHECKED(scratch.Alloc(&q, n));
     const float* src[3] = { color, normal, albedo };
     for (int i = 0; i < 3; ++i) HIPCHECK(hipMemcpyAsync(d[i], src[i], bytes, hipMemcpyHostToDevice, t->stream));
-    CHECKED(t->Denoise(*p, width, height, d[0], d[1], d[2], d[3]));
+    CHECKED(t->denoiser.Run(t->stream, t->extTiming, *p, width, height, d[0], d[1], d[2], d[3]));
     HIPCHECK(hipMemcpyAsync(out, d[3], bytes, hipMemcpyDeviceToHost, t->stream));
     HIPCHECK(hipStreamSynchronize(t->stream));
     return DCRT_OK;
@@ -3806,9 +3889,7 @@ DCRT_API int dcrt_tracer_read_denoised(dcrt_tracer* t, float* out)
     TRACER_GUARD(t);
     if (!out) return DCRT_E_INVALID_ARG;
     if (!t->hasDenoised) { SetLastError("no denoised image (dcrt_tracer_denoise)"); return DCRT_E_INVALID_ARG; }
-    HIPCHECK(hipMemcpyAsync(out, t->denoised, (size_t)t->filmW * t->filmH * sizeof(float4), hipMemcpyDeviceToHost, t->stream));
-    HIPCHECK(hipStreamSynchronize(t->stream));
-    return DCRT_OK;
+    return t->ReadImage(t->denoised, out);
 }
 
 DCRT_API int dcrt_tracer_denoised_device_ptr(dcrt_tracer* t, void** out)
@@ -3832,11 +3913,7 @@ DCRT_API int dcrt_tracer_denoise_timings(dcrt_tracer* t, float* out_ms, uint32_t
 {
     TRACER_GUARD(t);
     if (!out_count || (capacity && !out_ms)) return DCRT_E_INVALID_ARG;
-    const uint32_t kernels = t->dnEventsUsed ? t->dnEventsUsed - 1u : 0u;
-    *out_count = kernels;
-    for (uint32_t i = 0; i < kernels && i < capacity; ++i)
-        HIPCHECK(hipEventElapsedTime(&out_ms[i], t->dnEvents[i], t->dnEvents[i + 1]));
-    return DCRT_OK;
+    return t->denoiser.Timings(out_ms, capacity, out_count);
 }
 
 DCRT_API int dcrt_device_math_eval(dcrt_tracer* t, int function, const float* x, uint32_t n, float* y)
