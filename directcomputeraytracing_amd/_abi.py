@@ -231,6 +231,11 @@ class BsdfProbeMaterial(C.Structure):
                 ("two_sided", C.c_uint32), ("multiscattering", C.c_uint32), ("internal_scattering_mode", C.c_uint32)]
 
 
+class RouletteParams(C.Structure):
+    """dcrt_roulette_params (dcrt.h "Russian roulette")."""
+    _fields_ = [("enable", C.c_uint32), ("start_bounce", C.c_uint32), ("min_survival", C.c_float), ("max_survival", C.c_float)]
+
+
 OBJ_SCENE_LAYOUT = 1
 
 # Every symbol include/dcrt.h declares: (name, restype, argtypes)
@@ -377,6 +382,10 @@ SIGNATURES = [
     ("dcrt_tracer_get_environment_sampling", _I, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("dcrt_tracer_read_environment_distribution", _I, [_P, _FP, _FP, _FP]),
     ("dcrt_tracer_environment_build_timing", _I, [_P, _FP]),
+    ("dcrt_roulette_default_params", _I, [C.POINTER(RouletteParams)]),
+    ("dcrt_tracer_set_roulette", _I, [_P, C.POINTER(RouletteParams)]),
+    ("dcrt_tracer_get_roulette", _I, [_P, C.POINTER(RouletteParams)]),
+    ("dcrt_device_roulette", _I, [_P, C.POINTER(RouletteParams), _FP, _FP, _U, _FP, C.POINTER(C.c_uint32), _FP]),
     ("dcrt_write_bmp", _I, [C.c_char_p, _U, _U, C.POINTER(C.c_uint8)]),
     ("dcrt_device_math_eval", _I, [_P, _I, _FP, _U, _FP]),
     ("dcrt_device_bsdf_eval", _I, [_P, C.POINTER(BsdfProbeMaterial), _U, _FP, _FP, _U, _FP, _FP]),

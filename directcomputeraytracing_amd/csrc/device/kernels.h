@@ -233,7 +233,27 @@ struct FrameConstants {
     // MATERIAL's FUSED variant tests a shadow ray itself only if (path slot & mask) == 0; the others
     // take the shadow queue. 0 but for DCRT_FUSED_SHADOW's test value, which mixes the two routes in a wave.
     uint32_t shadowInlineMask;
+    // Russian roulette (dcrt_roulette_params; dcrt.h "Russian roulette"): nothing of it runs while the first word is 0
+    uint32_t rouletteEnable, rouletteStart;
+    float rouletteMin, rouletteMax;
 };
+
+// Russian roulette at a shaded vertex whose BSDF sample was accepted (dcrt.h "Russian roulette" pins the rule;
+// tests/roulette_ref.py restates it): T is the throughput after the sample, q = clamp(max component, lo, hi)
+// with a NaN component falling to lo. q >= 1: nothing happens and `draw` is not called. Otherwise u = draw():
+// u < q keeps the path with T / q (a division per component), else it ends -- false. One function for
+// shade_path, the megakernel and the probe (roulette_probe_kernel), which differ in where u comes from.
+template <class Draw>
+DEV bool roulette(float lo, float hi, V3& T, Draw draw, float* qOut = nullptr)
+{
+    const float q = fminf(fmaxf(fmaxf(fmaxf(T.x, T.y), T.z), lo), hi);
+    if (qOut) *qOut = q;
+    if (q >= 1.0f) return true;
+    const float u = draw();
+    if (!(u < q)) return false;
+    T = mk(T.x / q, T.y / q, T.z / q);
+    return true;
+}
 
 // What MATERIAL's FUSED variant reads of the flat cast's scene (CastPlan::sceneFlat) for
 // cells_occluded_cached: the entry-free node array -- the order the cell table's leaf words index --

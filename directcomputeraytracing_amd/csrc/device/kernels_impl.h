@@ -530,6 +530,14 @@ __device__ __forceinline__ void shade_path(const DeviceScene& sc, const FrameCon
                 nO = offset_ray_origin(it.position, it.geometryNormal, wi);
                 nD = wi;   // (written into the extension queue after the append)
                 flags = (flags & 0xFFFFFF00u) | ((bounce + 1) & 0xFFu);
+                // Russian roulette (off: one scalar test, and the lines above are the code without it): its draw
+                // follows the three above, ahead of the opacity draws. A path it ends is a path whose sample was
+                // rejected: the bounce index as it was and kFlagTerminate (T and the ray are read of survivors only).
+                if (fc.rouletteEnable != 0u && bounce >= fc.rouletteStart &&
+                    !roulette(fc.rouletteMin, fc.rouletteMax, T, [&] { return next1(rng); })) {
+                    flags = (flags & 0xFFFFFF00u) | bounce | kFlagTerminate;
+                    terminate = true;
+                }
             } else {
                 flags |= kFlagTerminate;
                 terminate = true;
@@ -1604,6 +1612,11 @@ __global__ __launch_bounds__(256) void megakernel(DeviceScene sc, const FrameCon
                     ro = offset_ray_origin(it.position, it.geometryNormal, wi);
                     rd = wi;
                     ++bounce;
+                    // Russian roulette, as in shade_path (the vertex's bounce index is bounce - 1): the draw follows
+                    // the three above, ahead of the next turn's; a path it ends leaves the loop below
+                    if (fc.rouletteEnable != 0u && bounce > fc.rouletteStart &&
+                        !roulette(fc.rouletteMin, fc.rouletteMax, T, [&] { return next1(rng); }))
+                        terminate = true;
                 } else {
                     terminate = true;
                 }
@@ -1996,6 +2009,20 @@ __global__ void camera_ray_probe_kernel(FrameConstants fc, const float* film, co
     generate_ray(fc, film[2 * i], film[2 * i + 1], aperture[3 * i], aperture[3 * i + 1], aperture[3 * i + 2], &o, &d);
     origins[3 * i] = o.x; origins[3 * i + 1] = o.y; origins[3 * i + 2] = o.z;
     directions[3 * i] = d.x; directions[3 * i + 1] = d.y; directions[3 * i + 2] = d.z;
+}
+// dcrt_device_roulette: the path kernels' roulette on given throughputs, u standing in for the path's draw. q, whether
+// the path goes on (1 / 0), and the throughput it goes on with (as given where it ends or q >= 1).
+__global__ void roulette_probe_kernel(float lo, float hi, const float* throughputs, const float* u, uint32_t n, float* outQ, uint32_t* outSurvive,
+                                      float* outScaled)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    V3 T = mk(throughputs[3 * i], throughputs[3 * i + 1], throughputs[3 * i + 2]);
+    float q;
+    const bool survives = roulette(lo, hi, T, [&] { return u[i]; }, &q);
+    outQ[i] = q;
+    outSurvive[i] = survives ? 1u : 0u;
+    outScaled[3 * i] = T.x; outScaled[3 * i + 1] = T.y; outScaled[3 * i + 2] = T.z;
 }
 template <bool TABLE>
 __global__ void intersection_probe_kernel(DeviceScene sc, const uint4* records, uint32_t n, float* outFloats, uint32_t* outWords)

@@ -838,6 +838,15 @@ struct MaterialPlan {
     }
 };
 
+// dcrt_roulette_default_params: off; on, from the third vertex on with the throughput as the survival probability
+constexpr dcrt_roulette_params kRouletteDefaults = {0u, 2u, 0.05f, 1.0f};
+
+// 0 < min_survival <= max_survival <= 1 (a NaN fails every comparison), start_bounce within the bounce limit
+bool RouletteParamsValid(const dcrt_roulette_params& p)
+{
+    return p.min_survival > 0.0f && p.min_survival <= p.max_survival && p.max_survival <= 1.0f && p.start_bounce <= DCRT_MAX_RAY_BOUNCE;
+}
+
 }  // namespace
 
 struct dcrt_tracer {
@@ -900,6 +909,9 @@ struct dcrt_tracer {
     float* dEnvMarginal = nullptr;
     float envBuildMs = 0.0f;
     bool EnvTableActive() const { return hasScene && envSampling == DCRT_ENV_SAMPLING_IMPORTANCE && dEnvProb != nullptr; }
+    // Russian roulette (dcrt.h): the tracer's setting, kept across uploads and edits; BeginImage writes it into the
+    // frame constants beside maxBounce, so a change costs no graph
+    dcrt_roulette_params roulette = kRouletteDefaults;
     // MATERIAL of the next launch tests its shadow rays itself: where the cast is the CELLS kernel
     bool FusedShadow() const
     {
@@ -2296,6 +2308,10 @@ int dcrt_tracer::BeginImage()
     fc.seedStride = seedStride;
     fc.shadowInlineMask = material.fusedMask;
     fc.maxBounce = frame.max_bounce_count;
+    fc.rouletteEnable = roulette.enable ? 1u : 0u;
+    fc.rouletteStart = roulette.start_bounce;
+    fc.rouletteMin = roulette.min_survival;
+    fc.rouletteMax = roulette.max_survival;
     fc.lightCount = frame.light_count;
     fc.envLightIndex = frame.environment_light_index;
     fc.features = frame.features;
@@ -4139,6 +4155,49 @@ DCRT_API int dcrt_tracer_get_environment_sampling(dcrt_tracer* t, int* mode, int
     if (mode) *mode = t->envSampling;
     if (active) *active = t->EnvTableActive() ? 1 : 0;
     return DCRT_OK;
+}
+
+// ---- Russian roulette -----------------------------------------------------------------------
+DCRT_API int dcrt_roulette_default_params(dcrt_roulette_params* out)
+{
+    if (!out) return DCRT_E_INVALID_ARG;
+    *out = kRouletteDefaults;
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_set_roulette(dcrt_tracer* t, const dcrt_roulette_params* params)
+{
+    if (!t || !params) return DCRT_E_INVALID_ARG;
+    if (!RouletteParamsValid(*params)) {
+        SetLastError("Russian roulette: 0 < min_survival <= max_survival <= 1 and start_bounce <= DCRT_MAX_RAY_BOUNCE");
+        return DCRT_E_INVALID_ARG;
+    }
+    // (BeginImage writes it into the frame constants with the next image: no graph holds it)
+    t->roulette = *params;
+    t->roulette.enable = params->enable ? 1u : 0u;
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_get_roulette(dcrt_tracer* t, dcrt_roulette_params* out)
+{
+    if (!t || !out) return DCRT_E_INVALID_ARG;
+    *out = t->roulette;
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_device_roulette(dcrt_tracer* t, const dcrt_roulette_params* params, const float* throughputs, const float* u, uint32_t n,
+                                  float* out_q, uint32_t* out_survive, float* out_scaled)
+{
+    TRACER_GUARD(t);
+    if (!params || ((!throughputs || !u || !out_q || !out_survive || !out_scaled) && n)) return DCRT_E_INVALID_ARG;
+    if (!RouletteParamsValid(*params)) { SetLastError("Russian roulette probe: invalid parameters"); return DCRT_E_INVALID_ARG; }
+    const float lo = params->min_survival, hi = params->max_survival;
+    DeviceGroup scratch;
+    HostArray a[5] = {{throughputs, nullptr, 12}, {u, nullptr, 4}, {nullptr, out_q, 4}, {nullptr, out_survive, 4}, {nullptr, out_scaled, 12}};
+    return RoundTrip(t, scratch, n, a, [&] {
+        hipLaunchKernelGGL(roulette_probe_kernel, ItemGrid(n), dim3(256), 0, t->stream, lo, hi, (const float*)a[0].device, (const float*)a[1].device, n,
+                           (float*)a[2].device, (uint32_t*)a[3].device, (float*)a[4].device);
+    });
 }
 
 DCRT_API int dcrt_tracer_read_environment_distribution(dcrt_tracer* t, float* prob, float* row_cdf, float* marginal_cdf)

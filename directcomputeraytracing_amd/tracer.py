@@ -461,6 +461,46 @@ class WavefrontPathTracer:
         check(self._lib.dcrt_tracer_get_environment_sampling(self._h, C.byref(mode), C.byref(active)), "GetEnvironmentSampling")
         return self.ENV_SAMPLING[mode.value], bool(active.value)
 
+    # ---- Russian roulette (include/dcrt.h) -------------------------------------------
+    def set_russian_roulette(self, enable: bool = True, start_bounce: int | None = None, min_survival: float | None = None,
+                             max_survival: float | None = None) -> None:
+        """Russian roulette path termination (off by default); a value left None is dcrt_roulette_default_params'.
+        Lives on the tracer (kept across uploads and edits), takes effect with the next image: the caller
+        restarts the image. Refused unless 0 < min_survival <= max_survival <= 1 and start_bounce <= 20."""
+        p = roulette_defaults()
+        p.enable = 1 if enable else 0
+        if start_bounce is not None:
+            if not 0 <= int(start_bounce) <= 0xFFFFFFFF:
+                raise ValueError(f"Russian roulette start bounce {start_bounce!r}")
+            p.start_bounce = int(start_bounce)
+        if min_survival is not None:
+            p.min_survival = float(min_survival)
+        if max_survival is not None:
+            p.max_survival = float(max_survival)
+        check(self._lib.dcrt_tracer_set_roulette(self._h, C.byref(p)), "SetRoulette")
+
+    def russian_roulette(self) -> dict:
+        """The setting: {"enable", "start_bounce", "min_survival", "max_survival"}."""
+        p = _abi.RouletteParams()
+        check(self._lib.dcrt_tracer_get_roulette(self._h, C.byref(p)), "GetRoulette")
+        return {"enable": bool(p.enable), "start_bounce": int(p.start_bounce), "min_survival": float(p.min_survival),
+                "max_survival": float(p.max_survival)}
+
+    def device_roulette(self, throughputs, u, min_survival: float, max_survival: float):
+        """dcrt_device_roulette: (q [n], survive [n] bool, scaled [n, 3]) of the kernels' roulette on throughputs [n, 3]
+        with u [n] in place of the paths' draws."""
+        T = np.ascontiguousarray(throughputs, np.float32).reshape(-1, 3)
+        uu = np.ascontiguousarray(u, np.float32).reshape(-1)
+        if len(uu) != len(T):
+            raise ValueError("device_roulette: one u per throughput")
+        n = len(T)
+        q, alive, scaled = np.empty(n, np.float32), np.empty(n, np.uint32), np.empty((n, 3), np.float32)
+        p = _abi.RouletteParams(1, 0, float(min_survival), float(max_survival))
+        fp = _abi._FP
+        check(self._lib.dcrt_device_roulette(self._h, C.byref(p), T.ctypes.data_as(fp), uu.ctypes.data_as(fp), n, q.ctypes.data_as(fp),
+                                             alive.ctypes.data_as(C.POINTER(C.c_uint32)), scaled.ctypes.data_as(fp)), "DeviceRoulette")
+        return q, alive != 0, scaled
+
     def environment_distribution(self):
         """The stored table of the uploaded cube (size n): P [6n, n], the per-row CDF [6n, n], the marginal CDF [6n].
         Raises (no scene) while inactive."""
@@ -695,6 +735,13 @@ def denoise_default_params() -> _abi.DenoiseParams:
     return p
 
 
+def roulette_defaults() -> _abi.RouletteParams:
+    """dcrt_roulette_default_params: off, start bounce 2, survival within [0.05, 1] (no device needed)."""
+    p = _abi.RouletteParams()
+    check(_abi.load_library().dcrt_roulette_default_params(C.byref(p)), "RouletteDefaultParams")
+    return p
+
+
 def noise_stats_dict(s: _abi.NoiseStats) -> dict:
     return {k: getattr(s, k) for k, _ in _abi.NoiseStats._fields_}
 
@@ -722,7 +769,7 @@ def device_count() -> int:
 def make_pipelines(scene, pool: int, streams: int = 2, images: int = 1, iterations: int = 16, world: int = 1,
                    rank: int = 0, stripe: int = 64, mode: str = "wavefront", image_batch: int = 0, device: int = 0,
                    debug_rng: bool = False, row_cost=None, fixed_pool: bool = False, interleave: bool = False,
-                   bands_per_rank: int = 0, env_sampling: str = "uniform") -> list:
+                   bands_per_rank: int = 0, env_sampling: str = "uniform", roulette: dict | None = None) -> list:
     """The concurrent wavefront pipelines bench.py renders with, each a tracer with its share of
     `pool` slots (grown to whole batches of `images` images, partition.pipeline_pool), the
     filter's halo rows, its own stream. With `row_cost` (rays per film row, probe_row_cost) the
@@ -731,14 +778,14 @@ def make_pipelines(scene, pool: int, streams: int = 2, images: int = 1, iteratio
     band of each 1/streams of the film and a cost trend down the image evens out; without it, one GPU splits the film into
     `streams` equal horizontal bands and N GPUs deal this rank's round-robin stripes to its
     pipelines (partition.stream_partition). Their films have disjoint supports: add_film_device
-    sums them into the rank's film bit for bit."""
+    sums them into the rank's film bit for bit. `roulette`: set_russian_roulette's arguments, given to every pipeline."""
     from .partition import balanced_bands, band_render_rows, halo_for_radius, pipeline_pool, render_rows, stream_partition
     W, H = scene.resolution
     halo = max(1, halo_for_radius(scene.filter_params().radius, H))
     K = max(1, streams)
     if interleave:
         return _make_interleaved(scene, pool, K, images, iterations, world, rank, stripe, mode, image_batch, device, debug_rng,
-                                 row_cost, fixed_pool, bands_per_rank or K, halo, env_sampling)
+                                 row_cost, fixed_pool, bands_per_rank or K, halo, env_sampling, roulette)
     bands = balanced_bands(row_cost, world * K, halo) if row_cost is not None and world * K > 1 else None
     tracers = []
     try:
@@ -752,6 +799,8 @@ def make_pipelines(scene, pool: int, streams: int = 2, images: int = 1, iteratio
             tracers.append(t)
             t.on_scene_loaded(scene)
             t.set_environment_sampling(env_sampling)
+            if roulette is not None:
+                t.set_russian_roulette(**roulette)
             t.set_mode(mode)
             t.set_image_batch(image_batch)
             if band is not None:
@@ -766,7 +815,7 @@ def make_pipelines(scene, pool: int, streams: int = 2, images: int = 1, iteratio
 
 
 def _make_interleaved(scene, pool, K, images, iterations, world, rank, stripe, mode, image_batch, device, debug_rng, row_cost,
-                      fixed_pool, bands_per_rank, halo, env_sampling="uniform") -> list:
+                      fixed_pool, bands_per_rank, halo, env_sampling="uniform", roulette=None) -> list:
     """make_pipelines(interleave=True): K tracers over the SAME rows -- the whole film on one GPU,
     the rank's share of it on N (`bands_per_rank` cost-balanced bands dealt round-robin, or the
     round-robin stripes without a row cost) -- that split the images instead of the rows
@@ -793,6 +842,8 @@ def _make_interleaved(scene, pool, K, images, iterations, world, rank, stripe, m
             tracers.append(t)
             t.on_scene_loaded(scene)
             t.set_environment_sampling(env_sampling)
+            if roulette is not None:
+                t.set_russian_roulette(**roulette)
             t.set_mode(mode)
             t.set_image_batch(image_batch)
             if bands is not None:

@@ -10,6 +10,10 @@
 //               [--edit N:KIND:ARGS]... [--output NAME [--iteration-threshold N]] [--denoise]
 //               [--converge THRESHOLD[:FRACTION] [--check-points MIN:INTERVAL]] [--noise-map out.bmp]
 //               [--adaptive THRESHOLD:FRACTION[:MARGIN]] [--sample-map out.bmp] [--env-importance]
+//               [--roulette START[:MIN[:MAX]]]
+//
+// --roulette turns Russian roulette on from bounce START (dcrt.h "Russian roulette"): a path survives a vertex with
+// the probability clamp(max throughput component, MIN, MAX), defaults 0.05 and 1, and survivors are weighted up.
 //
 // --env-importance draws the light samples of an environment cube by its power instead of uniformly
 // (dcrt.h "environment importance sampling"); a scene without a cube renders as without the flag.
@@ -88,7 +92,8 @@ int Usage(const char* exe)
                  "       [--output path_tracing|normal|tangent|albedo|negative_ndotv|backface|iteration_count]\n"
                  "       [--iteration-threshold N] [--denoise]\n"
                  "       [--converge THRESHOLD[:FRACTION] [--check-points MIN:INTERVAL]] [--noise-map out.bmp]\n"
-                 "       [--adaptive THRESHOLD:FRACTION[:MARGIN]] [--sample-map out.bmp] [--env-importance]\n",
+                 "       [--adaptive THRESHOLD:FRACTION[:MARGIN]] [--sample-map out.bmp] [--env-importance]\n"
+                 "       [--roulette START[:MIN[:MAX]]]\n",
                  exe);
     return 2;
 }
@@ -208,6 +213,8 @@ int main(int argc, char** argv)
     uint32_t adaptiveMargin = 0xFFFFFFFFu;   // (the filter's window rows)
     const char* sampleMapPath = nullptr;
     bool envImportance = false;
+    dcrt_roulette_params roulette;
+    if (dcrt_roulette_default_params(&roulette) != DCRT_OK) return 1;
     for (int i = 7; i < argc; ++i) {
         const bool more = i + 1 < argc;
         if (!std::strcmp(argv[i], "--batch")) {
@@ -216,6 +223,13 @@ int main(int argc, char** argv)
             denoise = true;
         } else if (!std::strcmp(argv[i], "--env-importance")) {
             envImportance = true;
+        } else if (!std::strcmp(argv[i], "--roulette") && more) {
+            const std::vector<std::string> f = Split(argv[++i], ':');
+            if (f.empty() || f.size() > 3 || f[0].empty() || f[0].find_first_not_of("0123456789") != std::string::npos ||
+                (f.size() >= 2 && !ParseFloats(f[1], &roulette.min_survival, 1)) || (f.size() == 3 && !ParseFloats(f[2], &roulette.max_survival, 1)))
+                return Usage(argv[0]);
+            roulette.start_bounce = (uint32_t)std::atoi(f[0].c_str());
+            roulette.enable = 1u;
         } else if (!std::strcmp(argv[i], "--point") && i + 6 < argc) {
             pointLight = true;
             for (int k = 0; k < 3; ++k) lightPos[k] = (float)std::atof(argv[i + 1 + k]);
@@ -295,6 +309,7 @@ int main(int argc, char** argv)
     if (!scene.m_Handle) return 1;
     if (!tracer.Create()) return 1;
     if (outputType != DCRT_OUTPUT_PATH_TRACING && !tracer.SetOutputType(outputType, iterationThreshold)) return 1;
+    if (roulette.enable && !tracer.SetRoulette(roulette)) return 1;   // (on the tracer: kept across uploads and --edit)
 
     // LoadScene: Reset + LoadFromFile (+ UI "Create -> Point Light", max bounce), then
     // OnSceneLoaded and the small-resolution size

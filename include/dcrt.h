@@ -1009,6 +1009,56 @@ DCRT_API int dcrt_tracer_read_environment_distribution(dcrt_tracer* tracer, floa
 /* The HIP-event time in ms of the last table build's three kernels (0: none built). */
 DCRT_API int dcrt_tracer_environment_build_timing(dcrt_tracer* tracer, float* out_ms);
 
+/* ===== Russian roulette ==========================================================
+ * A path runs to max_bounce_count unless it leaves the scene or its BSDF sample is rejected. With Russian
+ * roulette on, a path whose throughput has fallen is ended at random and the survivors are weighted up, which
+ * leaves every pixel's expectation as it was and removes the late, dim bounces' rays. Off by default: every
+ * result is then bit for bit what it was before this existed. No reference counterpart. tests/roulette_ref.py
+ * restates the rule in numpy float32.
+ *
+ * Where. At a shaded vertex whose bounce index b (0 at the camera ray's hit) is >= start_bounce, and only when
+ * the vertex's BSDF sample was accepted (bsdf nonzero and pdf nonzero). T' is the throughput after the sample,
+ * T' = T * bsdf * |n . wi| / pdf, all float32.
+ * Survival probability. q = fminf(fmaxf(fmaxf(fmaxf(T'.x, T'.y), T'.z), min_survival), max_survival), with
+ * fmaxf / fminf semantics, so q is always in [min_survival, max_survival]: a NaN component does not count (all
+ * three NaN: min_survival) and an infinite one gives max_survival.
+ * q >= 1. Nothing happens and no random number is drawn: with min_survival = max_survival = 1 the result is the
+ * roulette-off result bit for bit.
+ * Draw order. Otherwise u is the path's next random number, drawn immediately after the three numbers of the
+ * BSDF sample (the lobe selector, then the two sample coordinates). In the wavefront mode that is before the
+ * vertex's opacity draws (ALLOW_ANYHIT_SHADER: extension ray, then shadow ray); in the megakernel mode it is
+ * before anything the next bounce draws.
+ * Outcome. u < q: the path goes on with T' / q, a division per component (not a multiplication by 1 / q).
+ * Otherwise the path ends exactly as one whose BSDF sample was rejected: no extension ray, and the vertex's
+ * shadow ray, if it has one, is still cast and its light sample still added.
+ * Untouched. The vertex's light sample uses the throughput from before the roulette; the BSDF pdf carried to
+ * the next vertex's MIS weight and the delta flag are as without it; shadow rays are never rouletted.
+ * Depends on nothing but the path's own random numbers and throughput: pool size, image batch, film bands and
+ * the kernel route (early finish, drain, fused shadow test) do not change a bit of the result.
+ * Output views, dcrt_tracer_render_guides, the noise estimate, render_converged, adaptive sampling and the
+ * denoiser are unaffected and work on top of it unchanged. */
+typedef struct dcrt_roulette_params {
+    uint32_t enable;          /* 0: off (the other fields are kept and ignored) */
+    uint32_t start_bounce;    /* first bounce index tested; <= DCRT_MAX_RAY_BOUNCE */
+    float    min_survival;    /* 0 < min_survival <= max_survival <= 1 */
+    float    max_survival;
+} dcrt_roulette_params;       /* 16 bytes */
+/* The suggested setting, still off: enable 0, start_bounce 2, min_survival 0.05, max_survival 1. Needs no device. */
+DCRT_API int dcrt_roulette_default_params(dcrt_roulette_params* out);
+/* The setting lives on the tracer: kept across dcrt_tracer_upload_scene and the partial updates, read at the
+ * start of every image beside max_bounce_count (no captured graph depends on it). DCRT_E_INVALID_ARG unless
+ * 0 < min_survival <= max_survival <= 1 (non-finite values fail that) and start_bounce <= DCRT_MAX_RAY_BOUNCE;
+ * the setting then stays as it was. Film and path state are not touched: restart the image, as after
+ * dcrt_tracer_set_frame_params. */
+DCRT_API int dcrt_tracer_set_roulette(dcrt_tracer* tracer, const dcrt_roulette_params* params);
+DCRT_API int dcrt_tracer_get_roulette(dcrt_tracer* tracer, dcrt_roulette_params* out);
+/* The kernels' roulette on count given throughputs T' (3 floats each) with u in place of the path's draw (tests):
+ * out_q the survival probability, out_survive 1 where the path goes on (q >= 1 or u < q) else 0, out_scaled the
+ * throughput it goes on with (T' / q; T' itself where q >= 1 or the path ends). Of params only min_survival and
+ * max_survival are read; they are checked as the setter checks them. */
+DCRT_API int dcrt_device_roulette(dcrt_tracer* tracer, const dcrt_roulette_params* params, const float* throughputs,
+                                  const float* u, uint32_t count, float* out_q, uint32_t* out_survive, float* out_scaled);
+
 /* 24-bit BMP writer ("Save Image to File", SaveImageToFile.cpp:92-182). */
 DCRT_API int dcrt_write_bmp(const char* path, uint32_t width, uint32_t height, const uint8_t* rgba8);
 
