@@ -236,6 +236,11 @@ class RouletteParams(C.Structure):
     _fields_ = [("enable", C.c_uint32), ("start_bounce", C.c_uint32), ("min_survival", C.c_float), ("max_survival", C.c_float)]
 
 
+class LightTableInfo(C.Structure):
+    """dcrt_light_table_info (dcrt.h "light selection")."""
+    _fields_ = [("light_count", C.c_uint32), ("triangle_entries", C.c_uint32), ("scene_radius", C.c_double), ("total_weight", C.c_double)]
+
+
 OBJ_SCENE_LAYOUT = 1
 
 # Every symbol include/dcrt.h declares: (name, restype, argtypes)
@@ -382,6 +387,10 @@ SIGNATURES = [
     ("dcrt_tracer_get_environment_sampling", _I, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("dcrt_tracer_read_environment_distribution", _I, [_P, _FP, _FP, _FP]),
     ("dcrt_tracer_environment_build_timing", _I, [_P, _FP]),
+    ("dcrt_tracer_set_light_sampling", _I, [_P, _I]),
+    ("dcrt_tracer_get_light_sampling", _I, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("dcrt_tracer_read_light_distribution", _I, [_P, C.POINTER(LightTableInfo), _FP, _FP, C.POINTER(C.c_uint32), _FP, _FP]),
+    ("dcrt_tracer_light_table_build_timing", _I, [_P, _FP]),
     ("dcrt_roulette_default_params", _I, [C.POINTER(RouletteParams)]),
     ("dcrt_tracer_set_roulette", _I, [_P, C.POINTER(RouletteParams)]),
     ("dcrt_tracer_get_roulette", _I, [_P, C.POINTER(RouletteParams)]),

@@ -37,7 +37,13 @@ constexpr uint32_t kCapAll = (1u << 12) - 1u;
 // kCapAll and kCapOpaqueDelta keep their values and their code.
 constexpr uint32_t kCapEnvImportance = 1u << 12;
 constexpr uint32_t kCapAllEnvImportance = kCapAll | kCapEnvImportance;
-// CAPS covers any scene (kCapAll, with or without kCapEnvImportance)
+// ... and the one any-scene variant that picks lights and lamp triangles by the light table
+// (DeviceScene::lightProb, "light selection" in dcrt.h). It carries kCapEnvImportance too and tests
+// both tables by pointer at run time: one variant serves the light table with the environment table
+// on or off, not two.
+constexpr uint32_t kCapLightTable = 1u << 13;
+constexpr uint32_t kCapAllLightTable = kCapAll | kCapEnvImportance | kCapLightTable;
+// CAPS covers any scene (kCapAll, with or without the bits beyond it)
 constexpr bool caps_any_scene(uint32_t caps) { return (caps & kCapAll) == kCapAll; }
 constexpr uint32_t kCapMaterialsMask = 0x1Fu;
 constexpr uint32_t kCapLightShift = 7;
@@ -133,6 +139,15 @@ struct DeviceScene {
     // MATERIAL finishes a path at its last shaded bounce (material_kernel's EARLY; DCRT_EARLY_FINISH): 0 off,
     // 1 on, 2 on for even path slots only. MaterialPlan sets it where the variant's CAPS admit it.
     uint32_t earlyFinish;
+    // The light table (DCRT_LIGHT_SAMPLING_POWER, dcrt.h; light_tri_area_kernel and its successors build
+    // it): per light its probability and the CDF over the lights, the first of its entries among the
+    // emissive triangles; per emissive triangle, in light order, its probability within its lamp and the
+    // lamp's CDF. Null: lights and triangles are picked uniformly.
+    const float* lightProb;
+    const float* lightCdf;
+    const uint32_t* triBase;
+    const float* triProb;
+    const float* triCdf;
 };
 
 // DCRT_SHADING_TABLES bits: per-hit work whose inputs are fixed at scene upload
@@ -1430,13 +1445,29 @@ DEV V3 tri_pos(const DeviceScene& s, uint32_t tri, int k)
     return mk(q.x, q.y, q.z);
 }
 
+// ---- light selection (dcrt.h) ---------------------------------------------------------
+// The uniform share of P(l): every light stays reachable, 1 / P <= 16 n
+constexpr double kLightUniformShare = 1.0 / 16.0;
+// A lamp triangle's area as the table counts it: the sampler's float32 area, 0 below its threshold or not finite
+DEV float light_table_area(float area) { return area >= 1e-6f && area <= 3.402823466e38f ? area : 0.0f; }
+// The selection factor of triangle k of mesh light li, per unit area: P(l) P(t | l) / a_t. Light sampling and
+// light evaluation both take their density from here, so the MIS pair stays a partition of unity.
+DEV float light_table_mesh_factor(const DeviceScene& s, uint32_t li, uint32_t k, float area)
+{
+    const float sel = s.lightProb[li] * s.triProb[s.triBase[li] + k];
+    return light_table_area(area) > 0.0f ? sel / area : 0.0f;
+}
+
 template <uint32_t CAPS = kCapAll>
 DEV LightSample sample_light(const DeviceScene& s, V3 p, uint32_t lightCount, Rng& rng)
 {
     LightSample r;
     r.radiance = mk(0.0f, 0.0f, 0.0f); r.wi = mk(0.0f, 0.0f, 0.0f); r.pdf = 0.0f; r.distance = 0.0f; r.isDelta = false;
     const float sel = next1(rng);
-    const uint32_t li = (uint32_t)floorf(sel * (float)lightCount);
+    if constexpr ((CAPS & kCapLightTable) == 0u) __builtin_assume(s.lightProb == nullptr);
+    bool byTable = false;
+    if constexpr ((CAPS & kCapLightTable) != 0u) byTable = s.lightProb != nullptr;
+    const uint32_t li = byTable ? env_cdf_search(s.lightCdf, lightCount, sel) : (uint32_t)floorf(sel * (float)lightCount);
     const dcrt_light& L = s.lights[li];
     assume_light_caps<CAPS>(L.flags);
     if constexpr ((CAPS & kCapEnvCube) == 0u) __builtin_assume(s.envCube == nullptr);
@@ -1460,7 +1491,8 @@ DEV LightSample sample_light(const DeviceScene& s, V3 p, uint32_t lightCount, Rn
         const uint32_t triOffset = asu(L.position_or_triangle_range[0]);
         const uint32_t triCount = asu(L.position_or_triangle_range[1]);
         const uint32_t instance = asu(L.position_or_triangle_range[2]);
-        const uint32_t tri = (uint32_t)((float)triOffset + floorf(triSel * (float)triCount));
+        const uint32_t triPick = byTable ? env_cdf_search(s.triCdf + s.triBase[li], triCount, triSel) : 0u;
+        const uint32_t tri = byTable ? triOffset + triPick : (uint32_t)((float)triOffset + floorf(triSel * (float)triCount));
         const V3 v0 = tri_pos(s, tri, 0), v1 = tri_pos(s, tri, 1), v2 = tri_pos(s, tri, 2);
         const float4* M = s.transforms + (size_t)instance * 3;
         const V3 w0 = mul43(v0, 1.0f, M), w1 = mul43(v1, 1.0f, M), w2 = mul43(v2, 1.0f, M);
@@ -1470,6 +1502,7 @@ DEV LightSample sample_light(const DeviceScene& s, V3 p, uint32_t lightCount, Rn
         V3 sp = bary3(v0, v1, v2, bu, bv);
         V3 nrm = normalize(cross(v2 - v0, v1 - v0));
         float pdf = area >= 1e-6f ? 1.0f / (area * 0.5f) : 0.0f;
+        if (byTable) pdf = light_table_mesh_factor(s, li, triPick, area);
         sp = mul43(sp, 1.0f, M);
         nrm = normalize(mul43(nrm, 0.0f, M));
         r.wi = sp - p;
@@ -1479,7 +1512,7 @@ DEV LightSample sample_light(const DeviceScene& s, V3 p, uint32_t lightCount, Rn
         pdf = pdf * (r.distance * r.distance / WIdotN);
         r.radiance = (WIdotN > 0.0f && pdf > 0.0f) ? ld3(L.radiance) : mk(0.0f, 0.0f, 0.0f);
         r.pdf = WIdotN > 0.0f ? pdf : 0.0f;
-        r.pdf = r.pdf / (float)triCount;
+        if (!byTable) r.pdf = r.pdf / (float)triCount;
     } else if (L.flags & DCRT_LIGHT_FLAGS_ENVIRONMENT_LIGHT) {
         const float a = next1(rng), b = next1(rng);
         bool table = false;
@@ -1495,7 +1528,9 @@ DEV LightSample sample_light(const DeviceScene& s, V3 p, uint32_t lightCount, Rn
         r.radiance = s.envCube ? sample_env(s, r.wi) * ld3(L.radiance) : ld3(L.radiance);
         r.distance = inf();
     }
-    r.pdf = r.pdf / (float)lightCount;
+    // (under the table a mesh light's factor holds P(l) already; the other kinds take it here)
+    if (byTable) r.pdf = (L.flags & DCRT_LIGHT_FLAGS_MESH_LIGHT) ? r.pdf : r.pdf * s.lightProb[li];
+    else r.pdf = r.pdf / (float)lightCount;
     if (r.distance != inf()) r.distance = r.distance * (1.0f - kShadowEpsilon);
     return r;
 }
@@ -1506,6 +1541,9 @@ DEV void evaluate_light(const DeviceScene& s, uint32_t li, uint32_t tri, V3 norm
 {
     *radiance = mk(0.0f, 0.0f, 0.0f);
     *pdf = 0.0f;
+    if constexpr ((CAPS & kCapLightTable) == 0u) __builtin_assume(s.lightProb == nullptr);
+    bool byTable = false;
+    if constexpr ((CAPS & kCapLightTable) != 0u) byTable = s.lightProb != nullptr;
     const dcrt_light& L = s.lights[li];
     assume_light_caps<CAPS>(L.flags);
     if constexpr ((CAPS & kCapEnvCube) == 0u) __builtin_assume(s.envCube == nullptr);
@@ -1517,8 +1555,11 @@ DEV void evaluate_light(const DeviceScene& s, uint32_t li, uint32_t tri, V3 norm
         float p = area >= 1e-6f ? 1.0f / (area * 0.5f) : 0.0f;
         const float WIdotN = -dot(wi, normal);
         *radiance = WIdotN > 0.0f ? ld3(L.radiance) : mk(0.0f, 0.0f, 0.0f);
+        // (the k of a triangle outside the lamp's range is clamped into it: no input reads past the table)
+        const uint32_t triOffset = asu(L.position_or_triangle_range[0]), triCount = asu(L.position_or_triangle_range[1]);
+        if (byTable) p = light_table_mesh_factor(s, li, tri >= triOffset && tri - triOffset < triCount ? tri - triOffset : 0u, area * 0.5f);
         p = p * (WIdotN > 0.0f ? distance * distance / dot(-wi, normal) : 0.0f);
-        *pdf = p / (float)asu(L.position_or_triangle_range[1]);
+        *pdf = byTable ? p : p / (float)triCount;
     } else if (L.flags & DCRT_LIGHT_FLAGS_ENVIRONMENT_LIGHT) {
         *radiance = s.envCube ? sample_env(s, wi) * ld3(L.radiance) : ld3(L.radiance);
         *pdf = uniform_sphere_pdf();
@@ -1526,7 +1567,8 @@ DEV void evaluate_light(const DeviceScene& s, uint32_t li, uint32_t tri, V3 norm
             if (s.envProb != nullptr) *pdf = env_pdf(s, wi);
         }
     }
-    *pdf = *pdf / (float)lightCount;
+    if (byTable) *pdf = (L.flags & DCRT_LIGHT_FLAGS_MESH_LIGHT) ? *pdf : *pdf * s.lightProb[li];
+    else *pdf = *pdf / (float)lightCount;
 }
 
 }  // namespace dev

@@ -232,6 +232,118 @@ __global__ __launch_bounds__(256) void env_finish_kernel(const float* cube, uint
     if (x == 0u) marginal[r] = r == rows - 1u ? 1.0f : (float)(marginalSums[r] / total);
 }
 
+// ---- the light table (dcrt.h, "light selection") ------------------------------------------------
+// Four plain 256-thread launches at upload; a light edit that keeps the lamps reruns the third alone.
+// Sums are float64 throughout; a stored value is one rounding of a float64 quotient. `triBase` comes
+// from the host (dcrt_tracer::BuildLightTable), which also holds every mesh light's range to the scene.
+// The kind light sampling takes a light for: its tests' order (point, directional, mesh, environment)
+DEV uint32_t light_table_kind(uint32_t flags)
+{
+    if (flags & DCRT_LIGHT_FLAGS_POINT_LIGHT) return DCRT_LIGHT_FLAGS_POINT_LIGHT;
+    if (flags & DCRT_LIGHT_FLAGS_DIRECTIONAL_LIGHT) return DCRT_LIGHT_FLAGS_DIRECTIONAL_LIGHT;
+    if (flags & DCRT_LIGHT_FLAGS_MESH_LIGHT) return DCRT_LIGHT_FLAGS_MESH_LIGHT;
+    return flags & DCRT_LIGHT_FLAGS_ENVIRONMENT_LIGHT;
+}
+DEV uint32_t light_table_tri_count(const dcrt_light& L)
+{
+    return light_table_kind(L.flags) == DCRT_LIGHT_FLAGS_MESH_LIGHT ? asu(L.position_or_triangle_range[1]) : 0u;
+}
+// The light of emissive entry e: the last l with triBase[l] <= e (triBase[0] = 0; lights without entries share
+// their successor's base and come before it)
+DEV uint32_t light_of_entry(const uint32_t* triBase, uint32_t n, uint32_t e)
+{
+    uint32_t lo = 0u, hi = n;
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (triBase[mid] <= e) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// One thread per emissive entry: a_t as sample_light computes it, 0 where the sampler's threshold rejects it
+__global__ __launch_bounds__(256) void light_tri_area_kernel(DeviceScene sc, const uint32_t* triBase, uint32_t n, uint32_t entries, float* areas)
+{
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= entries) return;
+    const uint32_t l = light_of_entry(triBase, n, e);
+    const dcrt_light& L = sc.lights[l];
+    const uint32_t tri = asu(L.position_or_triangle_range[0]) + (e - triBase[l]);
+    const float4* M = sc.transforms + (size_t)asu(L.position_or_triangle_range[2]) * 3;
+    const V3 w0 = mul43(tri_pos(sc, tri, 0), 1.0f, M), w1 = mul43(tri_pos(sc, tri, 1), 1.0f, M), w2 = mul43(tri_pos(sc, tri, 2), 1.0f, M);
+    areas[e] = light_table_area(length(cross(w2 - w0, w1 - w0)) * 0.5f);
+}
+// One wave per light: its triangles' areas scanned in chunks of 64 entries with a carry; the unnormalised
+// triangle CDF and the lamp's area A_l (0 for a light that is no mesh light)
+__global__ __launch_bounds__(256) void light_tri_scan_kernel(const dcrt_light* lights, const uint32_t* triBase, uint32_t n, const float* areas,
+                                                             double* triSums, double* lightAreas)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t l = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (l >= n) return;   // (whole waves leave: l is wave-uniform)
+    const uint32_t count = light_table_tri_count(lights[l]), base = triBase[l];
+    double carry = 0.0;
+    for (uint32_t k0 = 0u; k0 < count; k0 += 64u) {
+        const uint32_t k = k0 + lane;
+        const double inc = carry + env_wave_scan(k < count ? (double)areas[base + k] : 0.0);
+        if (k < count) triSums[base + k] = inc;
+        carry = __shfl(inc, 63, 64);
+    }
+    if (lane == 0u) lightAreas[l] = carry;
+}
+// A light's weight: its power up to the factors the definition keeps (radius: R, meanY: the cube's Ybar or 1)
+DEV double light_table_weight(const dcrt_light& L, double area, double radius, double meanY)
+{
+    const double pi = 3.14159265358979323846;
+    const double y = (double)fmaxf(0.0f, L.radiance[0] * 0.299f + L.radiance[1] * 0.587f + L.radiance[2] * 0.114f);
+    switch (light_table_kind(L.flags)) {
+    case DCRT_LIGHT_FLAGS_POINT_LIGHT: return 4.0 * pi * y;
+    case DCRT_LIGHT_FLAGS_DIRECTIONAL_LIGHT: return pi * radius * radius * y;
+    case DCRT_LIGHT_FLAGS_MESH_LIGHT: return pi * y * area;
+    case DCRT_LIGHT_FLAGS_ENVIRONMENT_LIGHT: return 4.0 * pi * (pi * radius * radius) * y * meanY;
+    default: return 0.0;
+    }
+}
+// One workgroup over the lights: the weights scanned in chunks of its width with a carry, then P(l) with its
+// uniform share and the CDF of P; the total behind the sums' last entry, for the host's "inactive" test.
+__global__ __launch_bounds__(256) void light_weights_kernel(const dcrt_light* lights, uint32_t n, const double* lightAreas, double radius, double meanY,
+                                                            double* weightSums, float* lightProb, float* lightCdf)
+{
+    __shared__ double waveTotals[4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    double carry = 0.0;
+    for (uint32_t l0 = 0u; l0 < n; l0 += 256u) {
+        const uint32_t l = l0 + threadIdx.x;
+        const double inc = env_wave_scan(l < n ? light_table_weight(lights[l], lightAreas[l], radius, meanY) : 0.0);
+        if (lane == 63u) waveTotals[wave] = inc;
+        __syncthreads();
+        double before = carry;
+        for (uint32_t w = 0u; w < wave; ++w) before += waveTotals[w];
+        if (l < n) weightSums[l] = before + inc;
+        carry = carry + waveTotals[0] + waveTotals[1] + waveTotals[2] + waveTotals[3];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0u) weightSums[n] = carry;
+    // (every thread holds the same total, and reads back only the sums it wrote itself)
+    const double total = carry, share = kLightUniformShare;
+    for (uint32_t l = threadIdx.x; l < n; l += 256u) {
+        const double w = light_table_weight(lights[l], lightAreas[l], radius, meanY);
+        lightProb[l] = (float)((1.0 - share) * (w / total) + share / (double)n);
+        lightCdf[l] = l == n - 1u ? 1.0f : (float)((1.0 - share) * (weightSums[l] / total) + share * (double)(l + 1u) / (double)n);
+    }
+}
+// Per emissive entry: P(t | l) = a_t / A_l and the lamp's CDF, its last entry exactly 1; zeros for a lamp without area
+__global__ __launch_bounds__(256) void light_tri_finish_kernel(const dcrt_light* lights, const uint32_t* triBase, uint32_t n, uint32_t entries,
+                                                               const float* areas, const double* triSums, const double* lightAreas,
+                                                               float* triProb, float* triCdf)
+{
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= entries) return;
+    const uint32_t l = light_of_entry(triBase, n, e);
+    const double A = lightAreas[l];
+    const bool last = e - triBase[l] == light_table_tri_count(lights[l]) - 1u;
+    triProb[e] = A > 0.0 ? (float)((double)areas[e] / A) : 0.0f;
+    triCdf[e] = A > 0.0 ? (last ? 1.0f : (float)(triSums[e] / A)) : 0.0f;
+}
+
 // The per-material rows of the plastic dielectric LUT (DeviceScene::dielRows; a launch per upload of
 // the materials or the LUTs): float k of material m at rows[m * kDielRowFloats + k], with alpha as
 // hit_to_intersection forms it for a material without the roughness checkerboard.
@@ -1502,7 +1614,8 @@ __device__ __forceinline__ bool trace_full(const DeviceScene& sc, V3 o, V3 d, fl
     return s.found;
 }
 
-// CAPS: kCapAll, or kCapAllEnvImportance where the environment cube is sampled by its table
+// CAPS: kCapAll, kCapAllEnvImportance where the environment cube is sampled by its table, or kCapAllLightTable
+// where lights are picked by the light table (and the cube by its table, if one stands)
 template <bool OPACITY, uint32_t CAPS = kCapAll>
 __global__ __launch_bounds__(256) void megakernel(DeviceScene sc, const FrameConstants* __restrict__ fcp, Film film, Globals* g, uint32_t debugRng)
 {
@@ -3033,6 +3146,8 @@ template __global__ void megakernel<false>(DeviceScene, const FrameConstants*, F
 template __global__ void megakernel<true>(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t);
 template __global__ void megakernel<false, kCapAllEnvImportance>(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t);
 template __global__ void megakernel<true, kCapAllEnvImportance>(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t);
+template __global__ void megakernel<false, kCapAllLightTable>(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t);
+template __global__ void megakernel<true, kCapAllLightTable>(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t);
 template __global__ void view_kernel<false>(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t, uint32_t, uint32_t);
 template __global__ void view_kernel<true>(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t, uint32_t, uint32_t);
 template __global__ void batch_trace_kernel<false, false>(DeviceScene, const dcrt_ray*, uint32_t, uint32_t, dcrt_ray_hit*, uint32_t*, unsigned long long*);

@@ -773,6 +773,14 @@ struct MaterialPlan {
     const float* envProb = nullptr;
     const float* envRowCdf = nullptr;
     const float* envMarginal = nullptr;
+    // The light table in force (dcrt_tracer::BuildLightTable) with the light count it was built for, or null / 0:
+    // uniform selection
+    const float* lightProb = nullptr;
+    const float* lightCdf = nullptr;
+    const uint32_t* triBase = nullptr;
+    const float* triProb = nullptr;
+    const float* triCdf = nullptr;
+    uint32_t lightTableCount = 0;
     uint32_t fusedMask = 0;            // DCRT_FUSED_SHADOW's path-slot mask (FrameConstants::shadowInlineMask: not baked into a graph)
     uint32_t drainGrid = 0;            // drain_kernel's grid: resident workgroups on the whole chip
     // DCRT_EARLY_FINISH as it stands for the variant: 0 unless its CAPS admit it (caps_early_finish). The same
@@ -785,6 +793,15 @@ struct MaterialPlan {
     MaterialFn Kernel(bool probe, bool fused) const
     {
         const bool od = caps == kCapOpaqueDelta;
+        // (no fused form under the light table either: such a plan never launches it, as below)
+        if (caps == kCapAllLightTable && !fused) {
+            if (probe) return material_kernel<kCapAllLightTable, 0, true>;
+            switch (mode) {
+            case 1: return material_kernel<kCapAllLightTable, 1>;
+            case 2: return material_kernel<kCapAllLightTable, 2>;
+            default: return material_kernel<kCapAllLightTable, 0>;
+            }
+        }
         if (caps == kCapAllEnvImportance && !fused) {
             if (probe) return material_kernel<kCapAllEnvImportance, 0, true>;
             switch (mode) {
@@ -805,11 +822,13 @@ struct MaterialPlan {
     }
     auto DrainKernel() const
     {
+        if (caps == kCapAllLightTable) return drain_kernel<kCapAllLightTable>;
         return caps == kCapOpaqueDelta ? drain_kernel<kCapOpaqueDelta> : caps == kCapAllEnvImportance ? drain_kernel<kCapAllEnvImportance> : drain_kernel<kCapAll>;
     }
     using MegaFn = void (*)(DeviceScene, const FrameConstants*, Film, Globals*, uint32_t);
     MegaFn Megakernel(bool opacity) const
     {
+        if (caps == kCapAllLightTable) return opacity ? megakernel<true, kCapAllLightTable> : megakernel<false, kCapAllLightTable>;
         if (caps == kCapAllEnvImportance) return opacity ? megakernel<true, kCapAllEnvImportance> : megakernel<false, kCapAllEnvImportance>;
         return opacity ? megakernel<true> : megakernel<false>;
     }
@@ -827,6 +846,11 @@ struct MaterialPlan {
         d->envProb = envProb;
         d->envRowCdf = envRowCdf;
         d->envMarginal = envMarginal;
+        d->lightProb = lightProb;
+        d->lightCdf = lightCdf;
+        d->triBase = triBase;
+        d->triProb = triProb;
+        d->triCdf = triCdf;
         d->earlyFinish = earlyFinish;
     }
     // What a captured graph bakes in: kernels, LDS bytes, the drain grid, what Apply writes (the pointers follow the bits)
@@ -834,7 +858,9 @@ struct MaterialPlan {
     {
         return caps == o.caps && mode == o.mode && materials == o.materials && lights == o.lights && lds.shading == o.lds.shading &&
                lds.rows == o.lds.rows && lds.frames == o.lds.frames && lds.cells == o.lds.cells && tables == o.tables && drainGrid == o.drainGrid &&
-               envProb == o.envProb && envRowCdf == o.envRowCdf && envMarginal == o.envMarginal && earlyFinish == o.earlyFinish;
+               envProb == o.envProb && envRowCdf == o.envRowCdf && envMarginal == o.envMarginal && earlyFinish == o.earlyFinish &&
+               lightProb == o.lightProb && lightCdf == o.lightCdf && triBase == o.triBase && triProb == o.triProb && triCdf == o.triCdf &&
+               lightTableCount == o.lightTableCount;
     }
 };
 
@@ -909,6 +935,31 @@ struct dcrt_tracer {
     float* dEnvMarginal = nullptr;
     float envBuildMs = 0.0f;
     bool EnvTableActive() const { return hasScene && envSampling == DCRT_ENV_SAMPLING_IMPORTANCE && dEnvProb != nullptr; }
+    // Light selection (dcrt.h): the mode asked for, which outlives the scene, and the table of the lights as they
+    // stand -- null when there is none ("inactive": no lights, one light that is no lamp, a total weight that is zero
+    // or not finite, a lamp whose triangles lie outside the scene). The buffers live in a group of their own: a
+    // rebuild for other lamps frees them, an edit of the colours alone rewrites lightProb and lightCdf in place.
+    int lightSampling = DCRT_LIGHT_SAMPLING_UNIFORM;
+    DeviceGroup lightAllocs;
+    struct LightTable {
+        float* prob = nullptr;
+        float* cdf = nullptr;
+        uint32_t* triBase = nullptr;
+        float* triProb = nullptr;
+        float* triCdf = nullptr;
+        float* areas = nullptr;          // a_t per entry, and the float64 sums the finish pass normalises
+        double* triSums = nullptr;
+        double* lightAreas = nullptr;    // A_l: what the light-level kernel reads again after a colour edit
+        double* weightSums = nullptr;    // n + 1: the unnormalised CDF and the total
+        uint32_t entries = 0;
+        double total = 0.0;
+        std::vector<dcrt_light> lights;  // the lights it was built for
+    } lightTable;
+    double sceneRadius = 0.0;            // R: half the diagonal of the uploaded BVH root's box
+    double envMeanY = 1.0;               // Ybar of the uploaded cube (1 without one), once envMeanYKnown
+    bool envMeanYKnown = true;
+    float lightBuildMs = 0.0f;
+    bool LightTableActive() const { return hasScene && lightSampling == DCRT_LIGHT_SAMPLING_POWER && lightTable.prob != nullptr; }
     // Russian roulette (dcrt.h): the tracer's setting, kept across uploads and edits; BeginImage writes it into the
     // frame constants beside maxBounce, so a change costs no graph
     dcrt_roulette_params roulette = kRouletteDefaults;
@@ -1042,6 +1093,10 @@ struct dcrt_tracer {
     int PlanMaterial(const MaterialPlan* before, MaterialPlan* out);
     int ApplyMaterialPlan(const MaterialPlan& p);
     int BuildEnvTable();
+    int BuildLightTable();
+    int LightWeights();
+    int CubeMeanLuminance();
+    int SetLightSampling(int mode);
     int SetEnvSampling(int mode);
     int BuildDielRows();
     int RederiveShading();
@@ -1386,6 +1441,17 @@ int dcrt_tracer::PlanMaterial(const MaterialPlan* before, MaterialPlan* out)
         p.envRowCdf = dEnvRowCdf;
         p.envMarginal = dEnvMarginal;
     }
+    // (the light table, where the mode is on and one stands: the one any-scene variant that reads it, and the cube's
+    // table through the same variant if that stands too)
+    if (lightSampling == DCRT_LIGHT_SAMPLING_POWER && lightTable.prob) {
+        p.caps = kCapAllLightTable;
+        p.lightProb = lightTable.prob;
+        p.lightCdf = lightTable.cdf;
+        p.triBase = lightTable.triBase;
+        p.triProb = lightTable.triProb;
+        p.triCdf = lightTable.triCdf;
+        p.lightTableCount = L;
+    }
     // 2. the LDS scene copy within the knob's budget: the whole shading data (mode 1), else all but the triangles (mode 2)
     const bool counts = T > 0 && T < (1u << 20) && I < (1u << 20) && M < (1u << 20) && L < (1u << 20);
     const uint64_t whole = material_lds_layout(T, I, M, L, 0u, false, 0u, false).shading;
@@ -1510,6 +1576,7 @@ int dcrt_tracer::UpdateLights(const dcrt_light* lights, uint32_t count)
     if (count) HIPCHECK(hipMemcpyAsync(dLights, hostLights.data(), (size_t)count * sizeof(dcrt_light), hipMemcpyHostToDevice, stream));
     uploadStats.shading_bytes += (uint64_t)count * sizeof(dcrt_light);
     ++uploadStats.light_updates;
+    if (lightSampling == DCRT_LIGHT_SAMPLING_POWER) CHECKED(BuildLightTable());
     CHECKED(RederiveShading());
     CHECKED(RebuildShadowCells());
     HIPCHECK(hipStreamSynchronize(stream));
@@ -1571,6 +1638,12 @@ int dcrt_tracer::CheckFrameLights() const
                      " lights uploaded");
         return DCRT_E_INVALID_ARG;
     }
+    // (the light table's CDF covers the lights uploaded, all of them)
+    if (LightTableActive() && frame.light_count != hostLights.size()) {
+        SetLastError("frame light_count " + std::to_string(frame.light_count) + " differs from the " + std::to_string(hostLights.size()) +
+                     " lights the light table was built for");
+        return DCRT_E_INVALID_ARG;
+    }
     return DCRT_OK;
 }
 
@@ -1609,6 +1682,8 @@ int dcrt_tracer::UploadArrays(const dcrt_flat_scene& s, std::vector<uint32_t>* i
     sceneAllocs.Free();
     hasScene = false;
     dEnvProb = dEnvRowCdf = dEnvMarginal = nullptr;   // (the last scene's table went with sceneAllocs)
+    lightAllocs.Free();
+    lightTable = LightTable{};
     ++uploadStats.scene_uploads;
     DeviceScene d{};
     // (shading_bytes: the three arrays an edit replaces)
@@ -1725,6 +1800,17 @@ int dcrt_tracer::UploadArrays(const dcrt_flat_scene& s, std::vector<uint32_t>* i
     d.singlePrimLeaves = dcrt::SingleTriangleLeaves(s) ? 1u : 0u;
     plan.scene = d;
     if (envSampling == DCRT_ENV_SAMPLING_IMPORTANCE) CHECKED(BuildEnvTable());
+    // what the light table's weights take from the scene (dcrt.h, "light selection"): R of the BVH root's box here; Ybar of
+    // the cube only once a table asks for it (CubeMeanLuminance: with the mode off an upload does none of that work)
+    {
+        const dcrt_bvh_node& root = s.bvh_nodes[0];
+        double q = 0.0;
+        for (int a = 0; a < 3; ++a) q += ((double)root.bbox_max[a] - (double)root.bbox_min[a]) * ((double)root.bbox_max[a] - (double)root.bbox_min[a]);
+        sceneRadius = 0.5 * std::sqrt(q);
+        envMeanY = 1.0;
+        envMeanYKnown = dEnv == nullptr;
+    }
+    if (lightSampling == DCRT_LIGHT_SAMPLING_POWER) CHECKED(BuildLightTable());
     return DCRT_OK;
 }
 
@@ -4032,10 +4118,12 @@ static bool LightInScene(const dcrt_light& L, const DeviceScene& sc)
 // The light probes' kernels for the scene's MATERIAL variant: the cube sampled by its table, or the any-scene stack
 static auto LightSampleProbe(const dcrt_tracer* t)
 {
+    if (t->material.caps == kCapAllLightTable) return light_sample_probe_kernel<kCapAllLightTable>;
     return t->material.caps == kCapAllEnvImportance ? light_sample_probe_kernel<kCapAllEnvImportance> : light_sample_probe_kernel<kCapAll>;
 }
 static auto LightEvalProbe(const dcrt_tracer* t)
 {
+    if (t->material.caps == kCapAllLightTable) return light_eval_probe_kernel<kCapAllLightTable>;
     return t->material.caps == kCapAllEnvImportance ? light_eval_probe_kernel<kCapAllEnvImportance> : light_eval_probe_kernel<kCapAll>;
 }
 
@@ -4076,6 +4164,7 @@ static int ProbeLights(dcrt_tracer* t, uint32_t* lightCount)
     if (!t->hasScene) { SetLastError("no scene uploaded"); return DCRT_E_NO_SCENE; }
     if (!t->hasFrame) { SetLastError("no frame parameters"); return DCRT_E_INVALID_ARG; }
     *lightCount = t->frame.light_count;
+    CHECKED(t->CheckFrameLights());   // (under the light table: exactly the lights it was built for)
     if (*lightCount == 0u || *lightCount > t->hostLights.size()) { SetLastError("light probe: the frame has no lights"); return DCRT_E_INVALID_ARG; }
     for (uint32_t i = 0; i < *lightCount; ++i) {
         if (!LightInScene(t->hostLights[i], t->plan.scene)) { SetLastError("light probe: a mesh light's triangles or instance lie outside the scene"); return DCRT_E_INVALID_ARG; }
@@ -4092,8 +4181,10 @@ DCRT_API int dcrt_device_light_sample(dcrt_tracer* t, const float* points, const
     CHECKED(ProbeLights(t, &lightCount));
     // the two selections a state leads to stay inside the arrays: float(draw) * count can round up to count
     // (xoshiro128**'s output and state step, as dmath.h has them)
+    // Under the light table both searches are clamped to the arrays and every lamp lies inside the scene
+    // (BuildLightTable); ProbeLights has held the frame to the table's light count.
     auto rotl = [](uint32_t x, int k) { return (x << k) | (x >> (32 - k)); };
-    for (uint32_t i = 0; i < n; ++i) {
+    for (uint32_t i = 0; i < n && !t->LightTableActive(); ++i) {
         uint32_t s[4];
         std::memcpy(s, states + 4 * (size_t)i, sizeof(s));
         float draw[2];
@@ -4217,6 +4308,204 @@ DCRT_API int dcrt_tracer_environment_build_timing(dcrt_tracer* t, float* out_ms)
 {
     if (!t || !out_ms) return DCRT_E_INVALID_ARG;
     *out_ms = t->envBuildMs;
+    return DCRT_OK;
+}
+
+// The light table of the lights as they stand (dcrt.h, "light selection"; the kernels: kernels_impl.h), on the
+// tracer's stream between two events. Where the lights' count, kinds, triangle ranges and instances are those the
+// standing table was built for, only the light-level kernel runs again, into the same buffers: A_l is kept on the
+// device, and no captured graph notices. Otherwise the buffers are freed and the whole table is built. No table:
+// see dcrt_tracer::lightTable.
+int dcrt_tracer::BuildLightTable()
+{
+    const uint32_t n = (uint32_t)hostLights.size();
+    auto lamp = [](const dcrt_light& a, uint32_t w[3]) { return MeshLightRange(a, w) && !(a.flags & DCRT_LIGHT_FLAGS_POINT_LIGHT); };
+    auto sameLamps = [&]() {
+        if (!lightTable.prob || lightTable.lights.size() != n) return false;
+        for (uint32_t i = 0; i < n; ++i) {
+            const dcrt_light &a = lightTable.lights[i], &b = hostLights[i];
+            if (a.flags != b.flags) return false;
+            uint32_t wa[3], wb[3];
+            if (lamp(a, wa) && lamp(b, wb) && std::memcmp(wa, wb, sizeof(wa)) != 0) return false;
+        }
+        return true;
+    };
+    lightBuildMs = 0.0f;
+    if (sameLamps()) {
+        lightTable.lights = hostLights;
+        CHECKED(LightWeights());
+        if (!(lightTable.total > 0.0 && std::isfinite(lightTable.total))) {
+            lightAllocs.Free();
+            lightTable = LightTable{};
+        }
+        return DCRT_OK;
+    }
+    lightAllocs.Free();
+    lightTable = LightTable{};
+    if (n == 0u) return DCRT_OK;
+    uint32_t w[3];
+    if (n == 1u && !lamp(hostLights[0], w)) return DCRT_OK;   // (nothing to choose: the Cornell configs keep their variants)
+    std::vector<uint32_t> base(n);
+    uint64_t entries = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        base[i] = (uint32_t)entries;
+        if (!lamp(hostLights[i], w)) continue;
+        if (!LightInScene(hostLights[i], plan.scene)) return DCRT_OK;   // (a lamp the kernels could not read)
+        entries += w[1];
+        if (entries > 0x7FFFFFFFu) return DCRT_OK;
+    }
+    CHECKED(CubeMeanLuminance());
+    LightTable t;
+    t.entries = (uint32_t)entries;
+    t.lights = hostLights;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto build = [&]() -> int {
+        CHECKED(lightAllocs.Alloc(&t.prob, n));
+        CHECKED(lightAllocs.Alloc(&t.cdf, n));
+        CHECKED(lightAllocs.Alloc(&t.triBase, n));
+        CHECKED(lightAllocs.Alloc(&t.triProb, t.entries));
+        CHECKED(lightAllocs.Alloc(&t.triCdf, t.entries));
+        CHECKED(lightAllocs.Alloc(&t.areas, t.entries));
+        CHECKED(lightAllocs.Alloc(&t.triSums, t.entries));
+        CHECKED(lightAllocs.Alloc(&t.lightAreas, n));
+        CHECKED(lightAllocs.Alloc(&t.weightSums, (size_t)n + 1));
+        HIPCHECK(hipMemcpyAsync(t.triBase, base.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        HIPCHECK(hipEventCreate(&e0));
+        HIPCHECK(hipEventCreate(&e1));
+        HIPCHECK(hipEventRecord(e0, stream));
+        if (t.entries)
+            hipLaunchKernelGGL(light_tri_area_kernel, dim3((t.entries + 255u) / 256u), dim3(256), 0, stream, plan.scene, (const uint32_t*)t.triBase, n, t.entries, t.areas);
+        hipLaunchKernelGGL(light_tri_scan_kernel, dim3((n + 3u) / 4u), dim3(256), 0, stream, (const dcrt_light*)dLights, (const uint32_t*)t.triBase, n,
+                           (const float*)t.areas, t.triSums, t.lightAreas);
+        hipLaunchKernelGGL(light_weights_kernel, dim3(1), dim3(256), 0, stream, (const dcrt_light*)dLights, n, (const double*)t.lightAreas, sceneRadius, envMeanY,
+                           t.weightSums, t.prob, t.cdf);
+        if (t.entries)
+            hipLaunchKernelGGL(light_tri_finish_kernel, dim3((t.entries + 255u) / 256u), dim3(256), 0, stream, (const dcrt_light*)dLights, (const uint32_t*)t.triBase, n,
+                               t.entries, (const float*)t.areas, (const double*)t.triSums, (const double*)t.lightAreas, t.triProb, t.triCdf);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipEventRecord(e1, stream));
+        HIPCHECK(hipMemcpyAsync(&t.total, t.weightSums + n, sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHECK(hipStreamSynchronize(stream));   // (base ends with this function)
+        HIPCHECK(hipEventElapsedTime(&lightBuildMs, e0, e1));
+        return DCRT_OK;
+    };
+    const int rc = build();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (rc != DCRT_OK || !(t.total > 0.0 && std::isfinite(t.total))) {
+        lightAllocs.Free();
+        return rc;
+    }
+    lightTable = std::move(t);
+    return DCRT_OK;
+}
+
+// Ybar of the uploaded cube, once per upload and only when a table is built: the cube read back from the device (the
+// caller's array is not kept) and summed on the host in float64 in index order, as the definition has it. Measured
+// figures for a large cube: DESIGN.md, "Light selection".
+int dcrt_tracer::CubeMeanLuminance()
+{
+    if (envMeanYKnown) return DCRT_OK;
+    const uint32_t n = plan.scene.envCubeSize;
+    std::vector<float> cube((size_t)6 * n * n * 3);
+    HIPCHECK(hipMemcpyAsync(cube.data(), plan.scene.envCube, cube.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+    double sumY = 0.0, sumOmega = 0.0;
+    for (size_t i = 0; i < (size_t)6 * n * n; ++i) {
+        const float* t = cube.data() + i * 3;
+        const float y = std::fmax(0.0f, t[0] * 0.299f + t[1] * 0.587f + t[2] * 0.114f);
+        const uint32_t x = (uint32_t)(i % n), row = (uint32_t)((i / n) % n);
+        const double sc = (double)(2 * x + 1) / (double)n - 1.0, tc = (double)(2 * row + 1) / (double)n - 1.0;
+        const double r2 = 1.0 + sc * sc + tc * tc;
+        const double omega = (4.0 / ((double)n * (double)n)) / (r2 * std::sqrt(r2));
+        sumY += (double)y * omega;
+        sumOmega += omega;
+    }
+    envMeanY = sumY / sumOmega;
+    envMeanYKnown = true;
+    return DCRT_OK;
+}
+
+// The light-level kernel alone, over the standing table's A_l: lightProb and lightCdf rewritten in place
+int dcrt_tracer::LightWeights()
+{
+    const uint32_t n = (uint32_t)lightTable.lights.size();
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto run = [&]() -> int {
+        HIPCHECK(hipEventCreate(&e0));
+        HIPCHECK(hipEventCreate(&e1));
+        HIPCHECK(hipEventRecord(e0, stream));
+        hipLaunchKernelGGL(light_weights_kernel, dim3(1), dim3(256), 0, stream, (const dcrt_light*)dLights, n, (const double*)lightTable.lightAreas, sceneRadius,
+                           envMeanY, lightTable.weightSums, lightTable.prob, lightTable.cdf);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipEventRecord(e1, stream));
+        HIPCHECK(hipMemcpyAsync(&lightTable.total, lightTable.weightSums + n, sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHECK(hipStreamSynchronize(stream));
+        HIPCHECK(hipEventElapsedTime(&lightBuildMs, e0, e1));
+        return DCRT_OK;
+    };
+    const int rc = run();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return rc;
+}
+
+// DCRT_LIGHT_SAMPLING_*: set on an uploaded scene, like the scene edits, and kept for it and every later scene. The
+// table is built when the mode first asks for it and dropped when it no longer does; the plan is rederived, and the
+// captured graphs go exactly when the variant or the table's pointers changed. Film and path state stay as they are.
+int dcrt_tracer::SetLightSampling(int mode)
+{
+    if (mode != DCRT_LIGHT_SAMPLING_UNIFORM && mode != DCRT_LIGHT_SAMPLING_POWER) { SetLastError("unknown light sampling mode"); return DCRT_E_INVALID_ARG; }
+    if (!hasScene) { SetLastError("no scene uploaded"); return DCRT_E_NO_SCENE; }
+    if (mode == lightSampling) return DCRT_OK;
+    lightSampling = mode;
+    HIPCHECK(hipStreamSynchronize(stream));
+    if (mode == DCRT_LIGHT_SAMPLING_POWER) CHECKED(BuildLightTable());
+    CHECKED(RederiveShading());
+    HIPCHECK(hipStreamSynchronize(stream));
+    if (mode == DCRT_LIGHT_SAMPLING_UNIFORM) {   // (no launch reads it any more: the plan above named none)
+        lightAllocs.Free();
+        lightTable = LightTable{};
+    }
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_set_light_sampling(dcrt_tracer* t, int mode)
+{
+    TRACER_GUARD(t);
+    return t->SetLightSampling(mode);
+}
+
+DCRT_API int dcrt_tracer_get_light_sampling(dcrt_tracer* t, int* mode, int* active)
+{
+    if (!t || (!mode && !active)) return DCRT_E_INVALID_ARG;
+    if (mode) *mode = t->lightSampling;
+    if (active) *active = t->LightTableActive() ? 1 : 0;
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_read_light_distribution(dcrt_tracer* t, dcrt_light_table_info* out_info, float* light_prob, float* light_cdf,
+                                                 uint32_t* tri_base, float* tri_prob, float* tri_cdf)
+{
+    TRACER_GUARD(t);
+    if (!out_info && !light_prob && !light_cdf && !tri_base && !tri_prob && !tri_cdf) return DCRT_E_INVALID_ARG;
+    if (!t->LightTableActive()) { SetLastError("no light table: the mode is uniform, or no scene, or lights without finite positive weight, or nothing to choose"); return DCRT_E_NO_SCENE; }
+    const dcrt_tracer::LightTable& lt = t->lightTable;
+    const size_t n = lt.lights.size(), e = lt.entries;
+    if (out_info) *out_info = dcrt_light_table_info{ (uint32_t)n, lt.entries, t->sceneRadius, lt.total };
+    if (light_prob) HIPCHECK(hipMemcpyAsync(light_prob, lt.prob, n * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+    if (light_cdf) HIPCHECK(hipMemcpyAsync(light_cdf, lt.cdf, n * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+    if (tri_base) HIPCHECK(hipMemcpyAsync(tri_base, lt.triBase, n * sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream));
+    if (tri_prob && e) HIPCHECK(hipMemcpyAsync(tri_prob, lt.triProb, e * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+    if (tri_cdf && e) HIPCHECK(hipMemcpyAsync(tri_cdf, lt.triCdf, e * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+    HIPCHECK(hipStreamSynchronize(t->stream));
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_light_table_build_timing(dcrt_tracer* t, float* out_ms)
+{
+    if (!t || !out_ms) return DCRT_E_INVALID_ARG;
+    *out_ms = t->lightBuildMs;
     return DCRT_OK;
 }
 

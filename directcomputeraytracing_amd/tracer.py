@@ -516,6 +516,45 @@ class WavefrontPathTracer:
         check(self._lib.dcrt_tracer_environment_build_timing(self._h, C.byref(ms)), "EnvironmentBuildTiming")
         return float(ms.value)
 
+    # ---- light selection (include/dcrt.h) ---------------------------------------------
+    LIGHT_SAMPLING = ("uniform", "power")
+
+    def set_light_sampling(self, mode: str) -> None:
+        """"uniform" (the default, the reference's selection) or "power": lights are picked in proportion to their power
+        and a lamp's triangles in proportion to their area. Needs an uploaded scene; kept across later uploads; the caller
+        restarts the image."""
+        if mode not in self.LIGHT_SAMPLING:
+            raise ValueError(f"light sampling {mode!r}: one of {self.LIGHT_SAMPLING}")
+        check(self._lib.dcrt_tracer_set_light_sampling(self._h, self.LIGHT_SAMPLING.index(mode)), "SetLightSampling")
+
+    def light_sampling(self) -> tuple[str, bool]:
+        """(mode, active): active while the mode is on and a table stands for the lights as they are."""
+        mode, active = C.c_int(), C.c_int()
+        check(self._lib.dcrt_tracer_get_light_sampling(self._h, C.byref(mode), C.byref(active)), "GetLightSampling")
+        return self.LIGHT_SAMPLING[mode.value], bool(active.value)
+
+    def light_distribution(self) -> dict:
+        """The stored light table: light_prob, light_cdf [n], tri_base [n] (uint32), tri_prob, tri_cdf [E], and n, E, the
+        scene radius R and the total weight. Raises (no scene) while inactive."""
+        info = _abi.LightTableInfo()
+        check(self._lib.dcrt_tracer_read_light_distribution(self._h, C.byref(info), None, None, None, None, None), "ReadLightDistribution")
+        n, e = int(info.light_count), int(info.triangle_entries)
+        out = {"light_prob": np.empty(n, np.float32), "light_cdf": np.empty(n, np.float32), "tri_base": np.empty(n, np.uint32),
+               "tri_prob": np.empty(e, np.float32), "tri_cdf": np.empty(e, np.float32)}
+        fp = _abi._FP
+        check(self._lib.dcrt_tracer_read_light_distribution(self._h, C.byref(info), out["light_prob"].ctypes.data_as(fp),
+                                                            out["light_cdf"].ctypes.data_as(fp),
+                                                            out["tri_base"].ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                            out["tri_prob"].ctypes.data_as(fp), out["tri_cdf"].ctypes.data_as(fp)),
+              "ReadLightDistribution")
+        out.update(n=n, entries=e, radius=float(info.scene_radius), total_weight=float(info.total_weight))
+        return out
+
+    def light_table_build_ms(self) -> float:
+        ms = C.c_float()
+        check(self._lib.dcrt_tracer_light_table_build_timing(self._h, C.byref(ms)), "LightTableBuildTiming")
+        return float(ms.value)
+
     # ---- statistics ----------------------------------------------------------
     def counters(self) -> dict:
         s = _abi.RayStats()
@@ -769,7 +808,8 @@ def device_count() -> int:
 def make_pipelines(scene, pool: int, streams: int = 2, images: int = 1, iterations: int = 16, world: int = 1,
                    rank: int = 0, stripe: int = 64, mode: str = "wavefront", image_batch: int = 0, device: int = 0,
                    debug_rng: bool = False, row_cost=None, fixed_pool: bool = False, interleave: bool = False,
-                   bands_per_rank: int = 0, env_sampling: str = "uniform", roulette: dict | None = None) -> list:
+                   bands_per_rank: int = 0, env_sampling: str = "uniform", roulette: dict | None = None,
+                   light_sampling: str = "uniform") -> list:
     """The concurrent wavefront pipelines bench.py renders with, each a tracer with its share of
     `pool` slots (grown to whole batches of `images` images, partition.pipeline_pool), the
     filter's halo rows, its own stream. With `row_cost` (rays per film row, probe_row_cost) the
@@ -778,14 +818,15 @@ def make_pipelines(scene, pool: int, streams: int = 2, images: int = 1, iteratio
     band of each 1/streams of the film and a cost trend down the image evens out; without it, one GPU splits the film into
     `streams` equal horizontal bands and N GPUs deal this rank's round-robin stripes to its
     pipelines (partition.stream_partition). Their films have disjoint supports: add_film_device
-    sums them into the rank's film bit for bit. `roulette`: set_russian_roulette's arguments, given to every pipeline."""
+    sums them into the rank's film bit for bit. `roulette`: set_russian_roulette's arguments, given to every pipeline;
+    `light_sampling`: set_light_sampling's mode, likewise."""
     from .partition import balanced_bands, band_render_rows, halo_for_radius, pipeline_pool, render_rows, stream_partition
     W, H = scene.resolution
     halo = max(1, halo_for_radius(scene.filter_params().radius, H))
     K = max(1, streams)
     if interleave:
         return _make_interleaved(scene, pool, K, images, iterations, world, rank, stripe, mode, image_batch, device, debug_rng,
-                                 row_cost, fixed_pool, bands_per_rank or K, halo, env_sampling, roulette)
+                                 row_cost, fixed_pool, bands_per_rank or K, halo, env_sampling, roulette, light_sampling)
     bands = balanced_bands(row_cost, world * K, halo) if row_cost is not None and world * K > 1 else None
     tracers = []
     try:
@@ -799,6 +840,7 @@ def make_pipelines(scene, pool: int, streams: int = 2, images: int = 1, iteratio
             tracers.append(t)
             t.on_scene_loaded(scene)
             t.set_environment_sampling(env_sampling)
+            t.set_light_sampling(light_sampling)
             if roulette is not None:
                 t.set_russian_roulette(**roulette)
             t.set_mode(mode)
@@ -815,7 +857,8 @@ def make_pipelines(scene, pool: int, streams: int = 2, images: int = 1, iteratio
 
 
 def _make_interleaved(scene, pool, K, images, iterations, world, rank, stripe, mode, image_batch, device, debug_rng, row_cost,
-                      fixed_pool, bands_per_rank, halo, env_sampling="uniform", roulette=None) -> list:
+                      fixed_pool, bands_per_rank, halo, env_sampling="uniform", roulette=None,
+                      light_sampling="uniform") -> list:
     """make_pipelines(interleave=True): K tracers over the SAME rows -- the whole film on one GPU,
     the rank's share of it on N (`bands_per_rank` cost-balanced bands dealt round-robin, or the
     round-robin stripes without a row cost) -- that split the images instead of the rows
@@ -842,6 +885,7 @@ def _make_interleaved(scene, pool, K, images, iterations, world, rank, stripe, m
             tracers.append(t)
             t.on_scene_loaded(scene)
             t.set_environment_sampling(env_sampling)
+            t.set_light_sampling(light_sampling)
             if roulette is not None:
                 t.set_russian_roulette(**roulette)
             t.set_mode(mode)

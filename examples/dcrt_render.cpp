@@ -10,7 +10,10 @@
 //               [--edit N:KIND:ARGS]... [--output NAME [--iteration-threshold N]] [--denoise]
 //               [--converge THRESHOLD[:FRACTION] [--check-points MIN:INTERVAL]] [--noise-map out.bmp]
 //               [--adaptive THRESHOLD:FRACTION[:MARGIN]] [--sample-map out.bmp] [--env-importance]
-//               [--roulette START[:MIN[:MAX]]]
+//               [--roulette START[:MIN[:MAX]]] [--light-power]
+//
+// --light-power picks the light of every light sample in proportion to the lights' power, and a lamp's triangle in
+// proportion to its area, instead of uniformly (dcrt.h "light selection").
 //
 // --roulette turns Russian roulette on from bounce START (dcrt.h "Russian roulette"): a path survives a vertex with
 // the probability clamp(max throughput component, MIN, MAX), defaults 0.05 and 1, and survivors are weighted up.
@@ -93,7 +96,7 @@ int Usage(const char* exe)
                  "       [--iteration-threshold N] [--denoise]\n"
                  "       [--converge THRESHOLD[:FRACTION] [--check-points MIN:INTERVAL]] [--noise-map out.bmp]\n"
                  "       [--adaptive THRESHOLD:FRACTION[:MARGIN]] [--sample-map out.bmp] [--env-importance]\n"
-                 "       [--roulette START[:MIN[:MAX]]]\n",
+                 "       [--roulette START[:MIN[:MAX]]] [--light-power]\n",
                  exe);
     return 2;
 }
@@ -213,6 +216,7 @@ int main(int argc, char** argv)
     uint32_t adaptiveMargin = 0xFFFFFFFFu;   // (the filter's window rows)
     const char* sampleMapPath = nullptr;
     bool envImportance = false;
+    bool lightPower = false;
     dcrt_roulette_params roulette;
     if (dcrt_roulette_default_params(&roulette) != DCRT_OK) return 1;
     for (int i = 7; i < argc; ++i) {
@@ -223,6 +227,8 @@ int main(int argc, char** argv)
             denoise = true;
         } else if (!std::strcmp(argv[i], "--env-importance")) {
             envImportance = true;
+        } else if (!std::strcmp(argv[i], "--light-power")) {
+            lightPower = true;
         } else if (!std::strcmp(argv[i], "--roulette") && more) {
             const std::vector<std::string> f = Split(argv[++i], ':');
             if (f.empty() || f.size() > 3 || f[0].empty() || f[0].find_first_not_of("0123456789") != std::string::npos ||
@@ -325,6 +331,7 @@ int main(int argc, char** argv)
     if (!Check(dcrt_scene_set_max_bounce(scene.m_Handle, maxBounce), "SetMaxBounce")) return 1;
     if (!loop.AfterSceneEdited()) return 1;
     if (envImportance && !tracer.SetEnvironmentSampling(DCRT_ENV_SAMPLING_IMPORTANCE)) return 1;   // (on the uploaded scene; kept across --edit uploads)
+    if (lightPower && !tracer.SetLightSampling(DCRT_LIGHT_SAMPLING_POWER)) return 1;
     if (seedType == CRendererLoop::EFrameSeedType::Fixed) scene.m_FrameSeed = fixedSeed;   // the UI's seed field (ImGui.cpp:157-160)
 
     const auto t0 = std::chrono::steady_clock::now();

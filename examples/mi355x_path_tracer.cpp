@@ -212,6 +212,11 @@ bool CMI355XPathTracer::SetRoulette(const dcrt_roulette_params& params)
     return m_Tracer && Ok(dcrt_tracer_set_roulette(m_Tracer, &params), "SetRoulette");
 }
 
+bool CMI355XPathTracer::SetLightSampling(int mode)
+{
+    return m_Tracer && Ok(dcrt_tracer_set_light_sampling(m_Tracer, mode), "SetLightSampling");
+}
+
 bool CMI355XPathTracer::GetSampleTextures(void** devicePosition, void** deviceValue)
 {
     return m_Tracer && Ok(dcrt_tracer_sample_device_ptrs(m_Tracer, devicePosition, deviceValue), "SampleTextures");

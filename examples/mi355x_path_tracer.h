@@ -134,6 +134,8 @@ public:
     bool SetOutputType(uint32_t type, uint32_t iterationThreshold);
     // DCRT_ENV_SAMPLING_*: how light samples of the environment cube are drawn (dcrt.h "environment importance sampling")
     bool SetEnvironmentSampling(int mode);
+    // DCRT_LIGHT_SAMPLING_*: how a light sample picks its light and a lamp's triangle (dcrt.h "light selection")
+    bool SetLightSampling(int mode);
     // Russian roulette path termination (dcrt.h "Russian roulette"): lives on the tracer, read at every image's start
     bool SetRoulette(const dcrt_roulette_params& params);
     dcrt_tracer* GetTracer() const { return m_Tracer; }

@@ -1059,6 +1059,67 @@ DCRT_API int dcrt_tracer_get_roulette(dcrt_tracer* tracer, dcrt_roulette_params*
 DCRT_API int dcrt_device_roulette(dcrt_tracer* tracer, const dcrt_roulette_params* params, const float* throughputs,
                                   const float* u, uint32_t count, float* out_q, uint32_t* out_survive, float* out_scaled);
 
+/* ===== light selection ===========================================================
+ * Next-event estimation picks its light as floor(sel * light_count) and, inside a mesh light, its triangle as
+ * floor(triSel * triangle_count), as in the reference (DCRT_LIGHT_SAMPLING_UNIFORM, the default: every result
+ * is then bit for bit what it was before this existed). With DCRT_LIGHT_SAMPLING_POWER lights are picked in
+ * proportion to their power and a lamp's triangles in proportion to their area, from a table built by device
+ * kernels at upload. No reference counterpart. tests/light_table_ref.py restates all of this in float64.
+ *
+ * Weights, float64; n = the lights uploaded. Y(c) = max(0, 0.299 r + 0.587 g + 0.114 b) in float32, products
+ * summed left to right (the film kernels' and the environment table's luminance; a NaN counts 0).
+ *   point light        w = 4 pi Y(radiance)
+ *   directional light  w = pi R^2 Y(radiance)
+ *   mesh light         w = pi Y(radiance) A, A = the sum over its triangle range, in ascending order, of a_t: the
+ *                      world-space area as light sampling computes it -- float32, 0.5 * length(cross(w2 - w0,
+ *                      w1 - w0)) of the transformed vertices -- counting 0 below 1e-6 or when not finite
+ *   environment light  w = 4 pi . pi R^2 Y(colour) Ybar; Ybar = 1 without a cube, else sum(Y(texel) omega) /
+ *                      sum(omega) over the texels in index order, omega = (4 / n^2) (1 + sc^2 + tc^2)^(-3/2) at the
+ *                      texel's centre (the environment section's face coordinates), both sums float64
+ * R = half the diagonal of the uploaded BVH root's box (float32 bounds, float64 arithmetic), taken at
+ * dcrt_tracer_upload_scene and kept for later light edits.
+ * Probabilities. P(l) = (1 - e) w_l / sum(w) + e / n, e = 1/16 (the environment table's uniform share: every light
+ * stays reachable and 1 / P <= 16 n). P(t | l) = a_t / A_l. Stored as float32: lightProb[n], lightCdf[n], and for
+ * the E = sum of the mesh lights' triangle counts emissive triangles in light order triProb[E] and triCdf[E] (a CDF
+ * per light), triBase[n] (uint32: the first entry of light l; a light that is no mesh light has no entries). CDFs are
+ * float64 sums in ascending order, normalised, rounded once; each CDF's last entry is exactly 1. A mesh light with
+ * A = 0 has w = 0 and a triangle CDF of zeros: selecting it gives pdf 0 and radiance 0. sum(w) zero or not finite:
+ * no table ("inactive": uniform selection). Also inactive: a scene whose only light is not a mesh light.
+ * Sampling. The same numbers in the same order as uniform selection: sel, then what the kind draws. The light is
+ * the first l with lightCdf[l] > sel; a mesh light's triangle the first k with triCdf[triBase[l] + k] > triSel
+ * (triangle triangle_offset + k); both clamped to the last index. Point on the triangle, environment direction and
+ * radiance are unchanged.
+ * Density. One function serves light sampling and light evaluation. The selection factor is P(l) for a point,
+ * directional or environment light -- the kind's own pdf (1 for the delta lights) times lightProb[l] in place of the
+ * division by light_count -- and for a mesh light (lightProb[l] * triProb[triBase[l] + k]) / a_t, zero where a_t
+ * counts 0, in place of 1 / area / triangle_count / light_count; the pdf is that factor times d^2 / cos, all float32
+ * in this order. Light sampling thus reports the density it draws from, 1 / A_l over the lamp times d^2 / cos times
+ * P(l): the reference's doubled sampler pdf (Light.inc.hlsl:50,61) does not carry into this mode.
+ * Frames. While a table stands, a render or probe whose frame.light_count differs from n is DCRT_E_INVALID_ARG. */
+#define DCRT_LIGHT_SAMPLING_UNIFORM 0
+#define DCRT_LIGHT_SAMPLING_POWER 1
+typedef struct dcrt_light_table_info {
+    uint32_t light_count;        /* n */
+    uint32_t triangle_entries;   /* E */
+    double   scene_radius;       /* R */
+    double   total_weight;       /* sum(w) */
+} dcrt_light_table_info;         /* 24 bytes */
+/* The mode: set on an uploaded scene, as the scene edits are (DCRT_E_NO_SCENE without one), and kept across every
+ * later dcrt_tracer_upload_scene; another value is DCRT_E_INVALID_ARG. The table is built at once, at every later
+ * upload and at every dcrt_tracer_update_lights while the mode is on (an edit that keeps the lights' count, kinds,
+ * triangle ranges and instances rewrites lightProb and lightCdf in place and keeps the captured graphs; any other
+ * rebuilds the table and drops them). Film and path state are not touched: restart the image. */
+DCRT_API int dcrt_tracer_set_light_sampling(dcrt_tracer* tracer, int mode);
+/* *mode: the mode set; *active: 1 while a table stands for the uploaded scene and the mode is on. Either pointer
+ * may be null. */
+DCRT_API int dcrt_tracer_get_light_sampling(dcrt_tracer* tracer, int* mode, int* active);
+/* The table as stored: light_prob, light_cdf n floats, tri_base n words, tri_prob, tri_cdf E floats (null: not
+ * wanted; take n and E from a first call with only out_info). DCRT_E_NO_SCENE when inactive. */
+DCRT_API int dcrt_tracer_read_light_distribution(dcrt_tracer* tracer, dcrt_light_table_info* out_info, float* light_prob,
+                                                 float* light_cdf, uint32_t* tri_base, float* tri_prob, float* tri_cdf);
+/* The HIP-event time in ms of the last table build's kernels (0: none built). */
+DCRT_API int dcrt_tracer_light_table_build_timing(dcrt_tracer* tracer, float* out_ms);
+
 /* 24-bit BMP writer ("Save Image to File", SaveImageToFile.cpp:92-182). */
 DCRT_API int dcrt_write_bmp(const char* path, uint32_t width, uint32_t height, const uint8_t* rgba8);
 
