@@ -467,7 +467,9 @@ def sampled_density(L, mat, wi, wo, dtype=np.float64):
     everything, u < E picks the microfacet lobe and then u < F reflects, so reflection has
     probability min(E, F) and refraction max(E - F, 0) instead of E F and E (1 - F); u >= E picks
     the compensation lobe, which transmits when u < ratio: max(ratio - E, 0) of the draws, and
-    1 - max(E, ratio) of them reflect."""
+    1 - max(E, ratio) of them reflect. A smooth material draws delta lobes only and has density 0 --
+    except smooth plastic, whose Lambert base is drawn with the weight 1 - coat of `lobe_weights`:
+    w_l cos / pi on wo's side (the coat's share of the draws is the delta lobe of `delta_lobes`)."""
     wi, wo = _a(wi, dtype).reshape(-1, 3).copy(), _a(wo, dtype).reshape(-1, 3).copy()
     inside = bool((wo[:, 2] < 0).all())
     assert inside or (wo[:, 2] > 0).all()
@@ -475,7 +477,7 @@ def sampled_density(L, mat, wi, wo, dtype=np.float64):
         wi[:, 2], wo[:, 2] = -wi[:, 2], -wo[:, 2]
     t, a = mat["type"], _a(mat["alpha"], dtype)
     n = len(wi)
-    if is_smooth(mat) or t == THIN or (inside and not mat["two_sided"] and t != DIELECTRIC):
+    if (is_smooth(mat) and t != PLASTIC) or t == THIN or (inside and not mat["two_sided"] and t != DIELECTRIC):
         return np.zeros(n, dtype)
     cos_o = wo[:, 2]
     cosine = np.where(wi[:, 2] > 0, wi[:, 2], 0) / _a(np.pi, dtype)
@@ -493,7 +495,7 @@ def sampled_density(L, mat, wi, wo, dtype=np.float64):
     if t in (DIFFUSE, PLASTIC, CONDUCTOR):
         w_l, w_ct, w_ms = lobe_weights(L, mat, cos_o, inside, dtype)
         d = (w_l + w_ms) * cosine
-        if t != DIFFUSE:
+        if t != DIFFUSE and not is_smooth(mat):     # (a smooth plastic's coat is a delta lobe: `delta_lobes`)
             d = d + w_ct * mirror_density()[0]
         return d.astype(dtype)
     ior = _a(mat["ior"][0], dtype)
@@ -520,20 +522,29 @@ def sampled_density(L, mat, wi, wo, dtype=np.float64):
     return d.astype(dtype)
 
 
-def delta_lobes(mat, wo, dtype=np.float64):
+def delta_lobes(mat, wo, dtype=np.float64, L=None):
     """The delta lobes of a smooth or thin material at one wo (3,): a list of (wi, f-weight (3,),
     probability) with f-weight = f cos integrated over the delta, divided by |wi.n| as the sampler
     reports it. Smooth dielectric: mirror with F / |cos| and the refracted direction with
     (1 - F) (eta_o / eta_i)^2 / |cos_t|; a thin sheet sums the inter-reflections, R' = F + T^2 F /
     (1 - F^2), and passes straight through without a scale; a smooth conductor mirrors with its
-    Fresnel term. (A smooth plastic's coat is a delta lobe next to its Lambert base; it is left to
-    the device-against-oracle comparison.)"""
+    Fresnel term. A smooth plastic's coat is one delta lobe next to its Lambert base (which
+    `evaluate` and `sampled_density` describe): the mirror direction with F(|wo.n|, 1, ior) / |cos|,
+    the boundary always seen from the air side (a two-sided plastic is mirrored, not entered), and
+    as its probability the coat weight of `lobe_weights` -- the dielectric-BRDF table at the
+    material's alpha, which is data and needs the tables L (the table's smooth row holds k F,
+    k = 1.00352 the builder's sample weight times its sample count, so the lobe carries F / (k F)
+    = 0.9965 of the light per draw and the Lambert base weighs 1 - k F: tests/test_bsdf_ref.py,
+    test_lut_smooth_rows). It exists from outside, or from inside when the material is two-sided."""
     wo = _a(wo, dtype)
     t = mat["type"]
     inside = bool(wo[2] < 0)
     c = abs(wo[2])
     mirror = np.array([-wo[0], -wo[1], wo[2]], dtype)
     ior = _a(mat["ior"][0], dtype)
+    if t == PLASTIC and is_smooth(mat) and (not inside or mat["two_sided"]):
+        coat = lobe_weights(L, mat, c, inside, dtype)[1]
+        return [(mirror, np.full(3, fresnel_dielectric(c, 1, ior, dtype) / c, dtype), _a(coat, dtype))]
     if t == CONDUCTOR and (not inside or mat["two_sided"]):
         return [(mirror, fresnel_conductor(c, mat["ior"], mat["albedo"], dtype) / c, _a(1, dtype))]
     if t in (DIELECTRIC, THIN):

@@ -9,7 +9,7 @@ What it builds on (each independent of the renderer and pinned by its own tests)
 (instance, triangle) pair, and the any-hit opacity value); tests/shading_ref.py -- `from_flat`,
 `camera_ray`, `hit`, `env_lookup`, `evaluate_light`; tests/bsdf_ref.py -- `evaluate`, `sampled_density`,
 the Fresnel terms and the LUT lookups (`delta_lobes` is the scalar definition the vectorised
-`delta_lobes_many` here is held to, tests/test_path_ref.py).
+`delta_lobes_many` here is held to, tests/test_path_ref.py; a smooth plastic's coat included).
 
 The estimand. Vertex k = 0 is the camera ray's first hit, B = max_bounce.
   * Cast: the nearest hit. Under the any-hit feature (0x10) a crossing of opacity a is accepted with
@@ -32,8 +32,10 @@ The estimand. Vertex k = 0 is the camera ray's first hit, B = max_bounce.
     pair (p_s = p, s = q) has m = 1; `mis_model=False` forces m = 1.
 
 How it integrates: its own generator (np.random.default_rng) and its own proposals -- a cosine
-direction about the shading normal on wo's side at reflecting vertices, a uniform direction on the
-sphere at a rough dielectric, a lobe chosen by its probability at delta vertices -- and NO next-event
+direction about the shading normal on wo's side at reflecting vertices, at a rough dielectric a uniform
+direction on the sphere or one of Walter's single-scattering sampler, half and half
+(`dielectric_proposal`), a lobe chosen by its probability at delta vertices, at a mixed vertex (smooth
+plastic) the coat's delta lobe with a probability of its own choosing and the cosine direction otherwise -- and NO next-event
 estimation towards area lights or the environment: the strategy differs from the product's on purpose,
 only the expectation is shared. One run serves every B of a scene (the terms of vertex k count for
 every B >= k, its emission for every B >= k - 1) and both states of LIGHT_VISIBLE (the k = 0 emission
@@ -46,9 +48,16 @@ AnyHitShader call), so a ray that crosses opacities a1, a2 passes both with prob
 1 - max(a1, a2), not (1 - a1)(1 - a2), and stops at the first crossing whose opacity exceeds the draw.
 `shared_opacity_draw=False` draws per crossing.
 
+Mixed vertices. A smooth plastic has a continuous lobe (its Lambert base, which `evaluate` and
+`sampled_density` describe, weighted 1 - coat) next to a delta lobe (the coat, `delta_lobes`): delta lights
+reach it through `evaluate`; the continuation picks the coat with a probability P of this reference's
+choosing (the coat weight) and weights it 1 / P, delta = True, q = s = 1, or else proposes a cosine
+direction weighted 1 / (1 - P) with q and s as at any reflecting vertex. A rough dielectric with
+multiscattering (BSDF QUIRK Q1) needs nothing of its own here: s / q is in the continuation and in m.
+
 Kept out of the scenes, because this reference does not cover them:
-  * rough dielectrics with multiscattering (BSDF QUIRK Q1: s != q there; work of its own);
-  * smooth plastic (`delta_lobes` does not cover its coat);
+  * roughness textures (the checkerboard of alphas): no loader and no scene call sets has_roughness_texture,
+    so only a hand-edited flat scene reaches it, and tests/shading_ref.py pins the per-hit alpha it gives;
   * non-rigid or non-uniformly scaled instances (shading QUIRK Q1: the renderer's normals are then
     not the true ones);
   * lamps near the 1e-6 area threshold (shading QUIRK Q4);
@@ -85,10 +94,11 @@ def _ph(a, b):
     return np.where((a == 0) & (b == 0), 0.0, w)
 
 
-def delta_lobes_many(mat, wo):
+def delta_lobes_many(mat, wo, L=None):
     """`bsdf_ref.delta_lobes` for (N, 3) wo of one material: a list of (wi (N, 3), f-weight (N, 3),
     probability (N,)); a lobe that does not exist for a row has probability 0 there. Built from the
-    same Fresnel terms; tests/test_path_ref.py holds it to the scalar definition row by row."""
+    same Fresnel terms (and, for a smooth plastic's coat weight, the same table lookup: L are the
+    tables); tests/test_path_ref.py holds it to the scalar definition row by row."""
     wo = np.asarray(wo, np.float64)
     t = mat["type"]
     inside = wo[:, 2] < 0
@@ -100,6 +110,12 @@ def delta_lobes_many(mat, wo):
         with np.errstate(invalid="ignore", divide="ignore"):
             fw = R.fresnel_conductor(c, mat["ior"], mat["albedo"]) / c[:, None]
         return [(mirror, np.where(ok[:, None], fw, 0.0), ok.astype(np.float64))]
+    if t == R.PLASTIC and R.is_smooth(mat):
+        ok = ~inside | mat["two_sided"]
+        coat = R.lut_brdf_dielectric(L, c, np.float64(mat["alpha"]), ior, False)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            fw = R.fresnel_dielectric(c, 1.0, ior) / c
+        return [(mirror, np.where(ok[:, None], np.repeat(fw[:, None], 3, 1), 0.0), np.where(ok, coat, 0.0))]
     if t not in (R.DIELECTRIC, R.THIN):
         return []
     thin = t == R.THIN
@@ -120,6 +136,53 @@ def delta_lobes_many(mat, wo):
             wt = np.stack([-eta * wo[:, 0], -eta * wo[:, 1], np.where(inside, 1.0, -1.0) * ct], -1)
             out.append((wt, np.repeat(np.where(T > 0, T * eta * eta / ct, 0.0)[:, None], 3, 1), np.where(T > 0, T, 0.0)))
     return out
+
+
+def visible_normal(wo, alpha, u):
+    """A GGX normal drawn from the distribution of normals visible from wo (N, 3), wo.n > 0, with the numbers
+    u (N, 2): Heitz 2018, listing 1 (stretch the view, draw a point of the projected disk, unstretch)."""
+    vh = np.stack([alpha * wo[:, 0], alpha * wo[:, 1], wo[:, 2]], -1)
+    vh /= np.sqrt(_dot(vh, vh))[:, None]
+    lensq = vh[:, 0] ** 2 + vh[:, 1] ** 2
+    with np.errstate(invalid="ignore", divide="ignore"):
+        t1 = np.where((lensq > 0)[:, None], np.stack([-vh[:, 1], vh[:, 0], 0 * lensq], -1) / np.sqrt(lensq)[:, None], np.array([1.0, 0.0, 0.0]))
+    t2 = np.cross(vh, t1)
+    r, phi = np.sqrt(u[:, 0]), 2 * np.pi * u[:, 1]
+    a, b = r * np.cos(phi), r * np.sin(phi)
+    sh = 0.5 * (1 + vh[:, 2])
+    b = (1 - sh) * np.sqrt(np.maximum(0.0, 1 - a * a)) + sh * b
+    nh = a[:, None] * t1 + b[:, None] * t2 + np.sqrt(np.maximum(0.0, 1 - a * a - b * b))[:, None] * vh
+    m = np.stack([alpha * nh[:, 0], alpha * nh[:, 1], np.maximum(0.0, nh[:, 2])], -1)
+    return m / np.sqrt(_dot(m, m))[:, None]
+
+
+def dielectric_proposal(rng, luts, mat, wo):
+    """This reference's proposal at a rough dielectric, wo (N, 3) all on one side: (wi, its density g). Half
+    of the directions are uniform on the sphere (so g > 0 wherever any lobe is), half follow Walter's sampler
+    of the single-scattering BSDF -- a visible normal, reflected about with probability F and refracted
+    through otherwise -- whose density bsdf_ref states (`sampled_density` of the material without
+    multiscattering: no QUIRK Q1 in it, F and 1 - F). f |cos| / g then stays bounded along a chain of
+    vertices inside a solid, where the uniform proposal alone leaves a heavy tail. tests/test_path_ref.py
+    checks that the directions follow g."""
+    n = len(wo)
+    z = rng.random((n, 4))
+    cz = 1 - 2 * z[:, 0]
+    sr = np.sqrt(np.maximum(0.0, 1 - cz * cz))
+    wi = np.stack([sr * np.cos(2 * np.pi * z[:, 1]), sr * np.sin(2 * np.pi * z[:, 1]), cz], -1)
+    inside = bool((wo[:, 2] < 0).all())
+    flip = np.array([1.0, 1.0, -1.0 if inside else 1.0])
+    w = wo * flip
+    ior = np.float64(mat["ior"][0])
+    n_o, n_i = (ior, 1.0) if inside else (1.0, ior)
+    m = visible_normal(w, np.float64(mat["alpha"]), z[:, 0:2])
+    c = _dot(w, m)
+    eta = n_o / n_i
+    k = 1 - eta * eta * (1 - c * c)
+    reflect = z[:, 3] < R.fresnel_dielectric(c, n_o, n_i)              # (1 beyond the critical angle)
+    walter = np.where(reflect[:, None], 2 * c[:, None] * m - w, -eta * w + (eta * c - np.sqrt(np.maximum(k, 0.0)))[:, None] * m) * flip
+    wi = np.where((z[:, 2] < 0.5)[:, None], wi, walter)
+    single = dict(mat, multiscattering=False)
+    return wi, 0.5 / (4 * np.pi) + 0.5 * R.sampled_density(luts, single, wi, wo)
 
 
 class PathRef:
@@ -203,8 +266,6 @@ class PathRef:
         m["albedo"] = h["albedo"][rows]          # per hit: the texture is in it (a conductor's k is constant)
         if t == R.CONDUCTOR:
             m["albedo"] = matf[0:3].copy()
-        assert not (t == R.PLASTIC and R.is_smooth(m)), "smooth plastic is not covered"
-        assert not (t == R.DIELECTRIC and not R.is_smooth(m) and m["multiscattering"]), "BSDF QUIRK Q1 is not covered"
         return m
 
     # ---- the estimator -------------------------------------------------------------------------------
@@ -309,13 +370,11 @@ class PathRef:
                             tr[lit] = self.transmittance(pos[rows][lit], w[lit], reach[lit])
                         direct[rows] += f * np.abs(wl[:, 2:3]) * Le * tr[:, None]
                     # -- the continuation's proposal
-                    z = rng.random((len(rows), 2))
+                    mixed = mat["type"] == R.PLASTIC and R.is_smooth(mat)
                     if mat["type"] == R.DIELECTRIC:
-                        cz = 1 - 2 * z[:, 0]
-                        sr = np.sqrt(np.maximum(0.0, 1 - cz * cz))
-                        wi = np.stack([sr * np.cos(2 * np.pi * z[:, 1]), sr * np.sin(2 * np.pi * z[:, 1]), cz], -1)
-                        g = np.full(len(rows), 1 / (4 * np.pi))
+                        wi, g = dielectric_proposal(rng, self.luts, mat, wo[rows])
                     else:
+                        z = rng.random((len(rows), 2))
                         sr = np.sqrt(z[:, 0])
                         cz = np.sqrt(np.maximum(0.0, 1 - z[:, 0])) * np.sign(wo[rows, 2])
                         wi = np.stack([sr * np.cos(2 * np.pi * z[:, 1]), sr * np.sin(2 * np.pi * z[:, 1]), cz], -1)
@@ -323,7 +382,18 @@ class PathRef:
                     f, qq = R.evaluate(self.luts, mat, wi, wo[rows])
                     ss = R.sampled_density(self.luts, mat, wi, wo[rows])
                     with np.errstate(invalid="ignore", divide="ignore"):
-                        fcos_g[rows] = np.where(g[:, None] > 0, f * np.abs(wi[:, 2:3]) / g[:, None], 0.0)
+                        fc = np.where(g[:, None] > 0, f * np.abs(wi[:, 2:3]) / g[:, None], 0.0)
+                    if mixed:
+                        # a mixed vertex: the coat's delta lobe with a probability P of this reference's choosing
+                        # (its weight in the sampler will do: 0 where there is no coat, never 1), the Lambert
+                        # base by the cosine proposal otherwise
+                        (cwi, cfw, P), = delta_lobes_many(mat, wo[rows], self.luts)
+                        coat = rng.random(len(rows)) < P
+                        with np.errstate(invalid="ignore", divide="ignore"):
+                            fc = np.where(coat[:, None], cfw * np.abs(cwi[:, 2:3]) / P[:, None], fc / (1.0 - P)[:, None])
+                        wi, qq, ss = np.where(coat[:, None], cwi, wi), np.where(coat, 1.0, qq), np.where(coat, 1.0, ss)
+                        delta[rows] = coat
+                    fcos_g[rows] = fc
                     new_d[rows], q[rows], sdens[rows] = wi, qq, ss
             L[alive[:, None], np.flatnonzero(shades)[None, :]] += (T * direct)[:, None, :]
             Te = T * fcos_g

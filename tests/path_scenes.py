@@ -6,6 +6,11 @@ Every part is its own OBJ in world coordinates under an identity transform (no i
 QUIRK Q1), flat-shaded (the shading normal is the face's), with texcoords (0,0) (1,0) (1,1) (0,1) on quads,
 and lies at least 1e-2 from every other part. Lamps are well above the 1e-6 area threshold.
 
+Two shipped material states have a scene of their own: `coat` -- smooth plastic, the one vertex kind at which one
+selection number chooses between a continuous lobe and a delta lobe -- and `frost` -- a rough dielectric with
+multiscattering, whose sampler draws from another density than the pdf it reports (BSDF QUIRK Q1). A roughness
+texture has none: no loader and no scene call can set it.
+
 SCENES[name]: the B the scene runs at, the states of LIGHT_VISIBLE, the reference's path count, the
 device's image count. The path counts make the reference's standard error at most the device side's on
 every statistic (tests/test_gpu_path_ref.py asserts it; DESIGN.md section 3 has the measured ratios)."""
@@ -24,8 +29,10 @@ SCENES = {
     "bleed": {"bounces": (0, 1, 3), "visible": (True, False), "paths": 12 << 20, "images": 16},
     "mixed": {"bounces": (0, 1, 3), "visible": (True,), "paths": 1 << 20, "images": 16},
     "glass": {"bounces": (1, 3, 6), "visible": (True,), "paths": 1 << 20, "images": 16},
-    "sheet": {"bounces": (0, 1, 3), "visible": (True,), "paths": 8 << 20, "images": 16},
+    "sheet": {"bounces": (0, 1, 3), "visible": (True,), "paths": 1 << 20, "images": 16},
     "veil": {"bounces": (0, 1, 3), "visible": (True,), "paths": 4 << 20, "images": 16},
+    "coat": {"bounces": (0, 1, 3), "visible": (True, False), "paths": 1 << 20, "images": 16},
+    "frost": {"bounces": (1, 3, 6), "visible": (True,), "paths": 1 << 20, "images": 16},
 }
 
 
@@ -222,6 +229,62 @@ def _sheet(Scene, d):
             + _shape("floor", _diffuse("0.5, 0.6, 0.7")))
     (d / "sheet.xml").write_text(_xml(_integrator(3) + _camera((0, 0.9, -1.6), pitch=5, fov=70) + body))
     s = _load(Scene, d / "sheet.xml")
+    s.set_environment_light((1.0, 1.0, 1.0), env_cube(8))
+    return s
+
+
+def _coat(Scene, d):
+    """The bleed box's shape with a smooth-plastic floor (ior 1.5, internal scattering SINGLE: the loader's
+    default for `plastic`), a smooth-plastic left wall (two-sided, ior 1.8, `nonlinear`: MULTIPLE) whose face
+    looks OUT of the box, so that every path meets it from behind and takes the two-sided mirror branch, a
+    bitmap back wall, plain right wall and ceiling, a lamp before the back wall that faces the camera -- seen
+    directly and, below it, in the floor's coat -- and a point light, which a mixed vertex receives through
+    its Lambert base alone."""
+    rng = np.random.default_rng(9)
+    _ppm(d / "back.ppm", rng.integers(30, 256, (4, 5, 3)))
+    parts = {
+        "floor": (_quad((0, 0, 0), (1, 0, 0), (0, 0, -1)), '<bsdf type="plastic"><rgb name="diffuse_reflectance" value="0.75, 0.6, 0.2"/>'
+                  '<float name="int_ior" value="1.5"/></bsdf>'),
+        "left": (_quad((-1, 1, 0), (0, 0, 1), (0, 1, 0)), '<bsdf type="twosided"><bsdf type="plastic"><rgb name="diffuse_reflectance" value="0.2, 0.5, 0.8"/>'
+                 '<float name="int_ior" value="1.8"/><boolean name="nonlinear" value="true"/></bsdf></bsdf>'),
+        "ceiling": (_quad((0, 2, 0), (1, 0, 0), (0, 0, 1)), _diffuse("0.7, 0.7, 0.6")),
+        "back": (_quad((0, 1, 1), (-1, 0, 0), (0, 1, 0)), '<bsdf type="diffuse"><texture name="reflectance" type="bitmap">'
+                 '<string name="filename" value="back.ppm"/></texture></bsdf>'),
+        "right": (_quad((1, 1, 0), (0, 0, 1), (0, 1, 0)), _diffuse("0.8, 0.15, 0.1")),
+    }
+    body = ""
+    for name, (face, bsdf) in parts.items():
+        _write_faces(d / f"{name}.obj", [face])
+        body += _shape(name, bsdf)
+    _write_faces(d / "lamp.obj", [_quad((0.2, 0.7, 0.9), (-0.35, 0, 0), (0, 0.3, 0))])
+    body += _shape("lamp", emitter="6, 5, 4")
+    (d / "coat.xml").write_text(_xml(_integrator(3) + _camera((0.1, 0.9, -0.95), yaw=-6, pitch=12, fov=90) + body))
+    s = _load(Scene, d / "coat.xml")
+    s.add_point_light((-0.4, 1.5, -0.2), (1.5, 1.3, 1.0))
+    return s
+
+
+def _frost(Scene, d):
+    """The sheet scene's closed rough-dielectric octahedron (alpha 0.6) with multiscattering ON (BSDF QUIRK Q1:
+    the drawn density is not the reported pdf) over a matte floor, a lamp behind it that faces the camera, the
+    environment cube."""
+    import ray_truth as RT
+    V, F = RT.closed_polyhedron(np.random.default_rng(3), levels=0)
+    assert RT.is_closed(F)
+    V = V * 0.9 + np.array([0.45, 0.8, 0.6])
+    faces = []
+    for a, b, c in F:
+        n = np.cross(V[b] - V[a], V[c] - V[a])
+        faces.append(([tuple(V[a]), tuple(V[b]), tuple(V[c])], tuple(n / np.linalg.norm(n))))
+    _write_faces(d / "solid.obj", faces)
+    _write_faces(d / "floor.obj", [_quad((0, 0, 0.5), (2, 0, 0), (0, 0, -2))])
+    _write_faces(d / "lamp.obj", [_quad((0.45, 0.8, 1.6), (-0.8, 0, 0), (0, 0.6, 0))])
+    body = (_shape("solid", '<bsdf type="roughdielectric"><float name="int_ior" value="1.5"/><float name="alpha" value="0.6"/></bsdf>')
+            + _shape("floor", _diffuse("0.5, 0.6, 0.7")) + _shape("lamp", emitter="1.6, 2, 1.2"))
+    (d / "frost.xml").write_text(_xml(_integrator(6) + _camera((0, 0.9, -1.6), pitch=5, fov=70) + body))
+    s = _load(Scene, d / "frost.xml")
+    changed = s.enable_multiscattering()
+    assert len(changed) == 1 and s.material_setting(changed[0]).multiscattering          # the solid
     s.set_environment_light((1.0, 1.0, 1.0), env_cube(8))
     return s
 

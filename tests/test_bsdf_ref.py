@@ -2,6 +2,8 @@
 written from the literature: BSDF values and pdfs at seeded direction pairs, the samplers' draws
 against the pdf (chi-square), and every table against a quadrature of the directional albedo. The
 same checks run through the device entries in tests/test_gpu_bsdf.py."""
+from statistics import NormalDist
+
 import numpy as np
 import pytest
 
@@ -35,6 +37,12 @@ EVAL_MATERIALS = MATERIALS + [
     ("dielectric_2.4_ms", dict(type=DIELECTRIC, alpha=0.35, ior=2.4, multiscattering=True)),
 ]
 EVAL_CASES = [(n, kw, two, feat) for n, kw in EVAL_MATERIALS for two in (False, True) for feat in (VNDF, 0)]
+# smooth plastic: the evaluator describes the Lambert base alone, weighted 1 - coat (the coat is a delta lobe)
+SMOOTH_PLASTICS = [
+    ("plastic_smooth", dict(type=PLASTIC, albedo=(0.7, 0.6, 0.5), alpha=0.0, ior=1.5), False),
+    ("plastic_smooth_two_isf2", dict(type=PLASTIC, albedo=(0.9, 0.5, 0.1), alpha=0.0, ior=1.8, internal_scattering=2), True),
+]
+EVAL_CASES += [(n, kw, two, feat) for n, kw, two in SMOOTH_PLASTICS for feat in (VNDF, 0)]
 EVAL_PAIRS = 4000
 
 
@@ -150,6 +158,9 @@ CHI_DRAWS = 200_000
 CHI_BINS = (32, 64)     # cos(theta) in [-1, 1] x phi in [-pi, pi]: the horizon is a bin edge
 CHI_SUB = (16, 8)       # sub-grid per bin in cos and in phi for the expected counts
 CHI_CASES = [(n, kw, z) for n, kw in MATERIALS for z in (0.9, 0.3)]
+# (the two-sided one once from below)
+CHI_CASES += [(n, dict(kw, two_sided=two), z) for n, kw, two in SMOOTH_PLASTICS for z in (0.9, -0.3 if two else 0.3)]
+DELTA_RATE = 1e-6       # the two-sided false-alarm rate of the delta-draw count, CHI_Z's 1e-6
 
 
 def sampler_numbers(seed, n):
@@ -180,19 +191,35 @@ def expected_bin_mass(L, kw, wo1, sub=CHI_SUB):
 def check_sampler(bsdf_sample, L, name, kw, woz):
     """Chi-square of CHI_DRAWS draws of bsdf_sample(kw, wo, u) -> (wi, f, pdf, delta) against the
     expected bin masses, and the share of draws with a positive pdf against its integral. Returns
-    chi-square per degree of freedom."""
+    chi-square per degree of freedom.
+
+    A sampler with a delta lobe (smooth plastic's coat, probability c = the sum of `delta_lobes`'
+    probabilities at wo; 0 for every rough material, which then may not flag a single draw): the
+    draws that are not flagged delta follow sampled_density / (1 - c), by the same chi-square over
+    their own number; the count of flagged draws is binomial(n, c), held to |k - n c| <=
+    z sqrt(n c (1 - c)) + 1, z the two-sided normal quantile of DELTA_RATE (n c is in the
+    thousands: the normal approximation is good) and the 1 for the sampler's own arithmetic: the
+    numbers are multiples of 2^-24 and its float32 weight is a float32 ulp from c, which together
+    move the expected count by n (2^-24 + 2^-23 c) < 0.04."""
     wo1 = np.array([np.sqrt(1.0 - woz * woz), 0.0, woz], np.float32)
     n = CHI_DRAWS
     u = sampler_numbers(hash_name(name) + int(woz * 10), n)
     wi, f, pdf, delta = bsdf_sample(kw, np.broadcast_to(wo1, (n, 3)), u)
-    assert not delta.any()
+    mat = R.material(**kw)
+    c = float(sum(l[2] for l in R.delta_lobes(mat, wo1, L=L))) if R.is_smooth(mat) else 0.0
+    assert 0.0 <= c < 1.0
+    z = NormalDist().inv_cdf(1.0 - DELTA_RATE / 2.0)
+    k_bound = z * np.sqrt(n * c * (1.0 - c)) + (1.0 if c else 0.0)
+    assert abs(delta.sum() - n * c) <= k_bound, (int(delta.sum()), n * c, k_bound)
     mass, lit_mass = expected_bin_mass(L, kw, wo1)
-    drawn = np.isfinite(wi).all(1) & (np.abs(wi).max(1) > 0)
+    mass = mass / (1.0 - c)
+    m = int((~delta).sum())                     # the chi-square is over the draws that are not delta
+    drawn = ~delta & np.isfinite(wi).all(1) & (np.abs(wi).max(1) > 0)
     w = wi[drawn].astype(np.float64)
     obs, _, _ = np.histogram2d(w[:, 2], np.arctan2(w[:, 1], w[:, 0]), bins=CHI_BINS, range=[[-1, 1], [-np.pi, np.pi]])
     # merge bins in raster order until each group expects at least 5 draws; "no direction" is a group
-    e = np.append(mass.ravel() * n, max(1.0 - mass.sum(), 0.0) * n)
-    o = np.append(obs.ravel(), n - drawn.sum())
+    e = np.append(mass.ravel() * m, max(1.0 - mass.sum(), 0.0) * m)
+    o = np.append(obs.ravel(), m - drawn.sum())
     ge, go, ae, ao = [], [], 0.0, 0.0
     for ei, oi in zip(e, o):
         ae, ao = ae + ei, ao + oi
@@ -204,7 +231,8 @@ def check_sampler(bsdf_sample, L, name, kw, woz):
     valid = (~delta & (pdf > 0)).mean()
     lit = min(lit_mass.sum(), 1.0)
     print(f"{name} wo.z={woz}: chi2/dof {chi2 / dof:.3f} (dof {dof}, bound {chi_square_quantile(dof) / dof:.3f}), "
-          f"valid {valid:.4f} against {lit:.4f}, density integral {mass.sum():.4f}")
+          f"valid {valid:.4f} against {lit:.4f}, density integral {mass.sum():.4f}, "
+          f"delta draws {int(delta.sum())} against {n * c:.1f} +- {k_bound:.1f}")
     assert dof >= 100
     assert chi2 < chi_square_quantile(dof), (chi2, dof)
     assert abs(valid - lit) < 5.0 * np.sqrt(lit * (1.0 - lit) / n) + 1e-3, (valid, lit)
@@ -222,7 +250,9 @@ def test_samplers_draw_from_their_pdf(oracle_mod, golden_luts, ref_luts, name, k
     mass VNDF sampling sends below the horizon is drawn but invalid) within 5 standard errors +
     1e-3. Tried once on a scratch copy of the oracle: with sample_ggx always drawing from the NDF
     while the pdf stays the VNDF's, all twelve cases fail (chi-square per degree of freedom from
-    1.9 for plastic_rough at wo.z = 0.9 to above 70 000)."""
+    1.9 for plastic_rough at wo.z = 0.9 to above 70 000). The four smooth-plastic cases (CHI_CASES' tail)
+    draw their coat as a delta lobe: chi-square per degree of freedom 0.97 to 1.00 over the Lambert draws,
+    and 8 093 to 50 386 delta draws, each within 0.3 of its binomial bound (see check_sampler)."""
     def smp(kw, wo, u):
         return oracle_mod.bsdf_sample(golden_luts, oracle_mod.bsdf_material(**kw), wo, u, VNDF)
     check_sampler(smp, ref_luts, name, kw, woz)
@@ -518,26 +548,84 @@ DELTA_MATERIALS = [
     ("smooth_dielectric_2.4", dict(type=DIELECTRIC, alpha=0.0, ior=2.4)),
     ("thin_dielectric", dict(type=THIN, alpha=0.0, ior=1.5)),
     ("smooth_conductor", dict(type=CONDUCTOR, albedo=(3.9, 2.4, 1.1), alpha=0.0, ior=(0.2, 0.9, 1.4), two_sided=True)),
+    ("smooth_plastic", dict(type=PLASTIC, albedo=(0.7, 0.6, 0.5), alpha=0.0, ior=1.5, internal_scattering=0)),
+    ("smooth_plastic_1.8_isf1", dict(type=PLASTIC, albedo=(0.9, 0.5, 0.1), alpha=0.0, ior=1.8, internal_scattering=1)),
+    ("smooth_plastic_two_isf2", dict(type=PLASTIC, albedo=(0.9, 0.5, 0.1), alpha=0.0, ior=1.5, two_sided=True, internal_scattering=2)),
 ]
+DELTA_DIRECTIONS = 64
+
+
+def check_delta_lobes(bsdf_sample, bsdf_eval, L, name, kw):
+    """One material of DELTA_MATERIALS for a sampler bsdf_sample(kw, wo, u) -> (wi, f, pdf, delta) and an
+    evaluator bsdf_eval(kw, wi, wo, features) -> (f, pdf), at 64 seeded wo, alternately above and below.
+
+    A smooth dielectric, thin sheet or conductor has delta lobes only: with the selection number at 0
+    and just below 1 the sampler returns bsdf_ref's first and last lobe at that wo -- direction, f
+    and probability to a relative 2e-5 (a refracted direction's float32 cancellation at grazing wo
+    included) -- every draw flagged delta.
+
+    A smooth plastic is mixed, and its delta lobe is the LAST interval of the selection number
+    (`sel < w_l` is Lambert): at sel = 1 - 2^-24 the draw is the coat of `delta_lobes`, to the same
+    2e-5 and flagged delta; at sel = 0 it is a Lambert draw, not flagged, whose f and pdf are
+    `evaluate` at the returned direction within check_values_and_pdfs' tolerance. Every wo that has
+    the coat has a coat weight strictly between 0 and 1 (asserted), so both branches are reached;
+    from inside a one-sided plastic there is no lobe at all: f = 0, pdf = 0, not delta."""
+    rng = np.random.default_rng(hash_name(name))
+    n = DELTA_DIRECTIONS
+    z = rng.uniform(0.05, 1.0, n) * np.where(np.arange(n) % 2, -1.0, 1.0)
+    phi = rng.uniform(0.0, 2.0 * np.pi, n)
+    wo = np.stack([np.sqrt(1 - z * z) * np.cos(phi), np.sqrt(1 - z * z) * np.sin(phi), z], 1).astype(np.float32)
+    mat = R.material(**kw)
+    lobes = [R.delta_lobes(mat, wo[i], L=L) for i in range(n)]
+    if kw["type"] != PLASTIC:
+        for sel, pick in ((0.0, 0), (1.0 - 2.0 ** -24, -1)):
+            u = np.tile(np.array([0.3, 0.6, sel], np.float32), (n, 1))
+            wi, f, pdf, delta = bsdf_sample(kw, wo, u)
+            assert delta.all()
+            for i in range(n):
+                rwi, rf, rp = lobes[i][pick]
+                np.testing.assert_allclose(wi[i], rwi, rtol=2e-5, atol=2e-6)
+                np.testing.assert_allclose(f[i], rf, rtol=2e-5)
+                np.testing.assert_allclose(pdf[i], rp, rtol=2e-5)
+        return
+    has = np.array([len(l) == 1 for l in lobes])
+    assert (has == ((z > 0) | bool(kw.get("two_sided")))).all() and has.sum() >= n // 2
+    coat = np.array([float(l[0][2]) if l else 0.0 for l in lobes])
+    assert ((coat[has] > 0) & (coat[has] < 1)).all(), (coat[has].min(), coat[has].max())
+    u = sampler_numbers(hash_name(name) + 1, n)
+    # -- the last interval: the coat
+    u[:, 2] = 1.0 - 2.0 ** -24
+    wi, f, pdf, delta = bsdf_sample(kw, wo, u)
+    assert (delta == has).all()
+    assert not f[~has].any() and not pdf[~has].any()
+    for i in np.flatnonzero(has):
+        rwi, rf, rp = lobes[i][0]
+        np.testing.assert_allclose(wi[i], rwi, rtol=2e-5, atol=2e-6)
+        np.testing.assert_allclose(f[i], rf, rtol=2e-5)
+        np.testing.assert_allclose(pdf[i], rp, rtol=2e-5)
+    # -- the first: the Lambert base, described by `evaluate`
+    u[:, 2] = 0.0
+    wi, f, pdf, delta = bsdf_sample(kw, wo, u)
+    assert not delta.any()
+    assert not f[~has].any() and not pdf[~has].any()
+    wi, wo_h, f, pdf = wi[has], wo[has], f[has], pdf[has]
+    assert (wi[:, 2] * wo_h[:, 2] > 0).all() and (pdf > 0).all() and (f > 0).all()
+    r64 = R.evaluate(L, mat, wi, wo_h, True, np.float64)
+    r32 = tuple(x.astype(np.float64) for x in R.evaluate(L, mat, wi, wo_h, True, np.float32))
+    kf, kp = tolerance_ratio(f, r64[0], r32[0]), tolerance_ratio(pdf, r64[1], r32[1])
+    print(f"{name}: coat weight {coat[has].min():.4f} to {coat[has].max():.4f}; Lambert draw K f {kf.max():.2f} pdf {kp.max():.2f}")
+    assert kf.max() <= TOLERANCE_K and kp.max() <= TOLERANCE_K, (kf.max(), kp.max())
+    ef, ep = bsdf_eval(kw, wi, wo_h, VNDF)          # ... and the evaluator says the same of the pair
+    assert tolerance_ratio(ef, r64[0], r32[0]).max() <= TOLERANCE_K and tolerance_ratio(ep, r64[1], r32[1]).max() <= TOLERANCE_K
 
 
 @pytest.mark.parametrize("name,kw", DELTA_MATERIALS, ids=[m[0] for m in DELTA_MATERIALS])
-def test_delta_lobes_against_float64_reference(oracle_mod, golden_luts, name, kw):
-    """The smooth and thin materials' delta lobes: with the selection number at 0 and just below 1
-    the oracle's sampler returns bsdf_ref's first and last lobe at that wo -- direction, f and
-    probability to a relative 2e-5 (a refracted direction's float32 cancellation at grazing wo
-    included), from outside and from inside, every draw flagged delta."""
-    rng = np.random.default_rng(hash_name(name))
-    z = rng.uniform(0.05, 1.0, 64) * np.where(np.arange(64) % 2, -1.0, 1.0)
-    phi = rng.uniform(0.0, 2.0 * np.pi, 64)
-    wo = np.stack([np.sqrt(1 - z * z) * np.cos(phi), np.sqrt(1 - z * z) * np.sin(phi), z], 1).astype(np.float32)
-    mat = R.material(**kw)
-    for sel, pick in ((0.0, 0), (1.0 - 2.0 ** -24, -1)):
-        u = np.tile(np.array([0.3, 0.6, sel], np.float32), (64, 1))
-        wi, f, pdf, delta = oracle_mod.bsdf_sample(golden_luts, oracle_mod.bsdf_material(**kw), wo, u, VNDF)
-        assert delta.all()
-        for i in range(64):
-            rwi, rf, rp = R.delta_lobes(mat, wo[i])[pick]
-            np.testing.assert_allclose(wi[i], rwi, rtol=2e-5, atol=2e-6)
-            np.testing.assert_allclose(f[i], rf, rtol=2e-5)
-            np.testing.assert_allclose(pdf[i], rp, rtol=2e-5)
+def test_delta_lobes_against_float64_reference(oracle_mod, golden_luts, ref_luts, name, kw):
+    """check_delta_lobes on the oracle's SampleBSDF / EvaluateBSDF: the smooth and thin materials' delta
+    lobes, and both intervals of a smooth plastic's selection number."""
+    def smp(kw, wo, u):
+        return oracle_mod.bsdf_sample(golden_luts, oracle_mod.bsdf_material(**kw), wo, u, VNDF)
+
+    def ev(kw, wi, wo, features):
+        return oracle_mod.bsdf_eval(golden_luts, oracle_mod.bsdf_material(**kw), wi, wo, features)
+    check_delta_lobes(smp, ev, ref_luts, name, kw)

@@ -9,7 +9,7 @@ import pytest
 
 import bsdf_ref as R
 from conftest import GOLDEN
-from test_bsdf_ref import (CHI_CASES, EVAL_CASES, VNDF, check_sampler, check_values_and_pdfs)
+from test_bsdf_ref import (CHI_CASES, DELTA_MATERIALS, EVAL_CASES, VNDF, check_delta_lobes, check_sampler, check_values_and_pdfs)
 from test_gpu_parity import same_bits
 
 pytestmark = pytest.mark.gpu
@@ -191,3 +191,17 @@ def test_device_samplers_draw_from_their_pdf(probe, ref_luts, name, kw, woz):
     def smp(kw, wo, u):
         return probe.bsdf_sample(device_material(kw), wo, u, VNDF)
     check_sampler(smp, ref_luts, name, kw, woz)
+
+
+@pytest.mark.parametrize("name,kw", DELTA_MATERIALS, ids=[m[0] for m in DELTA_MATERIALS])
+def test_device_delta_lobes_against_float64_reference(probe, ref_luts, name, kw):
+    """test_bsdf_ref.test_delta_lobes_against_float64_reference through the device entries: the smooth
+    and thin materials' delta lobes and both intervals of a smooth plastic's selection number, at the
+    same 64 directions and with the same tolerances, so the device's delta lobes stand against
+    float64 directly and not only through the oracle."""
+    def smp(kw, wo, u):
+        return probe.bsdf_sample(device_material(kw), wo, u, VNDF)
+
+    def ev(kw, wi, wo, features):
+        return probe.bsdf_eval(device_material(kw), wi, wo, features)
+    check_delta_lobes(smp, ev, ref_luts, name, kw)
