@@ -9,8 +9,8 @@ from ._abi import (DCRTError, FEATURE_ALLOW_ANYHIT, FEATURE_DEFAULT, FEATURE_GGX
                    FEATURE_NO_FRONT_TO_BACK, FEATURE_WATERTIGHT, FILTER_BOX, FILTER_GAUSSIAN, FILTER_LANCZOS,
                    FILTER_MITCHELL, FILTER_TRIANGLE, FilterParams, FrameParams, LIB_PATH, load_library)
 from .scene import Scene  # noqa: F401
-from ._abi import ConvergeParams, DenoiseParams, NoiseStats, PostFxParams  # noqa: F401
-from .tracer import (HIT_DTYPE, RAY_DTYPE, WavefrontPathTracer, denoise_default_params, device_count, make_pipelines, make_rays, prepare_pipelines, probe_row_cost,  # noqa: F401
+from ._abi import ConvergeParams, DenoiseParams, FireflyParams, NoiseStats, PostFxParams  # noqa: F401
+from .tracer import (HIT_DTYPE, RAY_DTYPE, WavefrontPathTracer, denoise_default_params, device_count, firefly_default_params, make_pipelines, make_rays, prepare_pipelines, probe_row_cost,  # noqa: F401
                      render_images_concurrently, save_bmp, srgb_thresholds)
 
 __version__ = "0.1.0"

@@ -137,6 +137,11 @@ class DenoiseParams(C.Structure):
                 ("sigma_albedo", C.c_float), ("demodulate", C.c_uint32)]
 
 
+class FireflyParams(C.Structure):
+    """dcrt_firefly_params (dcrt.h "firefly re-weighting"); dcrt_firefly_default_params fills in 6, 1.0, 8.0, 3.0."""
+    _fields_ = [("cascades", C.c_uint32), ("start", C.c_float), ("base", C.c_float), ("min_support", C.c_float)]
+
+
 class NoiseStats(C.Structure):
     """dcrt_noise_stats: the half-film noise estimate of a film (dcrt.h "film noise estimate")."""
     _fields_ = [("images", C.c_uint32), ("valid_pixels", C.c_uint32), ("converged_pixels", C.c_uint32),
@@ -363,6 +368,18 @@ SIGNATURES = [
     ("dcrt_tracer_denoised_device_ptr", _I, [_P, C.POINTER(_P)]),
     ("dcrt_tracer_resolve_denoised", _I, [_P, C.POINTER(PostFxParams), C.POINTER(C.c_uint8), _FP]),
     ("dcrt_tracer_denoise_timings", _I, [_P, _FP, _U, C.POINTER(C.c_uint32)]),
+    ("dcrt_firefly_default_params", _I, [C.POINTER(FireflyParams)]),
+    ("dcrt_tracer_set_firefly", _I, [_P, C.POINTER(FireflyParams)]),
+    ("dcrt_tracer_get_firefly", _I, [_P, C.POINTER(C.c_int), C.POINTER(FireflyParams)]),
+    ("dcrt_tracer_firefly_resolve", _I, [_P]),
+    ("dcrt_tracer_read_firefly", _I, [_P, _FP]),
+    ("dcrt_tracer_firefly_device_ptr", _I, [_P, C.POINTER(_P)]),
+    ("dcrt_tracer_resolve_firefly", _I, [_P, C.POINTER(PostFxParams), C.POINTER(C.c_uint8), _FP]),
+    ("dcrt_tracer_denoise_firefly", _I, [_P, C.POINTER(DenoiseParams)]),
+    ("dcrt_tracer_read_cascades", _I, [_P, _FP]),
+    ("dcrt_tracer_cascade_device_ptrs", _I, [_P, C.POINTER(_P), _U, C.POINTER(C.c_uint32)]),
+    ("dcrt_tracer_firefly_resolve_device", _I, [_P, C.POINTER(FireflyParams), _U, _U, _U, _P, C.POINTER(_P), _P]),
+    ("dcrt_tracer_firefly_timings", _I, [_P, _FP, _FP]),
     ("dcrt_tracer_set_convergence", _I, [_P, _I]),
     ("dcrt_tracer_film_image_count", _I, [_P, C.POINTER(C.c_uint32)]),
     ("dcrt_tracer_half_film_device_ptr", _I, [_P, C.POINTER(_P)]),

@@ -2454,6 +2454,218 @@ __global__ __launch_bounds__(kFilmThreads) void film_half_kernel(Film film, cons
     film_pass<true>(film, fcon, images, guard, posList, valList, half, firstIndex);
 }
 
+// ---- firefly re-weighting (dcrt.h "firefly re-weighting"; tests/firefly_ref.py restates it) ----
+// Zirr, Hanika, Dachsbacher 2018: K cascade films beside the film take each sample's share by its
+// brightness band, and a resolve pass keeps a band at a pixel to the extent its neighbourhood
+// supports it.
+constexpr int kFireflyMaxCascades = 8;
+// scale[j] = s_j for j < cascades (the host's float32 products), top = s_{K-1}, invBase = 1 / b,
+// invSpan = 1 - invBase: all float32, from the host
+struct FireflyConsts { float scale[kFireflyMaxCascades]; float top, invBase, invSpan, minSupport; uint32_t cascades; };
+struct CascadeFilms { float4* film[kFireflyMaxCascades]; };
+
+__device__ __forceinline__ float firefly_luminance(float r, float g, float b) { return fmaxf(0.0f, r * 0.299f + g * 0.587f + b * 0.114f); }
+
+// The split of a sample (dcrt.h): its lower cascade `band` and that cascade's share alpha; cascade
+// band + 1 takes 1 - alpha (no cascade where band + 1 == K: alpha is 1 there).
+__device__ __forceinline__ void firefly_split(const FireflyConsts& k, float Y, uint32_t* band, float* alpha)
+{
+    uint32_t j = 0u;
+    float a = 1.0f;
+    if (Y > k.top) {
+        j = k.cascades - 1u;
+    } else if (Y > k.scale[0]) {
+        float sj = k.scale[0];
+#pragma unroll
+        for (int i = 1; i < kFireflyMaxCascades - 1; ++i)
+            if ((uint32_t)i + 1u < k.cascades && Y > k.scale[i]) { j = (uint32_t)i; sj = k.scale[i]; }
+        a = fminf(fmaxf((sj / Y - k.invBase) / k.invSpan, 0.0f), 1.0f);
+    }
+    *band = j;
+    *alpha = a;
+}
+
+// One tap of a pixel's gather into its per-image cascade sums: the sample's two shares times the
+// filter weight, (alpha v) w, each added to its own cascade's sum. The selects unroll, so the sums
+// stay in registers whatever the band.
+__device__ __forceinline__ void firefly_tap(V3 (&sum)[kFireflyMaxCascades], V3 v, float alpha, uint32_t band, float w)
+{
+    const float beta = 1.0f - alpha;
+    const V3 lo = mk(v.x * alpha, v.y * alpha, v.z * alpha) * w;
+    const V3 hi = mk(v.x * beta, v.y * beta, v.z * beta) * w;
+#pragma unroll
+    for (int j = 0; j < kFireflyMaxCascades; ++j) {
+        const bool isLo = band == (uint32_t)j, isHi = band + 1u == (uint32_t)j;
+        if (isLo || isHi) sum[j] = sum[j] + (isLo ? lo : hi);
+    }
+}
+
+// The cascade pass: film_pass's gather (same tiles, same windows, same filter weight, images in
+// order, window rows then columns, a per-image sum added to the accumulator) into the K cascade
+// films. A sample's band and alpha are computed once, when it is staged; wide filters take the
+// direct gather and split per tap. Cascade .w is left as it is (0 from the clear): the film's .w is
+// the weight sum of every cascade.
+__global__ __launch_bounds__(kFilmThreads) void film_cascade_kernel(Film film, CascadeFilms cas, FireflyConsts ff, const FilterConsts* fcon,
+                                                                    uint32_t images, const Globals* guard,
+                                                                    const float2* const* __restrict__ posList,
+                                                                    const float4* const* __restrict__ valList)
+{
+    if (guard && (!guard->imageComplete || guard->skipFilm)) return;
+    const uint32_t count = guard ? guard->batchImages : images;
+    const FilterConsts c = *fcon;
+    const uint32_t W = film.width, H = film.height;
+    const uint32_t total = W * H;
+    const uint32_t tilesX = (W + kFilmTile - 1) / kFilmTile, tiles = tilesX * ((H + kFilmTile - 1) / kFilmTile);
+    // two tile buffers, so one barrier per image separates a buffer's writes from its reads
+    __shared__ float2 tPos[2][kFilmSpan * kFilmSpan];
+    __shared__ float4 tVal[2][kFilmSpan * kFilmSpan];    // (v.rgb, alpha)
+    __shared__ uint32_t tBand[2][kFilmSpan * kFilmSpan];
+    for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int x0 = (int)(tile % tilesX) * kFilmTile, y0 = (int)(tile / tilesX) * kFilmTile;
+        const uint32_t px = (uint32_t)x0 + (threadIdx.x % kFilmTile), py = (uint32_t)y0 + (threadIdx.x / kFilmTile);
+        const bool mine = px < W && py < H && !(film.rowOwned && !film.rowOwned[py]);
+        const size_t p = (size_t)py * W + px;
+        int xs = 0, xe = -1, ys = 0, ye = -1;
+        V3 acc[kFireflyMaxCascades];
+#pragma unroll
+        for (int j = 0; j < kFireflyMaxCascades; ++j) acc[j] = mk(0.0f, 0.0f, 0.0f);
+        if (mine) {
+            film_pixel_window(c, px, py, W, H, &xs, &xe, &ys, &ye);
+#pragma unroll
+            for (int j = 0; j < kFireflyMaxCascades; ++j)
+                if ((uint32_t)j < ff.cascades) {
+                    const float4 a = cas.film[j][p];
+                    acc[j] = mk(a.x, a.y, a.z);
+                }
+        }
+        const float cx = (float)px + 0.5f, cy = (float)py + 0.5f;
+        // the tile's staged span, as film_pass takes it
+        int txs, txe, tys, tye, unused0, unused1;
+        film_pixel_window(c, (uint32_t)x0, (uint32_t)y0, W, H, &txs, &unused0, &tys, &unused1);
+        film_pixel_window(c, min((uint32_t)x0 + kFilmTile - 1u, W - 1u), min((uint32_t)y0 + kFilmTile - 1u, H - 1u), W, H,
+                          &unused0, &txe, &unused1, &tye);
+        const int spanX = txe - txs + 1, spanY = tye - tys + 1;
+        const bool staged = spanX <= kFilmSpan && spanY <= kFilmSpan;
+        const int nStage = spanX * spanY;
+        for (uint32_t b = 0; b < count; ++b) {
+            const float2* sPos = posList ? posList[b] : film.samplePosition + (size_t)b * total;
+            const float4* sVal = valList ? valList[b] : film.sampleValue + (size_t)b * total;
+            V3 sum[kFireflyMaxCascades];
+#pragma unroll
+            for (int j = 0; j < kFireflyMaxCascades; ++j) sum[j] = mk(0.0f, 0.0f, 0.0f);
+            if (staged) {
+                const uint32_t buf = b & 1u;
+                for (int i = (int)threadIdx.x; i < nStage; i += kFilmThreads) {
+                    const size_t q = (size_t)(tys + i / spanX) * W + (size_t)(txs + i % spanX);   // inside the film by construction
+                    const float4 sv = sVal[q];
+                    uint32_t band;
+                    float alpha;
+                    firefly_split(ff, firefly_luminance(sv.x, sv.y, sv.z), &band, &alpha);
+                    tPos[buf][i] = sPos[q];
+                    tVal[buf][i] = make_float4(sv.x, sv.y, sv.z, alpha);
+                    tBand[buf][i] = band;
+                }
+                __syncthreads();   // (buffer `buf` was last read at image b - 2, before image b - 1's barrier)
+                for (int y = ys; y <= ye; ++y)
+                    for (int x = xs; x <= xe; ++x) {
+                        const int i = (y - tys) * spanX + (x - txs);
+                        const float2 sp = tPos[buf][i];
+                        const float4 sv = tVal[buf][i];
+                        const float w = evaluate_filter(c, cx - (sp.x + (float)x), cy - (sp.y + (float)y));
+                        firefly_tap(sum, mk(sv.x, sv.y, sv.z), sv.w, tBand[buf][i], w);
+                    }
+            } else {
+                // wide filters: the direct gather from memory
+                for (int y = ys; y <= ye; ++y)
+                    for (int x = xs; x <= xe; ++x) {
+                        const size_t q = (size_t)y * W + x;
+                        const float2 sp = sPos[q];
+                        const float4 sv = sVal[q];
+                        uint32_t band;
+                        float alpha;
+                        firefly_split(ff, firefly_luminance(sv.x, sv.y, sv.z), &band, &alpha);
+                        const float w = evaluate_filter(c, cx - (sp.x + (float)x), cy - (sp.y + (float)y));
+                        firefly_tap(sum, mk(sv.x, sv.y, sv.z), alpha, band, w);
+                    }
+            }
+#pragma unroll
+            for (int j = 0; j < kFireflyMaxCascades; ++j) acc[j] = acc[j] + sum[j];
+        }
+        if (mine) {
+#pragma unroll
+            for (int j = 0; j < kFireflyMaxCascades; ++j)
+                if ((uint32_t)j < ff.cascades) {
+                    float4* dst = cas.film[j] + p;
+                    dst->x = acc[j].x; dst->y = acc[j].y; dst->z = acc[j].z;
+                }
+        }
+        __syncthreads();   // the tile buffers are reused by the next tile
+    }
+}
+
+// The resolve (dcrt.h): one thread per pixel of a 16 x 16 tile. The counts count_i(q) of the tile
+// plus a one-pixel ring are staged in LDS -- each costs a division and is read by up to nine
+// pixels -- and every pixel then sums its 3 x 3 from there.
+constexpr int kFireflyTile = 16;
+constexpr int kFireflySpan = kFireflyTile + 2;
+__global__ __launch_bounds__(kFireflyTile * kFireflyTile) void firefly_resolve_kernel(const float4* __restrict__ film, CascadeFilms cas,
+                                                                                      FireflyConsts ff, float imageCount, uint32_t W, uint32_t H,
+                                                                                      float4* __restrict__ out)
+{
+    __shared__ float cnt[kFireflyMaxCascades][kFireflySpan * kFireflySpan];
+    const int x0 = (int)blockIdx.x * kFireflyTile, y0 = (int)blockIdx.y * kFireflyTile;
+    for (int i = (int)threadIdx.x; i < kFireflySpan * kFireflySpan; i += kFireflyTile * kFireflyTile) {
+        const int qx = x0 - 1 + i % kFireflySpan, qy = y0 - 1 + i / kFireflySpan;
+        const bool inside = qx >= 0 && qy >= 0 && qx < (int)W && qy < (int)H;
+        const size_t q = inside ? (size_t)qy * W + (size_t)qx : 0;
+        const float wq = inside ? film[q].w : 0.0f;
+        const bool valid = wq > 0.0f;
+#pragma unroll
+        for (int j = 0; j < kFireflyMaxCascades; ++j) {
+            float n = 0.0f;
+            if (valid && (uint32_t)j < ff.cascades) {
+                const float4 cq = cas.film[j][q];
+                n = (imageCount * firefly_luminance(cq.x, cq.y, cq.z)) / (wq * ff.scale[j]);
+            }
+            if ((uint32_t)j < ff.cascades) cnt[j][i] = n;   // (the rows past K are never read)
+        }
+    }
+    __syncthreads();
+    const int tx = (int)threadIdx.x % kFireflyTile, ty = (int)threadIdx.x / kFireflyTile;
+    const uint32_t px = (uint32_t)(x0 + tx), py = (uint32_t)(y0 + ty);
+    if (px >= W || py >= H) return;
+    const size_t p = (size_t)py * W + px;
+    const float wp = film[p].w;
+    if (!(wp > 0.0f)) { out[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); return; }
+    // T_i = the 3 x 3 sum of count_i, rows then columns
+    float T[kFireflyMaxCascades];
+#pragma unroll
+    for (int j = 0; j < kFireflyMaxCascades; ++j) {
+        float s = 0.0f;
+        if ((uint32_t)j < ff.cascades)
+            for (int dy = 0; dy < 3; ++dy)
+                for (int dx = 0; dx < 3; ++dx) s = s + cnt[j][(ty + dy) * kFireflySpan + (tx + dx)];
+        T[j] = s;
+    }
+    V3 sum = mk(0.0f, 0.0f, 0.0f);
+#pragma unroll
+    for (int j = 0; j < kFireflyMaxCascades; ++j) {
+        if ((uint32_t)j < ff.cascades) {
+            const float4 cj = cas.film[j][p];
+            if (j == 0) {
+                sum = mk(cj.x, cj.y, cj.z);   // omega_0 = 1
+            } else {
+                // S_j = T_{j-1} + T_j + T_{j+1}, in that order (no T_K: the last cascade has two terms)
+                float S = T[j - 1] + T[j];
+                if ((uint32_t)j + 1u < ff.cascades) S = S + T[j + 1 < kFireflyMaxCascades ? j + 1 : j];
+                const float omega = fminf(fmaxf((S - 1.0f) / ff.minSupport, 0.0f), 1.0f);
+                sum = sum + mk(cj.x, cj.y, cj.z) * omega;
+            }
+        }
+    }
+    out[p] = make_float4(sum.x / wp, sum.y / wp, sum.z / wp, 1.0f);
+}
+
 // film += src (dcrt_tracer_add_film_device): the films of disjoint film partitions
 __global__ void add_film_kernel(float4* film, const float4* src, uint32_t n)
 {

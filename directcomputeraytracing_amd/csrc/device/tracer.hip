@@ -275,6 +275,100 @@ private:
     Pinned<uint32_t, 2> hostCount;
     EventMarks maskMarks, fillMarks;          // 3 and 2 marks when timed, else none
 };
+// The cascade pass and the resolve of dcrt.h "firefly re-weighting". The cascade films belong to the caller.
+class FireflyFilter {
+public:
+    // The kernels' constants of `p`: the scales by float32 products; refuses what dcrt.h refuses
+    static int MakeConsts(const dcrt_firefly_params& p, FireflyConsts* out);
+    // film_cascade_kernel beside a film pass of `film` (its sample textures, or the lists), on `grid` workgroups
+    int Cascade(hipStream_t stream, bool timing, uint32_t grid, const Film& film, const CascadeFilms& cas, const FireflyConsts& k,
+                const FilterConsts* filter, uint32_t images, const Globals* guard, const float2* const* posList, const float4* const* valList);
+    int Resolve(hipStream_t stream, bool timing, const FireflyConsts& k, uint32_t w, uint32_t h, uint32_t imageCount, const float4* film,
+                const CascadeFilms& cas, float4* out);
+    // ms of the last Cascade and the last Resolve, 0 where that one was not timed
+    int Timings(float* cascadeMs, float* resolveMs) const;
+
+private:
+    EventMarks cascadeMarks, resolveMarks;    // 2 marks each when timed, else none
+};
+
+int FireflyFilter::MakeConsts(const dcrt_firefly_params& p, FireflyConsts* out)
+{
+    if (p.cascades < 2u || p.cascades > (uint32_t)kFireflyMaxCascades) { SetLastError("firefly: cascades 2..8"); return DCRT_E_INVALID_ARG; }
+    if (!std::isfinite(p.start) || !std::isfinite(p.base) || !std::isfinite(p.min_support) || !(p.start > 0.0f) || !(p.base > 1.0f) ||
+        !(p.min_support > 0.0f)) {
+        SetLastError("firefly: start > 0, base > 1 and min_support > 0, all finite");
+        return DCRT_E_INVALID_ARG;
+    }
+    FireflyConsts k;
+    std::memset(&k, 0, sizeof(k));
+    volatile float s = p.start;   // (volatile: every product is rounded to float32, whatever the host's evaluation method)
+    for (uint32_t j = 0; j < p.cascades; ++j) {
+        k.scale[j] = s;
+        s = s * p.base;
+    }
+    k.top = k.scale[p.cascades - 1u];
+    if (!std::isfinite(k.top)) { SetLastError("firefly: the last cascade's scale start * base^(K-1) is not finite"); return DCRT_E_INVALID_ARG; }
+    volatile float r = 1.0f / p.base;
+    volatile float d = 1.0f - r;
+    k.invBase = r;
+    k.invSpan = d;
+    k.minSupport = p.min_support;
+    k.cascades = p.cascades;
+    *out = k;
+    return DCRT_OK;
+}
+
+int FireflyFilter::Cascade(hipStream_t stream, bool timing, uint32_t grid, const Film& film, const CascadeFilms& cas, const FireflyConsts& k,
+                           const FilterConsts* filter, uint32_t images, const Globals* guard, const float2* const* posList,
+                           const float4* const* valList)
+{
+    if (timing) {
+        cascadeMarks.Reset();
+        CHECKED(cascadeMarks.Mark(stream));
+    }
+    hipLaunchKernelGGL(film_cascade_kernel, dim3(grid), dim3(kFilmThreads), 0, stream, film, cas, k, filter, images, guard, posList, valList);
+    if (timing) CHECKED(cascadeMarks.Mark(stream));
+    return DCRT_OK;
+}
+
+// The resolve of dcrt.h over W x H device images in film convention, into `out` (not an input). Synchronous.
+int FireflyFilter::Resolve(hipStream_t stream, bool timing, const FireflyConsts& k, uint32_t w, uint32_t h, uint32_t imageCount,
+                           const float4* film, const CascadeFilms& cas, float4* out)
+{
+    Annotation an("Firefly resolve");
+    if (w == 0 || h == 0 || w > 65535u || h > 65535u) { SetLastError("firefly: invalid image size"); return DCRT_E_INVALID_ARG; }
+    if (imageCount == 0) { SetLastError("firefly: no image reached the film"); return DCRT_E_INVALID_ARG; }
+    if (!film || !out) { SetLastError("firefly: null image"); return DCRT_E_INVALID_ARG; }
+    const size_t bytes = (size_t)w * h * sizeof(float4);
+    auto overlaps = [&](const void* in) {
+        const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
+        return a < b + bytes && b < a + bytes;
+    };
+    bool bad = overlaps(film);
+    for (uint32_t j = 0; j < k.cascades; ++j) {
+        if (!cas.film[j]) { SetLastError("firefly: null cascade image"); return DCRT_E_INVALID_ARG; }
+        bad = bad || overlaps(cas.film[j]);
+    }
+    if (bad) { SetLastError("firefly: the output image overlaps an input"); return DCRT_E_INVALID_ARG; }
+    resolveMarks.Reset();
+    if (timing) CHECKED(resolveMarks.Mark(stream));
+    const uint32_t T = (uint32_t)kFireflyTile;
+    hipLaunchKernelGGL(firefly_resolve_kernel, dim3((w + T - 1) / T, (h + T - 1) / T), dim3(T * T), 0, stream, film, cas, k, (float)imageCount, w,
+                       h, out);
+    HIPCHECK(hipGetLastError());
+    if (timing) CHECKED(resolveMarks.Mark(stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+    return DCRT_OK;
+}
+
+int FireflyFilter::Timings(float* cascadeMs, float* resolveMs) const
+{
+    *cascadeMs = *resolveMs = 0.0f;
+    if (cascadeMarks.Count() == 2u) CHECKED(cascadeMarks.ElapsedBetween(0, 1, cascadeMs));
+    if (resolveMarks.Count() == 2u) CHECKED(resolveMarks.ElapsedBetween(0, 1, resolveMs));
+    return DCRT_OK;
+}
 
 int FilmDenoiser::EnsureWork(hipStream_t stream, uint32_t w, uint32_t h)
 {
@@ -1080,6 +1174,19 @@ struct dcrt_tracer {
     bool listFrame = false;            // BeginImage: the frame constants' blocksPerImage is the list's length
     uint64_t pathsSkipped = 0;         // pixels the lists left out since the last ResetStats (counters())
 
+    // ---- firefly re-weighting (dcrt_tracer_set_firefly): the K cascade films and the re-weighted image of
+    // the last resolve (cascadeAllocs: they follow the film's size, only while the feature is on); the
+    // tracer's own film passes launch the cascade pass beside them (LaunchFilm). The kernels' launches and
+    // their event marks are `fireflyFilter` ----
+    bool firefly = false;
+    dcrt_firefly_params fireflyParams{};
+    FireflyConsts fireflyConsts{};
+    DeviceGroup cascadeAllocs;
+    CascadeFilms cascades{};
+    float4* reweighted = nullptr;
+    bool hasReweighted = false;
+    FireflyFilter fireflyFilter;
+
     ~dcrt_tracer();
     int Create(const dcrt_tracer_config& cfg);
     int BuildLuts();
@@ -1129,7 +1236,13 @@ struct dcrt_tracer {
     int LaunchFilm(uint32_t images, const Globals* guard, const float2* const* posList, const float4* const* valList,
                    uint32_t firstIndex)
     {
-        return LaunchFilm(film, convergence ? halfFilm : nullptr, extTiming && !capturing, images, guard, posList, valList, firstIndex);
+        CHECKED(LaunchFilm(film, convergence ? halfFilm : nullptr, extTiming && !capturing, images, guard, posList, valList, firstIndex));
+        // firefly re-weighting: the cascades take the same images (timed outside the graph-shaped iteration only:
+        // the in-graph pass returns at once unless a batch completed)
+        if (firefly)
+            return fireflyFilter.Cascade(stream, extTiming && !guard, FilmGrid(), film, cascades, fireflyConsts, dFilter, images, guard, posList,
+                                         valList);
+        return DCRT_OK;
     }
     int AddFilm(float4* dst, const void* src);
     int ReadImage(const float4* image, float* out);
@@ -1154,6 +1267,10 @@ struct dcrt_tracer {
     int EnsureGuides();
     int RenderGuides(uint32_t firstSeed, uint32_t count);
     int SetConvergence(bool on);
+    int SetFirefly(const dcrt_firefly_params* p);
+    int AllocCascades();
+    int AllocCascadesOrOff();
+    bool Partitioned() const { return partition.world_size > 1 || !bands.empty(); }
     int NoiseOwn(float threshold, dcrt_noise_stats* out);
     // render_converged, and with `adaptiveCall` render_adaptive
     struct AdaptiveCall {
@@ -2142,6 +2259,10 @@ int dcrt_tracer::EnsureFilm(uint32_t w, uint32_t h)
     halfFilm = nullptr;
     noisePixelMap = noiseTileMap = nullptr;
     hasNoiseMaps = false;
+    cascadeAllocs.Free();                             // (and the cascades)
+    cascades = CascadeFilms{};
+    reweighted = nullptr;
+    hasReweighted = false;
     filmImages = 0;
     const size_t n = (size_t)w * h;
     CHECKED(filmAllocs.Alloc(&film.accum, n));
@@ -2152,6 +2273,7 @@ int dcrt_tracer::EnsureFilm(uint32_t w, uint32_t h)
     }
     filmW = w; filmH = h;
     film.width = w; film.height = h;
+    if (firefly) CHECKED(AllocCascadesOrOff());
     CHECKED(EnsureSamples(1));
     CHECKED(BuildRows());
     return adaptive ? AllocBlockList() : DCRT_OK;   // (a new resolution: its own blocks, all of them active)
@@ -2331,6 +2453,7 @@ int dcrt_tracer::SetPartition(const dcrt_film_partition& p)
         return DCRT_E_INVALID_ARG;
     }
     if (adaptive && p.world_size > 1) { SetLastError("adaptive sampling is on: the film cannot be partitioned"); return DCRT_E_INVALID_ARG; }
+    if (firefly && p.world_size > 1) { SetLastError("firefly re-weighting is on: the film cannot be partitioned"); return DCRT_E_INVALID_ARG; }
     partition = p;
     bands.clear();
     if (filmW) {
@@ -2350,6 +2473,7 @@ int dcrt_tracer::SetBands(const uint32_t* b, uint32_t count, uint32_t halo)
 {
     if (count == 0 || !b) { SetLastError("no film bands"); return DCRT_E_INVALID_ARG; }
     if (adaptive) { SetLastError("adaptive sampling is on: the film cannot be cut into bands"); return DCRT_E_INVALID_ARG; }
+    if (firefly) { SetLastError("firefly re-weighting is on: the film cannot be cut into bands"); return DCRT_E_INVALID_ARG; }
     for (uint32_t i = 0; i < count; ++i) {
         if (b[2 * i] >= b[2 * i + 1] || (i > 0 && b[2 * i] < b[2 * i - 1])) {
             SetLastError("film bands: ascending, disjoint, non-empty [y0, y1) ranges");
@@ -2933,6 +3057,8 @@ int dcrt_tracer::ClearFilm()
     const size_t bytes = (size_t)filmW * filmH * sizeof(float4);
     HIPCHECK(hipMemsetAsync(film.accum, 0, bytes, stream));
     if (halfFilm) HIPCHECK(hipMemsetAsync(halfFilm, 0, bytes, stream));
+    for (uint32_t j = 0; firefly && j < fireflyParams.cascades; ++j) HIPCHECK(hipMemsetAsync(cascades.film[j], 0, bytes, stream));
+    hasReweighted = false;
     filmImages = 0;
     if (adaptive) CHECKED(ResetBlockList());   // (an empty film is noisy everywhere)
     return DCRT_OK;
@@ -2949,6 +3075,67 @@ int dcrt_tracer::SetConvergence(bool on)
         halfFilm = nullptr;
     }
     convergence = on;
+    return ClearFilm();
+}
+
+// The K cascade films and the re-weighted image, W x H of the film (EnsureFilm and SetFirefly drop them first)
+int dcrt_tracer::AllocCascades()
+{
+    const size_t n = (size_t)filmW * filmH;
+    for (uint32_t j = 0; j < fireflyParams.cascades; ++j) {
+        CHECKED(cascadeAllocs.Alloc(&cascades.film[j], n));
+        HIPCHECK(hipMemsetAsync(cascades.film[j], 0, n * sizeof(float4), stream));
+    }
+    return cascadeAllocs.Alloc(&reweighted, n);
+}
+
+// ... or, where that fails, none of them and the feature off: no film pass launches onto a missing cascade
+int dcrt_tracer::AllocCascadesOrOff()
+{
+    const int rc = AllocCascades();
+    firefly = rc == DCRT_OK;
+    if (!firefly) {
+        cascadeAllocs.Free();
+        cascades = CascadeFilms{};
+        reweighted = nullptr;
+    }
+    return rc;
+}
+
+// dcrt_tracer_set_firefly: on with `p`, off with null; either way the films are cleared
+int dcrt_tracer::SetFirefly(const dcrt_firefly_params* p)
+{
+    if (!film.accum) { SetLastError("set_firefly: no film (set the frame parameters first)"); return DCRT_E_INVALID_ARG; }
+    FireflyConsts k{};
+    if (p) {
+        CHECKED(FireflyFilter::MakeConsts(*p, &k));
+        if (Partitioned()) {
+            SetLastError("set_firefly: a banded or partitioned film; reduce the films and cascades and use dcrt_tracer_firefly_resolve_device");
+            return DCRT_E_INVALID_ARG;
+        }
+    }
+    HIPCHECK(hipStreamSynchronize(stream));
+    const bool on = p != nullptr;
+    // the in-graph cascade launch carries K and the scales as kernel arguments; min_support is the resolve's alone
+    const bool same = on == firefly && (!on || (p->cascades == fireflyParams.cascades && p->start == fireflyParams.start &&
+                                                p->base == fireflyParams.base));
+    if (!same) {
+        InvalidateGraph();
+        CHECKED(ClearFilm());   // (with the cascades it had: nothing in flight writes them after the free below)
+        HIPCHECK(hipStreamSynchronize(stream));
+        cascadeAllocs.Free();
+        cascades = CascadeFilms{};
+        reweighted = nullptr;
+        firefly = false;
+        if (on) {
+            fireflyParams = *p;
+            CHECKED(AllocCascadesOrOff());
+        }
+    }
+    if (on) {
+        fireflyParams = *p;
+        fireflyConsts = k;
+    }
     return ClearFilm();
 }
 
@@ -3419,6 +3606,7 @@ DCRT_API int dcrt_tracer_add_film_device(dcrt_tracer* t, const void* d_src)
 {
     TRACER_GUARD(t);
     if (!d_src || !t->film.accum) return DCRT_E_INVALID_ARG;
+    if (t->firefly) { SetLastError("add_film_device: firefly re-weighting is on, and the film would hold more than the cascades"); return DCRT_E_INVALID_ARG; }
     return t->AddFilm(t->film.accum, d_src);
 }
 
@@ -3901,6 +4089,122 @@ DCRT_API int dcrt_tracer_resolve_image(dcrt_tracer* t, const dcrt_postfx_params*
     return ResolveFrom(t, (const float4*)t->film.accum, prm, out, outSumLogLum);
 }
 
+// ---- firefly re-weighting -----------------------------------------------------------------
+DCRT_API int dcrt_firefly_default_params(dcrt_firefly_params* out)
+{
+    if (!out) return DCRT_E_INVALID_ARG;
+    out->cascades = 6u;
+    out->start = 1.0f;
+    out->base = 8.0f;
+    out->min_support = 3.0f;
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_set_firefly(dcrt_tracer* t, const dcrt_firefly_params* p)
+{
+    TRACER_GUARD(t);
+    return t->SetFirefly(p);
+}
+
+DCRT_API int dcrt_tracer_get_firefly(dcrt_tracer* t, int* out_enabled, dcrt_firefly_params* out)
+{
+    TRACER_GUARD(t);
+    if (!out_enabled) return DCRT_E_INVALID_ARG;
+    *out_enabled = t->firefly ? 1 : 0;
+    if (out && t->firefly) *out = t->fireflyParams;
+    return DCRT_OK;
+}
+
+static int NeedFirefly(const dcrt_tracer* t)
+{
+    if (!t->firefly) { SetLastError("firefly re-weighting is off (dcrt_tracer_set_firefly)"); return DCRT_E_INVALID_ARG; }
+    return DCRT_OK;
+}
+static int NeedReweighted(const dcrt_tracer* t)
+{
+    if (!t->hasReweighted) { SetLastError("no re-weighted image (dcrt_tracer_firefly_resolve)"); return DCRT_E_INVALID_ARG; }
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_firefly_resolve(dcrt_tracer* t)
+{
+    TRACER_GUARD(t);
+    CHECKED(NeedFirefly(t));
+    t->hasReweighted = false;
+    CHECKED(t->fireflyFilter.Resolve(t->stream, t->extTiming, t->fireflyConsts, t->filmW, t->filmH, t->filmImages, t->film.accum, t->cascades,
+                                     t->reweighted));
+    t->hasReweighted = true;
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_read_firefly(dcrt_tracer* t, float* out)
+{
+    TRACER_GUARD(t);
+    if (!out) return DCRT_E_INVALID_ARG;
+    CHECKED(NeedReweighted(t));
+    return t->ReadImage(t->reweighted, out);
+}
+
+DCRT_API int dcrt_tracer_firefly_device_ptr(dcrt_tracer* t, void** out)
+{
+    TRACER_GUARD(t);
+    if (!out) return DCRT_E_INVALID_ARG;
+    CHECKED(NeedReweighted(t));
+    *out = t->reweighted;
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_resolve_firefly(dcrt_tracer* t, const dcrt_postfx_params* prm, uint8_t* out, float* outSumLogLum)
+{
+    TRACER_GUARD(t);
+    if (!prm || !out) return DCRT_E_INVALID_ARG;
+    CHECKED(NeedReweighted(t));
+    return ResolveFrom(t, (const float4*)t->reweighted, prm, out, outSumLogLum);
+}
+
+DCRT_API int dcrt_tracer_read_cascades(dcrt_tracer* t, float* out)
+{
+    TRACER_GUARD(t);
+    if (!out) return DCRT_E_INVALID_ARG;
+    CHECKED(NeedFirefly(t));
+    const size_t n = (size_t)t->filmW * t->filmH;
+    for (uint32_t j = 0; j < t->fireflyParams.cascades; ++j)
+        HIPCHECK(hipMemcpyAsync(out + j * n * 4, t->cascades.film[j], n * sizeof(float4), hipMemcpyDeviceToHost, t->stream));
+    HIPCHECK(hipStreamSynchronize(t->stream));
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_cascade_device_ptrs(dcrt_tracer* t, void** out, uint32_t capacity, uint32_t* out_count)
+{
+    TRACER_GUARD(t);
+    if (!out || !out_count) return DCRT_E_INVALID_ARG;
+    CHECKED(NeedFirefly(t));
+    *out_count = t->fireflyParams.cascades;
+    if (capacity < t->fireflyParams.cascades) { SetLastError("cascade_device_ptrs: room for fewer than K pointers"); return DCRT_E_INVALID_ARG; }
+    for (uint32_t j = 0; j < t->fireflyParams.cascades; ++j) out[j] = t->cascades.film[j];
+    return DCRT_OK;
+}
+
+DCRT_API int dcrt_tracer_firefly_resolve_device(dcrt_tracer* t, const dcrt_firefly_params* p, uint32_t width, uint32_t height,
+                                                uint32_t image_count, const void* d_film, const void* const* d_cascades, void* d_out)
+{
+    TRACER_GUARD(t);
+    if (!p || !d_cascades) return DCRT_E_INVALID_ARG;
+    FireflyConsts k{};
+    CHECKED(FireflyFilter::MakeConsts(*p, &k));
+    CascadeFilms cas{};
+    for (uint32_t j = 0; j < p->cascades; ++j) cas.film[j] = (float4*)const_cast<void*>(d_cascades[j]);
+    return t->fireflyFilter.Resolve(t->stream, t->extTiming, k, width, height, image_count, (const float4*)d_film, cas, (float4*)d_out);
+}
+
+DCRT_API int dcrt_tracer_firefly_timings(dcrt_tracer* t, float* out_cascade_ms, float* out_resolve_ms)
+{
+    TRACER_GUARD(t);
+    if (!out_cascade_ms || !out_resolve_ms) return DCRT_E_INVALID_ARG;
+    HIPCHECK(hipStreamSynchronize(t->stream));
+    return t->fireflyFilter.Timings(out_cascade_ms, out_resolve_ms);
+}
+
 // ---- film denoiser ------------------------------------------------------------------------
 DCRT_API int dcrt_denoise_default_params(dcrt_denoise_params* out)
 {
@@ -3955,6 +4259,22 @@ DCRT_API int dcrt_tracer_denoise(dcrt_tracer* t, const dcrt_denoise_params* p)
         return DCRT_E_INVALID_ARG;
     }
     CHECKED(t->denoiser.Run(t->stream, t->extTiming, *p, t->filmW, t->filmH, t->film.accum, t->guideNormal, t->guideAlbedo, t->denoised));
+    t->hasDenoised = true;
+    return DCRT_OK;
+}
+
+// ... with the re-weighted image of the last dcrt_tracer_firefly_resolve as the colour input
+DCRT_API int dcrt_tracer_denoise_firefly(dcrt_tracer* t, const dcrt_denoise_params* p)
+{
+    TRACER_GUARD(t);
+    if (!p) return DCRT_E_INVALID_ARG;
+    if (!t->hasReweighted) { SetLastError("denoise_firefly: no re-weighted image (dcrt_tracer_firefly_resolve)"); return DCRT_E_INVALID_ARG; }
+    if (!t->guidesRendered || !t->guideNormal) {
+        SetLastError("denoise: no guides rendered at this resolution (dcrt_tracer_render_guides)");
+        return DCRT_E_INVALID_ARG;
+    }
+    t->hasDenoised = false;
+    CHECKED(t->denoiser.Run(t->stream, t->extTiming, *p, t->filmW, t->filmH, t->reweighted, t->guideNormal, t->guideAlbedo, t->denoised));
     t->hasDenoised = true;
     return DCRT_OK;
 }

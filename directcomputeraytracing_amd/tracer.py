@@ -245,15 +245,20 @@ class WavefrontPathTracer:
         """film += the RGBA32F film at device address d_src (another partition's film)."""
         check(self._lib.dcrt_tracer_add_film_device(self._h, C.c_void_p(d_src)), "AddFilmDevice")
 
-    def resolve_image(self, params: _abi.PostFxParams | None = None, with_luminance: bool = False, denoised: bool = False):
+    def resolve_image(self, params: _abi.PostFxParams | None = None, with_luminance: bool = False, denoised: bool = False,
+                      firefly: bool = False):
         """Post-processing (exposure + Reinhard) into sRGB8 RGBA, H x W x 4 uint8: of the film, or
-        with denoised=True of the last denoise()'s image."""
+        with denoised=True of the last denoise()'s image, or with firefly=True of the last
+        firefly_filtered()'s."""
         p = params or _abi.PostFxParams(1, 1, 15.0, 1.0)
         out = np.empty((self.height, self.width, 4), np.uint8)
         lum = C.c_float()
-        fn = self._lib.dcrt_tracer_resolve_denoised if denoised else self._lib.dcrt_tracer_resolve_image
-        check(fn(self._h, C.byref(p), out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(lum)),
-              "ResolveDenoised" if denoised else "ResolveImage")
+        fn, what = (self._lib.dcrt_tracer_resolve_image, "ResolveImage")
+        if denoised:
+            fn, what = (self._lib.dcrt_tracer_resolve_denoised, "ResolveDenoised")
+        elif firefly:
+            fn, what = (self._lib.dcrt_tracer_resolve_firefly, "ResolveFirefly")
+        check(fn(self._h, C.byref(p), out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(lum)), what)
         return (out, lum.value) if with_luminance else out
 
     # ---- film denoiser ---------------------------------------------------------
@@ -275,11 +280,15 @@ class WavefrontPathTracer:
         check(self._lib.dcrt_tracer_guide_device_ptrs(self._h, C.byref(nrm), C.byref(alb)), "GuideDevicePtrs")
         return nrm.value or 0, alb.value or 0
 
-    def denoise(self, params: _abi.DenoiseParams | None = None) -> np.ndarray:
-        """Filter the film with the rendered guides; returns the denoised image (H x W x 4 float32,
-        film convention with w = 1), which resolve_image(denoised=True) tone-maps."""
+    def denoise(self, params: _abi.DenoiseParams | None = None, firefly: bool = False) -> np.ndarray:
+        """Filter the film -- with firefly=True the re-weighted image of the last firefly_filtered() -- with the
+        rendered guides; returns the denoised image (H x W x 4 float32, film convention with w = 1), which
+        resolve_image(denoised=True) tone-maps."""
         p = params or denoise_default_params()
-        check(self._lib.dcrt_tracer_denoise(self._h, C.byref(p)), "Denoise")
+        if firefly:
+            check(self._lib.dcrt_tracer_denoise_firefly(self._h, C.byref(p)), "DenoiseFirefly")
+        else:
+            check(self._lib.dcrt_tracer_denoise(self._h, C.byref(p)), "Denoise")
         out = np.empty((self.height, self.width, 4), np.float32)
         check(self._lib.dcrt_tracer_read_denoised(self._h, out.ctypes.data_as(_abi._FP)), "ReadDenoised")
         return out
@@ -314,6 +323,64 @@ class WavefrontPathTracer:
         n = C.c_uint32()
         check(self._lib.dcrt_tracer_denoise_timings(self._h, ms, 16, C.byref(n)), "DenoiseTimings")
         return [float(ms[i]) for i in range(min(16, n.value))]
+
+    # ---- firefly re-weighting (include/dcrt.h) ------------------------------------------
+    def set_firefly_filter(self, params: _abi.FireflyParams | None) -> None:
+        """Firefly re-weighting (off by default): with params, keep K cascade films beside the film and feed them in
+        every film pass; None switches it off and frees them. Either way the film, the half film and the cascades
+        are cleared and the film image count is reset. Needs the frame parameters (a film)."""
+        check(self._lib.dcrt_tracer_set_firefly(self._h, C.byref(params) if params is not None else None), "SetFirefly")
+
+    def firefly_filter(self) -> _abi.FireflyParams | None:
+        """The parameters while firefly re-weighting is on, else None."""
+        on, p = C.c_int(), _abi.FireflyParams()
+        check(self._lib.dcrt_tracer_get_firefly(self._h, C.byref(on), C.byref(p)), "GetFirefly")
+        return p if on.value else None
+
+    def firefly_filtered(self) -> np.ndarray:
+        """Resolve the film and its cascades; returns the re-weighted image (H x W x 4 float32, film convention
+        with w = 1), which resolve_image(firefly=True) tone-maps and denoise_device takes as its colour input."""
+        check(self._lib.dcrt_tracer_firefly_resolve(self._h), "FireflyResolve")
+        out = np.empty((self.height, self.width, 4), np.float32)
+        check(self._lib.dcrt_tracer_read_firefly(self._h, out.ctypes.data_as(_abi._FP)), "ReadFirefly")
+        return out
+
+    def firefly_device_ptr(self) -> int:
+        p = C.c_void_p()
+        check(self._lib.dcrt_tracer_firefly_device_ptr(self._h, C.byref(p)), "FireflyDevicePtr")
+        return p.value or 0
+
+    def read_cascades(self) -> np.ndarray:
+        """The cascade films, K x H x W x 4 float32 (rgb: the band's share of sum w * L; w: 0)."""
+        p = self.firefly_filter()
+        if p is None:
+            raise _abi.DCRTError("ReadCascades failed (DCRT_E_INVALID_ARG): firefly re-weighting is off")
+        out = np.empty((int(p.cascades), self.height, self.width, 4), np.float32)
+        check(self._lib.dcrt_tracer_read_cascades(self._h, out.ctypes.data_as(_abi._FP)), "ReadCascades")
+        return out
+
+    def cascade_device_ptrs(self) -> list:
+        ptrs = (C.c_void_p * 8)()
+        n = C.c_uint32()
+        check(self._lib.dcrt_tracer_cascade_device_ptrs(self._h, ptrs, 8, C.byref(n)), "CascadeDevicePtrs")
+        return [ptrs[i] or 0 for i in range(n.value)]
+
+    def firefly_resolve_device(self, width: int, height: int, image_count: int, d_film: int, d_cascades, d_out: int,
+                               params: _abi.FireflyParams | None = None) -> None:
+        """The resolve over device images, e.g. the reduced film and cascades of a multi-GPU render: d_cascades holds
+        params.cascades device addresses; d_out may not overlap an input."""
+        p = params or firefly_default_params()
+        ptrs = (C.c_void_p * len(d_cascades))(*[C.c_void_p(int(x)) for x in d_cascades])
+        if len(d_cascades) != int(p.cascades):
+            raise ValueError("firefly_resolve_device: one device image per cascade")
+        check(self._lib.dcrt_tracer_firefly_resolve_device(self._h, C.byref(p), int(width), int(height), int(image_count),
+                                                           C.c_void_p(d_film), ptrs, C.c_void_p(d_out)), "FireflyResolveDevice")
+
+    def firefly_timings(self) -> tuple[float, float]:
+        """(cascade pass ms, resolve ms) of the last ones that ran with ext_timing on (0: none did)."""
+        a, b = C.c_float(), C.c_float()
+        check(self._lib.dcrt_tracer_firefly_timings(self._h, C.byref(a), C.byref(b)), "FireflyTimings")
+        return float(a.value), float(b.value)
 
     # ---- film noise estimate, render until converged --------------------------------
     def set_convergence(self, enable: bool) -> None:
@@ -771,6 +838,14 @@ def denoise_default_params() -> _abi.DenoiseParams:
     """dcrt_denoise_default_params: 5 iterations, sigmas 4 / 0.2 / 0.1, demodulation on (no device needed)."""
     p = _abi.DenoiseParams()
     check(_abi.load_library().dcrt_denoise_default_params(C.byref(p)), "DenoiseDefaultParams")
+    return p
+
+
+def firefly_default_params() -> _abi.FireflyParams:
+    """dcrt_firefly_default_params: 6 cascades from luminance 1 in steps of 8, support 3 (no device needed). The
+    defaults come from a prototype on a synthetic run, not from a render."""
+    p = _abi.FireflyParams()
+    check(_abi.load_library().dcrt_firefly_default_params(C.byref(p)), "FireflyDefaultParams")
     return p
 
 

@@ -10,7 +10,13 @@
 //               [--edit N:KIND:ARGS]... [--output NAME [--iteration-threshold N]] [--denoise]
 //               [--converge THRESHOLD[:FRACTION] [--check-points MIN:INTERVAL]] [--noise-map out.bmp]
 //               [--adaptive THRESHOLD:FRACTION[:MARGIN]] [--sample-map out.bmp] [--env-importance]
-//               [--roulette START[:MIN[:MAX]]] [--light-power]
+//               [--roulette START[:MIN[:MAX]]] [--light-power] [--firefly [K:START:BASE:KAPPA]]
+//
+// --firefly keeps K cascade films beside the film and writes the BMP from the re-weighted image (dcrt.h "firefly
+// re-weighting"; without the fields: dcrt_firefly_default_params, which come from a synthetic prototype and not from
+// a render). With --denoise the re-weighted image is the denoiser's colour input (dcrt_tracer_denoise_firefly). --film still writes the film, which
+// the feature never alters. The JSON line gains "firefly": the parameters and the share of the film's summed
+// luminance that the resolve removed.
 //
 // --light-power picks the light of every light sample in proportion to the lights' power, and a lamp's triangle in
 // proportion to its area, instead of uniformly (dcrt.h "light selection").
@@ -96,7 +102,7 @@ int Usage(const char* exe)
                  "       [--iteration-threshold N] [--denoise]\n"
                  "       [--converge THRESHOLD[:FRACTION] [--check-points MIN:INTERVAL]] [--noise-map out.bmp]\n"
                  "       [--adaptive THRESHOLD:FRACTION[:MARGIN]] [--sample-map out.bmp] [--env-importance]\n"
-                 "       [--roulette START[:MIN[:MAX]]] [--light-power]\n",
+                 "       [--roulette START[:MIN[:MAX]]] [--light-power] [--firefly [K:START:BASE:KAPPA]]\n",
                  exe);
     return 2;
 }
@@ -213,6 +219,9 @@ int main(int argc, char** argv)
     dcrt_converge_params convergeParams = {0.0f, 0.95f, 16u, 0u, 16u};
     const char* noiseMapPath = nullptr;
     bool adaptive = false;
+    bool firefly = false;
+    dcrt_firefly_params fireflyParams;
+    if (!Check(dcrt_firefly_default_params(&fireflyParams), "FireflyDefaultParams")) return 1;
     uint32_t adaptiveMargin = 0xFFFFFFFFu;   // (the filter's window rows)
     const char* sampleMapPath = nullptr;
     bool envImportance = false;
@@ -280,6 +289,25 @@ int main(int argc, char** argv)
                 return Usage(argv[0]);
             if (f.size() == 3) adaptiveMargin = (uint32_t)std::atoi(f[2].c_str());
             converge = adaptive = true;
+        } else if (!std::strcmp(argv[i], "--firefly")) {
+            firefly = true;
+            // the optional fields: whatever follows that is not the next option (the positional arguments all come
+            // first) has to be four numbers, each read to its end; set_firefly refuses values out of range
+            if (more && std::strncmp(argv[i + 1], "--", 2) != 0) {
+                const std::vector<std::string> f = Split(argv[++i], ':');
+                if (f.size() != 4) return Usage(argv[0]);
+                float v[4];
+                for (int k = 0; k < 4; ++k) {
+                    char* end = nullptr;
+                    v[k] = std::strtof(f[k].c_str(), &end);
+                    if (f[k].empty() || *end != '\0') return Usage(argv[0]);
+                }
+                if (!(v[0] >= 0.0f && v[0] <= 64.0f) || v[0] != std::floor(v[0])) return Usage(argv[0]);
+                fireflyParams.cascades = (uint32_t)v[0];
+                fireflyParams.start = v[1];
+                fireflyParams.base = v[2];
+                fireflyParams.min_support = v[3];
+            }
         } else if (!std::strcmp(argv[i], "--sample-map") && more) {
             sampleMapPath = argv[++i];
         } else if (!std::strcmp(argv[i], "--check-points") && more) {
@@ -333,6 +361,8 @@ int main(int argc, char** argv)
     if (envImportance && !tracer.SetEnvironmentSampling(DCRT_ENV_SAMPLING_IMPORTANCE)) return 1;   // (on the uploaded scene; kept across --edit uploads)
     if (lightPower && !tracer.SetLightSampling(DCRT_LIGHT_SAMPLING_POWER)) return 1;
     if (seedType == CRendererLoop::EFrameSeedType::Fixed) scene.m_FrameSeed = fixedSeed;   // the UI's seed field (ImGui.cpp:157-160)
+    // (on the tracer's film, which the upload sized; kept across --edit uploads and the preview frames' resolution changes)
+    if (firefly && !Check(dcrt_tracer_set_firefly(tracer.GetTracer(), &fireflyParams), "SetFirefly")) return 1;
 
     const auto t0 = std::chrono::steady_clock::now();
     uint32_t firstSeed = 0;
@@ -423,6 +453,22 @@ int main(int argc, char** argv)
     if (!Check(dcrt_scene_get_postfx_params(scene.m_Handle, &post), "GetPostFxParams")) return 1;
     std::vector<uint8_t> rgba(n * 4);
     float sumLogLuminance = 0.0f;
+    double fireflyRemoved = 0.0;   // the share of the film's summed luminance the resolve took out
+    if (firefly) {
+        std::vector<float> film(n * 4), kept(n * 4);
+        if (!Check(dcrt_tracer_firefly_resolve(tracer.GetTracer()), "FireflyResolve") ||
+            !Check(dcrt_tracer_read_film(tracer.GetTracer(), film.data()), "ReadFilm") ||
+            !Check(dcrt_tracer_read_firefly(tracer.GetTracer(), kept.data()), "ReadFirefly"))
+            return 1;
+        double before = 0.0, after = 0.0;
+        for (size_t p = 0; p < n; ++p) {
+            const float* f = &film[4 * p];
+            const float* k = &kept[4 * p];
+            if (f[3] > 0.0f) before += std::fmax(0.0, (0.299 * f[0] + 0.587 * f[1] + 0.114 * f[2]) / f[3]);
+            after += std::fmax(0.0, 0.299 * k[0] + 0.587 * k[1] + 0.114 * k[2]);
+        }
+        fireflyRemoved = before > 0.0 ? 1.0 - after / before : 0.0;
+    }
     if (denoise) {
         // the guides of the film's own images: the same seeds, so the same sub-pixel positions
         // (a fixed seed repeats one image: its guides are every image's)
@@ -438,9 +484,12 @@ int main(int argc, char** argv)
         dcrt_denoise_params dn;
         if (!Check(dcrt_denoise_default_params(&dn), "DenoiseDefaultParams") ||
             !Check(dcrt_tracer_render_guides(tracer.GetTracer(), seeds[0], consecutive ? (uint32_t)seeds.size() : 1u), "RenderGuides") ||
-            !Check(dcrt_tracer_denoise(tracer.GetTracer(), &dn), "Denoise") ||
-            !Check(dcrt_tracer_resolve_denoised(tracer.GetTracer(), &post, rgba.data(), &sumLogLuminance), "ResolveDenoised"))
+            // (with --firefly the re-weighted image is the colour input)
+            !Check(firefly ? dcrt_tracer_denoise_firefly(tracer.GetTracer(), &dn) : dcrt_tracer_denoise(tracer.GetTracer(), &dn), "Denoise"))
             return 1;
+        if (!Check(dcrt_tracer_resolve_denoised(tracer.GetTracer(), &post, rgba.data(), &sumLogLuminance), "ResolveDenoised")) return 1;
+    } else if (firefly) {
+        if (!Check(dcrt_tracer_resolve_firefly(tracer.GetTracer(), &post, rgba.data(), &sumLogLuminance), "ResolveFirefly")) return 1;
     } else if (!Check(dcrt_tracer_resolve_image(tracer.GetTracer(), &post, rgba.data(), &sumLogLuminance), "ResolveImage")) {
         return 1;
     }
@@ -506,6 +555,13 @@ int main(int argc, char** argv)
                       "\"total_blocks\": %u}",
                       adaptiveReport.images, adaptiveReport.check_points, (unsigned long long)adaptiveReport.pixel_samples,
                       adaptiveReport.active_blocks, adaptiveReport.total_blocks);
+        editReport += buf;
+    }
+    if (firefly) {   // (only with --firefly)
+        char buf[256];
+        std::snprintf(buf, sizeof(buf), ", \"firefly\": {\"cascades\": %u, \"start\": %.9g, \"base\": %.9g, \"min_support\": %.9g, \"removed\": %.6g}",
+                      fireflyParams.cascades, (double)fireflyParams.start, (double)fireflyParams.base, (double)fireflyParams.min_support,
+                      fireflyRemoved);
         editReport += buf;
     }
     std::printf("{\"images\": %u, \"seconds\": %.4f, \"ms_per_spp\": %.3f, \"mrays_per_s\": %.1f, \"extension_rays\": %llu, "

@@ -966,6 +966,100 @@ DCRT_API int dcrt_tracer_render_adaptive(dcrt_tracer* tracer, uint32_t first_see
                                          uint32_t margin, const dcrt_filter_params* filter, dcrt_noise_stats* out_stats,
                                          int* out_converged, dcrt_adaptive_report* out_report_or_null);
 
+/* ===== firefly re-weighting: a cascaded film =================================
+ * Zirr, Hanika and Dachsbacher, "Re-weighting Firefly Samples for Improved Finite-Sample Monte
+ * Carlo Estimates" (CGF 2018). Beside the film, K cascade films each receive the part of every
+ * sample that belongs to their brightness band; a resolve pass keeps a band at a pixel only to the
+ * extent that enough samples of similar brightness landed nearby. It is consistent: a feature of
+ * non-zero probability gathers support as images accumulate and its weight goes to 1; what it costs
+ * is a downward bias at low image counts. The film itself is never altered. No reference
+ * counterpart. Off by default, and then every film pass is the launch it was before this existed.
+ *
+ * All arithmetic is fp32 in exactly this order (no contraction, correctly rounded /), so a float32
+ * restatement matches bit for bit (tests/firefly_ref.py).
+ *   Scales: s_0 = start, s_j = s_{j-1} * base, float32 products on the host; r = 1 / base and
+ *   d = 1 - r, float32 on the host too. The kernels and the reference use these numbers.
+ *   Y(v) = fmaxf(0, v.r * 0.299f + v.g * 0.587f + v.b * 0.114f), the film kernels' weights, summed
+ *   left to right.
+ *   Split of a sample v of luminance Y into (band, alpha): Y <= s_0 (and a NaN Y, which fmaxf
+ *   makes 0): band 0, alpha 1. Y > s_{K-1}: band K - 1, alpha 1 -- nothing is clamped. Otherwise
+ *   band = the j with s_j < Y <= s_{j+1} and alpha = fminf(fmaxf((s_j / Y - r) / d, 0), 1).
+ *   Cascade `band` takes alpha * v.rgb, cascade band + 1 (if there is one) takes (1 - alpha) * v.rgb,
+ *   1 - alpha rounded to float32 first; with exact arithmetic a sample counts once across the two:
+ *   alpha Y / s_j + (1 - alpha) Y / s_{j+1} = 1.
+ *   Accumulation: cascade film j is W x H RGBA32F. Per film pass and pixel, with the film pass's
+ *   windows and weights w (images in order, window rows then columns): sum_j = 0 per image;
+ *   sum_j = sum_j + (share_j(v) * w) per tap whose sample has a share in j -- the share first, then
+ *   times w, per channel -- and C_j.rgb = C_j.rgb + sum_j after each image. (A tap without a share
+ *   in j adds nothing, which equals adding +0.) C_j.w is never written: it stays 0 from the clear,
+ *   and the film's own .w is the weight sum for every cascade.
+ *   Resolve at pixel p, W(p) = film.w, N = (float)image count:
+ *   count_i(q) = (N * Y(C_i(q).rgb)) / (W(q) * s_i), 0 for a q outside the image or with
+ *   !(W(q) > 0);  T_i(p) = the sum of count_i(q) over the 3 x 3 pixels q around p, sequential adds
+ *   from 0, rows then columns;  S_j = (T_{j-1} + T_j) + T_{j+1} without the terms outside [0, K);
+ *   omega_0 = 1, omega_j = fminf(fmaxf((S_j - 1) / min_support, 0), 1) for j >= 1: a sample does
+ *   not support itself.  acc = C_0(p).rgb; acc = acc + C_j(p).rgb * omega_j for j = 1 .. K-1;
+ *   out(p) = (acc / W(p), 1), and (0, 0, 0, 0) where !(W(p) > 0).
+ * The output is film convention, as the denoised image is: dcrt_tracer_denoise_device takes it as
+ * its colour input and the resolve / post-processing path takes it as it takes the film.
+ * Non-finite sample values are out of scope, as for the denoiser.
+ * The defaults (6, 1, 8, 3) come from a float64 prototype on a synthetic run only; nobody has
+ * measured them on a render. */
+typedef struct dcrt_firefly_params {
+    uint32_t cascades;   /* K, 2..8            (default 6) */
+    float start;         /* s_0 > 0, luminance (default 1) */
+    float base;          /* b > 1              (default 8) */
+    float min_support;   /* kappa > 0          (default 3) */
+} dcrt_firefly_params;
+/* K outside 2..8, a non-finite float, start <= 0, base <= 1, min_support <= 0 or an s_{K-1} that is
+ * not finite is DCRT_E_INVALID_ARG in every call that takes the parameters. */
+DCRT_API int dcrt_firefly_default_params(dcrt_firefly_params* out_params);   /* needs no device */
+/* With params: allocates the K cascade films (K * W * H * 16 B, only while on); null: frees them
+ * and switches the feature off. Either way the film, the half film if any and the cascades are
+ * cleared and the film image count is reset; on a change of K, start or base, or of on / off, the
+ * captured graphs are dropped -- a change of min_support alone reallocates and drops nothing (it
+ * still clears). Needs a film (frame parameters); a later resolution change resizes the cascades
+ * with the film, dcrt_tracer_clear_film clears them, and the parameters persist across
+ * dcrt_tracer_upload_scene. While on, every film pass into the film (render_images / _strided in
+ * either mode and in the output views, accumulate_film, accumulate_images) also launches the
+ * cascade pass over the same images, so the cascades' image count is the film's; the guide films
+ * are not covered, and dcrt_tracer_add_film_device, a partition of world_size > 1 and film bands
+ * are DCRT_E_INVALID_ARG (the film would hold what the cascades lack). On a partitioned or banded
+ * tracer set_firefly itself is DCRT_E_INVALID_ARG: reduce film and cascades yourself, then
+ * dcrt_tracer_firefly_resolve_device. get_firefly: *out_enabled, and the parameters when on. */
+DCRT_API int dcrt_tracer_set_firefly(dcrt_tracer* tracer, const dcrt_firefly_params* params_or_null);
+DCRT_API int dcrt_tracer_get_firefly(dcrt_tracer* tracer, int* out_enabled, dcrt_firefly_params* out_params);
+/* The resolve over the tracer's film and cascades into the tracer-owned re-weighted image.
+ * DCRT_E_INVALID_ARG while the feature is off or before any image reached the film. Synchronous. */
+DCRT_API int dcrt_tracer_firefly_resolve(dcrt_tracer* tracer);
+/* The result of the last dcrt_tracer_firefly_resolve (W*H*4 floats); DCRT_E_INVALID_ARG before
+ * one, or after a resolution change or a set_firefly. */
+DCRT_API int dcrt_tracer_read_firefly(dcrt_tracer* tracer, float* out_rgba);
+DCRT_API int dcrt_tracer_firefly_device_ptr(dcrt_tracer* tracer, void** out_ptr);
+/* dcrt_tracer_resolve_image with the re-weighted image in the film's place. */
+DCRT_API int dcrt_tracer_resolve_firefly(dcrt_tracer* tracer, const dcrt_postfx_params* params, uint8_t* out_rgba8,
+                                         float* out_sum_log_luminance);
+/* dcrt_tracer_denoise with the re-weighted image of the last dcrt_tracer_firefly_resolve in the film's place as the
+ * colour input (the guides are the film's); the result is the tracer's denoised image, as dcrt_tracer_denoise's.
+ * DCRT_E_INVALID_ARG before a resolve, or without guides rendered at the current resolution. */
+DCRT_API int dcrt_tracer_denoise_firefly(dcrt_tracer* tracer, const dcrt_denoise_params* params);
+/* The K cascade films, K * W*H*4 floats, cascade 0 first / their K device pointers (`capacity`
+ * entries of room; *out_count = K). DCRT_E_INVALID_ARG while the feature is off. */
+DCRT_API int dcrt_tracer_read_cascades(dcrt_tracer* tracer, float* out_rgba);
+DCRT_API int dcrt_tracer_cascade_device_ptrs(dcrt_tracer* tracer, void** out_ptrs, uint32_t capacity, uint32_t* out_count);
+/* The resolve over caller-provided device images (width * height RGBA32F each, on the tracer's
+ * device; d_cascades: params->cascades host-side pointers to device images) into d_out, which must
+ * not overlap an input. image_count >= 1. The tracer's own film is not used: any tracer will do,
+ * e.g. rank 0 after the reduce, or one without a scene. Synchronous. */
+DCRT_API int dcrt_tracer_firefly_resolve_device(dcrt_tracer* tracer, const dcrt_firefly_params* params, uint32_t width, uint32_t height,
+                                                uint32_t image_count, const void* d_film, const void* const* d_cascades, void* d_out);
+/* With ext_timing on (dcrt_tracer_set_instrumentation): the HIP-event times in ms of the last
+ * cascade pass launched on its own (the megakernel mode, the output views, accumulate_film,
+ * accumulate_images; the pass inside the wavefront iteration is launched every iteration, returns at
+ * once unless a batch completed, and is not timed) and of the last resolve; 0 for one that has
+ * not run with ext_timing on. */
+DCRT_API int dcrt_tracer_firefly_timings(dcrt_tracer* tracer, float* out_cascade_ms, float* out_resolve_ms);
+
 /* ===== environment importance sampling ==========================================
  * The environment light is sampled with a uniform direction and pdf 1 / (4 pi), as in the reference
  * (DCRT_ENV_SAMPLING_UNIFORM, the default: every result is then what it was before this existed). With

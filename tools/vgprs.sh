@@ -10,7 +10,7 @@ cur = None
 for line in sys.stdin:
     m = re.search(r"Function Name: (\S+)", line)
     if m: cur = m.group(1); continue
-    for key in ("VGPRs:", "AGPRs:", "ScratchSize", "Occupancy", "VGPRs Spill"):
-        if key in line and cur and ("cast_kernel" in cur or "material_kernel" in cur or "control_kernel" in cur or "megakernel" in cur or "drain_kernel" in cur or "film_" in cur or "noise_" in cur):
+    for key in ("VGPRs:", "AGPRs:", "SGPRs:", "ScratchSize", "Occupancy", "VGPRs Spill", "LDS Size"):
+        if key in line and cur and ("cast_kernel" in cur or "material_kernel" in cur or "control_kernel" in cur or "megakernel" in cur or "drain_kernel" in cur or "film_" in cur or "noise_" in cur or "firefly_" in cur):
             print(cur[:60], line.split("remark:")[-1].strip())
 '
